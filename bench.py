@@ -2,9 +2,15 @@
 """bench.py -- LP instances/s (forward + backward + Adam) on the Netlib batch, and achieved HBM GB/s
 of the CSR SpMM on the synthetic roofline batch (BASELINE.json metric).
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
       bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, runs W warm-up steps and K timed steps of the headline (`value`, `ms_per_step`) and prints the
+line.  `--full` adds everything else below (the other scaling mode, per_instance_steps, roofline, synthetic,
+synthetic_strong, the parity gates, cpu_baseline).  `--dump-outputs DIR` writes what the last timed step handed its
+caller (rank 0): DIR/loss.npy, DIR/logits.npy (LPTrainer.step's return) and DIR/params.npy (the parameters after
+its Adam update), float32; the inputs are seeded, so runs with the same arguments compare output for output.
 
 One JSON line on rank 0:
   value        whole-job LP instances/s on the full Netlib batch (BASELINE.json configs[2], 97 instances as
@@ -63,7 +69,26 @@ def parse(argv=None):
     ap.add_argument("--dry-launch", action="store_true",
                     help="with --gpus N > 1 and no WORLD_SIZE: print the launch command as JSON and exit (no device touched)")
     ap.add_argument("--master-port", type=int, default=29571)
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline (other scaling mode, per-instance steps, roofline "
+                         "and synthetic batch with their parity gates, cpu_baseline); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the arrays the last timed step computed as DIR/<name>.npy (float32)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+def dump_outputs(d, trainer, last):
+    """What the last timed step handed its caller: (loss, logits) as LPTrainer.step returns them, and the parameters
+    it updated in place."""
+    os.makedirs(d, exist_ok=True)
+    arrays = {"params": trainer.params}
+    if last is not None:                        # (None: this rank owned no instance of the step)
+        arrays["loss"], arrays["logits"] = last
+    for name, t in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), t.detach().float().cpu().numpy())
 
 
 def launch_command(args, argv):
@@ -228,9 +253,10 @@ def main():
             total = n_inst * world
         batch = LPBatch.from_instances([instances[i] for i in mine]) if mine else None
         trainer = LPTrainer(params0, lr=1e-3, use_hip_graph=use_graph, global_instances=total)
+        last = [None]
 
         def one():
-            trainer.step(batch) if batch is not None else trainer.step_empty()
+            last[0] = trainer.step(batch) if batch is not None else trainer.step_empty()
         for _ in range(max(args.warmup, 2)):          # >= 2: eager pass + graph capture
             one()
         barrier_sync(dist_on)
@@ -239,13 +265,17 @@ def main():
             one()
         barrier_sync(dist_on)
         dt = max_over_ranks(time.perf_counter() - t0, dist_on)
-        return dict(value=total * args.steps / dt, ms_per_step=1e3 * dt / args.steps, scaling=mode,
-                    global_batch=total, instances_this_rank=len(mine), nnz_this_rank=batch.nnz if batch else 0,
-                    hip_graph=trainer.uses_graph(batch) if batch else False,
-                    final_loss_rank0=float(trainer.last_loss(batch)[0]) if batch else None)
+        res = dict(value=total * args.steps / dt, ms_per_step=1e3 * dt / args.steps, scaling=mode,
+                   global_batch=total, instances_this_rank=len(mine), nnz_this_rank=batch.nnz if batch else 0,
+                   hip_graph=trainer.uses_graph(batch) if batch else False,
+                   final_loss_rank0=float(trainer.last_loss(batch)[0]) if batch else None)
+        return res, trainer, last[0]
 
     # ---------------- headline: Netlib batch, instances/s --------------------------------------
-    head = run_netlib(args.scaling)
+    head, head_trainer, head_last = run_netlib(args.scaling)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, head_trainer, head_last)
+    del head_trainer, head_last                  # (frees the Netlib batch before the --full sections allocate theirs)
     value = head["value"]
     out = {
         "metric": "LP instances/sec (fwd+bwd) on Netlib batch; achieved HBM GB/s on CSR SpMM",
@@ -263,13 +293,13 @@ def main():
                    "nnz_rank0": head["nnz_this_rank"], "hip_graph": head["hip_graph"],
                    "parallelism": f"dp{world}", "final_loss_rank0": head["final_loss_rank0"]},
     }
-    if world > 1:      # the other scaling mode beside the headline
+    if args.full and world > 1:      # the other scaling mode beside the headline
         other = "weak" if args.scaling == "strong" else "strong"
-        out["netlib_" + other] = run_netlib(other)
+        out["netlib_" + other] = run_netlib(other)[0]
 
     # reference semantics beside the batched headline: ONE Adam step per instance (experiment.py:123-144),
     # every instance its own HBM-resident batch; like-for-like with cpu_baseline (rank 0, single-GPU runs)
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         singles = [LPBatch.from_instances([i]) for i in instances]
         tr1 = LPTrainer(params0, lr=1e-3, use_hip_graph=use_graph, global_instances=1)
         for b in singles:
@@ -286,7 +316,7 @@ def main():
         del tr1, singles
 
     # ---------------- roofline + synthetic throughput ------------------------------------------
-    if not args.no_synthetic:
+    if args.full and not args.no_synthetic:
         t_gen = time.perf_counter()
         sb = synthetic_batch(args.synthetic_instances, seed=1234 + 100000 * rank)
         torch.cuda.synchronize()
@@ -553,7 +583,7 @@ def main():
         torch.cuda.empty_cache()
 
     # ---------------- CPU baseline (rank 0, single-GPU runs only) ------------------------------
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(instances, args.cpu_threads)
         out["speedup_vs_cpu_baseline"] = {"batched_step": value / out["cpu_baseline"]["value"],
                                           "per_instance_steps (like for like)":

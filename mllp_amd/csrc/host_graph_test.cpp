@@ -403,7 +403,10 @@ static void check_stream(std::mt19937& rng, int n_dst, int n_src, double mean_de
 int main(int argc, char** argv) {
     for (int a = 1; a < argc; ++a) check_mps(argv[a], false);
     {
-        const char* path = "/tmp/mllp_sanitize_synth.mps";
+        // in $TMPDIR (the test gives each run its own): a fixed name in a shared /tmp may belong to another user
+        const char* tmp = std::getenv("TMPDIR");
+        const std::string path_s = std::string(tmp && *tmp ? tmp : "/tmp") + "/mllp_sanitize_synth.mps";
+        const char* path = path_s.c_str();
         FILE* fh = std::fopen(path, "w");
         CHECK(fh != nullptr);
         std::fputs("NAME          SYNTH\nROWS\n N  COST\n L  R1\n G  R2\n E  R3\n G  R4\n L  R5\n N  FREE\nCOLUMNS\n"

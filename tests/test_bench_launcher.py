@@ -48,14 +48,52 @@ def test_launcher_decisions(monkeypatch):
     assert b.maybe_launch(a8, ["--gpus", "8"]) == 2                        # launched with the wrong world size: refuse
 
 
+def test_plain_run_is_the_default_and_steps_are_checked():
+    b = _bench()
+    a = b.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 2
+    a = b.parse(["--full", "--dump-outputs", "some/dir"])
+    assert a.full is True and a.dump_outputs == "some/dir"
+    with pytest.raises(SystemExit):
+        b.parse(["--steps", "0"])
+
+
+@pytest.mark.gpu
+def test_plain_bench_times_the_headline_and_dumps_its_outputs(tmp_path):
+    """`python bench.py --steps K --warmup W --dump-outputs DIR` without --full: the headline line only (no roofline,
+    synthetic or cpu_baseline sections), and DIR holds the last timed step's loss, logits and updated parameters."""
+    import numpy as np
+    d = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    res = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in res, k
+    assert res["steps"] == 3 and res["unit"] == "instances/s" and res["higher_is_better"] is True and res["dtype"] == "f32"
+    assert res["ms_per_step"] > 0 and abs(res["value"] - 97 * 1e3 / res["ms_per_step"]) < 1e-6 * res["value"]
+    for k in ("roofline", "synthetic", "synthetic_strong", "cpu_baseline", "per_instance_steps"):
+        assert k not in res, k
+    loss, logits, params = (np.load(d / f"{n}.npy") for n in ("loss", "logits", "params"))
+    assert loss.dtype == logits.dtype == params.dtype == np.float32
+    assert loss.shape == (1,) and float(loss[0]) == pytest.approx(res["config"]["final_loss_rank0"], rel=1e-6)
+    assert logits.ndim == 1 and logits.size > 97 and np.isfinite(logits).all()
+    from mllp_amd.model import GNNModel, set_seed
+    set_seed(42)                                                     # bench.py's seeded initial parameters
+    p0 = GNNModel().flat_parameters().detach().float().numpy()
+    assert params.shape == p0.shape and 0 < np.abs(params - p0).max() < 0.1    # moved by a few Adam steps of lr 1e-3
+
+
 @pytest.mark.gpu
 def test_bench_json_contract_on_the_gpu():
-    """`python bench.py` end to end at a reduced size (17 synthetic instances = the throughput regime, 3 timed steps):
+    """`python bench.py --full` end to end at a reduced size (17 synthetic instances = the throughput regime, 3 timed steps):
     exactly one JSON line with the contract's keys, a roofline object for the streamed SpMM with frac = achieved / peak,
     parity figures inside it, and a cpu_baseline object (one epoch's worth is enough here)."""
     import json
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1",
-                        "--synthetic-instances", "17", "--synthetic-steps", "2", "--spmm-reps", "3"],
+                        "--synthetic-instances", "17", "--synthetic-steps", "2", "--spmm-reps", "3", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -101,7 +139,8 @@ def test_bench_exits_nonzero_when_a_parity_gate_fails():
     to the measured SpMM difference) still prints the JSON line, lists the failed gate and exits 1."""
     env = dict(os.environ, MLLP_BENCH_PERTURB="1e-3")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1",
-                        "--synthetic-instances", "17", "--synthetic-steps", "1", "--spmm-reps", "2", "--no-cpu-baseline"],
+                        "--synthetic-instances", "17", "--synthetic-steps", "1", "--spmm-reps", "2", "--no-cpu-baseline",
+                        "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 1, (r.returncode, r.stderr[-2000:])
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])

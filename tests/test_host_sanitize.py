@@ -17,8 +17,8 @@ def built():
 
 
 @pytest.mark.parametrize("binary", ["host_graph_asan", "host_graph_tsan"])
-def test_host_graph_build_is_clean_under_sanitizers(built, binary):
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", TSAN_OPTIONS="halt_on_error=1")
+def test_host_graph_build_is_clean_under_sanitizers(built, binary, tmp_path):
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1", TSAN_OPTIONS="halt_on_error=1", TMPDIR=str(tmp_path))
     mps = sorted(os.path.join(CSRC, "..", "..", "tests", "golden", "mps", f)
                  for f in os.listdir(os.path.join(CSRC, "..", "..", "tests", "golden", "mps")))
     r = subprocess.run([os.path.join(CSRC, binary)] + mps, capture_output=True, text=True, timeout=600, env=env)

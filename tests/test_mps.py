@@ -1,10 +1,12 @@
 """MPS -> normalized tensors.  CPU only (the parser and the normalisation are host code of the
-library).  Three layers: (1) the oracle (oracle/mps_norm.py) against every tensor the reference holds, when
-/root/reference is present (it is in the build container; the GPU box has no reference); (2) the oracle and the
+library).  Three layers: (1) the oracle (oracle/mps_norm.py) against every tensor the reference holds for the instances
+stored under tests/golden/netlib_ref (the reference's own data files, see the README there); (2) the oracle and the
 library against the five committed fixtures and the packed reference tensors (data/netlib_norm.npz, byte-identical to
 the reference's files); (3) library == oracle on a synthetic file that exercises RANGES on L / G / E rows, a G row,
 negative right-hand sides, blank set names, a right-hand side on the objective, Fortran exponents and a MARKER line."""
+import gzip
 import os
+import shutil
 
 import numpy as np
 import pytest
@@ -15,7 +17,9 @@ from oracle import mps_norm as mn
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 FIX = os.path.join(HERE, "golden", "mps")
-REF = "/root/reference"
+REF = os.path.join(HERE, "golden", "netlib_ref")
+REF_NAMES = ["adlittle.mps", "afiro.mps", "blend.mps", "kb2.mps", "sc105.mps", "sc205.mps", "sc50a.mps", "sc50b.mps",
+             "scagr7.mps", "stocfor1.mps", "wood1p.mps"]
 
 SYNTH = """NAME          SYNTH
 ROWS
@@ -54,15 +58,17 @@ def _csr(inst):
     return sp.csr_matrix((inst.values, inst.indices, inst.indptr), shape=(inst.m, inst.n))
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "netlib_mps")), reason="the reference is not on this machine")
-def test_oracle_reproduces_every_reference_tensor():
-    """Pins the oracle: all 97 instances, raw stage exact, normalized stage to 1e-12, labels from the solver outputs."""
+def test_oracle_reproduces_every_reference_tensor(tmp_path):
+    """Pins the oracle: every stored instance, raw stage exact, normalized stage to 1e-12, labels from the solver outputs."""
     from mllp_amd.mps import read_mps
     label_mismatch = []
-    names = sorted(os.listdir(os.path.join(REF, "netlib_mps")))
-    assert len(names) == 97
+    names = sorted(f[:-len(".gz")] for f in os.listdir(os.path.join(REF, "netlib_mps")))
+    assert names == REF_NAMES
     for nm in names:
-        p = mn.parse_mps(os.path.join(REF, "netlib_mps", nm))
+        mps = str(tmp_path / nm)
+        with gzip.open(os.path.join(REF, "netlib_mps", nm + ".gz"), "rb") as src, open(mps, "wb") as dst:
+            shutil.copyfileobj(src, dst)
+        p = mn.parse_mps(mps)
         A, c, b = mn.raw_tensors(p)
         raw = os.path.join(REF, "dataset", "netlib_mps", nm)
         R = sp.load_npz(raw + "_constrs.npz")
@@ -78,11 +84,11 @@ def test_oracle_reproduces_every_reference_tensor():
         if not np.array_equal(mn.basis_labels(p, v, cs), np.load(nrm + "_basis.npy")):
             label_mismatch.append(nm)
         # the library on the same file
-        inst, info = read_mps(os.path.join(REF, "netlib_mps", nm), True, var_status=v, constr_status=cs)
+        inst, info = read_mps(mps, True, var_status=v, constr_status=cs)
         assert abs(_csr(inst) - N).max() < 1e-12 and inst.nnz == N.nnz, nm
         assert np.abs(inst.coefs - np.load(nrm + "_coefs.npy")).max() < 1e-12, nm
         assert np.abs(inst.rhs - np.load(nrm + "_rhs.npy")).max() < 1e-12, nm
-        raw_inst, _ = read_mps(os.path.join(REF, "netlib_mps", nm), False)
+        raw_inst, _ = read_mps(mps, False)
         assert abs(_csr(raw_inst) - R).max() == 0 and np.array_equal(raw_inst.coefs, np.load(raw + "_coefs.npy")), nm
     # the reference's wood1p labels do not follow from its own _v / _c files (every other instance does)
     assert label_mismatch in ([], ["wood1p.mps"]), label_mismatch
