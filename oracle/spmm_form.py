@@ -155,9 +155,11 @@ def conv_bwd(p, ptr, idx, val, X_src, x_dst, saved, dh, need_input_grads=True):
     return grads, dx_dst, dX_src, dict(g=g, gv=gv, ge=ge, c=c, dqp=dqp, ds=ds, dt=dt, alpha=alpha, dl=dl)
 
 
-def gnn_forward_backward(sd, batch: BatchCSR, want_grads=True):
+def gnn_forward_backward(sd, batch: BatchCSR, want_grads=True, dlogits=None):
     """Whole model in the kernels' decomposition.  Returns dict(logits, loss, grads (flat, state_dict
-    order), hidden...).  Loss = sum_i wnode_i * BCE(z_i, y_i)  ==  (1/B) sum_k mean-BCE(instance k)."""
+    order), hidden...).  Loss = sum_i wnode_i * BCE(z_i, y_i)  ==  (1/B) sum_k mean-BCE(instance k).
+    `dlogits` (N,): the backward starts from this dL/dz instead of the BCE gradient (the `backward` entry point of
+    the library); the loss is still the BCE loss."""
     x1 = batch.x1[:, None]
     x2 = batch.x2[:, None]
     P = {name: conv_params(sd, name) for name in CONV_CIN}
@@ -177,7 +179,11 @@ def gnn_forward_backward(sd, batch: BatchCSR, want_grads=True):
                saved=dict(s1v=s1v, s1c=s1c, s2v=s2v, s2c=s2c, s3v=s3v))
     if not want_grads:
         return out
-    dz = batch.wnode * (1.0 / (1.0 + np.exp(-z)) - y)
+    if dlogits is None:
+        dz = batch.wnode * (1.0 / (1.0 + np.exp(-z)) - y)
+    else:
+        dz = np.asarray(dlogits, dtype=np.float64)
+        assert dz.shape == z.shape
     G = {}
     G["fc.weight"] = (dz @ h3v)[None, :]
     G["fc.bias"] = np.array([dz.sum()])

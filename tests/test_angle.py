@@ -119,10 +119,12 @@ def test_angle_driver_end_to_end(tmp_path, monkeypatch, capsys):
 
 
 @pytest.mark.gpu
-def test_angle_stepper_equals_module_loop():
+@pytest.mark.parametrize("feat_dim", [32, 256])
+def test_angle_stepper_equals_module_loop(feat_dim):
     """AngleStepper (flat parameters, C ABI forward / backward, the library's Adam kernel) follows the nn.Module +
     autograd + torch.optim.Adam loop of the reference (linear_program_experiment.py:88-96) step for step; feat_dim
-    outside {16, 32, 64, 128, 256} is refused loudly."""
+    outside {16, 32, 64, 128, 256} is refused loudly.  At the reference's feat_dim 256 (530 k parameters) Adam runs on the
+    multi-workgroup kernels."""
     from mllp_amd import _lib
     from mllp_amd.angle import AngleModel, AngleStepper, build_graph_from_Q_sets
     from mllp_amd.model import set_seed
@@ -134,7 +136,7 @@ def test_angle_stepper_equals_module_loop():
     assert torch.equal(g.cos, g.cos.T)
     y = torch.tensor(basis, dtype=torch.float, device="cuda")
     set_seed(3)
-    model = AngleModel(feat_dim=32).to("cuda")
+    model = AngleModel(feat_dim=feat_dim).to("cuda")
     st = AngleStepper(model, lr=1e-3)
     opt = torch.optim.Adam(model.parameters(), lr=1e-3)
     crit = torch.nn.BCEWithLogitsLoss()

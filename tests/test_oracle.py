@@ -188,3 +188,61 @@ def test_topk_metrics_matches_sklearn():
     pred = np.zeros(50)
     pred[np.argsort(-z)[:17]] = 1
     assert tp == pred @ y and abs(f1 - f1_score(y, pred)) < 1e-12
+
+
+# ---- identities the throughput-regime GPU tests (tests/test_throughput_oracle.py) rely on -------------------------------
+def _sd_np(golden):
+    return {k: v.numpy() for k, v in _sd_from_flat(golden["weights_flat"]).items()}
+
+
+def test_dlogits_equal_to_the_bce_gradient_gives_the_default_gradients(golden, subset5):
+    sd, b = _sd_np(golden), o2.BatchCSR(subset5)
+    r = o2.gnn_forward_backward(sd, b)
+    dz = b.wnode * (1.0 / (1.0 + np.exp(-r["logits"])) - b.basis)
+    r2 = o2.gnn_forward_backward(sd, b, dlogits=dz)
+    assert r2["loss"] == r["loss"]
+    np.testing.assert_array_equal(r2["logits"], r["logits"])
+    np.testing.assert_array_equal(r2["grads"], r["grads"])
+
+
+def test_dlogits_on_one_instance_equal_that_instance_alone(golden, subset5):
+    """Block-diagonal batching: a dL/dz that is nonzero on instance k only gives instance k's own gradients, and the
+    logits of the batch cut at instance k are the logits of the instance alone."""
+    sd, b = _sd_np(golden), o2.BatchCSR(subset5)
+    full = o2.gnn_forward_backward(sd, b, want_grads=False)
+    off = np.concatenate([[0], np.cumsum(b.inst_n)])
+    rng = np.random.default_rng(17)
+    for k, inst in enumerate(subset5):
+        alone = o2.gnn_forward_backward(sd, o2.BatchCSR([inst]), want_grads=False)
+        np.testing.assert_allclose(full["logits"][off[k]:off[k + 1]], alone["logits"], rtol=1e-12, atol=1e-14)
+        dz_k = rng.standard_normal(inst.n) / inst.n
+        dz = np.zeros(b.N)
+        dz[off[k]:off[k + 1]] = dz_k
+        gb = o2.gnn_forward_backward(sd, b, dlogits=dz)["grads"]
+        ga = o2.gnn_forward_backward(sd, o2.BatchCSR([inst]), dlogits=dz_k)["grads"]
+        scale = np.abs(ga).max()
+        assert scale > 0
+        assert np.abs(gb - ga).max() <= 1e-12 * scale, inst.name
+
+
+def test_replicated_batch_has_the_same_loss_and_gradients(golden, subset5):
+    """loss = (1/B) sum_k mean-BCE(k): subset5 repeated three times in a shuffled order trains exactly like subset5."""
+    sd = _sd_np(golden)
+    order = np.random.default_rng(23).permutation(3 * len(subset5))
+    rep = [subset5[i % len(subset5)] for i in order]
+    r1 = o2.gnn_forward_backward(sd, o2.BatchCSR(subset5))
+    r3 = o2.gnn_forward_backward(sd, o2.BatchCSR(rep))
+    np.testing.assert_allclose(r3["loss"], r1["loss"], rtol=1e-12)
+    assert np.abs(r3["grads"] - r1["grads"]).max() <= 1e-12 * np.abs(r1["grads"]).max()
+
+
+def test_cut_instance_returns_every_netlib_instance():
+    from batch_slices import cut_instance
+    inst = load_packed()
+    b = o2.BatchCSR(inst)
+    for k, i in enumerate(inst):
+        c = cut_instance(b.rp, b.ci, b.va, b.x1, b.x2, b.basis, b.inst_m, b.inst_n, k, name=i.name)
+        assert (c.m, c.n, c.nnz) == (i.m, i.n, i.nnz), i.name
+        for a, w in ((c.indptr, i.indptr), (c.indices, i.indices), (c.values, i.values), (c.coefs, i.coefs),
+                     (c.rhs, i.rhs), (c.basis, i.basis)):
+            assert a.dtype == w.dtype and np.array_equal(a, w), i.name
