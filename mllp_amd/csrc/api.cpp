@@ -271,13 +271,14 @@ extern "C" int mllp_spmm_csr_f32(const mllp_graph_t* g, int transpose, const flo
 extern "C" int mllp_spmm_csr_bf16(const mllp_graph_t* g, int transpose, const void* d_H_bf16, float* d_Y, void* stream) {
     REQUIRE(g && d_H_bf16 && d_Y, "null argument");
     const Orient& o = transpose ? g->At : g->A;
-    REQUIRE(o.tiled.n_tiles > 0 || o.n_dst == 0 || g->nnz == 0,
+    const Tiled& tl = o.tiled[TILED_SPMM];
+    REQUIRE(tl.n_tiles > 0 || o.n_dst == 0 || g->nnz == 0,
             "mllp_spmm_csr_bf16 runs on the LDS-tiled copy of the orientation (mllp_graph_attach_tiled, variant 0): attach it first");
-    if (o.tiled.n_tiles == 0) {     // no nonzeros: Y = 0
+    if (tl.n_tiles == 0) {     // no nonzeros: Y = 0
         if (o.n_dst > 0) MLLP_HIP_TRY(hipMemsetAsync(d_Y, 0, (size_t)o.n_dst * 16 * sizeof(float), (hipStream_t)stream));
         return MLLP_OK;
     }
-    return launch_spmm_tiled_bf16(o.tiled, o.n_dst, o.n_src, d_H_bf16, d_Y, (hipStream_t)stream);
+    return launch_spmm_tiled_bf16(tl, o.n_dst, o.n_src, d_H_bf16, d_Y, (hipStream_t)stream);
 }
 
 extern "C" int mllp_graph_invalidate_inputs(mllp_graph_t* g) {
@@ -315,8 +316,7 @@ extern "C" int mllp_graph_attach_tiled(mllp_graph_t* g, int transpose, int varia
     REQUIRE(g, "null graph");
     REQUIRE(variant >= 0 && variant <= 4, "variant must be 0 (SpMM), 1 (attention forward), 2 / 4 (attention backward, source- / destination-major) or 3 (layer-1 sweeps)");
     Orient& o = transpose ? g->At : g->A;
-    Tiled* tls[5] = {&o.tiled, &o.tiled_attn, &o.tiled_bsrc, &o.tiled_scalar, &o.tiled_bdst};
-    Tiled& tl = *tls[variant];
+    Tiled& tl = o.tiled[variant];
     if (n_tiles == 0) {   // detach
         tiled_free(tl);
         return MLLP_OK;
@@ -335,19 +335,17 @@ extern "C" int mllp_graph_attach_tiled(mllp_graph_t* g, int transpose, int varia
     return MLLP_OK;
 }
 
-static Tiled* tiled_slot(mllp_graph_t* g, int transpose, int variant) {
-    Orient& o = transpose ? g->At : g->A;
-    Tiled* tls[5] = {&o.tiled, &o.tiled_attn, &o.tiled_bsrc, &o.tiled_scalar, &o.tiled_bdst};
-    return tls[variant];
-}
-
 extern "C" int mllp_graph_build_tiled(mllp_graph_t* g, int transpose, int variant, void* stream) {
     REQUIRE(g, "null graph");
     REQUIRE(variant >= 0 && variant <= 4, "variant must be 0 (SpMM), 1 (attention forward), 2 / 4 (attention backward, source- / destination-major) or 3 (layer-1 sweeps)");
+    Orient& o = transpose ? g->At : g->A;
     Tiled fresh;
-    int rc = build_tiled_device(transpose ? g->At : g->A, g->nnz, variant, fresh, (hipStream_t)stream);
-    if (rc) return rc;
-    Tiled& tl = *tiled_slot(g, transpose, variant);
+    const int rc = build_tiled_device(o, g->nnz, variant, fresh, (hipStream_t)stream);
+    if (rc) {
+        tiled_free(fresh);
+        return rc;
+    }
+    Tiled& tl = o.tiled[variant];
     tiled_free(tl);
     tl = fresh;
     return MLLP_OK;
@@ -356,7 +354,7 @@ extern "C" int mllp_graph_build_tiled(mllp_graph_t* g, int transpose, int varian
 extern "C" int mllp_graph_tiled_info(const mllp_graph_t* g, int transpose, int variant, int64_t* info) {
     REQUIRE(g && info, "null argument");
     REQUIRE(variant >= 0 && variant <= 4, "variant must be 0..4");
-    const Tiled& tl = *tiled_slot(const_cast<mllp_graph_t*>(g), transpose, variant);
+    const Tiled& tl = (transpose ? g->At : g->A).tiled[variant];
     info[0] = tl.n_tiles; info[1] = tl.n_tb; info[2] = tl.max_nbt; info[3] = tl.owned ? 1 : 0; info[4] = tl.max_run;
     return MLLP_OK;
 }
@@ -365,15 +363,13 @@ extern "C" int mllp_graph_export_tiled(const mllp_graph_t* g, int transpose, int
                                        int64_t count, void* stream) {
     REQUIRE(g && d_dst, "null argument");
     REQUIRE(variant >= 0 && variant <= 4, "variant must be 0..4");
-    const Tiled& tl = *tiled_slot(const_cast<mllp_graph_t*>(g), transpose, variant);
+    Tiled& tl = const_cast<Tiled&>((transpose ? g->At : g->A).tiled[variant]);
     REQUIRE(tl.n_tiles > 0, "no tiled copy of this variant is attached");
-    int R, CB, CAP;
-    tiled_geometry(variant, &R, &CB, &CAP);
-    const int* src[5] = {tl.tile_blk, tl.blk_id, tl.ptr2, tl.perm, tl.ent};
-    const int64_t n[5] = {tl.n_tiles + 1, tl.n_tb, (int64_t)tl.n_tb * R + 1, (int64_t)tl.n_tb * R, (g->nnz + 1) * 2};
-    REQUIRE(which >= 0 && which < 5, "which must be 0 (tile_blk), 1 (blk_id), 2 (ptr2), 3 (perm) or 4 (ent)");
-    REQUIRE(count == n[which], "count does not match the array's length");
-    MLLP_HIP_TRY(hipMemcpyAsync(d_dst, src[which], (size_t)count * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    const std::vector<CopyArray> arrays = tiled_arrays(tl, variant, g->nnz);
+    REQUIRE(which >= 0 && which < (int)arrays.size(), "which must be 0 (tile_blk), 1 (blk_id), 2 (ptr2), 3 (perm) or 4 (ent)");
+    const CopyArray& a = arrays[which];
+    REQUIRE(count * 4 == a.bytes, "count does not match the array's length");
+    MLLP_HIP_TRY(hipMemcpyAsync(d_dst, *a.p, (size_t)a.bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return MLLP_OK;
 }
 

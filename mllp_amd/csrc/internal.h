@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -27,6 +28,14 @@ int hip_fail(hipError_t e, const char* what);
         if (_e != hipSuccess) return ::mllp::hip_fail(_e, #expr);       \
     } while (0)
 
+// scratch device buffer of a builder, freed when it goes out of scope
+template <class T>
+struct DevBuf {
+    T* p = nullptr;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    int alloc(size_t n) { return hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T)) == hipSuccess ? 0 : 1; }
+};
+
 // One traversal orientation: destination-major CSR over the sparsity pattern of A (dst = constraint
 // rows) or of A^T (dst = variable columns).  Rows are split in three tiers by nonzero count:
 //   group tier: 16 lanes per row (4 rows per wavefront), wave tier: 64 lanes per row,
@@ -42,6 +51,13 @@ struct Tiled {
     const int* perm = nullptr;       // [n_tb * rows_per_tile] row of each sorted position
     const int* ent = nullptr;        // [nnz][2] {col_local * 64 (byte offset of the source row in the staged block), value bits}
 };
+// variants of the LDS-tiled copy (mllp_graph_attach_tiled / _build_tiled): the sweep whose geometry each one has
+constexpr int TILED_SPMM = 0;     // plain SpMM
+constexpr int TILED_ATTN = 1;     // attention forward
+constexpr int TILED_BSRC = 2;     // source-major attention backward (this orientation = its rows)
+constexpr int TILED_SCALAR = 3;   // layer-1 (one channel) attention sweeps, destination-major
+constexpr int TILED_BDST = 4;     // destination-major attention backward
+constexpr int TILED_VARIANTS = 5;
 
 // streamed copy of an orientation (stream_layout.h): library-owned device arrays, built by mllp_graph_build_spmm_copy
 struct StreamCopy {
@@ -72,17 +88,28 @@ struct LaneCopy {
     double build_seconds = 0.0;
 };
 
+// One device array of a re-blocked copy: the copy's pointer member and its byte count, computed from the copy's counts.
+// A copy kind's table lists its arrays in the order of their export index (mllp_graph_export_stream_copy /
+// mllp_graph_export_tiled `which`); allocation, upload, export, free and the copy's byte count all read it.
+struct CopyArray {
+    void** p;
+    int64_t bytes;
+};
+enum { SC_TILE_BLK, SC_BLK_ID, SC_ROWS, SC_ENT, SC_TILE_ROW, SC_HDR };                    // StreamCopy
+enum { LC_TILE_BLK, LC_TILE_COL, LC_ROWS, LC_OFFS, LC_TILE_ROW, LC_WHDR, LC_VALS };       // LaneCopy
+enum { TL_TILE_BLK, TL_BLK_ID, TL_PTR2, TL_PERM, TL_ENT };                                // Tiled
+std::vector<CopyArray> stream_copy_arrays(StreamCopy& sc, int geom);        // stream_api.cpp (geom: STREAM_GEOM_*)
+std::vector<CopyArray> lane_copy_arrays(LaneCopy& lc);                      // stream_api.cpp
+std::vector<CopyArray> tiled_arrays(Tiled& tl, int variant, int64_t nnz);   // tiled_build.hip (nnz: of the graph)
+int copy_alloc(const CopyArray& a);                        // hipMalloc of *a.p, at least 4 bytes
+void copy_free(const std::vector<CopyArray>& arrays);      // hipFree of the non-null ones
+
+// Sweep precedence: a streamed copy over the LDS-tiled copy of the same sweep over the generic kernels; for the layer-1
+// sweeps the lane copy over the TILED_SCALAR copy.
 struct Orient {
-    LaneCopy lane1;     // geometry 4: layer-1 sweeps, destination-major (lane_stream.hip); takes precedence over tiled_scalar
-    StreamCopy stream;  // plain SpMM on the streamed copy (stream_spmm.hip); takes precedence over `tiled`
-    StreamCopy stream_attn;  // geometry 1: attention forward (stream_attn.hip); takes precedence over tiled_attn
-    StreamCopy stream_bdst;  // geometry 3: destination-major attention backward; over tiled_bdst
-    StreamCopy stream_bsrc;  // geometry 2: source-major attention backward (this orientation = its rows); over tiled_bsrc
-    Tiled tiled;        // variant 0: geometry of the plain SpMM
-    Tiled tiled_attn;   // variant 1: geometry of the attention forward sweep
-    Tiled tiled_bdst;   // variant 4: geometry of the destination-major attention backward sweep
-    Tiled tiled_scalar; // variant 3: geometry of the layer-1 (one channel) attention sweeps, destination-major
-    Tiled tiled_bsrc;   // variant 2: geometry of the source-major attention backward sweep (this orientation = its rows)
+    LaneCopy lane1;                     // geometry 4: layer-1 sweeps, destination-major (lane_stream.hip)
+    StreamCopy stream[4];               // by STREAM_GEOM_* (stream_layout.h; stream_spmm.hip, stream_attn.hip)
+    Tiled tiled[TILED_VARIANTS];        // by TILED_* (tiled_kernels.hip)
     int n_dst = 0, n_src = 0;
     int* ptr = nullptr;    // [n_dst + 1]
     int* idx = nullptr;    // [nnz] source ids

@@ -27,13 +27,6 @@ namespace mllp {
 
 namespace {
 
-template <class T>
-struct LbBuf {
-    T* p = nullptr;
-    ~LbBuf() { if (p) (void)hipFree(p); }
-    int alloc(size_t n) { return hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T)) == hipSuccess ? 0 : 1; }
-};
-
 // ------------------------------------------------------------------------------------------------ builder
 // rows of the tile ordered by their number of entries (descending, ties by row id); the tile's column range
 __global__ __launch_bounds__(L1_R) void lb_tile_sort(const int* __restrict__ ptr, const int* __restrict__ idx,
@@ -302,23 +295,18 @@ LaneDev lane_dev(const LaneCopy& lc, int n_src) {
 
 }  // namespace
 
-void lane_copy_free(LaneCopy& lc) {
-    for (void* p : {(void*)lc.tile_row, (void*)lc.tile_blk, (void*)lc.tile_col, (void*)lc.rows, (void*)lc.whdr, (void*)lc.offs, (void*)lc.vals})
-        if (p) (void)hipFree(p);
-    lc = LaneCopy();
-}
-
 int build_lane_copy(const Orient& o, int64_t nnz, const std::vector<int64_t>& seg, LaneCopy& lc, hipStream_t s) {
     const std::vector<int> tile_row = lane_tiles(seg, o.n_dst);
     const int n_tiles = (int)tile_row.size() - 1;
     if (n_tiles <= 0) return MLLP_OK;
-    LbBuf<int> nblk;
+    DevBuf<int> nblk;
     if (nblk.alloc(n_tiles)) return fail(MLLP_ENOMEM, "lane copy: hipMalloc failed");
-    MLLP_HIP_TRY(hipMalloc((void**)&lc.tile_row, ((size_t)n_tiles + 1) * 4));
-    MLLP_HIP_TRY(hipMalloc((void**)&lc.tile_blk, ((size_t)n_tiles + 1) * 4));
-    MLLP_HIP_TRY(hipMalloc((void**)&lc.tile_col, (size_t)n_tiles * 8));
-    MLLP_HIP_TRY(hipMalloc((void**)&lc.rows, (size_t)n_tiles * L1_R * 4));
-    MLLP_HIP_TRY(hipMemcpyAsync(lc.tile_row, tile_row.data(), ((size_t)n_tiles + 1) * 4, hipMemcpyHostToDevice, s));
+    lc.n_tiles = n_tiles;
+    lc.nnz = nnz;
+    std::vector<CopyArray> arrays = lane_copy_arrays(lc);
+    for (int i : {LC_TILE_ROW, LC_TILE_BLK, LC_TILE_COL, LC_ROWS})
+        if (int rc = copy_alloc(arrays[i])) return rc;
+    MLLP_HIP_TRY(hipMemcpyAsync(lc.tile_row, tile_row.data(), arrays[LC_TILE_ROW].bytes, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(lb_tile_sort, dim3(n_tiles), dim3(L1_R), 0, s, o.ptr, o.idx, lc.tile_row, lc.rows, lc.tile_col, nblk.p);
     std::vector<int> h_nb(n_tiles), h_tb((size_t)n_tiles + 1, 0);
     MLLP_HIP_TRY(hipMemcpyAsync(h_nb.data(), nblk.p, (size_t)n_tiles * 4, hipMemcpyDeviceToHost, s));
@@ -330,13 +318,15 @@ int build_lane_copy(const Orient& o, int64_t nnz, const std::vector<int64_t>& se
         if (n_tb >= (1 << 26)) return fail(MLLP_ERANGE, "lane copy: too many (tile, block) pairs");
     }
     h_tb[n_tiles] = (int)n_tb;
-    MLLP_HIP_TRY(hipMemcpyAsync(lc.tile_blk, h_tb.data(), ((size_t)n_tiles + 1) * 4, hipMemcpyHostToDevice, s));
+    MLLP_HIP_TRY(hipMemcpyAsync(lc.tile_blk, h_tb.data(), arrays[LC_TILE_BLK].bytes, hipMemcpyHostToDevice, s));
+    lc.n_tb = (int)n_tb;
     const size_t n_h = (size_t)n_tb * L1_NW;
-    MLLP_HIP_TRY(hipMalloc((void**)&lc.whdr, std::max<size_t>(n_h, 1) * 8));
+    const CopyArray whdr = lane_copy_arrays(lc)[LC_WHDR];
+    if (int rc = copy_alloc(whdr)) return rc;
     hipLaunchKernelGGL(lb_walk<false>, dim3(n_tiles), dim3(L1_R), 0, s, o.ptr, o.idx, o.val, lc.tile_row, lc.tile_blk, lc.tile_col,
                        lc.rows, lc.whdr, (uint2*)nullptr, (float4*)nullptr);
     std::vector<int> h_h(std::max<size_t>(n_h, 1) * 2, 0);
-    if (n_h) MLLP_HIP_TRY(hipMemcpyAsync(h_h.data(), lc.whdr, n_h * 8, hipMemcpyDeviceToHost, s));
+    if (n_h) MLLP_HIP_TRY(hipMemcpyAsync(h_h.data(), lc.whdr, whdr.bytes, hipMemcpyDeviceToHost, s));
     MLLP_HIP_TRY(hipStreamSynchronize(s));
     int64_t n_groups = 0;
     for (size_t i = 0; i < n_h; ++i) {
@@ -344,19 +334,17 @@ int build_lane_copy(const Orient& o, int64_t nnz, const std::vector<int64_t>& se
         n_groups += h_h[2 * i + 1];
         if (n_groups >= (1ll << 31) / 64) return fail(MLLP_ERANGE, "lane copy: the stream exceeds int32 indexing");
     }
-    if (n_h) MLLP_HIP_TRY(hipMemcpyAsync(lc.whdr, h_h.data(), n_h * 8, hipMemcpyHostToDevice, s));
-    MLLP_HIP_TRY(hipMalloc((void**)&lc.offs, (size_t)(n_groups + L1_PADG) * 64 * 8));
-    MLLP_HIP_TRY(hipMalloc((void**)&lc.vals, (size_t)(n_groups + L1_PADG) * 64 * 16));
+    if (n_h) MLLP_HIP_TRY(hipMemcpyAsync(lc.whdr, h_h.data(), whdr.bytes, hipMemcpyHostToDevice, s));
+    lc.n_groups = n_groups;
+    arrays = lane_copy_arrays(lc);
+    for (int i : {LC_OFFS, LC_VALS})
+        if (int rc = copy_alloc(arrays[i])) return rc;
     hipLaunchKernelGGL(lb_walk<true>, dim3(n_tiles), dim3(L1_R), 0, s, o.ptr, o.idx, o.val, lc.tile_row, lc.tile_blk, lc.tile_col,
                        lc.rows, lc.whdr, reinterpret_cast<uint2*>(lc.offs), reinterpret_cast<float4*>(lc.vals));
     hipLaunchKernelGGL(lb_pad, dim3(L1_PADG), dim3(64), 0, s, reinterpret_cast<uint2*>(lc.offs), reinterpret_cast<float4*>(lc.vals),
                        (long long)n_groups);
     MLLP_HIP_TRY(hipGetLastError());
     MLLP_HIP_TRY(hipStreamSynchronize(s));
-    lc.n_tiles = n_tiles;
-    lc.n_tb = (int)n_tb;
-    lc.n_groups = n_groups;
-    lc.nnz = nnz;
     return MLLP_OK;
 }
 

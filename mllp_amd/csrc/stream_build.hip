@@ -22,8 +22,6 @@
 
 namespace mllp {
 
-void stream_copy_free(StreamCopy& sc);
-
 namespace {
 
 
@@ -299,22 +297,18 @@ __global__ __launch_bounds__(SbFill<G>::T) void sb_fill(const int* __restrict__ 
     }
 }
 
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int alloc(size_t n) { return hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T)) == hipSuccess ? 0 : 1; }
-};
-
 }  // namespace
 
 template <class G>
-static int build_stream_device_t(const Orient& o, int64_t nnz, const std::vector<int>& tile_row, StreamCopy& sc, hipStream_t s) {
-    constexpr int SB_T = G::R, S_R = G::R, S_NW = G::NW, S_GS = G::GS, S_K0 = G::K0, S_ENT = G::ENT;
+static int build_stream_device_t(const Orient& o, int64_t nnz, const std::vector<int>& tile_row, StreamCopy& sc, hipStream_t s,
+                                 int geom) {
+    constexpr int SB_T = G::R, S_R = G::R, S_NW = G::NW, S_GS = G::GS, S_K0 = G::K0;
     (void)nnz;
     const int n_tiles = (int)tile_row.size() - 1;
-    MLLP_HIP_TRY(hipMalloc((void**)&sc.tile_row, ((size_t)n_tiles + 1) * 4));
-    MLLP_HIP_TRY(hipMemcpyAsync(sc.tile_row, tile_row.data(), ((size_t)n_tiles + 1) * 4, hipMemcpyHostToDevice, s));
+    sc.n_tiles = n_tiles;
+    const CopyArray a_tile_row = stream_copy_arrays(sc, geom)[SC_TILE_ROW];
+    if (int rc = copy_alloc(a_tile_row)) return rc;
+    MLLP_HIP_TRY(hipMemcpyAsync(sc.tile_row, tile_row.data(), a_tile_row.bytes, hipMemcpyHostToDevice, s));
     DevBuf<int> lo, hi, bm_off, nb, bm_pref, cnt, start, order, npass, groups, base, sstart;
     DevBuf<unsigned> bm;
     if (lo.alloc(n_tiles) || hi.alloc(n_tiles) || bm_off.alloc(n_tiles) || nb.alloc(n_tiles))
@@ -353,13 +347,11 @@ static int build_stream_device_t(const Orient& o, int64_t nnz, const std::vector
         if (n_tb >= (1 << 24)) return fail(MLLP_ERANGE, "streamed copy: too many (tile, block) pairs");
     }
     h_tile_blk[n_tiles] = (int)n_tb;
-    sc.n_tiles = n_tiles;
     sc.n_tb = (int)n_tb;
-    MLLP_HIP_TRY(hipMalloc((void**)&sc.tile_blk, ((size_t)n_tiles + 1) * 4));
-    MLLP_HIP_TRY(hipMalloc((void**)&sc.blk_id, std::max<size_t>(n_tb, 1) * 4));
-    MLLP_HIP_TRY(hipMalloc((void**)&sc.rows, std::max<size_t>(n_tb, 1) * S_NW * 256));
-    MLLP_HIP_TRY(hipMalloc((void**)&sc.hdr, std::max<size_t>(n_tb, 1) * S_NW * 16));
-    MLLP_HIP_TRY(hipMemcpyAsync(sc.tile_blk, h_tile_blk.data(), ((size_t)n_tiles + 1) * 4, hipMemcpyHostToDevice, s));
+    const std::vector<CopyArray> arrays = stream_copy_arrays(sc, geom);
+    for (int i : {SC_TILE_BLK, SC_BLK_ID, SC_ROWS, SC_HDR})
+        if (int rc = copy_alloc(arrays[i])) return rc;
+    MLLP_HIP_TRY(hipMemcpyAsync(sc.tile_blk, h_tile_blk.data(), arrays[SC_TILE_BLK].bytes, hipMemcpyHostToDevice, s));
     const size_t n_slots = (size_t)n_tb * S_R;
     if (cnt.alloc(n_slots) || start.alloc(n_slots) || order.alloc(n_slots) || npass.alloc((size_t)n_tb * S_NW * 2) ||
         sstart.alloc((size_t)n_tb * S_NW) || groups.alloc((size_t)n_tiles * S_NW) || base.alloc((size_t)n_tiles * S_NW))
@@ -387,7 +379,7 @@ static int build_stream_device_t(const Orient& o, int64_t nnz, const std::vector
     hipLaunchKernelGGL(sb_step_starts<G>, dim3((nw + 255) / 256), dim3(256), 0, s, sc.tile_blk, npass.p, n_tiles, base.p,
                        sstart.p);
     const long long n_ent = (long long)(n_groups + S_K0) * 64;
-    MLLP_HIP_TRY(hipMalloc((void**)&sc.ent, (size_t)n_ent * S_ENT * 4));
+    if (int rc = copy_alloc(stream_copy_arrays(sc, geom)[SC_ENT])) return rc;
     hipLaunchKernelGGL(sb_fill_padding<G>, dim3(4096), dim3(256), 0, s, sc.ent, n_ent);
     if (n_tb > 0)
         hipLaunchKernelGGL(sb_fill<G>, dim3((unsigned)n_tb), dim3(SbFill<G>::T), 0, s, o.idx, o.val, sc.blk_id, cnt.p, start.p,
@@ -401,10 +393,10 @@ static int build_stream_device_t(const Orient& o, int64_t nnz, const std::vector
 
 int build_stream_device(const Orient& o, int64_t nnz, const std::vector<int>& tile_row, StreamCopy& sc, hipStream_t s, int geom) {
     switch (geom) {
-        case STREAM_GEOM_SPMM: return build_stream_device_t<SpmmGeom>(o, nnz, tile_row, sc, s);
-        case STREAM_GEOM_ATTN: return build_stream_device_t<AttnGeom>(o, nnz, tile_row, sc, s);
-        case STREAM_GEOM_BSRC: return build_stream_device_t<BsrcGeom>(o, nnz, tile_row, sc, s);
-        case STREAM_GEOM_BDST: return build_stream_device_t<BdstGeom>(o, nnz, tile_row, sc, s);
+        case STREAM_GEOM_SPMM: return build_stream_device_t<SpmmGeom>(o, nnz, tile_row, sc, s, geom);
+        case STREAM_GEOM_ATTN: return build_stream_device_t<AttnGeom>(o, nnz, tile_row, sc, s, geom);
+        case STREAM_GEOM_BSRC: return build_stream_device_t<BsrcGeom>(o, nnz, tile_row, sc, s, geom);
+        case STREAM_GEOM_BDST: return build_stream_device_t<BdstGeom>(o, nnz, tile_row, sc, s, geom);
         default: return fail(MLLP_EINVAL, "streamed copy: unknown geometry");
     }
 }

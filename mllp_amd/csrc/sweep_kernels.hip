@@ -26,6 +26,7 @@
 // rows gathered by neighbouring tiles then come out of one XCD's L2.
 #include "device_utils.h"
 #include "internal.h"
+#include "stream_layout.h"
 
 namespace mllp {
 
@@ -691,8 +692,10 @@ static int launch_sweep(const Orient& o, const typename Op::Args& args, float* s
 }
 
 int launch_spmm(const Orient& o, const float* H, float* Y, float* scratch, hipStream_t s) {
-    if (o.stream.n_tiles > 0) return launch_spmm_stream(o.stream, o.n_dst, o.n_src, H, Y, s);
-    if (o.tiled.n_tiles > 0) return launch_spmm_tiled(o.tiled, o.n_dst, o.n_src, H, Y, s);
+    const StreamCopy& sc = o.stream[STREAM_GEOM_SPMM];
+    const Tiled& tl = o.tiled[TILED_SPMM];
+    if (sc.n_tiles > 0) return launch_spmm_stream(sc, o.n_dst, o.n_src, H, Y, s);
+    if (tl.n_tiles > 0) return launch_spmm_tiled(tl, o.n_dst, o.n_src, H, Y, s);
     SpmmOp::Args a{H, Y};
     return launch_sweep<SpmmOp, 4, 4>(o, a, scratch, s, "spmm_csr");
 }
@@ -703,14 +706,13 @@ int launch_attn_fwd(const Orient& o, int cin, const float* conv_params, const Co
     a.X = x_src; a.xd = x_dst; a.qp = w.qp; a.t = w.t; a.derived = w.derived;
     a.p = conv_params_at(conv_params, cin);
     a.h = h_out; a.Z = w.Z; a.aux = w.aux;
-    if (cin == 16 && o.stream_attn.n_tiles > 0)
-        return launch_fwd16_stream(o.stream_attn, o.n_dst, o.n_src, conv_params, w, x_src, x_dst, h_out, s);
-    if (cin == 16 && o.tiled_attn.n_tiles > 0)
-        return launch_fwd16_tiled(o.tiled_attn, o.n_dst, o.n_src, conv_params, w, x_src, x_dst, h_out, s);
+    const StreamCopy& sc = o.stream[STREAM_GEOM_ATTN];
+    const Tiled &tl = o.tiled[TILED_ATTN], &tl1 = o.tiled[TILED_SCALAR];
+    if (cin == 16 && sc.n_tiles > 0) return launch_fwd16_stream(sc, o.n_dst, o.n_src, conv_params, w, x_src, x_dst, h_out, s);
+    if (cin == 16 && tl.n_tiles > 0) return launch_fwd16_tiled(tl, o.n_dst, o.n_src, conv_params, w, x_src, x_dst, h_out, s);
     if (cin == 16) return launch_sweep<Fwd16Op, 4, 4>(o, a, scratch, s, "attn_fwd16");
     if (o.lane1.n_tiles > 0) return launch_fwd1_lane(o.lane1, o.n_dst, o.n_src, conv_params, w, x_src, x_dst, h_out, s);
-    if (o.tiled_scalar.n_tiles > 0)
-        return launch_fwd1_tiled(o.tiled_scalar, o.n_dst, o.n_src, conv_params, w, x_src, x_dst, h_out, s);
+    if (tl1.n_tiles > 0) return launch_fwd1_tiled(tl1, o.n_dst, o.n_src, conv_params, w, x_src, x_dst, h_out, s);
     return launch_sweep<Fwd1Op, 2, 2>(o, a, scratch, s, "attn_fwd1");
 }
 
@@ -720,25 +722,24 @@ int launch_attn_bwd_dst(const Orient& o, int cin, const float* conv_params, cons
     BwdDstArgs a;
     a.X = x_src; a.rec = w.rec; a.g = g; a.derived = w.derived;
     a.dqp = w.dqp; a.dsdt = w.dsdt; a.dx_dst = dx_dst; a.accumulate = accumulate;
-    if (cin == 16 && o.stream_bdst.n_tiles > 0)
-        return launch_bwddst16_stream(o.stream_bdst, o.n_dst, o.n_src, w, x_src, g, dx_dst, accumulate, s);
-    if (cin == 16 && o.tiled_bdst.n_tiles > 0)
-        return launch_bwddst16_tiled(o.tiled_bdst, o.n_dst, o.n_src, w, x_src, g, dx_dst, accumulate, s);
+    const StreamCopy& sc = o.stream[STREAM_GEOM_BDST];
+    const Tiled &tl = o.tiled[TILED_BDST], &tl1 = o.tiled[TILED_SCALAR];
+    if (cin == 16 && sc.n_tiles > 0) return launch_bwddst16_stream(sc, o.n_dst, o.n_src, w, x_src, g, dx_dst, accumulate, s);
+    if (cin == 16 && tl.n_tiles > 0) return launch_bwddst16_tiled(tl, o.n_dst, o.n_src, w, x_src, g, dx_dst, accumulate, s);
     if (cin == 16) return launch_sweep<BwdDst16Op, 4, 4>(o, a, scratch, s, "attn_bwd_dst16");
     a.dx_dst = nullptr;
     if (o.lane1.n_tiles > 0) return launch_bwddst1_lane(o.lane1, o.n_dst, o.n_src, w, x_src, s);
-    if (o.tiled_scalar.n_tiles > 0) return launch_bwddst1_tiled(o.tiled_scalar, o.n_dst, o.n_src, w, x_src, s);
+    if (tl1.n_tiles > 0) return launch_bwddst1_tiled(tl1, o.n_dst, o.n_src, w, x_src, s);
     return launch_sweep<BwdDst1Op, 2, 2>(o, a, scratch, s, "attn_bwd_dst1");
 }
 
 int launch_attn_bwd_src(const Orient& o_src_major, const ConvWs& w, const float* x_src, float* dx_src, int accumulate,
                         float* scratch, hipStream_t s) {
-    if (o_src_major.stream_bsrc.n_tiles > 0)
-        return launch_bwdsrc16_stream(o_src_major.stream_bsrc, o_src_major.n_dst, o_src_major.n_src, w.rec, x_src, dx_src,
-                                      accumulate, s);
-    if (o_src_major.tiled_bsrc.n_tiles > 0)
-        return launch_bwdsrc16_tiled(o_src_major.tiled_bsrc, o_src_major.n_dst, o_src_major.n_src, w.rec, x_src, dx_src,
-                                     accumulate, s);
+    const StreamCopy& sc = o_src_major.stream[STREAM_GEOM_BSRC];
+    const Tiled& tl = o_src_major.tiled[TILED_BSRC];
+    const int n_rows = o_src_major.n_dst, n_cols = o_src_major.n_src;
+    if (sc.n_tiles > 0) return launch_bwdsrc16_stream(sc, n_rows, n_cols, w.rec, x_src, dx_src, accumulate, s);
+    if (tl.n_tiles > 0) return launch_bwdsrc16_tiled(tl, n_rows, n_cols, w.rec, x_src, dx_src, accumulate, s);
     BwdSrcArgs a{x_src, w.rec, dx_src, accumulate};
     return launch_sweep<BwdSrc16Op, 2, 2>(o_src_major, a, scratch, s, "attn_bwd_src16");
 }

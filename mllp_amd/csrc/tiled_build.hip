@@ -22,14 +22,20 @@
 
 namespace mllp {
 
+std::vector<CopyArray> tiled_arrays(Tiled& tl, int variant, int64_t nnz) {
+    int R, CB, CAP;
+    tiled_geometry(variant, &R, &CB, &CAP);
+    const int64_t n_slots = (int64_t)tl.n_tb * R;
+    return {{(void**)&tl.tile_blk, ((int64_t)tl.n_tiles + 1) * 4},
+            {(void**)&tl.blk_id, (int64_t)tl.n_tb * 4},
+            {(void**)&tl.ptr2, (n_slots + 1) * 4},
+            {(void**)&tl.perm, n_slots * 4},
+            {(void**)&tl.ent, (nnz + 1) * 8}};
+}
+
+// (a copy attached from borrowed arrays is not freed; the pointer members do not depend on the variant)
 void tiled_free(Tiled& tl) {
-    if (tl.owned) {
-        (void)hipFree((void*)tl.tile_blk);
-        (void)hipFree((void*)tl.blk_id);
-        (void)hipFree((void*)tl.ptr2);
-        (void)hipFree((void*)tl.perm);
-        (void)hipFree((void*)tl.ent);
-    }
+    if (tl.owned) copy_free(tiled_arrays(tl, TILED_SPMM, 0));
     tl = Tiled();
 }
 
@@ -259,19 +265,12 @@ __global__ void tb_fill(const int* __restrict__ idx, const float* __restrict__ v
     }
 }
 
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int alloc(size_t n) { return hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T)) == hipSuccess ? 0 : 1; }
-};
-
 }  // namespace
 
 int build_tiled_device(const Orient& o, int64_t nnz, int variant, Tiled& out, hipStream_t s) {
     int R, CB, CAP;
     tiled_geometry(variant, &R, &CB, &CAP);
-    const int item_bytes = variant == 2 ? 160 : variant == 3 ? 4 : 64;
+    const int item_bytes = variant == TILED_BSRC ? 160 : variant == TILED_SCALAR ? 4 : 64;
     const int n_tiles = (int)(((int64_t)o.n_dst + R - 1) / R);
     if (nnz == 0 || n_tiles == 0) return fail(MLLP_EINVAL, "tiled copy: the matrix has no nonzeros");
     DevBuf<int> lo, hi, cnt, start, off, seg, seg_start, longest;
@@ -298,40 +297,36 @@ int build_tiled_device(const Orient& o, int64_t nnz, int variant, Tiled& out, hi
     std::vector<int> h_blk((size_t)n_tb);
     for (int t = 0; t < n_tiles; ++t)
         for (int b = h_tile_blk[t]; b < h_tile_blk[t + 1]; ++b) h_blk[b] = h_lo[t] + (b - h_tile_blk[t]);
-    Tiled tl;
-    tl.owned = true;
-    tl.n_tiles = n_tiles;
-    tl.n_tb = (int)n_tb;
-    int *d_tile_blk = nullptr, *d_blk = nullptr, *d_ptr2 = nullptr, *d_perm = nullptr, *d_ent = nullptr;
+    // the copy's arrays are allocated in `out` (owned): the caller frees them on any error
+    out.owned = true;
+    out.n_tiles = n_tiles;
+    out.n_tb = (int)n_tb;
+    const std::vector<CopyArray> arrays = tiled_arrays(out, variant, nnz);
+    for (const CopyArray& a : arrays)
+        if (int rc = copy_alloc(a)) return rc;
+    int *d_tile_blk = (int*)out.tile_blk, *d_blk = (int*)out.blk_id, *d_ptr2 = (int*)out.ptr2, *d_perm = (int*)out.perm,
+        *d_ent = (int*)out.ent;
     const size_t n_slots = (size_t)n_tb * R;
-    auto cleanup = [&]() {
-        (void)hipFree(d_tile_blk); (void)hipFree(d_blk); (void)hipFree(d_ptr2); (void)hipFree(d_perm); (void)hipFree(d_ent);
-    };
-    if (hipMalloc((void**)&d_tile_blk, ((size_t)n_tiles + 1) * 4) != hipSuccess || hipMalloc((void**)&d_blk, std::max<size_t>(n_tb, 1) * 4) != hipSuccess ||
-        hipMalloc((void**)&d_ptr2, (n_slots + 1) * 4) != hipSuccess || hipMalloc((void**)&d_perm, std::max<size_t>(n_slots, 1) * 4) != hipSuccess ||
-        hipMalloc((void**)&d_ent, ((size_t)nnz + 1) * 8) != hipSuccess || cnt.alloc(n_slots) || start.alloc(n_slots) || off.alloc(n_slots) ||
-        seg.alloc((size_t)n_tb) || seg_start.alloc((size_t)n_tb) || longest.alloc(1)) {
-        cleanup();
+    if (cnt.alloc(n_slots) || start.alloc(n_slots) || off.alloc(n_slots) || seg.alloc((size_t)n_tb) || seg_start.alloc((size_t)n_tb) ||
+        longest.alloc(1))
         return fail(MLLP_ENOMEM, "tiled copy: hipMalloc failed");
-    }
-    auto bail = [&](hipError_t e, const char* what) { cleanup(); return hip_fail(e, what); };
     hipError_t e;
-    if ((e = hipMemcpyAsync(d_tile_blk, h_tile_blk.data(), ((size_t)n_tiles + 1) * 4, hipMemcpyHostToDevice, s)) != hipSuccess ||
-        (e = hipMemcpyAsync(d_blk, h_blk.data(), (size_t)n_tb * 4, hipMemcpyHostToDevice, s)) != hipSuccess ||
+    if ((e = hipMemcpyAsync(d_tile_blk, h_tile_blk.data(), arrays[TL_TILE_BLK].bytes, hipMemcpyHostToDevice, s)) != hipSuccess ||
+        (e = hipMemcpyAsync(d_blk, h_blk.data(), arrays[TL_BLK_ID].bytes, hipMemcpyHostToDevice, s)) != hipSuccess ||
         (e = hipMemcpyAsync(lo.p, h_lo.data(), (size_t)n_tiles * 4, hipMemcpyHostToDevice, s)) != hipSuccess ||
         (e = hipMemsetAsync(cnt.p, 0, std::max<size_t>(n_slots, 1) * 4, s)) != hipSuccess ||
         (e = hipMemsetAsync(start.p, 0, std::max<size_t>(n_slots, 1) * 4, s)) != hipSuccess ||
         (e = hipMemsetAsync(d_ent + (size_t)nnz * 2, 0, 8, s)) != hipSuccess || (e = hipMemsetAsync(longest.p, 0, 4, s)) != hipSuccess)
-        return bail(e, "tiled copy: copy / memset");
+        return hip_fail(e, "tiled copy: copy / memset");
     hipLaunchKernelGGL(tb_count, dim3(n_tiles), dim3(T), 0, s, o.ptr, o.idx, o.n_dst, R, CB, lo.p, d_tile_blk, cnt.p, start.p);
-    hipLaunchKernelGGL(tb_sort, dim3((unsigned)n_tb), dim3(R), (size_t)2 * R * 4, s, cnt.p, R, variant == 4 ? 1 : 0, d_perm,
+    hipLaunchKernelGGL(tb_sort, dim3((unsigned)n_tb), dim3(R), (size_t)2 * R * 4, s, cnt.p, R, variant == TILED_BDST ? 1 : 0, d_perm,
                        off.p, seg.p, longest.p);
     std::vector<int> h_seg((size_t)n_tb), h_seg_start((size_t)n_tb);
     int h_longest = 0;
     if ((e = hipMemcpyAsync(h_seg.data(), seg.p, (size_t)n_tb * 4, hipMemcpyDeviceToHost, s)) != hipSuccess ||
         (e = hipMemcpyAsync(&h_longest, longest.p, 4, hipMemcpyDeviceToHost, s)) != hipSuccess ||
         (e = hipStreamSynchronize(s)) != hipSuccess)
-        return bail(e, "tiled copy: segment lengths");
+        return hip_fail(e, "tiled copy: segment lengths");
     int64_t run = 0;
     int max_run = 0;
     for (int64_t b = 0; b < n_tb; ++b) {
@@ -339,22 +334,17 @@ int build_tiled_device(const Orient& o, int64_t nnz, int variant, Tiled& out, hi
         run += h_seg[b];
         max_run = std::max(max_run, h_seg[b]);
     }
-    if (run != nnz) {
-        cleanup();
-        return fail(MLLP_EINVAL, "tiled copy: the segments do not add up to nnz (column ids not ascending inside a row?)");
-    }
+    if (run != nnz) return fail(MLLP_EINVAL, "tiled copy: the segments do not add up to nnz (column ids not ascending inside a row?)");
     if ((e = hipMemcpyAsync(seg_start.p, h_seg_start.data(), (size_t)n_tb * 4, hipMemcpyHostToDevice, s)) != hipSuccess)
-        return bail(e, "tiled copy: segment starts");
+        return hip_fail(e, "tiled copy: segment starts");
     const long long n_p = (long long)n_slots;
     hipLaunchKernelGGL(tb_ptr2, dim3((unsigned)((n_p + 256) / 256)), dim3(256), 0, s, off.p, seg_start.p, R, n_p, (int)nnz, d_ptr2);
+    const bool joint = (variant == TILED_SPMM || variant == TILED_ATTN || variant == TILED_BDST) && h_longest <= 512;
     hipLaunchKernelGGL(tb_fill, dim3((unsigned)n_tb), dim3(R), (size_t)R * 4, s, o.idx, o.val, d_blk, cnt.p, start.p, d_perm,
-                       d_ptr2, R, CB, item_bytes, ((variant == 0 || variant == 1 || variant == 4) && h_longest <= 512) ? 1 : 0, variant == 4 ? 1 : 0,
-                       reinterpret_cast<int2*>(d_ent));
-    if ((e = hipGetLastError()) != hipSuccess || (e = hipStreamSynchronize(s)) != hipSuccess) return bail(e, "tiled copy: kernels");
-    tl.tile_blk = d_tile_blk; tl.blk_id = d_blk; tl.ptr2 = d_ptr2; tl.perm = d_perm; tl.ent = d_ent;
-    tl.max_nbt = max_nbt;
-    tl.max_run = max_run;
-    out = tl;
+                       d_ptr2, R, CB, item_bytes, joint ? 1 : 0, variant == TILED_BDST ? 1 : 0, reinterpret_cast<int2*>(d_ent));
+    if ((e = hipGetLastError()) != hipSuccess || (e = hipStreamSynchronize(s)) != hipSuccess) return hip_fail(e, "tiled copy: kernels");
+    out.max_nbt = max_nbt;
+    out.max_run = max_run;
     return MLLP_OK;
 }
 

@@ -193,6 +193,10 @@ class LPBatch:
         self.names = list(names) if names is not None else [f"inst{i}" for i in range(n_inst)]
         self._ws = None
         self._n_off = np.concatenate([[0], np.cumsum(self.inst_n)]).astype(np.int64)
+        self._tiled = {}              # {(transpose, variant): arrays the library borrows, or None when it owns them}
+        self._streams = None          # the streamed copies of the training step (LPTrainer._plan: enable_stream_step)
+        self.tiled_build_s = 0.0      # seconds spent building LDS-tiled copies
+        self.stream_build_s = 0.0     # ... streamed copies
         if LPBatch.default_path:
             self.set_path(LPBatch.default_path)
 
@@ -248,7 +252,6 @@ class LPBatch:
         built by the library (`mllp_csr_transpose_device`: counting, scatter, per-column ordering) -- or, with
         transpose="torch", by one stable device sort (the reference the tests compare with)."""
         L = _lib.lib()
-        import time
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         M, N, nnz = int(sum(inst_m)), int(sum(inst_n)), int(csr_idx.numel())
@@ -298,10 +301,7 @@ class LPBatch:
         builder="torch" (or explicit `arrays`): the torch reference builder `build_tiled_arrays`, whose arrays the
         library borrows.  `self.tiled_build_s` accumulates the seconds spent building."""
         L = _lib.lib()
-        R, CB, CAP = c_int32(), c_int32(), c_int32()
-        _lib.check(L.mllp_tiled_geometry(int(variant), ctypes.byref(R), ctypes.byref(CB), ctypes.byref(CAP)))
-        R, CB, CAP = R.value, CB.value, CAP.value
-        import time
+        R, CB = self._tiled_geometry(variant)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         if arrays is None and builder == "device":
@@ -309,12 +309,10 @@ class LPBatch:
                 return None                      # (nothing to re-block: the generic sweeps handle the empty matrix)
             rc = L.mllp_graph_build_tiled(self._h, int(transpose), int(variant), _lib.current_stream())
             torch.cuda.synchronize()
-            self.tiled_build_s = getattr(self, "tiled_build_s", 0.0) + time.perf_counter() - t0
+            self.tiled_build_s += time.perf_counter() - t0
             if rc == _lib.MLLP_ERANGE:
                 return None
             _lib.check(rc)
-            if not hasattr(self, "_tiled"):
-                self._tiled = {}
             self._tiled[(bool(transpose), int(variant))] = None      # library-owned: nothing to keep alive here
             d = (c_int64 * 5)()
             _lib.check(L.mllp_graph_tiled_info(self._h, int(transpose), int(variant), d))
@@ -325,7 +323,7 @@ class LPBatch:
         n_dst = self.N if transpose else self.M
         built = build_tiled_arrays(ptr, idx, val, n_dst, R, CB, variant)
         torch.cuda.synchronize()
-        self.tiled_build_s = getattr(self, "tiled_build_s", 0.0) + time.perf_counter() - t0
+        self.tiled_build_s += time.perf_counter() - t0
         if built is None:
             return None
         keep, info = built
@@ -335,21 +333,25 @@ class LPBatch:
                                              _lib.ptr(keep["tile_blk"]),
                                              _lib.ptr(keep["blk_id"]), _lib.ptr(keep["ptr2"]), _lib.ptr(keep["perm"]),
                                              _lib.ptr(keep["ent"])))
-        if not hasattr(self, "_tiled"):
-            self._tiled = {}
         self._tiled[(bool(transpose), int(variant))] = keep          # the library borrows these arrays
         info["builder"] = "torch"
         return info
 
+    @staticmethod
+    def _tiled_geometry(variant):
+        """(rows per tile, columns per block) of an LDS-tiled variant (mllp_tiled_geometry)."""
+        R, CB, CAP = c_int32(), c_int32(), c_int32()
+        _lib.check(_lib.lib().mllp_tiled_geometry(int(variant), ctypes.byref(R), ctypes.byref(CB), ctypes.byref(CAP)))
+        return R.value, CB.value
+
     def export_tiled(self, transpose=False, variant=0):
         """The attached tiled copy as torch int32 device tensors (tile_blk, blk_id, ptr2, perm, ent [nnz + 1, 2]) (tests)."""
         L = _lib.lib()
-        R, CB, CAP = c_int32(), c_int32(), c_int32()
-        _lib.check(L.mllp_tiled_geometry(int(variant), ctypes.byref(R), ctypes.byref(CB), ctypes.byref(CAP)))
+        R = self._tiled_geometry(variant)[0]
         d = (c_int64 * 5)()
         _lib.check(L.mllp_graph_tiled_info(self._h, int(transpose), int(variant), d))
         n_tiles, n_tb = int(d[0]), int(d[1])
-        sizes = [n_tiles + 1, n_tb, n_tb * R.value + 1, n_tb * R.value, (self.nnz + 1) * 2]
+        sizes = [n_tiles + 1, n_tb, n_tb * R + 1, n_tb * R, (self.nnz + 1) * 2]
         out = []
         for which, n in enumerate(sizes):
             t = torch.empty(n, dtype=torch.int32, device=self.x1.device)
@@ -361,40 +363,26 @@ class LPBatch:
         return dict(zip(["tile_blk", "blk_id", "ptr2", "perm", "ent"], out))
 
     # ---- streamed SpMM copy (library-owned; stream_layout.h) -----------------------------------------
+    # (geometry 0 of the streamed copies below)
     def build_spmm_copy(self, transpose=False, where="device"):
         """Build the streamed copy of A (or A^T) that `spmm` then runs on: `where` = "device" (HIP builder) or
         "host" (reference builder, same bytes).  Returns the info dict of `spmm_copy_info`."""
-        _lib.check(_lib.lib().mllp_graph_build_spmm_copy(self._h, int(transpose), {"device": 0, "host": 1}[where],
-                                                         _lib.current_stream()))
+        self.build_stream_copy(transpose, self.GEOM_SPMM, where)
         return self.spmm_copy_info(transpose)
 
     def drop_spmm_copy(self, transpose=False):
-        _lib.check(_lib.lib().mllp_graph_drop_spmm_copy(self._h, int(transpose)))
+        self.drop_stream_copy(transpose, self.GEOM_SPMM)
 
     def spmm_copy_info(self, transpose=False):
-        d = (c_int64 * 8)()
-        _lib.check(_lib.lib().mllp_graph_spmm_copy_info(self._h, int(transpose), d))
-        keys = ["n_tiles", "n_tb", "n_groups", "entry_slots", "bytes", "build_us", "rows_per_tile", "cols_per_block"]
-        out = dict(zip(keys, [int(v) for v in d]))
-        out["wavefronts"] = out["cols_per_block"] >> 16          # packed: wavefronts << 16 | columns per block
-        out["cols_per_block"] &= 0xffff
-        return out
+        i = self.stream_copy_info(transpose, self.GEOM_SPMM)
+        keys = ["n_tiles", "n_tb", "n_groups", "entry_slots", "bytes", "build_us"]
+        return dict({k: i[k] for k in keys}, rows_per_tile=i["row_slots"], cols_per_block=i["cols_per_block"],
+                    wavefronts=i["wavefronts"])
 
     def export_spmm_copy(self, transpose=False):
         """(tile_blk, blk_id, rows [n_tb, 8, 16, 4], ent [groups + padding, 64, 3], tile_row, hdr [n_tb, 8, 4]) as
         numpy int32 arrays (tests)."""
-        i = self.spmm_copy_info(transpose)
-        nw = i["wavefronts"]
-        n_ent_groups = (i["bytes"] - (i["n_tiles"] + 1) * 8 - i["n_tb"] * 4 - i["n_tb"] * nw * 272) // 768
-        shapes = [(i["n_tiles"] + 1,), (i["n_tb"],), (i["n_tb"], nw, 16, 4), (n_ent_groups, 64, 3),
-                  (i["n_tiles"] + 1,), (i["n_tb"], nw, 4)]
-        out = []
-        for which, shp in enumerate(shapes):
-            a = np.empty(shp, dtype=np.int32)
-            _lib.check(_lib.lib().mllp_graph_export_spmm_copy(self._h, int(transpose), which,
-                                                              a.ctypes.data_as(c_void_p), a.nbytes))
-            out.append(a)
-        return tuple(out)
+        return self.export_stream_copy(transpose, self.GEOM_SPMM)
 
     # ---- streamed copies of the attention sweeps (round 4; stream_attn.hip) ----------------------------
     GEOM_SPMM, GEOM_ATTN, GEOM_BSRC, GEOM_BDST = 0, 1, 2, 3
@@ -406,7 +394,7 @@ class LPBatch:
         t0 = time.perf_counter()
         _lib.check(_lib.lib().mllp_graph_build_stream_copy(self._h, int(transpose), int(geom),
                                                            {"device": 0, "host": 1}[where], _lib.current_stream()))
-        self.stream_build_s = getattr(self, "stream_build_s", 0.0) + time.perf_counter() - t0
+        self.stream_build_s += time.perf_counter() - t0
         return self.stream_copy_info(transpose, geom)
 
     def drop_stream_copy(self, transpose=False, geom=1):
@@ -422,29 +410,21 @@ class LPBatch:
         return out
 
     def export_stream_copy(self, transpose=False, geom=1):
-        """(tile_blk, blk_id, rows [n_tb, nw, 16, 4], ent [groups + padding, 64, 3], tile_row, hdr [n_tb, nw, 4]) as numpy
-        int32 arrays (tests)."""
+        """The copy's arrays as numpy arrays (tests), geometries 0-3 (stream_layout.h, int32): (tile_blk, blk_id,
+        rows [n_tb, nw, 16, 4], ent [groups + padding, 64, 3], tile_row, hdr [n_tb, nw, 4]); geometry 4 (lane_layout.h):
+        (tile_blk, tile_col [n_tiles, 2], rows [n_tiles, R], offs [groups + padding, 64, 2] uint32, tile_row,
+        whdr [n_tb * nw, 2], vals [groups + padding, 64, 4] float32)."""
         i = self.stream_copy_info(transpose, geom)
-        nw = i["wavefronts"]
+        nt, tb, nw, ng = i["n_tiles"], i["n_tb"], i["wavefronts"], i["n_groups"] + i["pad_groups"]
         if geom == 4:
-            # lane_layout.h: (tile_blk, tile_col [n_tiles, 2], rows [n_tiles, R], offs [groups + padding, 64, 2] uint32,
-            #                 tile_row, whdr [n_tb * nw, 2], vals [groups + padding, 64, 4] float32)
-            ng = i["n_groups"] + i["pad_groups"]
-            specs = [((i["n_tiles"] + 1,), np.int32), ((i["n_tiles"], 2), np.int32), ((i["n_tiles"], i["row_slots"]), np.int32),
-                     ((ng, 64, 2), np.uint32), ((i["n_tiles"] + 1,), np.int32), ((i["n_tb"] * nw, 2), np.int32),
-                     ((ng, 64, 4), np.float32)]
-            out = []
-            for which, (shp, dt) in enumerate(specs):
-                a = np.empty(shp, dtype=dt)
-                _lib.check(_lib.lib().mllp_graph_export_stream_copy(self._h, int(transpose), 4, which,
-                                                                    a.ctypes.data_as(c_void_p), a.nbytes))
-                out.append(a)
-            return tuple(out)
-        shapes = [(i["n_tiles"] + 1,), (i["n_tb"],), (i["n_tb"], nw, 16, 4), (i["n_groups"] + i["pad_groups"], 64, 3),
-                  (i["n_tiles"] + 1,), (i["n_tb"], nw, 4)]
+            specs = [((nt + 1,), np.int32), ((nt, 2), np.int32), ((nt, i["row_slots"]), np.int32), ((ng, 64, 2), np.uint32),
+                     ((nt + 1,), np.int32), ((tb * nw, 2), np.int32), ((ng, 64, 4), np.float32)]
+        else:
+            specs = [((nt + 1,), np.int32), ((tb,), np.int32), ((tb, nw, 16, 4), np.int32), ((ng, 64, 3), np.int32),
+                     ((nt + 1,), np.int32), ((tb, nw, 4), np.int32)]
         out = []
-        for which, shp in enumerate(shapes):
-            a = np.empty(shp, dtype=np.int32)
+        for which, (shp, dt) in enumerate(specs):
+            a = np.empty(shp, dtype=dt)
             _lib.check(_lib.lib().mllp_graph_export_stream_copy(self._h, int(transpose), int(geom), which,
                                                                 a.ctypes.data_as(c_void_p), a.nbytes))
             out.append(a)
@@ -490,8 +470,7 @@ class LPBatch:
     def disable_tiled(self, transpose=False, variant=0):
         _lib.check(_lib.lib().mllp_graph_attach_tiled(self._h, int(transpose), int(variant), 0, 0, 0, c_void_p(0),
                                                       c_void_p(0), c_void_p(0), c_void_p(0), c_void_p(0)))
-        if hasattr(self, "_tiled"):
-            self._tiled.pop((bool(transpose), int(variant)), None)
+        self._tiled.pop((bool(transpose), int(variant)), None)
 
     def __del__(self):
         try:

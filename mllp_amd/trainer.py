@@ -133,9 +133,9 @@ class LPTrainer:
             graph = (batch.nnz <= self.GRAPH_NNZ_LIMIT) if self.use_graph == "auto" else bool(self.use_graph)
             want_tiled = (batch.nnz >= self.TILED_NNZ_MIN) if self.tiled_copies == "auto" else bool(self.tiled_copies)
             if want_tiled and self.stream_copies:
-                if not getattr(batch, "_streams", None):
+                if not batch._streams:
                     batch._streams = batch.enable_stream_step()
-            elif want_tiled and not getattr(batch, "_tiled", None):
+            elif want_tiled and not batch._tiled:
                 batch.enable_tiled_step()
             p = dict(batch=batch, logits=torch.empty(batch.N, device=dev), loss=torch.zeros(1, device=dev),
                      grads=torch.zeros(NUM_PARAMS, device=dev), metrics=torch.zeros(batch.n_inst, 2, device=dev),
