@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define MLLP_ABI_VERSION 3 /* 2: streamed SpMM copy, device-built tiled copies, mllp_gnn_train_step, mllp_graph_invalidate_inputs; 3: streamed copies of the attention sweeps (mllp_graph_*_stream_copy) */
+#define MLLP_ABI_VERSION 4 /* 2: streamed SpMM copy, device-built tiled copies, mllp_gnn_train_step, mllp_graph_invalidate_inputs; 3: streamed copies of the attention sweeps (mllp_graph_*_stream_copy); 4: input gradients (mllp_gnn_backward_inputs) */
 #define MLLP_FEAT 16
 #define MLLP_NUM_PARAMS 4721 /* GNNModel.state_dict(), SURVEY.md appendix A.2 */
 
@@ -227,8 +227,8 @@ int mllp_graph_export_tiled(const mllp_graph_t* g, int transpose, int variant, i
  *   d_ws : mllp_tconv_workspace_floats() floats; holds what backward needs (kept by the caller
  *          between forward and backward).
  * Backward: d_dh [N_dst,16] = dL/dh_out (overwritten with the ReLU-masked gradient);
- *   d_dx_dst [N_dst,cin], d_dx_src [N_src,cin] may be NULL (then not computed; cin = 1 inputs are
- *   data, linear_program_methods.py:90-91); accumulate bit 0 / bit 1 = add into d_dx_dst / d_dx_src
+ *   d_dx_dst [N_dst,cin], d_dx_src [N_src,cin] may be NULL (then not computed; with cin = 1 they are never
+ *   computed here: the whole model's input gradients are mllp_gnn_backward_inputs); accumulate bit 0 / bit 1 = add into d_dx_dst / d_dx_src
  *   instead of overwriting; d_param_grads: same layout as d_conv_params (overwritten).
  * ---------------------------------------------------------------------------------------------- */
 int mllp_tconv_workspace_floats(const mllp_graph_t* g, int dst_is_var, int cin, int64_t* n_floats);
@@ -261,6 +261,25 @@ int mllp_gnn_backward(const mllp_graph_t* g, const float* d_params, const float*
 int mllp_gnn_loss_step(const mllp_graph_t* g, const float* d_params, const float* d_x1, const float* d_x2,
                        const float* d_labels, float inv_batch, void* d_ws, float* d_logits,
                        float* d_loss, float* d_grads, void* stream);
+
+/* Input gradients (reference: PyG's TransformerConv is plain autograd, so model(g) is differentiable in g.x1, g.x2 and
+ * g.edge_attr as well as in the weights).  Call after mllp_gnn_forward on the GENERIC path (path 1, or path 0 at 32 M
+ * nonzeros and above) on this workspace, with the graph still on a generic path; MLLP_EINVAL with a message when the
+ * forward on d_ws ran on the fused path.  Runs mllp_gnn_backward, then a post-pass (mllp_amd/csrc/input_grads.hip) that
+ * reads only what that backward leaves in the workspace and walks the plain CSR of A / A^T.
+ *   d_grads [MLLP_NUM_PARAMS] : as mllp_gnn_backward, bit for bit; may be NULL, then the gradients go to d_scratch
+ *   d_dx1 [N], d_dx2 [M], d_dvalues [nnz] : dL/dx1, dL/dx2, dL/da_ij in the CSR order of A (mllp_graph_export 2);
+ *     each may be NULL (not computed, costs nothing).  Overwritten, not accumulated.  Bitwise reproducible: fixed
+ *     launch order on `stream`, no float atomics.
+ *   d_scratch : mllp_gnn_input_grads_scratch_bytes() bytes, used only when d_grads is NULL (may then be NULL).
+ * A null graph, params, x1, x2, workspace or dlogits is rejected with a message before any HIP call.  All work is
+ * queued on `stream`.  The first call on a graph with d_dvalues != NULL also builds the graph-owned map from A^T
+ * positions to A positions (one hipMalloc of 4 * nnz bytes, freed by mllp_graph_destroy): make that first call
+ * outside a hipGraph capture; later calls allocate nothing and can be captured.                                   */
+int mllp_gnn_input_grads_scratch_bytes(const mllp_graph_t* g, int64_t* bytes);
+int mllp_gnn_backward_inputs(const mllp_graph_t* g, const float* d_params, const float* d_x1, const float* d_x2,
+                             void* d_ws, const float* d_dlogits, float* d_grads, float* d_dx1, float* d_dx2,
+                             float* d_dvalues, void* d_scratch, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * torch.optim.Adam(lr, betas=(0.9, 0.999), eps=1e-8), no weight decay

@@ -13,7 +13,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libmllp_hip.so")
 HEADER_PATH = os.path.abspath(os.path.join(_HERE, "..", "include", "mllp_hip.h"))
 
 NUM_PARAMS = 4721
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 
 class MllpError(RuntimeError):
@@ -64,6 +64,9 @@ _PROTOTYPES = {
     "mllp_gnn_workspace_bytes": (c_int, [c_void_p, POINTER(c_int64)]),
     "mllp_gnn_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mllp_gnn_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mllp_gnn_input_grads_scratch_bytes": (c_int, [c_void_p, POINTER(c_int64)]),
+    "mllp_gnn_backward_inputs": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p]),
     "mllp_gnn_loss_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p,
                                    c_void_p, c_void_p, c_void_p, c_void_p]),
     "mllp_gnn_train_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p,

@@ -445,6 +445,25 @@ extern "C" int mllp_gnn_backward(const mllp_graph_t* g, const float* d_params, c
     return model_backward_body(g, d_params, d_x1, d_x2, w, d_grads, s);
 }
 
+// Input gradients after the generic backward (post-pass on s; input_grads.hip, BwdSrc1Op).  Fixed order, no atomics:
+//   dx1 = dx_dst(gconv1_w2s) + dx_src(gconv1_s2w),  dx2 = dx_dst(gconv1_s2w) + dx_src(gconv1_w2s)
+//   dval = the edge terms of gconv1_s2w, gconv2_s2w (walking A), gconv1_w2s, gconv2_w2s, gconv3_w2s (walking A^T,
+//          placed by g->at_pos); the first stores, the others add
+static int input_grads_body(const mllp_graph* g, const float* x1, const float* x2, const ModelWs& w, float* dx1,
+                            float* dx2, float* dval, hipStream_t s) {
+    int rc;
+    if ((rc = launch_layer1_dst_grads(w.c1v, w.d1v, dx1, g->N, w.c1c, w.d1c, dx2, g->M, s))) return rc;
+    if (dx1 && (rc = launch_attn_bwd_src1(g->At, w.c1c, x1, dx1, 1, g->At.scratch, s))) return rc;
+    if (dx2 && (rc = launch_attn_bwd_src1(g->A, w.c1v, x2, dx2, 1, g->A.scratch, s))) return rc;
+    if (!dval) return MLLP_OK;
+    const int* pos = g->at_pos;
+    if ((rc = launch_edge_grad(g->A, g->nnz, 1, w.c1c, x1, nullptr, dval, 0, s))) return rc;
+    if ((rc = launch_edge_grad(g->A, g->nnz, 16, w.c2c, w.h1v, nullptr, dval, 1, s))) return rc;
+    if ((rc = launch_edge_grad(g->At, g->nnz, 1, w.c1v, x2, pos, dval, 1, s))) return rc;
+    if ((rc = launch_edge_grad(g->At, g->nnz, 16, w.c2v, w.h1c, pos, dval, 1, s))) return rc;
+    return launch_edge_grad(g->At, g->nnz, 16, w.c3v, w.h2c, pos, dval, 1, s);
+}
+
 extern "C" int mllp_gnn_loss_step(const mllp_graph_t* g, const float* d_params, const float* d_x1, const float* d_x2,
                                   const float* d_labels, float inv_batch, void* d_ws, float* d_logits, float* d_loss,
                                   float* d_grads, void* stream) {
@@ -464,6 +483,36 @@ extern "C" int mllp_gnn_loss_step(const mllp_graph_t* g, const float* d_params, 
     if ((rc = fork_to(s, g->aux, g->ev[1]))) return rc;
     if ((rc = launch_head_finalize(w.head_partials, head_blocks_for(g->N), d_grads + OFF_FC, d_loss, g->aux))) return rc;
     return model_backward_body(g, d_params, d_x1, d_x2, w, d_grads, s);
+}
+
+extern "C" int mllp_gnn_input_grads_scratch_bytes(const mllp_graph_t* g, int64_t* bytes) {
+    REQUIRE(g && bytes, "null argument");
+    *bytes = up16(MLLP_NUM_PARAMS) * (int64_t)sizeof(float);     // the parameter gradients when d_grads is null
+    return MLLP_OK;
+}
+
+extern "C" int mllp_gnn_backward_inputs(const mllp_graph_t* g, const float* d_params, const float* d_x1,
+                                        const float* d_x2, void* d_ws, const float* d_dlogits, float* d_grads,
+                                        float* d_dx1, float* d_dx2, float* d_dvalues, void* d_scratch, void* stream) {
+    REQUIRE(g && d_params && d_x1 && d_x2 && d_ws && d_dlogits, "null argument");
+    REQUIRE(g->ws_ptr == d_ws, "no mllp_gnn_forward on this workspace");
+    REQUIRE(g->ws_path == 0, "the forward on this workspace ran on the fused path: input gradients need the generic "
+                             "sweeps (mllp_graph_set_path(g, 1) before mllp_gnn_forward)");
+    REQUIRE(!use_fused(g), "the graph's path selects the fused kernels: set path 1 between the forward and this call");
+    REQUIRE(d_grads || d_scratch, "d_grads and d_scratch are both null (mllp_gnn_input_grads_scratch_bytes)");
+    hipStream_t s = (hipStream_t)stream;
+    mllp_graph* gm = const_cast<mllp_graph*>(g);
+    int rc;
+    if (d_dvalues && !g->at_pos && g->nnz > 0) {      // once per graph (allocates: make the first such call uncaptured)
+        int* pos = nullptr;
+        MLLP_HIP_TRY(hipMalloc((void**)&pos, (size_t)g->nnz * sizeof(int)));
+        gm->allocs.push_back(pos);
+        if ((rc = build_csc_to_csr(g, pos, s))) return rc;
+        gm->at_pos = pos;
+    }
+    float* grads = d_grads ? d_grads : (float*)d_scratch;
+    if ((rc = mllp_gnn_backward(g, d_params, d_x1, d_x2, d_ws, d_dlogits, grads, stream))) return rc;
+    return input_grads_body(g, d_x1, d_x2, model_ws(g, (float*)d_ws), d_dx1, d_dx2, d_dvalues, s);
 }
 
 extern "C" int mllp_gnn_train_step(const mllp_graph_t* g, float* d_params, const float* d_x1, const float* d_x2,

@@ -181,6 +181,9 @@ struct mllp_graph {
     // and the generic branch of train_step clear the record)
     const void* folded_ws = nullptr;
     const void* folded_params = nullptr;
+    // input gradients: CSR position in A of every nonzero of A^T, built on the first mllp_gnn_backward_inputs call that
+    // asks for dL/da (in `allocs`)
+    int* at_pos = nullptr;
     // second stream + events: the two convs of a layer (one per orientation) and the single-workgroup
     // finalize kernels run beside the main stream (fork/join by events, also under hipGraph capture)
     hipStream_t aux = nullptr;
@@ -286,6 +289,15 @@ int launch_attn_bwd_dst(const Orient& o, int cin, const float* conv_params, cons
                         const float* g, float* dx_dst, int accumulate, float* scratch, hipStream_t s);
 int launch_attn_bwd_src(const Orient& o_src_major, const ConvWs& w, const float* x_src, float* dx_src,
                         int accumulate, float* scratch, hipStream_t s);
+int launch_attn_bwd_src1(const Orient& o_src_major, const ConvWs& w, const float* x_src, float* dx_src,
+                         int accumulate, float* scratch, hipStream_t s);
+// input gradients (input_grads.hip): edge-parallel dL/da_ij of one conv walking the destination-major CSR `o`, stored
+// (accumulate = 0) or added into dval[pos ? pos[e] : e]; the At -> A position map; dx_dst of both layer-1 convs
+int launch_edge_grad(const Orient& o, int64_t nnz, int cin, const ConvWs& w, const float* x_src, const int* pos, float* dval,
+                     int accumulate, hipStream_t s);
+int build_csc_to_csr(const mllp_graph* g, int* pos, hipStream_t s);
+int launch_layer1_dst_grads(const ConvWs& wv, const float* gv, float* dx1, int64_t n, const ConvWs& wc, const float* gc,
+                            float* dx2, int64_t m, hipStream_t s);
 int launch_param_stats(int cin, int64_t n_dst, const ConvWs& w, const float* x_dst, const float* g, hipStream_t s);
 int launch_finalize_conv(int cin, const float* conv_params, const float* stats, int n_stat_blocks, float* grads,
                          hipStream_t s);

@@ -662,6 +662,56 @@ struct BwdSrc16Op {
     }
 };
 
+// C = 1 (layer 1, mllp_gnn_backward_inputs only): dx_j = sum_i alpha_ij gv_i + dl_ij q'_i with the 8-float records
+// of BwdDst1Op, one lane per nonzero.
+struct BwdSrc1Op {
+    using Args = BwdSrcArgs;
+    static constexpr int NS = 4, LPN = 1;
+    float xj, acc;
+
+    __device__ __forceinline__ void load_row(const Args& args, int row, int, int) {
+        xj = args.X[row];
+        acc = 0.0f;
+    }
+    template <int G, int U>
+    __device__ __forceinline__ void edges(const Args& args, const OrientDev& o, int beg, int end, int first, int stride,
+                                          int gl) {
+        for (int e0 = beg + first; e0 < end; e0 += stride) {
+            int col[U];
+            float a[U];
+            bool ok[U];
+            load_edges<G, U, LPN>(o, e0, end, gl, col, a, ok);
+            float4 s0[U], s1[U];
+#pragma unroll
+            for (int k = 0; k < U; ++k) {
+                s0[k] = ld4(args.rec + (size_t)col[k] * 8);       // {q', gv, t, rowmax}
+                s1[k] = ld4(args.rec + (size_t)col[k] * 8 + 4);   // {rinv, ge, c, 0}
+            }
+#pragma unroll
+            for (int k = 0; k < U; ++k) {
+                const float l = fmaf(s0[k].x, xj, a[k] * s0[k].z);
+                const float alpha = ok[k] ? exp_acc(l - s0[k].w) * s1[k].x : 0.0f;
+                const float dl = alpha * fmaf(s0[k].y, xj, fmaf(a[k], s1[k].y, s1[k].z));
+                acc = fmaf(alpha, s0[k].y, acc);
+                acc = fmaf(dl, s0[k].x, acc);
+            }
+        }
+    }
+    template <int G>
+    __device__ __forceinline__ void reduce() { acc = group_sum<G>(acc); }
+    __device__ __forceinline__ void to_mem(float* s) const {
+        *reinterpret_cast<float4*>(s) = make_float4(acc, 0.0f, 0.0f, 0.0f);   // lanes 0..3 write the same value
+    }
+    __device__ __forceinline__ void merge_from(const float* s, int n) {
+        float v = 0.0f;
+        for (int w = 0; w < n; ++w) v += s[w * NS];
+        acc = v;
+    }
+    __device__ __forceinline__ void epilogue(const Args& args, int row, int, int gl) {
+        if (gl == 0) args.dX[row] = args.accumulate ? args.dX[row] + acc : acc;
+    }
+};
+
 // -------------------------------------------------------------------------------------------------
 // launchers
 // -------------------------------------------------------------------------------------------------
@@ -742,6 +792,13 @@ int launch_attn_bwd_src(const Orient& o_src_major, const ConvWs& w, const float*
     if (tl.n_tiles > 0) return launch_bwdsrc16_tiled(tl, n_rows, n_cols, w.rec, x_src, dx_src, accumulate, s);
     BwdSrcArgs a{x_src, w.rec, dx_src, accumulate};
     return launch_sweep<BwdSrc16Op, 2, 2>(o_src_major, a, scratch, s, "attn_bwd_src16");
+}
+
+// always the generic sweep over the plain CSR (no re-blocked copy has this geometry)
+int launch_attn_bwd_src1(const Orient& o_src_major, const ConvWs& w, const float* x_src, float* dx_src, int accumulate,
+                         float* scratch, hipStream_t s) {
+    BwdSrcArgs a{x_src, w.rec, dx_src, accumulate};
+    return launch_sweep<BwdSrc1Op, 2, 2>(o_src_major, a, scratch, s, "attn_bwd_src1");
 }
 
 }  // namespace mllp

@@ -197,6 +197,7 @@ class LPBatch:
         self._streams = None          # the streamed copies of the training step (LPTrainer._plan: enable_stream_step)
         self.tiled_build_s = 0.0      # seconds spent building LDS-tiled copies
         self.stream_build_s = 0.0     # ... streamed copies
+        self.path = 0                 # the whole-model path last given to mllp_graph_set_path
         if LPBatch.default_path:
             self.set_path(LPBatch.default_path)
 
@@ -219,6 +220,7 @@ class LPBatch:
     def set_path(self, path):
         """0 = by size, 1 = generic / LDS-tiled sweeps, 2 = fused latency-regime kernels (whole-model calls only)."""
         _lib.check(_lib.lib().mllp_graph_set_path(self._h, int(path)))
+        self.path = int(path)
         self._folded = None
         return self
 
@@ -573,6 +575,23 @@ class LPBatch:
                                                 _lib.ptr(self.workspace()), _lib.ptr(dlogits), _lib.ptr(grads),
                                                 _lib.current_stream()))
         return grads
+
+    def backward_inputs(self, params, dlogits, x1=True, x2=True, values=True, grads=None):
+        """mllp_gnn_backward plus the gradients with respect to the inputs, after `forward` on a generic path (path 1, or
+        path 0 at 32 M nonzeros and above).  Returns (grads, dx1 [N], dx2 [M], dvalues [nnz]); dvalues is in the CSR order
+        of A (`export(2)`), and an input whose flag is False gets None (and is not computed)."""
+        dev = params.device
+        if grads is None:
+            grads = torch.empty(_lib.NUM_PARAMS, device=dev, dtype=torch.float32)
+        dx1 = torch.empty(self.N, device=dev, dtype=torch.float32) if x1 else None
+        dx2 = torch.empty(self.M, device=dev, dtype=torch.float32) if x2 else None
+        dv = torch.empty(self.nnz, device=dev, dtype=torch.float32) if values else None
+        dlogits = dlogits.contiguous().float()
+        _lib.check(_lib.lib().mllp_gnn_backward_inputs(self._h, _lib.ptr(params), _lib.ptr(self.x1), _lib.ptr(self.x2),
+                                                       _lib.ptr(self.workspace()), _lib.ptr(dlogits), _lib.ptr(grads),
+                                                       _lib.ptr(dx1), _lib.ptr(dx2), _lib.ptr(dv), c_void_p(0),
+                                                       _lib.current_stream()))
+        return grads, dx1, dx2, dv
 
     def loss_step(self, params, inv_batch=None, logits=None, loss=None, grads=None):
         """forward + BCEWithLogits + backward.  loss = inv_batch * sum_k mean_i BCE; default 1/n_inst."""

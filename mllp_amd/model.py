@@ -40,6 +40,7 @@ class BipartiteData:
         self.x2 = x_dst
         self.edge_attr = edge_attr
         self._lp_batch = None
+        self._csr_order = self._csr_order_dev = self._ea_key = None   # set with the LPBatch (lp_batch)
         self._sizes = None   # [(m_k, n_k)] when this object is a batch of several instances
 
     def __inc__(self, key, value=None):
@@ -69,6 +70,9 @@ class BipartiteData:
         self.x1, self.x2, self.edge_attr = self.x1.to(device), self.x2.to(device), self.edge_attr.to(device)
         return self
 
+    def _edge_attr_key(self):
+        return (self.edge_attr.data_ptr(), self.edge_attr._version)
+
     def lp_batch(self) -> LPBatch:
         if self._lp_batch is None:
             sizes = self._sizes or [(self.x2.size(0), self.x1.size(0))]
@@ -77,7 +81,7 @@ class BipartiteData:
             x1 = self.x1.detach().cpu().numpy().reshape(-1).astype(np.float64)
             x2 = self.x2.detach().cpu().numpy().reshape(-1).astype(np.float64)
             var, con = ei[0].astype(np.int64), ei[1].astype(np.int64)
-            order = np.lexsort((var, con))                     # CSR order whatever the edge order was
+            order = edge_order_to_csr(var, con)                # CSR order whatever the edge order was
             var, con, ea = var[order], con[order], ea[order]
             insts, m_off, n_off = [], 0, 0
             starts = np.searchsorted(con, np.cumsum([0] + [s[0] for s in sizes]))
@@ -91,7 +95,29 @@ class BipartiteData:
                 m_off += m
                 n_off += n
             self._lp_batch = LPBatch.from_instances(insts)
+            self._csr_order = order
+            self._csr_order_dev = None
+            self._ea_key = self._edge_attr_key()
         return self._lp_batch
+
+    def csr_to_edge_order(self, values_csr):
+        """Values in the graph's CSR order (LPBatch.backward_inputs) -> the caller's edge order, (E, 1)."""
+        if self._csr_order_dev is None or self._csr_order_dev.device != values_csr.device:
+            self._csr_order_dev = torch.from_numpy(self._csr_order).to(values_csr.device)
+        return csr_to_edge_order(values_csr, self._csr_order_dev).unsqueeze(-1)
+
+
+def edge_order_to_csr(var, con):
+    """The permutation that sorts an edge list (variable ids, constraint ids) into CSR order of A: by constraint, then
+    by variable.  Position k of the CSR holds edge order[k]."""
+    return np.lexsort((np.asarray(var), np.asarray(con)))
+
+
+def csr_to_edge_order(values_csr, order):
+    """Inverse of `edge_order_to_csr`: out[order[k]] = values_csr[k] (torch tensors, any device)."""
+    out = torch.empty_like(values_csr)
+    out[order] = values_csr
+    return out
 
 
 def build_graph_from_weights_sets(constrs, constr_weights, rhs, coefs, device=torch.device("cpu")):
@@ -143,6 +169,50 @@ class _GNNFunction(torch.autograd.Function):
         return ctx.batch.backward(flat, dlogits), None
 
 
+class _GNNInputsFunction(torch.autograd.Function):
+    """logits = GNN(params; x1, x2, edge_attr) through mllp_gnn_forward / mllp_gnn_backward_inputs on the generic
+    sweeps: differentiable in the graph's data as well as in the weights (PyG TransformerConv is plain autograd)."""
+
+    @staticmethod
+    def forward(ctx, flat, x1, x2, edge_attr, g):
+        flat = flat.contiguous()
+        batch = g.lp_batch()
+        with torch.no_grad():          # the gradients are those at the tensors' current values
+            batch.x1.copy_(x1.detach().reshape(-1))
+            batch.x2.copy_(x2.detach().reshape(-1))
+        path = batch.path
+        batch.set_path(1)
+        try:
+            logits = batch.forward(flat)
+        finally:
+            batch.set_path(path)
+        batch._fwd_token = getattr(batch, "_fwd_token", 0) + 1
+        ctx.g, ctx.batch, ctx.token = g, batch, batch._fwd_token
+        ctx.like = [(t.shape, t.dtype, t.device) for t in (x1, x2, edge_attr)]
+        ctx.save_for_backward(flat)
+        return logits
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        (flat,) = ctx.saved_tensors
+        batch = ctx.batch
+        if batch._fwd_token != ctx.token:
+            raise RuntimeError("GNNModel: backward after another forward on the same graph -- the saved "
+                               "activations live in the graph's workspace and were overwritten")
+        need = ctx.needs_input_grad
+        path = batch.path
+        batch.set_path(1)
+        try:
+            grads, dx1, dx2, dv = batch.backward_inputs(flat, dlogits, x1=need[1], x2=need[2], values=need[3])
+        finally:
+            batch.set_path(path)
+        if dv is not None:
+            dv = ctx.g.csr_to_edge_order(dv)
+        out = [None if d is None else d.reshape(shape).to(device=dev, dtype=dt)
+               for d, (shape, dt, dev) in zip((dx1, dx2, dv), ctx.like)]
+        return (grads, *out, None)
+
+
 class GNNModel(torch.nn.Module):
     """reference linear_program_methods.py:202-251: six TransformerConv((c,c),16,edge_dim=1) holders
     (gconv3_s2w is declared but never called, :248) and fc = Linear(16,1).  forward(g) -> (n,) logits."""
@@ -176,4 +246,9 @@ class GNNModel(torch.nn.Module):
         if not flat.is_cuda:
             raise _lib.MllpError("GNNModel runs on the MI355X HIP path only: call model.to('cuda') "
                                  "(there is no CPU fallback)")
+        data = (g.x1, g.x2, g.edge_attr)
+        if torch.is_grad_enabled() and any(t.requires_grad for t in data):
+            if g._lp_batch is not None and g._ea_key != g._edge_attr_key():
+                g._lp_batch = None             # edge_attr changed since the batch was built: rebuild it
+            return _GNNInputsFunction.apply(flat, *data, g)
         return _GNNFunction.apply(flat, g.lp_batch())
