@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define MLLP_ABI_VERSION 4 /* 2: streamed SpMM copy, device-built tiled copies, mllp_gnn_train_step, mllp_graph_invalidate_inputs; 3: streamed copies of the attention sweeps (mllp_graph_*_stream_copy); 4: input gradients (mllp_gnn_backward_inputs) */
+#define MLLP_ABI_VERSION 5 /* 2: streamed SpMM copy, device-built tiled copies, mllp_gnn_train_step, mllp_graph_invalidate_inputs; 3: streamed copies of the attention sweeps (mllp_graph_*_stream_copy); 4: input gradients (mllp_gnn_backward_inputs); 5: AngleModel input gradients (mllp_angle_backward_inputs) */
 #define MLLP_FEAT 16
 #define MLLP_NUM_PARAMS 4721 /* GNNModel.state_dict(), SURVEY.md appendix A.2 */
 
@@ -357,6 +357,22 @@ int mllp_angle_forward(int64_t n_nodes, int feat_dim, const float* d_cos, const 
                        float* d_ws, float* d_logits, void* stream);
 int mllp_angle_backward(int64_t n_nodes, int feat_dim, const float* d_cos, const float* d_x, const float* d_params,
                         float* d_ws, const float* d_dlogits, float* d_grads, void* stream);
+
+/* Input gradients of AngleModel (reference: PyG's TransformerConv is plain autograd, so model(g) is differentiable in g.x
+ * and g.edge_attr as well as in the weights).  Call after mllp_angle_forward on this workspace, as mllp_angle_backward.
+ * Runs mllp_angle_backward; the BQ sweep of each of the three layer applications also writes the gradient of the edge
+ * attributes of its pairs (dz_ij qe_i + p_ij u_i), and the first layer's backward also forms dL/dx.
+ *   d_grads : as mllp_angle_backward, bit for bit; required
+ *   d_dx [N, 2] : dL/d_x;  d_dcos [N, N] : dL/dA_ij, indexed as d_cos (row = target i, column = source j: the gradient of
+ *     the reference's edge j -> i), diagonal written as 0.  Each may be NULL (not computed, costs nothing); both NULL is
+ *     exactly mllp_angle_backward.  Overwritten, not accumulated.  Bitwise reproducible: fixed launch order on `stream`,
+ *     the three layers' terms summed in a fixed order, no float atomics.
+ *   The sweeps read either triangle of d_cos: d_dcos is the gradient of the per-edge model only for a symmetric d_cos.
+ * A null cos, x, params, workspace, dlogits or grads, a bad size or a bad feat_dim is rejected with a message before any
+ * HIP call.  All work is queued on `stream`; nothing is allocated.                                                     */
+int mllp_angle_backward_inputs(int64_t n_nodes, int feat_dim, const float* d_cos, const float* d_x,
+                               const float* d_params, float* d_ws, const float* d_dlogits, float* d_grads,
+                               float* d_dx, float* d_dcos, void* stream);
 
 #ifdef __cplusplus
 }

@@ -13,7 +13,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libmllp_hip.so")
 HEADER_PATH = os.path.abspath(os.path.join(_HERE, "..", "include", "mllp_hip.h"))
 
 NUM_PARAMS = 4721
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 
 class MllpError(RuntimeError):
@@ -54,6 +54,8 @@ _PROTOTYPES = {
     "mllp_angle_workspace_floats": (c_int, [c_int64, c_int, POINTER(c_int64)]),
     "mllp_angle_forward": (c_int, [c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mllp_angle_backward": (c_int, [c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mllp_angle_backward_inputs": (c_int, [c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_void_p]),
     "mllp_tiled_geometry": (c_int, [c_int, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)]),
     "mllp_graph_attach_tiled": (c_int, [c_void_p, c_int, c_int, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_void_p]),

@@ -101,17 +101,23 @@ def get_netlib_dataloader(train_dataset, device) -> List[AngleGraph]:
     return out
 
 
+def _angle_forward(ctx, flat, g, feat_dim):
+    """mllp_angle_forward on the graph's workspace; records on ctx what the backward checks"""
+    N = g.num_nodes
+    ws = g.workspace(feat_dim)
+    logits = torch.empty(N - 1, dtype=torch.float32, device=flat.device)
+    _lib.check(_lib.lib().mllp_angle_forward(N, int(feat_dim), _lib.ptr(g.cos), _lib.ptr(g.x), _lib.ptr(flat),
+                                             _lib.ptr(ws), _lib.ptr(logits), _lib.current_stream()))
+    g._token += 1
+    ctx.g, ctx.token, ctx.feat_dim = g, g._token, int(feat_dim)
+    return logits
+
+
 class _AngleFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, flat, g, feat_dim):
         flat = flat.contiguous()
-        N = g.num_nodes
-        ws = g.workspace(feat_dim)
-        logits = torch.empty(N - 1, dtype=torch.float32, device=flat.device)
-        _lib.check(_lib.lib().mllp_angle_forward(N, int(feat_dim), _lib.ptr(g.cos), _lib.ptr(g.x), _lib.ptr(flat),
-                                                 _lib.ptr(ws), _lib.ptr(logits), _lib.current_stream()))
-        g._token += 1
-        ctx.g, ctx.token, ctx.feat_dim = g, g._token, int(feat_dim)
+        logits = _angle_forward(ctx, flat, g, feat_dim)
         ctx.save_for_backward(flat)
         return logits
 
@@ -128,6 +134,40 @@ class _AngleFunction(torch.autograd.Function):
                                                   _lib.ptr(flat), _lib.ptr(g.workspace(ctx.feat_dim)), _lib.ptr(d),
                                                   _lib.ptr(grads), _lib.current_stream()))
         return grads, None, None
+
+
+class _AngleInputsFunction(torch.autograd.Function):
+    """_AngleFunction with the graph's node features x [N, 2] and cosine matrix cos [N, N] as autograd inputs: the same
+    forward, and a backward (mllp_angle_backward_inputs) that also returns dL/dx and dL/dcos, each only when asked for.
+    cos.grad[i, j] is the gradient of the reference's edge j -> i (g.edge_attr[e] with src = j, dst = i); the diagonal
+    gets 0."""
+
+    @staticmethod
+    def forward(ctx, flat, x, cos, g, feat_dim):
+        if ctx.needs_input_grad[2] and not torch.equal(cos, cos.mT):
+            raise ValueError("AngleModel: gradients with respect to g.cos need a symmetric cosine matrix (the kernels "
+                             "read either triangle, so for a non-symmetric matrix they are not the per-edge model's)")
+        flat = flat.contiguous()
+        logits = _angle_forward(ctx, flat, g, feat_dim)
+        ctx.save_for_backward(flat, x, cos)
+        return logits
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        flat, x, cos = ctx.saved_tensors
+        g = ctx.g
+        if g._token != ctx.token:
+            raise RuntimeError("AngleModel: backward after another forward on the same graph (the saved activations "
+                               "live in the graph's workspace)")
+        grads = torch.empty_like(flat)
+        dx = torch.empty_like(x) if ctx.needs_input_grad[1] else None
+        dcos = torch.empty_like(cos) if ctx.needs_input_grad[2] else None
+        d = dlogits.contiguous().float()
+        _lib.check(_lib.lib().mllp_angle_backward_inputs(g.num_nodes, ctx.feat_dim, _lib.ptr(cos), _lib.ptr(x),
+                                                         _lib.ptr(flat), _lib.ptr(g.workspace(ctx.feat_dim)),
+                                                         _lib.ptr(d), _lib.ptr(grads), _lib.ptr(dx), _lib.ptr(dcos),
+                                                         _lib.current_stream()))
+        return grads, dx, dcos, None, None
 
 
 class AngleStepper:
@@ -191,4 +231,6 @@ class AngleModel(torch.nn.Module):
         n = c_int64()
         _lib.check(_lib.lib().mllp_angle_num_params(self.feat_dim, ctypes.byref(n)))
         assert flat.numel() == n.value
+        if torch.is_grad_enabled() and (g.x.requires_grad or g.cos.requires_grad):
+            return _AngleInputsFunction.apply(flat, g.x, g.cos, g, self.feat_dim)
         return _AngleFunction.apply(flat, g, self.feat_dim)

@@ -22,6 +22,8 @@
 //         BQ   X = keys, Y = queries:  p from the saved row max / 1 / sum, dp = V dO^T + (dO . we) A,
 //              dz = p (dp - D) / sqrt(F) -> acc += K^T dz (dQ), r = sum dz A
 //         BKV  X = queries, Y = keys:  the same p, dz with the roles exchanged -> accV += dO^T p (dV), accK += Q^T dz (dK)
+//         BQ_DCOS, BQ_DCOS_ADD  the BQ sweep that also writes the gradient of the edge attributes of its tile,
+//              dA_yx = dz qe_y + p u_y, into dcos [N][N] (store / load, add, store: the three layer applications in a fixed order)
 //       The backward recomputes p from {row max, 1 / (sum + 1e-16)} as the sparse path does; D_i = dO_i . (alpha V)_i + u_i s_i.
 //   * gemm_kernel            one 64 x 64 x 16 LDS-tiled MFMA GEMM with general strides (X W^T, dY^T X, dY W), K split
 //       over workgroups where the output is small (weight gradients: K = N), a ones column for the bias gradients.
@@ -346,6 +348,8 @@ int launch_wcolsum(hipStream_t s, int K, int F, const float* A1, const float* b1
 
 // =================================================================================================== attention
 constexpr int MODE_FWD = 0, MODE_BQ = 1, MODE_BKV = 2;
+// the BQ sweep with the edge-attribute gradient: dcos = dA (the first backward layer application) / dcos += dA (the others)
+constexpr int MODE_BQ_DCOS = 3, MODE_BQ_DCOS_ADD = 4;
 struct AttnArgs {
     const float *Y1, *Y2;      // rows of the Y nodes   FWD: Q, -     BQ: Q, dO     BKV: K, V
     const float *X1, *X2;      // rows of the X nodes   FWD: K, -     BQ: K, V      BKV: Q, dO
@@ -355,7 +359,10 @@ struct AttnArgs {
     const float *qe, *m, *inv, *u, *D;     // per node (written by FWD / the row kernels; read by BQ / BKV)
     float *part1, *part2;      // [ranges][N][F]
     float* stats;              // [ranges][N][4]  FWD: {m, l, u}   BQ: {r}
-    float* qe_out;             // FWD: [N]
+    union {
+        float* qe_out;         // FWD: [N]
+        float* dcos;           // BQ_DCOS, BQ_DCOS_ADD: [N][N], indexed as cos
+    };
     int N, xb_per_range;
     float scale;
 };
@@ -459,8 +466,13 @@ namespace {
 // One workgroup = 4 wavefronts = 64 Y nodes, one range of X blocks.  The two matrices of an X block (FWD: K, V; BQ: K, V;
 // BKV: Q, dO -- each serves as the operand of a dot product AND of an accumulation) are staged by LDS-DMA one block ahead
 // (two buffers, one barrier per block).
-template <int F, int MODE>
-__global__ __launch_bounds__(64 * ATT_W, MODE == MODE_FWD ? 2 : 1) void attn_kernel(AttnArgs a) {
+// BQ_DCOS*: lane (g, y) also owns dcos[y][x0 + 4 g .. + 3] of every block (one 64-byte piece of a row per block), 16-byte
+// accesses when every row starts 16-byte aligned (N % 4 == 0), four dword accesses otherwise; BQ_DCOS_ADD loads the
+// previous sum one block ahead, with the tiles.
+template <int F, int MODE_>
+__global__ __launch_bounds__(64 * ATT_W, MODE_ == MODE_FWD ? 2 : 1) void attn_kernel(AttnArgs a) {
+    constexpr int MODE = MODE_ > MODE_BKV ? MODE_BQ : MODE_;
+    constexpr bool DCOS = MODE_ > MODE_BKV, DCOS_ADD = MODE_ == MODE_BQ_DCOS_ADD;
     constexpr int FJ = F / 16, NA = (F + 63) / 64 * 4, RS = F + 4, TILE = 16 * RS;
     __shared__ __attribute__((aligned(16))) float sm[2][2][TILE];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, g = lane >> 4;
@@ -494,10 +506,23 @@ __global__ __launch_bounds__(64 * ATT_W, MODE == MODE_FWD ? 2 : 1) void attn_ker
     };
     // the edge attributes of the block (and, BKV, the scalars of its X nodes) also come one block ahead
     // (no guards, hence no branches: clamped addresses; whatever belongs to a node >= N is masked where it is used)
-    float ncv[4], nst[MODE == MODE_BKV ? 20 : 1];
+    float ncv[4], nst[MODE == MODE_BKV ? 20 : 1], ndc[DCOS_ADD ? 4 : 1];
+    float* __restrict__ dcrow = nullptr;
+    bool dc4 = false;
+    if constexpr (DCOS) { dcrow = a.dcos + (size_t)min(y, N - 1) * N; dc4 = (N & 3) == 0; }
     auto fetch_small = [&](int xb) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) ncv[r] = cosrow[min(xb * 16 + 4 * g + r, N - 1)];     // (symmetric: A[y][x] serves both orientations)
+        if constexpr (DCOS_ADD) {
+            if (dc4) {
+                const f4 v = *reinterpret_cast<const f4*>(dcrow + min(xb * 16 + 4 * g, N - 4));
+#pragma unroll
+                for (int r = 0; r < 4; ++r) ndc[r] = v[r];
+            } else {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) ndc[r] = dcrow[min(xb * 16 + 4 * g + r, N - 1)];
+            }
+        }
         if constexpr (MODE == MODE_BKV) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
@@ -542,9 +567,12 @@ __global__ __launch_bounds__(64 * ATT_W, MODE == MODE_FWD ? 2 : 1) void attn_ker
         const int buf = (xb - xb_lo) & 1;
         const float* tA = sm[buf][0];
         const float* tB = sm[buf][1];
-        float cv[4], st[MODE == MODE_BKV ? 20 : 1];
+        float cv[4], st[MODE == MODE_BKV ? 20 : 1], dc[DCOS_ADD ? 4 : 1];
 #pragma unroll
         for (int r = 0; r < 4; ++r) cv[r] = ncv[r];
+        if constexpr (DCOS_ADD)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) dc[r] = ndc[r];
         if constexpr (MODE == MODE_BKV)
 #pragma unroll
             for (int r = 0; r < 20; ++r) st[r] = nst[r];
@@ -625,6 +653,23 @@ __global__ __launch_bounds__(64 * ATT_W, MODE == MODE_FWD ? 2 : 1) void attn_ker
             asm volatile("s_nop 0" : "+v"(p), "+v"(dz));
 #endif
             ANGLE_TICK(3)
+            if constexpr (DCOS) {      // dA_yx = dz qe_y + p u_y; 0 on the diagonal; nothing behind N is written
+                f4 o;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float v = fmaf(dz[r], qe_y, p[r] * u_y);
+                    o[r] = ok[r] ? (DCOS_ADD ? dc[r] + v : v) : 0.0f;
+                }
+                if (yok) {
+                    if (dc4) {
+                        if (xg < N) *reinterpret_cast<f4*>(dcrow + xg) = o;
+                    } else {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                            if (xg + r < N) dcrow[xg + r] = o[r];
+                    }
+                }
+            }
             if (AABL & 2) { acc1[0] += dz; acc1[1] += p; }
             else if constexpr (MODE == MODE_BQ) accumulate<F>(acc1, tA, lane, dz);      // dQ += K^T dz
             else {
@@ -898,10 +943,11 @@ int conv_forward(hipStream_t s, int64_t N, int C, int F, const float* A, const f
     return check("angle fwd_combine");
 }
 
-// dH (in: gradient of the layer's output, overwritten with dO) -> parameter gradients (accumulated when acc) and, if dX,
-// the gradient of the layer's input
+// dH (in: gradient of the layer's output, overwritten with dO) -> parameter gradients (accumulated when acc), if dX the
+// gradient of the layer's input, and if dcos the gradient of the edge attributes (added to dcos when dcos_add)
 int conv_backward(hipStream_t s, int64_t N, int C, int F, const float* A, const float* X, const ConvP& p, const LayerWs& L,
-                  const AngleWs& w, float* dH, float* dX, const ConvG& g, bool acc) {
+                  const AngleWs& w, float* dH, float* dX, const ConvG& g, bool acc, float* dcos = nullptr,
+                  bool dcos_add = false) {
     int rc;
     const float beta = acc ? 1.0f : 0.0f;
     hipLaunchKernelGGL(relu_bwd_kernel, dim3((unsigned)N), dim3(AT), 0, s, F, dH, L.H, L.Oa, p.we, L.s, w.u, w.D);   // dO, u, D
@@ -910,7 +956,13 @@ int conv_backward(hipStream_t s, int64_t N, int C, int F, const float* A, const 
     const int ranges = (int)(((N + 15) / 16 + a.xb_per_range - 1) / a.xb_per_range);
     // dQ = dz K + r we^T,  r = sum dz A
     a.Y1 = L.Q; a.Y2 = dH; a.X1 = L.K; a.X2 = L.V; a.W1 = L.K;
-    if ((rc = launch_attn<MODE_BQ>(s, F, a))) return rc;
+    if (!dcos) rc = launch_attn<MODE_BQ>(s, F, a);
+    else {      // (+ dA = dz qe + p u of every pair into dcos)
+        AttnArgs b = a;
+        b.dcos = dcos;
+        rc = dcos_add ? launch_attn<MODE_BQ_DCOS_ADD>(s, F, b) : launch_attn<MODE_BQ_DCOS>(s, F, b);
+    }
+    if (rc) return rc;
     hipLaunchKernelGGL(sum_ranges_kernel, dim3((unsigned)((N + RK_ROWS - 1) / RK_ROWS)), dim3(AT), 0, s, (int)N, F, ranges, w.part1, w.stats, p.we, w.dQ, w.r,
                        (const float*)nullptr, (float*)nullptr);
     // dV = alpha^T dO,  dK = dz^T Q
@@ -957,6 +1009,31 @@ extern "C" int mllp_debug_angle_stamps(unsigned long long* host) {
 #endif
 namespace mllp {
 namespace {
+
+// mllp_angle_backward, and with dx / dcos the input gradients: the first layer's dX branch and the edge-attribute
+// gradient of the three BQ sweeps, stored by the first (layer 3) and added by the next two, in that order
+int angle_backward(int64_t N, int F, const float* d_cos, const float* d_x, const float* d_params, float* d_ws,
+                   const float* d_dlogits, float* d_grads, float* d_dx, float* d_dcos, hipStream_t s) {
+    const AngleWs w = angle_carve(d_ws, N, F);
+    const int64_t o2 = conv_size(2, F), o3 = o2 + conv_size(F, F), ofc = o3 + conv_size(F, F);
+    const ConvP p1 = conv_at<ConvP>(d_params, 2, F);
+    const ConvP p2 = conv_at<ConvP>(d_params + o2, F, F);
+    const ConvG g1 = conv_at<ConvG>(d_grads, 2, F);
+    const ConvG g2 = conv_at<ConvG>(d_grads + o2, F, F);
+    const float* fcw = d_params + ofc;
+    int rc;
+    // gconv3 is never called (reference :198 applies gconv2 twice): its gradient is zero
+    MLLP_HIP_TRY(hipMemsetAsync(d_grads + o3, 0, (size_t)conv_size(F, F) * sizeof(float), s));
+    // fc: dW = sum_i dlogit_i H3_i, db = sum_i dlogit_i, dH3 = dlogit w (last node: 0)
+    if ((rc = launch_wcolsum(s, (int)(N - 1), F, w.L[2].H, d_dlogits, nullptr, nullptr, 0.0f, d_grads + ofc, w.gpart))) return rc;
+    hipLaunchKernelGGL(sum_kernel, dim3(1), dim3(AT), 0, s, N - 1, d_dlogits, d_grads + ofc + F);
+    hipLaunchKernelGGL(fc_bwd_kernel, dim3((unsigned)N), dim3(AT), 0, s, F, N - 1, d_dlogits, fcw, w.dA);
+    if ((rc = check("angle fc_bwd"))) return rc;
+    // third layer (gconv2, second use) -> dH2 in dB; second layer (gconv2, first use, accumulates) -> dH1 in dA; first layer
+    if ((rc = conv_backward(s, N, F, F, d_cos, w.L[1].H, p2, w.L[2], w, w.dA, w.dB, g2, false, d_dcos, false))) return rc;
+    if ((rc = conv_backward(s, N, F, F, d_cos, w.L[0].H, p2, w.L[1], w, w.dB, w.dA, g2, true, d_dcos, true))) return rc;
+    return conv_backward(s, N, 2, F, d_cos, d_x, p1, w.L[0], w, w.dA, d_dx, g1, false, d_dcos, true);
+}
 
 }  // namespace
 }  // namespace mllp
@@ -1009,26 +1086,16 @@ extern "C" int mllp_angle_backward(int64_t n_nodes, int feat_dim, const float* d
     REQUIRE(d_cos && d_x && d_params && d_ws && d_dlogits && d_grads, "null argument");
     REQUIRE(n_nodes >= 2 && n_nodes <= 46340, "bad size");
     REQUIRE(feat_ok(feat_dim), "AngleModel: feat_dim must be 16, 32, 64, 128 or 256");
-    const int64_t N = n_nodes;
-    const int F = feat_dim;
-    hipStream_t s = (hipStream_t)stream;
-    const AngleWs w = angle_carve(d_ws, N, F);
-    const int64_t o2 = conv_size(2, F), o3 = o2 + conv_size(F, F), ofc = o3 + conv_size(F, F);
-    const ConvP p1 = conv_at<ConvP>(d_params, 2, F);
-    const ConvP p2 = conv_at<ConvP>(d_params + o2, F, F);
-    const ConvG g1 = conv_at<ConvG>(d_grads, 2, F);
-    const ConvG g2 = conv_at<ConvG>(d_grads + o2, F, F);
-    const float* fcw = d_params + ofc;
-    int rc;
-    // gconv3 is never called (reference :198 applies gconv2 twice): its gradient is zero
-    MLLP_HIP_TRY(hipMemsetAsync(d_grads + o3, 0, (size_t)conv_size(F, F) * sizeof(float), s));
-    // fc: dW = sum_i dlogit_i H3_i, db = sum_i dlogit_i, dH3 = dlogit w (last node: 0)
-    if ((rc = launch_wcolsum(s, (int)(N - 1), F, w.L[2].H, d_dlogits, nullptr, nullptr, 0.0f, d_grads + ofc, w.gpart))) return rc;
-    hipLaunchKernelGGL(sum_kernel, dim3(1), dim3(AT), 0, s, N - 1, d_dlogits, d_grads + ofc + F);
-    hipLaunchKernelGGL(fc_bwd_kernel, dim3((unsigned)N), dim3(AT), 0, s, F, N - 1, d_dlogits, fcw, w.dA);
-    if ((rc = check("angle fc_bwd"))) return rc;
-    // third layer (gconv2, second use) -> dH2 in dB; second layer (gconv2, first use, accumulates) -> dH1 in dA; first layer
-    if ((rc = conv_backward(s, N, F, F, d_cos, w.L[1].H, p2, w.L[2], w, w.dA, w.dB, g2, false))) return rc;
-    if ((rc = conv_backward(s, N, F, F, d_cos, w.L[0].H, p2, w.L[1], w, w.dB, w.dA, g2, true))) return rc;
-    return conv_backward(s, N, 2, F, d_cos, d_x, p1, w.L[0], w, w.dA, nullptr, g1, false);
+    return angle_backward(n_nodes, feat_dim, d_cos, d_x, d_params, d_ws, d_dlogits, d_grads, nullptr, nullptr,
+                          (hipStream_t)stream);
+}
+
+extern "C" int mllp_angle_backward_inputs(int64_t n_nodes, int feat_dim, const float* d_cos, const float* d_x,
+                                          const float* d_params, float* d_ws, const float* d_dlogits, float* d_grads,
+                                          float* d_dx, float* d_dcos, void* stream) {
+    REQUIRE(d_cos && d_x && d_params && d_ws && d_dlogits && d_grads, "null argument");
+    REQUIRE(n_nodes >= 2 && n_nodes <= 46340, "bad size");
+    REQUIRE(feat_ok(feat_dim), "AngleModel: feat_dim must be 16, 32, 64, 128 or 256");
+    return angle_backward(n_nodes, feat_dim, d_cos, d_x, d_params, d_ws, d_dlogits, d_grads, d_dx, d_dcos,
+                          (hipStream_t)stream);
 }
