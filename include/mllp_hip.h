@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define MLLP_ABI_VERSION 5 /* 2: streamed SpMM copy, device-built tiled copies, mllp_gnn_train_step, mllp_graph_invalidate_inputs; 3: streamed copies of the attention sweeps (mllp_graph_*_stream_copy); 4: input gradients (mllp_gnn_backward_inputs); 5: AngleModel input gradients (mllp_angle_backward_inputs) */
+#define MLLP_ABI_VERSION 6 /* 2: streamed SpMM copy, device-built tiled copies, mllp_gnn_train_step, mllp_graph_invalidate_inputs; 3: streamed copies of the attention sweeps (mllp_graph_*_stream_copy); 4: input gradients (mllp_gnn_backward_inputs); 5: AngleModel input gradients (mllp_angle_backward_inputs); 6: the predicted basis (mllp_topm_select, mllp_topm_select_dense) */
 #define MLLP_FEAT 16
 #define MLLP_NUM_PARAMS 4721 /* GNNModel.state_dict(), SURVEY.md appendix A.2 */
 
@@ -313,6 +313,32 @@ int mllp_gnn_train_step(const mllp_graph_t* g, float* d_params, const float* d_x
 int mllp_metrics_scratch_bytes(const mllp_graph_t* g, int64_t* bytes);
 int mllp_topm_metrics(const mllp_graph_t* g, const float* d_logits, const float* d_labels,
                       void* d_scratch, float* d_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The predicted basis itself, without labels (the reference forms this vector before it scores it:
+ * `pred[pred_indices] = 1`, linear_program_experiment.py:146-148).  One workgroup per segment; order and tie rule
+ * are those of mllp_topm_metrics: logits are compared by the key of their bit pattern (negative: all bits
+ * flipped, otherwise: sign bit set), a total order in which -0.0 < +0.0 and every NaN has a place; the
+ * min(m_k, n_k) largest keys are selected, and among keys EQUAL to the m-th largest the lowest indices win.
+ * Each output may be NULL (not computed), but not all three:
+ *   d_mask  uint8 [sum n_k]  1 where the variable is in the predicted basis, 0 elsewhere (every byte written)
+ *   d_index int32 [sum m_k]  at offset sum_{j<k} m_j: the instance-LOCAL column indices of the selected variables,
+ *                            ascending; slots past min(m_k, n_k) hold -1
+ *   d_stats float [n_seg, 2] {threshold, runner_up} = the m-th largest logit and the largest logit NOT selected, both
+ *                            with the bits they have in d_logits.  runner_up = -inf when every column is selected
+ *                            (m_k >= n_k); threshold = +inf when nothing is (m_k = 0 or n_k = 0), and runner_up is then
+ *                            the largest logit (-inf for an empty segment).  threshold - runner_up is a margin a caller
+ *                            can read as confidence; equal bit patterns mean a tie was broken by index.
+ * mllp_topm_select takes the segments and m_k from the graph (instances; m_k = constraints of instance k);
+ * mllp_topm_select_dense is one segment of n logits with m to select (AngleModel: n = N - 1, m = basis_num).
+ * No float arithmetic and no global atomics: results are bitwise reproducible.  A null graph or logits, all three
+ * outputs NULL, or a negative n or m is rejected with a message before any HIP call.  Nothing is allocated; all
+ * work is queued on `stream` (capturable).
+ * ---------------------------------------------------------------------------------------------- */
+int mllp_topm_select(const mllp_graph_t* g, const float* d_logits, uint8_t* d_mask, int32_t* d_index,
+                     float* d_stats, void* stream);
+int mllp_topm_select_dense(int64_t n, int64_t m, const float* d_logits, uint8_t* d_mask, int32_t* d_index,
+                           float* d_stats, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * MPS -> the tensors the reference's loader reads (host only, no GPU needed).

@@ -13,7 +13,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libmllp_hip.so")
 HEADER_PATH = os.path.abspath(os.path.join(_HERE, "..", "include", "mllp_hip.h"))
 
 NUM_PARAMS = 4721
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 
 class MllpError(RuntimeError):
@@ -77,6 +77,8 @@ _PROTOTYPES = {
                                c_void_p]),
     "mllp_metrics_scratch_bytes": (c_int, [c_void_p, POINTER(c_int64)]),
     "mllp_topm_metrics": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mllp_topm_select": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mllp_topm_select_dense": (c_int, [c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mllp_mps_read": (c_int, [c_char_p, c_int, POINTER(c_void_p)]),
     "mllp_lp_dims": (c_int, [c_void_p, POINTER(c_int64)]),
     "mllp_lp_export": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

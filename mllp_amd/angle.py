@@ -234,3 +234,12 @@ class AngleModel(torch.nn.Module):
         if torch.is_grad_enabled() and (g.x.requires_grad or g.cos.requires_grad):
             return _AngleInputsFunction.apply(flat, g.x, g.cos, g, self.feat_dim)
         return _AngleFunction.apply(flat, g, self.feat_dim)
+
+    def predict(self, g, want=("mask", "index", "stats")):
+        """The predicted basis of the graph's instance: forward without autograd + the device top-m selection over the
+        N - 1 variable logits with m = g.basis_num (the reference's `torch.topk(latent_vars, k=basis_num)`,
+        linear_program_experiment.py:98-100, with the tie rule of `LPBatch.predict_basis`).  Returns a `BasisPrediction`."""
+        from .graph import topm_select_dense
+        with torch.no_grad():
+            logits = self.forward(g)
+            return topm_select_dense(logits.contiguous(), int(g.basis_num), want)

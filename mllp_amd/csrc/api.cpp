@@ -564,3 +564,21 @@ extern "C" int mllp_topm_metrics(const mllp_graph_t* g, const float* d_logits, c
     REQUIRE(g && d_logits && d_labels && d_out, "null argument");
     return launch_topm_metrics(g, d_logits, d_labels, d_scratch, d_out, (hipStream_t)stream);
 }
+
+extern "C" int mllp_topm_select(const mllp_graph_t* g, const float* d_logits, uint8_t* d_mask, int32_t* d_index,
+                                float* d_stats, void* stream) {
+    REQUIRE(g && d_logits, "null argument");
+    REQUIRE(d_mask || d_index || d_stats, "null outputs: at least one of mask, index, stats");
+    return launch_topm_select(g->inst_ptr_n, g->inst_ptr_m, g->n_inst, 0, 0, d_logits, d_mask, d_index, d_stats,
+                              (hipStream_t)stream);
+}
+
+extern "C" int mllp_topm_select_dense(int64_t n, int64_t m, const float* d_logits, uint8_t* d_mask, int32_t* d_index,
+                                      float* d_stats, void* stream) {
+    REQUIRE(n >= 0 && m >= 0, "bad size: n and m must not be negative");
+    REQUIRE(d_logits, "null argument");
+    REQUIRE(d_mask || d_index || d_stats, "null outputs: at least one of mask, index, stats");
+    if (n > INT32_MAX || m > INT32_MAX) return fail(MLLP_ERANGE, "mllp_topm_select_dense: sizes exceed int32 indexing");
+    return launch_topm_select(nullptr, nullptr, 1, (int)n, (int)m, d_logits, d_mask, d_index, d_stats,
+                              (hipStream_t)stream);
+}

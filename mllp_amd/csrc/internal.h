@@ -315,6 +315,9 @@ int launch_adam(float* p, const float* g, float* m, float* v, float* state, floa
 int launch_fill_zero(float* p, int64_t n, hipStream_t s);
 int launch_topm_metrics(const mllp_graph* g, const float* logits, const float* labels, void* scratch, float* out,
                         hipStream_t s);
+// select.hip: ptr_n / ptr_m [n_seg + 1] device, or ptr_n == nullptr for ONE segment of n_dense logits, m_dense to select
+int launch_topm_select(const int* ptr_n, const int* ptr_m, int64_t n_seg, int n_dense, int m_dense, const float* logits,
+                       unsigned char* mask, int* index, float* stats, hipStream_t s);
 
 // ---- fused latency-regime path of the whole model (fused_kernels.hip) ---------------------------------
 struct FusedModel {

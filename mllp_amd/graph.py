@@ -639,6 +639,76 @@ class LPBatch:
                                                 _lib.ptr(out), _lib.current_stream()))
         return out
 
+    def predict_basis(self, logits, want=("mask", "index", "stats")):
+        """The predicted basis of every instance, on the device and without labels (mllp_topm_select): the m_k largest
+        logits of instance k (m_k = its constraints), ordered and tie-broken as `topm_metrics` does -- by the key of the
+        bit pattern (-0.0 < +0.0), lowest index first among equal logits.  Returns a `BasisPrediction` whose `.mask`
+        (uint8 [N]), `.index` (int32 [M], instance-local column ids, ascending, at the instance's constraint offset) and
+        `.stats` (float32 [n_inst, 2] = threshold, runner-up) are device tensors; those not named in `want` are None and
+        cost nothing."""
+        want = (want,) if isinstance(want, str) else tuple(want)
+        bad = [w for w in want if w not in ("mask", "index", "stats")]
+        if bad or not want:
+            raise ValueError(f"predict_basis: want must name some of 'mask', 'index', 'stats' (got {want!r})")
+        if not (logits.is_cuda and logits.dtype == torch.float32 and logits.is_contiguous() and logits.numel() == self.N):
+            raise ValueError(f"predict_basis: logits must be a contiguous cuda float32 tensor of {self.N} elements")
+        bufs = _select_outputs(want, self.N, self.M, self.n_inst, logits.device)
+        _lib.check(_lib.lib().mllp_topm_select(self._h, _lib.ptr(logits), *[_lib.ptr(b) for b in bufs], _lib.current_stream()))
+        mask, index, stats = _select_views(bufs, self.N, self.M)
+        return BasisPrediction(mask, index, stats, self.inst_n, self.inst_m, self.names)
+
+
+def _select_outputs(want, n, m, n_seg, dev):
+    """(mask, index, stats) buffers of the select entry points, None where not wanted.  At least one element each: an
+    empty torch tensor has a null pointer, which the library reads as "not wanted"."""
+    return (torch.empty(max(n, 1), dtype=torch.uint8, device=dev) if "mask" in want else None,
+            torch.empty(max(m, 1), dtype=torch.int32, device=dev) if "index" in want else None,
+            torch.empty(max(n_seg, 1), 2, dtype=torch.float32, device=dev) if "stats" in want else None)
+
+
+def _select_views(bufs, n, m):
+    mask, index, stats = bufs
+    return (None if mask is None else mask[:n], None if index is None else index[:m], stats)
+
+
+class BasisPrediction:
+    """What `LPBatch.predict_basis`, `GNNModel.predict` and `AngleModel.predict` return: device tensors `.mask`
+    (uint8, 1 = in the predicted basis), `.index` (int32, per segment the selected local column ids in ascending order,
+    -1 in the slots past min(m, n)) and `.stats` (float32 [segments, 2] = threshold, runner-up); `seg_n` / `seg_m` are
+    the segments' column counts and basis sizes.  Nothing here synchronises except `split`."""
+
+    def __init__(self, mask, index, stats, seg_n, seg_m, names=None):
+        self.mask, self.index, self.stats = mask, index, stats
+        self.seg_n = [int(v) for v in seg_n]
+        self.seg_m = [int(v) for v in seg_m]
+        self.names = list(names) if names is not None else None
+
+    def split(self):
+        """Per instance, the selected column ids as a numpy int32 array (ONE copy back for the whole batch)."""
+        if self.index is None:
+            raise ValueError("BasisPrediction.split needs the index output (want=('index', ...))")
+        idx = self.index.cpu().numpy()
+        off = np.concatenate([[0], np.cumsum(self.seg_m)])
+        return [idx[off[k]:off[k] + min(self.seg_m[k], self.seg_n[k])] for k in range(len(self.seg_m))]
+
+
+def topm_select_dense(logits, m, want=("mask", "index", "stats")):
+    """`LPBatch.predict_basis` for ONE segment without a graph (mllp_topm_select_dense): the m largest of a contiguous
+    cuda float32 vector, same order and tie rule.  `.index` has m entries (-1 past the vector's length)."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    bad = [w for w in want if w not in ("mask", "index", "stats")]
+    if bad or not want:
+        raise ValueError(f"topm_select_dense: want must name some of 'mask', 'index', 'stats' (got {want!r})")
+    if not (logits.is_cuda and logits.dtype == torch.float32 and logits.is_contiguous() and logits.dim() == 1):
+        raise ValueError("topm_select_dense: logits must be a contiguous 1-d cuda float32 tensor")
+    n, m, dev = int(logits.numel()), int(m), logits.device
+    if m < 0:
+        raise ValueError("topm_select_dense: m must not be negative")
+    bufs = _select_outputs(want, n, m, 1, dev)
+    _lib.check(_lib.lib().mllp_topm_select_dense(n, m, _lib.ptr(logits), *[_lib.ptr(b) for b in bufs], _lib.current_stream()))
+    mask, index, stats = _select_views(bufs, n, m)
+    return BasisPrediction(mask, index, stats, [n], [m])
+
 
 def adam_step(params, grads, exp_avg, exp_avg_sq, state, eps=1e-8, grad_scale=1.0):
     """state: cuda float tensor [step, lr, beta1, beta2]; step is incremented on the device."""

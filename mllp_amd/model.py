@@ -252,3 +252,17 @@ class GNNModel(torch.nn.Module):
                 g._lp_batch = None             # edge_attr changed since the batch was built: rebuild it
             return _GNNInputsFunction.apply(flat, *data, g)
         return _GNNFunction.apply(flat, g.lp_batch())
+
+    def predict(self, g, want=("mask", "index", "stats")):
+        """The predicted basis of every instance of `g` (a `BipartiteData`, or an `LPBatch` built from instances):
+        forward without autograd + the device top-m selection (m = the instance's constraints), no labels needed.
+        Returns a `BasisPrediction` (`.mask`, `.index`, `.stats` on the device, `.split()` per instance)."""
+        batch = g.lp_batch() if isinstance(g, BipartiteData) else g
+        if not isinstance(batch, LPBatch):
+            raise TypeError("GNNModel.predict takes a BipartiteData or an LPBatch")
+        with torch.no_grad():
+            flat = self.flat_parameters().contiguous()
+            if not flat.is_cuda:
+                raise _lib.MllpError("GNNModel runs on the MI355X HIP path only: call model.to('cuda') "
+                                     "(there is no CPU fallback)")
+            return batch.predict_basis(batch.forward(flat), want)
