@@ -17,7 +17,8 @@
  *   - every launch is asynchronous on the hipStream_t passed as `stream` (void*; NULL = default
  *     stream); no entry point synchronises except mllp_graph_create_* / mllp_graph_export.
  *   - all launch functions are hipGraph-capturable (no malloc/free/sync inside).
- *   - a mllp_graph_t is immutable after creation except for an internal scratch buffer used by
+ *   - the sparsity pattern of a mllp_graph_t is immutable after creation; its values change only through
+ *     mllp_graph_set_values / mllp_graph_scale_values.  An internal scratch buffer is used by
  *     rows that are split over several workgroups: calls on ONE graph must be stream-ordered.
  *   - feature width is fixed at 16 (reference linear_program_methods.py:206-211), fp32 everywhere.
  *   - there is NO CPU fallback: without a HIP device every launch function fails with MLLP_EHIP.
@@ -31,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MLLP_ABI_VERSION 6 /* 2: streamed SpMM copy, device-built tiled copies, mllp_gnn_train_step, mllp_graph_invalidate_inputs; 3: streamed copies of the attention sweeps (mllp_graph_*_stream_copy); 4: input gradients (mllp_gnn_backward_inputs); 5: AngleModel input gradients (mllp_angle_backward_inputs); 6: the predicted basis (mllp_topm_select, mllp_topm_select_dense) */
+#define MLLP_ABI_VERSION 6 /* 2: streamed SpMM copy, device-built tiled copies, mllp_gnn_train_step, mllp_graph_invalidate_inputs; 3: streamed copies of the attention sweeps (mllp_graph_*_stream_copy); 4: input gradients (mllp_gnn_backward_inputs); 5: AngleModel input gradients (mllp_angle_backward_inputs); 6: the predicted basis (mllp_topm_select, mllp_topm_select_dense); mllp_graph_set_values, _set_values_bytes and _scale_values arrived after 6 WITHOUT a bump: they are additions only (no existing export changed signature or meaning), so every caller built against 6 stays valid; a caller that needs them checks for the symbols */
 #define MLLP_FEAT 16
 #define MLLP_NUM_PARAMS 4721 /* GNNModel.state_dict(), SURVEY.md appendix A.2 */
 
@@ -116,6 +117,33 @@ int mllp_graph_set_path(mllp_graph_t* g, int path);
  * copies inside the capture and leave the cache empty.  mllp_gnn_backward must follow an mllp_gnn_forward on the same
  * workspace with the same path (MLLP_EINVAL otherwise: the two paths lay the workspace out differently).          */
 int mllp_graph_invalidate_inputs(mllp_graph_t* g);
+
+/* New matrix values on the unchanged sparsity pattern, in place and on the device (mllp_amd/csrc/set_values.hip): what
+ * a step on dL/da (mllp_gnn_backward_inputs), a family of LPs that share a pattern, or a row / column rescaling needs,
+ * without building the batch again.
+ *   d_val : nnz floats in the graph's CSR(A) order -- the order of mllp_graph_export(g, 2, ...) and of d_dvalues.
+ * After the call EVERY array of the graph that holds values holds the new ones: both CSR orientations, the fused
+ * path's renumbered entries (and the value half of its gathered layer-1 inputs, so bound inputs stay bound), every
+ * streamed copy (geometries 0-4) and every library-built LDS-tiled copy, byte for byte what a fresh build from d_val
+ * would hold; indices, pointers and padding are not touched.  Explicit zeros are values like any other; nothing inspects
+ * the values.  Deterministic: gathers through int32 position maps, one writer per word, no atomics.
+ * The maps (CSR(A^T) -> CSR(A), shared with mllp_gnn_backward_inputs, and one per re-blocked copy) are library-owned and
+ * built lazily: the FIRST call, and the first call after a copy was built, allocate and synchronise `stream` (make
+ * them outside a capture).  Every other call is a launch function: one device-to-device copy + one launch per array on
+ * `stream` alone, no allocation, no synchronisation, hipGraph-capturable.  A map is freed with its copy (drop / rebuild)
+ * and with the graph.  mllp_graph_set_values_bytes: bytes of the maps of the copies attached now, built or not yet.
+ * The workspace record is cleared as by a path switch: mllp_gnn_backward* needs a new mllp_gnn_forward (MLLP_EINVAL
+ * otherwise; a captured call clears it when it is captured, not when it is replayed).  The folded weights are kept.
+ * MLLP_EINVAL, before anything is written: null g or d_val; a caller-owned LDS-tiled copy is attached
+ * (mllp_graph_attach_tiled) -- drop it or build it with mllp_graph_build_tiled.
+ * mllp_graph_scale_values: a_ij <- (r_i a_ij) s_j in fp32, in that order, i the constraint and j the variable of the
+ * nonzero; d_row_scale [M], d_col_scale [N], either may be NULL (all ones).  For positive r, s the LP (R A S, S c, R b)
+ * has the optimal basis of (A, c, b): scaling x1 = c and x2 = b is the caller's business (they are the caller's
+ * buffers, then mllp_graph_invalidate_inputs).  Works into a library-owned scratch array of nnz floats (allocated by the
+ * first call, counted by _set_values_bytes from then on), then refreshes as mllp_graph_set_values does.         */
+int mllp_graph_set_values(mllp_graph_t* g, const float* d_val, void* stream);
+int mllp_graph_set_values_bytes(const mllp_graph_t* g, int64_t* bytes);
+int mllp_graph_scale_values(mllp_graph_t* g, const float* d_row_scale, const float* d_col_scale, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Plain CSR SpMM (the roofline kernel named in BASELINE.json's metric):

@@ -503,13 +503,7 @@ extern "C" int mllp_gnn_backward_inputs(const mllp_graph_t* g, const float* d_pa
     hipStream_t s = (hipStream_t)stream;
     mllp_graph* gm = const_cast<mllp_graph*>(g);
     int rc;
-    if (d_dvalues && !g->at_pos && g->nnz > 0) {      // once per graph (allocates: make the first such call uncaptured)
-        int* pos = nullptr;
-        MLLP_HIP_TRY(hipMalloc((void**)&pos, (size_t)g->nnz * sizeof(int)));
-        gm->allocs.push_back(pos);
-        if ((rc = build_csc_to_csr(g, pos, s))) return rc;
-        gm->at_pos = pos;
-    }
+    if (d_dvalues && (rc = ensure_at_pos(gm, s))) return rc;      // once per graph (allocates: make the first such call uncaptured)
     float* grads = d_grads ? d_grads : (float*)d_scratch;
     if ((rc = mllp_gnn_backward(g, d_params, d_x1, d_x2, d_ws, d_dlogits, grads, stream))) return rc;
     return input_grads_body(g, d_x1, d_x2, model_ws(g, (float*)d_ws), d_dx1, d_dx2, d_dvalues, s);

@@ -7,6 +7,17 @@ namespace mllp {
 
 constexpr float NEG_BIG = -3.0e38f;  // "minus infinity" sentinel that never produces inf - inf
 
+// the row r with ptr[r] <= e < ptr[r + 1] (empty rows are skipped); ptr[0] <= e < ptr[n_rows]
+__device__ __forceinline__ int row_of(const int* __restrict__ ptr, int n_rows, int e) {
+    int lo = 0, hi = n_rows;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (ptr[mid] <= e) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
 // ---- DPP (data-parallel primitives): lane permutations inside a row of 16 lanes ------------------
 // dpp_ctrl encodings (CDNA ISA): quad_perm = 0x00..0xFF, row_mirror = 0x140, row_half_mirror = 0x141
 template <int CTRL>

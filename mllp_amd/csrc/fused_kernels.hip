@@ -1772,6 +1772,23 @@ static void set_tiers(FusedTiersDev& d, const FusedTiers& t) {
     d.n_block = t.n_block; d.n_wave = t.n_wave; d.n_group = t.n_group; d.n_base = t.n_base;
 }
 
+// {renumbered source id, value bits} of every nonzero of both orientations from A / A^T as they are now: the end of the
+// build, and again whenever mllp_graph_set_values has changed A.val / At.val
+int fused_refill_values(mllp_graph* g, hipStream_t s) {
+    int rc;
+    if (g->M > 0) {
+        hipLaunchKernelGGL(fused_fill_kernel, dim3((unsigned)((g->M + 3) / 4)), dim3(256), 0, s, (int)g->M, g->perm_c, g->A.ptr,
+                           g->A.idx, g->A.val, g->inv_v, g->FA.sptr, reinterpret_cast<int2*>(g->FA.sent));
+        if ((rc = check_launch("fused_fill A"))) return rc;
+    }
+    if (g->N > 0) {
+        hipLaunchKernelGGL(fused_fill_kernel, dim3((unsigned)((g->N + 3) / 4)), dim3(256), 0, s, (int)g->N, g->perm_v, g->At.ptr,
+                           g->At.idx, g->At.val, g->inv_c, g->FAt.sptr, reinterpret_cast<int2*>(g->FAt.sent));
+        if ((rc = check_launch("fused_fill At"))) return rc;
+    }
+    return MLLP_OK;
+}
+
 int fused_graph_build(mllp_graph* g, const int* h_csr_ptr, const int* h_csc_ptr) {
     if (g->fused_built) return MLLP_OK;
     if ((int64_t)g->h_csr_ptr.size() != g->M + 1 && !h_csr_ptr) return fail(MLLP_EINVAL, "fused path: no host row pointers");
@@ -1836,15 +1853,8 @@ int fused_graph_build(mllp_graph* g, const int* h_csr_ptr, const int* h_csc_ptr)
         *g->tail_err_host = 0u;
         MLLP_HIP_TRY(hipHostGetDevicePointer((void**)&g->tail_err_dev, g->tail_err_host, 0));
     }
-    if (g->M > 0) {
-        hipLaunchKernelGGL(fused_fill_kernel, dim3((unsigned)((g->M + 3) / 4)), dim3(256), 0, 0, (int)g->M, g->perm_c, g->A.ptr,
-                           g->A.idx, g->A.val, g->inv_v, A.sptr, reinterpret_cast<int2*>(A.sent));
-        if ((rc = check_launch("fused_fill A"))) return rc;
-    }
+    if ((rc = fused_refill_values(g, 0))) return rc;
     if (g->N > 0) {
-        hipLaunchKernelGGL(fused_fill_kernel, dim3((unsigned)((g->N + 3) / 4)), dim3(256), 0, 0, (int)g->N, g->perm_v, g->At.ptr,
-                           g->At.idx, g->At.val, g->inv_c, At.sptr, reinterpret_cast<int2*>(At.sent));
-        if ((rc = check_launch("fused_fill At"))) return rc;
         hipLaunchKernelGGL(fused_permute_kernel, dim3(256), dim3(256), 0, 0, (int)g->N, g->perm_v, g->inv_n, g->inv_n_p);
         if ((rc = check_launch("fused_permute inv_n"))) return rc;
     }

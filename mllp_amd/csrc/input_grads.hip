@@ -17,17 +17,6 @@
 
 namespace mllp {
 
-// the row r with ptr[r] <= e < ptr[r + 1] (empty rows are skipped); ptr[0] <= e < ptr[n_rows]
-__device__ __forceinline__ int row_of(const int* __restrict__ ptr, int n_rows, int e) {
-    int lo = 0, hi = n_rows;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (ptr[mid] <= e) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
 struct EdgeArgs {
     const int* __restrict__ ptr;
     const int* __restrict__ idx;

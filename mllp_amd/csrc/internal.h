@@ -50,6 +50,7 @@ struct Tiled {
     const int* ptr2 = nullptr;       // [n_tb * rows_per_tile + 1] offsets of the length-sorted positions
     const int* perm = nullptr;       // [n_tb * rows_per_tile] row of each sorted position
     const int* ent = nullptr;        // [nnz][2] {col_local * 64 (byte offset of the source row in the staged block), value bits}
+    int* vmap = nullptr;             // [nnz] value map of mllp_graph_set_values (set_values.hip; library-built copies)
 };
 // variants of the LDS-tiled copy (mllp_graph_attach_tiled / _build_tiled): the sweep whose geometry each one has
 constexpr int TILED_SPMM = 0;     // plain SpMM
@@ -70,6 +71,7 @@ struct StreamCopy {
     int* rows = nullptr;        // [n_tb * 8 * 16] int4
     int* hdr = nullptr;         // [n_tb * 8] int4
     int* ent = nullptr;         // [(n_groups + S_K0) * 64 * S_ENT]
+    int* vmap = nullptr;        // [(n_groups + S_K0) * 64 * 2] value map of mllp_graph_set_values (set_values.hip)
     double build_seconds = 0.0;
 };
 
@@ -85,6 +87,7 @@ struct LaneCopy {
     int* whdr = nullptr;        // [n_tb][L1_NW][2]
     unsigned* offs = nullptr;   // [(n_groups + L1_PADG) * 64 * 2]
     float* vals = nullptr;      // [(n_groups + L1_PADG) * 64 * 4]
+    int* vmap = nullptr;        // [(n_groups + L1_PADG) * 64 * 4] value map of mllp_graph_set_values (set_values.hip)
     double build_seconds = 0.0;
 };
 
@@ -183,7 +186,9 @@ struct mllp_graph {
     const void* folded_params = nullptr;
     // input gradients: CSR position in A of every nonzero of A^T, built on the first mllp_gnn_backward_inputs call that
     // asks for dL/da (in `allocs`)
+    // (mllp_graph_set_values refreshes At.val through the same map and builds it when it runs first)
     int* at_pos = nullptr;
+    float* scale_buf = nullptr;  // [nnz] the scaled values of mllp_graph_scale_values, made on its first call (in `allocs`)
     // second stream + events: the two convs of a layer (one per orientation) and the single-workgroup
     // finalize kernels run beside the main stream (fork/join by events, also under hipGraph capture)
     hipStream_t aux = nullptr;
@@ -296,6 +301,7 @@ int launch_attn_bwd_src1(const Orient& o_src_major, const ConvWs& w, const float
 int launch_edge_grad(const Orient& o, int64_t nnz, int cin, const ConvWs& w, const float* x_src, const int* pos, float* dval,
                      int accumulate, hipStream_t s);
 int build_csc_to_csr(const mllp_graph* g, int* pos, hipStream_t s);
+int ensure_at_pos(mllp_graph* g, hipStream_t s);   // set_values.hip: g->at_pos, built once per graph (allocates)
 int launch_layer1_dst_grads(const ConvWs& wv, const float* gv, float* dx1, int64_t n, const ConvWs& wc, const float* gc,
                             float* dx2, int64_t m, hipStream_t s);
 int launch_param_stats(int cin, int64_t n_dst, const ConvWs& w, const float* x_dst, const float* g, hipStream_t s);
@@ -332,6 +338,7 @@ struct FusedModel {
 };
 int fused_graph_build(mllp_graph* g, const int* h_csr_ptr, const int* h_csc_ptr);   // allocates: creation / set_path only
 int fused_grid(const mllp_graph* g);
+int fused_refill_values(mllp_graph* g, hipStream_t s);   // sent of both orientations from A.val / At.val again (launches only)
 int fused_bind(mllp_graph* g, const float* x1, const float* x2, const float* labels, hipStream_t s);
 // head_mode 1: logits (h3v kept), 2: logits + BCE + masked dL/dh3v in d3v + fc partials
 int fused_forward(mllp_graph* g, const FusedModel& m, int head_mode, hipStream_t s, bool skip_prep = false);

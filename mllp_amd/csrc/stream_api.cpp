@@ -60,11 +60,13 @@ void copy_free(const std::vector<CopyArray>& arrays) {
 // (the pointer members do not depend on the geometry)
 void stream_copy_free(StreamCopy& sc) {
     copy_free(stream_copy_arrays(sc, STREAM_GEOM_SPMM));
+    if (sc.vmap) (void)hipFree(sc.vmap);
     sc = StreamCopy();
 }
 
 void lane_copy_free(LaneCopy& lc) {
     copy_free(lane_copy_arrays(lc));
+    if (lc.vmap) (void)hipFree(lc.vmap);
     lc = LaneCopy();
 }
 

@@ -36,6 +36,7 @@ std::vector<CopyArray> tiled_arrays(Tiled& tl, int variant, int64_t nnz) {
 // (a copy attached from borrowed arrays is not freed; the pointer members do not depend on the variant)
 void tiled_free(Tiled& tl) {
     if (tl.owned) copy_free(tiled_arrays(tl, TILED_SPMM, 0));
+    if (tl.vmap) (void)hipFree(tl.vmap);
     tl = Tiled();
 }
 

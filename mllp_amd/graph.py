@@ -217,6 +217,41 @@ class LPBatch:
                 _lib.check(_lib.lib().mllp_graph_invalidate_inputs(self._h))
             self._in_versions = v
 
+    def set_values(self, values):
+        """New matrix values on the same sparsity pattern (mllp_graph_set_values): `values` is a cuda float32 tensor of
+        nnz elements in the CSR order of A (`export(2)`, the order of `backward_inputs`' dvalues).  Every array of the batch
+        that holds values -- both orientations, the fused path's copies, every streamed and device-built tiled copy -- is
+        refreshed on the device; a backward needs a new forward afterwards.  The first call (and the first after a copy
+        was built) allocates the position maps and synchronises; later calls only launch."""
+        if not (values.is_cuda and values.dtype == torch.float32 and values.is_contiguous() and values.numel() == self.nnz):
+            raise ValueError(f"set_values: values must be a contiguous cuda float32 tensor of {self.nnz} elements")
+        _lib.check(_lib.lib().mllp_graph_set_values(self._h, _lib.ptr(values) if self.nnz else _lib.ptr(self.x1),
+                                                    _lib.current_stream()))
+        self._fwd_token = getattr(self, "_fwd_token", 0) + 1      # (model.py: a pending autograd backward must not run)
+        return self
+
+    def set_values_bytes(self):
+        """Bytes of the position maps that `set_values` keeps for the copies attached now (mllp_graph_set_values_bytes)."""
+        n = c_int64()
+        _lib.check(_lib.lib().mllp_graph_set_values_bytes(self._h, ctypes.byref(n)))
+        return n.value
+
+    def rescale(self, row_scale=None, col_scale=None):
+        """a_ij <- (r_i a_ij) s_j, x2 <- x2 r, x1 <- x1 s, in place (mllp_graph_scale_values): for positive scales the
+        same LP in other units, with the same optimal basis -- the label-preserving augmentation of this model's data.
+        `row_scale` [M] / `col_scale` [N] are cuda float32 tensors; None = ones."""
+        for t, n, what in ((row_scale, self.M, "row_scale"), (col_scale, self.N, "col_scale")):
+            if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n):
+                raise ValueError(f"rescale: {what} must be a contiguous cuda float32 tensor of {n} elements")
+        _lib.check(_lib.lib().mllp_graph_scale_values(self._h, _lib.ptr(row_scale), _lib.ptr(col_scale),
+                                                      _lib.current_stream()))
+        self._fwd_token = getattr(self, "_fwd_token", 0) + 1
+        if row_scale is not None:
+            self.x2.mul_(row_scale.reshape(-1))
+        if col_scale is not None:
+            self.x1.mul_(col_scale.reshape(-1))
+        return self.invalidate_inputs()
+
     def set_path(self, path):
         """0 = by size, 1 = generic / LDS-tiled sweeps, 2 = fused latency-regime kernels (whole-model calls only)."""
         _lib.check(_lib.lib().mllp_graph_set_path(self._h, int(path)))

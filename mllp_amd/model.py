@@ -32,7 +32,8 @@ class BipartiteData:
     """Container with the attributes of the reference's PyG `Data` subclass
     (linear_program_methods.py:60-72): `edge_index` (2,E) rows [variable ; constraint], `x1` (n,1),
     `x2` (m,1), `edge_attr` (E,1).  `__inc__` keeps the block-diagonal batching rule; `batch()` applies
-    it to a list of graphs.  The HBM-resident `LPBatch` is built lazily, once, and cached."""
+    it to a list of graphs.  The HBM-resident `LPBatch` is built lazily, once, and cached; when only `edge_attr`
+    changes afterwards its values are refreshed in place (`LPBatch.set_values`), the batch is not built again."""
 
     def __init__(self, edge_index, x_src, x_dst, edge_attr):
         self.edge_index = edge_index
@@ -40,7 +41,7 @@ class BipartiteData:
         self.x2 = x_dst
         self.edge_attr = edge_attr
         self._lp_batch = None
-        self._csr_order = self._csr_order_dev = self._ea_key = None   # set with the LPBatch (lp_batch)
+        self._csr_order = self._csr_order_dev = self._ea_key = self._pat_key = None   # set with the LPBatch (lp_batch)
         self._sizes = None   # [(m_k, n_k)] when this object is a batch of several instances
 
     def __inc__(self, key, value=None):
@@ -73,7 +74,21 @@ class BipartiteData:
     def _edge_attr_key(self):
         return (self.edge_attr.data_ptr(), self.edge_attr._version)
 
+    def _pattern_key(self):
+        return (id(self.edge_index), tuple(self.edge_index.shape), self.edge_index.device, self.x1.size(0), self.x2.size(0),
+                self.edge_attr.numel())
+
     def lp_batch(self) -> LPBatch:
+        if self._lp_batch is not None and self._pattern_key() != self._pat_key:
+            self._lp_batch = None              # another edge_index, other sizes or another device: build again
+        if self._lp_batch is not None and self._ea_key != self._edge_attr_key():
+            # only edge_attr changed (an optimiser step on it, new coefficients on the same pattern): new values on the
+            # device, in CSR order through the permutation kept from the build -- no host round trip, no re-blocking
+            ea = self.edge_attr.detach().reshape(-1).to(device=self._lp_batch.x1.device, dtype=torch.float32)
+            if self._csr_order_dev is None or self._csr_order_dev.device != ea.device:
+                self._csr_order_dev = torch.from_numpy(self._csr_order).to(ea.device)
+            self._lp_batch.set_values(ea[self._csr_order_dev].contiguous())
+            self._ea_key = self._edge_attr_key()
         if self._lp_batch is None:
             sizes = self._sizes or [(self.x2.size(0), self.x1.size(0))]
             ei = self.edge_index.detach().cpu().numpy()
@@ -98,6 +113,7 @@ class BipartiteData:
             self._csr_order = order
             self._csr_order_dev = None
             self._ea_key = self._edge_attr_key()
+            self._pat_key = self._pattern_key()
         return self._lp_batch
 
     def csr_to_edge_order(self, values_csr):
@@ -248,8 +264,6 @@ class GNNModel(torch.nn.Module):
                                  "(there is no CPU fallback)")
         data = (g.x1, g.x2, g.edge_attr)
         if torch.is_grad_enabled() and any(t.requires_grad for t in data):
-            if g._lp_batch is not None and g._ea_key != g._edge_attr_key():
-                g._lp_batch = None             # edge_attr changed since the batch was built: rebuild it
             return _GNNInputsFunction.apply(flat, *data, g)
         return _GNNFunction.apply(flat, g.lp_batch())
 
