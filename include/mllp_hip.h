@@ -393,13 +393,18 @@ int mllp_lp_free(mllp_lp_t* lp);
  * linear_program_experiment.py:81-114): three TransformerConv layers (2 -> F, F -> F, and the same F -> F layer
  * again) + Linear(F, 1) on the COMPLETE directed graph over the N = n + 1 nodes of one instance, edge attribute =
  * cosine similarity (build_graph_from_Q_sets, :119-130).  Dense attention with a scalar edge bias:
- *   d_cos    [N, N]  cosine matrix, row = target node, column = source node; SYMMETRIC (the kernels read either triangle);
- *                    the diagonal is ignored: no self loops
+ *   d_cos    [N, N]  cosine matrix, row = target node, column = source node; SYMMETRIC: every sweep reads the whole
+ *                    matrix, the forward and the query sweep of the backward d_cos[i][j] for the edge j -> i, the key /
+ *                    value sweep of the backward d_cos[j][i] (the forward alone of a non-symmetric matrix is the per-edge
+ *                    model's); the diagonal may hold any FINITE value and is ignored: no self loops (an inf or NaN
+ *                    there reaches the outputs through 0 * d_cos[i][i])
  *   d_x      [N, 2]  node features {coef, |Q row|}
  *   d_params flat fp32 in PyG state_dict order: gconv1, gconv2, gconv3 (each lin_key {W [F,C], b [F]}, lin_query,
  *            lin_value, lin_edge {W [F,1]}, lin_skip {W, b}; C = 2 for gconv1, F otherwise), fc {W [1,F], b [1]}
  *            (mllp_angle_num_params floats; gconv3 is never called by the reference's forward: its gradient is 0)
- *   d_ws     mllp_angle_workspace_floats floats, kept between forward and backward
+ *   d_ws     mllp_angle_workspace_floats floats, kept between forward and backward; may be uninitialised (whatever
+ *            it holds, NaN included, the same bits come out); d_ws and d_params 16-byte aligned (they are read in 16-byte
+ *            pieces; MLLP_EINVAL otherwise); d_logits, d_dx and d_dcos need only their natural 4-byte alignment
  *   forward : d_logits [N - 1] = fc(h)[:-1]            backward: d_dlogits [N - 1] -> d_grads (layout of d_params)
  * Hand-written kernels on the fp32 matrix cores (v_mfma_f32_16x16x4_f32): flash-attention-style forward / backward
  * sweeps that keep no N x N matrix in HBM (the backward recomputes the weights from the saved row max / row sum) and one
@@ -421,7 +426,7 @@ int mllp_angle_backward(int64_t n_nodes, int feat_dim, const float* d_cos, const
  *     the reference's edge j -> i), diagonal written as 0.  Each may be NULL (not computed, costs nothing); both NULL is
  *     exactly mllp_angle_backward.  Overwritten, not accumulated.  Bitwise reproducible: fixed launch order on `stream`,
  *     the three layers' terms summed in a fixed order, no float atomics.
- *   The sweeps read either triangle of d_cos: d_dcos is the gradient of the per-edge model only for a symmetric d_cos.
+ *   The key / value sweep reads d_cos transposed (above): d_dcos and d_grads are the per-edge model's only for a symmetric d_cos.
  * A null cos, x, params, workspace, dlogits or grads, a bad size or a bad feat_dim is rejected with a message before any
  * HIP call.  All work is queued on `stream`; nothing is allocated.                                                     */
 int mllp_angle_backward_inputs(int64_t n_nodes, int feat_dim, const float* d_cos, const float* d_x,

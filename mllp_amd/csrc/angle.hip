@@ -995,6 +995,8 @@ int conv_backward(hipStream_t s, int64_t N, int C, int F, const float* A, const 
 }
 
 bool feat_ok(int F) { return F == 16 || F == 32 || F == 64 || F == 128 || F == 256; }
+// the workspace's arrays and the lin_edge weights are read in 16-byte pieces
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 }  // namespace mllp
@@ -1064,6 +1066,7 @@ extern "C" int mllp_angle_forward(int64_t n_nodes, int feat_dim, const float* d_
     REQUIRE(d_cos && d_x && d_params && d_ws && d_logits, "null argument");
     REQUIRE(n_nodes >= 2 && n_nodes <= 46340, "bad size");
     REQUIRE(feat_ok(feat_dim), "AngleModel: feat_dim must be 16, 32, 64, 128 or 256");
+    REQUIRE(aligned16(d_ws) && aligned16(d_params), "d_ws and d_params must be 16-byte aligned");
     const int64_t N = n_nodes;
     const int F = feat_dim;
     hipStream_t s = (hipStream_t)stream;
@@ -1086,6 +1089,7 @@ extern "C" int mllp_angle_backward(int64_t n_nodes, int feat_dim, const float* d
     REQUIRE(d_cos && d_x && d_params && d_ws && d_dlogits && d_grads, "null argument");
     REQUIRE(n_nodes >= 2 && n_nodes <= 46340, "bad size");
     REQUIRE(feat_ok(feat_dim), "AngleModel: feat_dim must be 16, 32, 64, 128 or 256");
+    REQUIRE(aligned16(d_ws) && aligned16(d_params), "d_ws and d_params must be 16-byte aligned");
     return angle_backward(n_nodes, feat_dim, d_cos, d_x, d_params, d_ws, d_dlogits, d_grads, nullptr, nullptr,
                           (hipStream_t)stream);
 }
@@ -1096,6 +1100,7 @@ extern "C" int mllp_angle_backward_inputs(int64_t n_nodes, int feat_dim, const f
     REQUIRE(d_cos && d_x && d_params && d_ws && d_dlogits && d_grads, "null argument");
     REQUIRE(n_nodes >= 2 && n_nodes <= 46340, "bad size");
     REQUIRE(feat_ok(feat_dim), "AngleModel: feat_dim must be 16, 32, 64, 128 or 256");
+    REQUIRE(aligned16(d_ws) && aligned16(d_params), "d_ws and d_params must be 16-byte aligned");
     return angle_backward(n_nodes, feat_dim, d_cos, d_x, d_params, d_ws, d_dlogits, d_grads, d_dx, d_dcos,
                           (hipStream_t)stream);
 }

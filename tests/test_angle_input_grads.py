@@ -2,31 +2,22 @@
 attributes: cos[i, j] belongs to the reference's edge j -> i), through `AngleModel` / `AngleGraph` and through the C ABI
 `mllp_angle_backward_inputs`.
 
-Oracles: fp64 autograd through the oracle's literal TransformerConv on the explicit N (N - 1) edge list (as
-tests/test_angle.py), and, where that list is too large (25fv47: 3.5 M edges), a dense fp64 restatement of the same model
-that this file first checks against the edge-list oracle on the small cases.  Tolerance as tests/test_angle.py:
+Oracles (tests/angle_oracle.py): fp64 autograd through the oracle's literal TransformerConv on the explicit N (N - 1) edge
+list (as tests/test_angle.py), and, where that list is too large (25fv47: 3.5 M edges), a dense fp64 restatement of the same
+model that this file first checks against the edge-list oracle on the small cases.  Tolerance as tests/test_angle.py:
 max|diff| / max|ref| <= 1e-5 for logits, 5e-5 for gradients.  The host-only test at the top runs without a GPU.
 """
 import ctypes
-import math
 
 import numpy as np
 import pytest
 import torch
 
+from angle_oracle import RTOL_GRAD, RTOL_LOGITS, close
+from angle_oracle import oracle as _oracle
 from mllp_amd import _lib
-from oracle import pyg_restatement as o1
 
-RTOL_LOGITS, RTOL_GRAD = 1e-5, 5e-5
 gpu = pytest.mark.gpu
-
-
-def close(got, want, rtol, what=""):
-    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
-    assert got.shape == want.shape, f"{what}: {got.shape} vs {want.shape}"
-    assert np.isfinite(got).all(), what
-    err = float(np.abs(got - want).max()) / max(float(np.abs(want).max()), 1e-30)
-    assert err <= rtol, f"{what}: max|diff|/max|ref| = {err:.3e} > {rtol}"
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -45,65 +36,6 @@ def test_angle_backward_inputs_rejects_bad_arguments_without_gpu():
     assert b"size" in L.mllp_last_error()
     assert L.mllp_angle_backward_inputs(52, 24, p, p, p, p, p, p, None, None, None) == -1
     assert b"feat_dim" in L.mllp_last_error()
-
-
-# ---------------------------------------------------------------------------------------------------
-# oracles
-# ---------------------------------------------------------------------------------------------------
-def _edge_forward(sd, x, ei, ea):
-    """reference linear_program_methods.py:195-200 with the oracle's literal TransformerConv on the edge list"""
-    h = torch.relu(o1.transformer_conv(sd, "gconv1", x, x, ei, ea))
-    h = torch.relu(o1.transformer_conv(sd, "gconv2", h, h, ei, ea))
-    h = torch.relu(o1.transformer_conv(sd, "gconv2", h, h, ei, ea))
-    return (h @ sd["fc.weight"].T + sd["fc.bias"]).squeeze(-1)[:-1]
-
-
-def _dense_conv(sd, prefix, X, A):
-    """the same TransformerConv on the complete graph as dense matrices: target i (row), source j (column),
-    A[i, j] = attribute of edge j -> i, no self loops; softmax as torch_geometric.utils.softmax"""
-    W = lambda name: sd[f"{prefix}.{name}"]
-    F = W("lin_query.weight").shape[0]
-    Q = X @ W("lin_query.weight").T + W("lin_query.bias")
-    K = X @ W("lin_key.weight").T + W("lin_key.bias")
-    V = X @ W("lin_value.weight").T + W("lin_value.bias")
-    we = W("lin_edge.weight")[:, 0]
-    S = (Q @ K.T + (Q @ we)[:, None] * A) / math.sqrt(F)
-    eye = torch.eye(A.shape[0], dtype=torch.bool)
-    S = S.masked_fill(eye, float("-inf"))
-    P = (S - S.detach().amax(dim=1, keepdim=True)).exp()
-    P = P / (P.sum(dim=1, keepdim=True) + 1e-16)
-    return P @ V + (P * A).sum(dim=1, keepdim=True) * we[None, :] + X @ W("lin_skip.weight").T + W("lin_skip.bias")
-
-
-def _dense_forward(sd, x, A):
-    h = torch.relu(_dense_conv(sd, "gconv1", x, A))
-    h = torch.relu(_dense_conv(sd, "gconv2", h, A))
-    h = torch.relu(_dense_conv(sd, "gconv2", h, A))
-    return (h @ sd["fc.weight"].T + sd["fc.bias"]).squeeze(-1)[:-1]
-
-
-def _oracle(model, g, y, dense):
-    """fp64 autograd: (logits, dx [N, 2], dcos [N, N] with zero diagonal, {name: parameter gradient})"""
-    sd = {k: v.detach().cpu().double().requires_grad_(True) for k, v in model.state_dict().items()}
-    x = g.x.detach().cpu().double().requires_grad_(True)
-    N = g.num_nodes
-    if dense:
-        A = g.cos.detach().cpu().double().requires_grad_(True)
-        z = _dense_forward(sd, x, A)
-    else:
-        ei = g.edge_index.cpu()
-        ea = g.cos.detach().cpu().double()[ei[1], ei[0]].unsqueeze(-1).requires_grad_(True)
-        z = _edge_forward(sd, x, ei, ea)
-    loss = torch.nn.functional.binary_cross_entropy_with_logits(z, y.cpu().double())
-    names = list(sd)
-    leaves = [x, A if dense else ea] + [sd[k] for k in names]
-    grads = torch.autograd.grad(loss, leaves, allow_unused=True)
-    if dense:
-        dcos = grads[1]
-    else:
-        dcos = torch.zeros(N, N, dtype=torch.float64)
-        dcos[ei[1], ei[0]] = grads[1][:, 0]
-    return z.detach(), grads[0], dcos, dict(zip(names, grads[2:]))
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -180,12 +112,14 @@ def test_input_grads_vs_edge_list_oracle(case):
 
 @gpu
 def test_input_grads_full_size_vs_dense_oracle():
-    """25fv47, N = 1 877, F = 256: several X ranges per group of Y nodes, rows not 16-byte aligned"""
+    """25fv47, N = 1 877, F = 256: several X ranges per group of Y nodes, rows not 16-byte aligned; the weight-gradient
+    GEMM runs with 7 K splits"""
     g, y, F = _graph("25fv47_F256")
     model = _model(F)
     logits, dx, dcos, _ = _run(model, g, y)
-    z, rdx, rdcos, _ = _oracle(model, g, y, dense=True)
+    z, rdx, rdcos, rparams = _oracle(model, g, y, dense=True)
     close(logits.cpu().numpy(), z.numpy(), RTOL_LOGITS, "logits")
+    _check_params(model, rparams)
     close(dx.cpu().numpy(), rdx.numpy(), RTOL_GRAD, "dx")
     close(dcos.cpu().numpy(), rdcos.numpy(), RTOL_GRAD, "dcos")
     assert bool((dcos.diagonal() == 0).all())
