@@ -1759,9 +1759,10 @@ static int check_launch(const char* what) {
 }
 
 template <class T>
-static int dev_alloc(mllp_graph* g, size_t count, T** out, const T* host = nullptr) {
+static int dev_alloc(mllp_graph* g, size_t count, T** out, const T* host = nullptr, size_t room = 1) {
     void* p = nullptr;
-    MLLP_HIP_TRY(hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)));
+    MLLP_HIP_TRY(hipMalloc(&p, std::max<size_t>(count, room) * sizeof(T)));
+    if (count < room) MLLP_HIP_TRY(hipMemset(p, 0, room * sizeof(T)));     // (what a load without a row reads is defined)
     g->allocs.push_back(p);
     if (host && count) MLLP_HIP_TRY(hipMemcpy(p, host, count * sizeof(T), hipMemcpyHostToDevice));
     *out = static_cast<T*>(p);
@@ -1836,12 +1837,16 @@ int fused_graph_build(mllp_graph* g, const int* h_csr_ptr, const int* h_csc_ptr)
             if ((rc = dev_alloc(g, l1.order.size(), &d.lst1, l1.order.data()))) return rc;
         }
     }
-    if ((rc = dev_alloc(g, (size_t)g->M + 1, &A.sptr, hc.sptr.data()))) return rc;
-    if ((rc = dev_alloc(g, (size_t)g->N + 1, &At.sptr, hv.sptr.data()))) return rc;
-    if ((rc = dev_alloc(g, (size_t)g->nnz * 2, &A.sent))) return rc;
-    if ((rc = dev_alloc(g, (size_t)g->nnz * 2, &At.sent))) return rc;
-    if ((rc = dev_alloc(g, (size_t)g->nnz * 2, &A.sax))) return rc;
-    if ((rc = dev_alloc(g, (size_t)g->nnz * 2, &At.sax))) return rc;
+    // The sweeps load without a branch where a unit has no row or no entry (item_request: sptr[0] and sptr[1];
+    // first_entries_any, ent8_load: entry 0 as int2 / float2), so every one of these arrays has room for that load even in
+    // a batch without nonzeros (dev_alloc alone rounds a count of 0 up to ONE int / float; tests/test_fused_oracle.py runs
+    // such a batch).  sptr gets the same room for an orientation without rows, which no test reaches.
+    if ((rc = dev_alloc(g, (size_t)g->M + 1, &A.sptr, hc.sptr.data(), 2))) return rc;
+    if ((rc = dev_alloc(g, (size_t)g->N + 1, &At.sptr, hv.sptr.data(), 2))) return rc;
+    if ((rc = dev_alloc(g, (size_t)g->nnz * 2, &A.sent, (const int*)nullptr, 2))) return rc;
+    if ((rc = dev_alloc(g, (size_t)g->nnz * 2, &At.sent, (const int*)nullptr, 2))) return rc;
+    if ((rc = dev_alloc(g, (size_t)g->nnz * 2, &A.sax, (const float*)nullptr, 2))) return rc;
+    if ((rc = dev_alloc(g, (size_t)g->nnz * 2, &At.sax, (const float*)nullptr, 2))) return rc;
     if ((rc = dev_alloc(g, (size_t)g->N, &g->inv_n_p))) return rc;
     if ((rc = dev_alloc(g, (size_t)g->N, &g->x1_p))) return rc;
     if ((rc = dev_alloc(g, (size_t)g->M, &g->x2_p))) return rc;
