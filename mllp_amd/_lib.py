@@ -12,8 +12,31 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libmllp_hip.so")
 HEADER_PATH = os.path.abspath(os.path.join(_HERE, "..", "include", "mllp_hip.h"))
 
-NUM_PARAMS = 4721
 ABI_VERSION = 6
+
+# Layout of the flat parameter vector: GNNModel.state_dict() order, the same table as
+# csrc/internal.h.  Six TransformerConvs (the last, gconv3_s2w, is never called), then fc (weight [16], bias).
+FEAT = 16
+CONV_NAMES = ("gconv1_w2s", "gconv1_s2w", "gconv2_w2s", "gconv2_s2w", "gconv3_w2s", "gconv3_s2w")
+CONV_CIN = (1, 1, 16, 16, 16, 16)
+
+
+def conv_param_count(cin):
+    """Parameters of one conv: key, query, value and skip (weight [16, cin] + bias [16]) and the edge weight [16]."""
+    return 4 * FEAT * cin + 5 * FEAT
+
+
+_CONV_OFFSETS = [0]
+for _cin in CONV_CIN:
+    _CONV_OFFSETS.append(_CONV_OFFSETS[-1] + conv_param_count(_cin))
+FC_OFFSET = _CONV_OFFSETS[-1]
+NUM_PARAMS = FC_OFFSET + FEAT + 1
+
+
+def conv_param_slice(conv):
+    """Slice of the flat parameter (or gradient) vector that holds one conv, by name or by index in CONV_NAMES."""
+    i = CONV_NAMES.index(conv) if isinstance(conv, str) else range(len(CONV_NAMES))[conv]
+    return slice(_CONV_OFFSETS[i], _CONV_OFFSETS[i + 1])
 
 
 class MllpError(RuntimeError):

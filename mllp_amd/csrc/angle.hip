@@ -1042,11 +1042,6 @@ int angle_backward(int64_t N, int F, const float* d_cos, const float* d_x, const
 
 using namespace mllp;
 
-#define REQUIRE(cond, msg) \
-    do {                   \
-        if (!(cond)) return fail(MLLP_EINVAL, msg); \
-    } while (0)
-
 extern "C" int mllp_angle_num_params(int feat_dim, int64_t* out) {
     REQUIRE(out && feat_dim >= 1, "bad argument");
     *out = conv_size(2, feat_dim) + 2 * conv_size(feat_dim, feat_dim) + feat_dim + 1;

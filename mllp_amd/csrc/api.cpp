@@ -8,27 +8,33 @@ namespace mllp {
 
 static inline int64_t up16(int64_t x) { return (x + 15) & ~int64_t(15); }
 
-int64_t conv_ws_floats(int64_t n, int cin) {
+ConvWs conv_ws_carve(float* base, int64_t n, int cin, float** end) {
     const int64_t recw = cin == 16 ? REC_W : 8;
-    return up16(DERIVED_W) + up16(n * cin) + up16(n) + up16(n * cin) + up16(n * 4) + up16(n * recw) + up16(n * cin) +
-           up16(n * 2) + up16((int64_t)STAT_BLOCKS_MAX * STAT_FLOATS) + up16(STAT_FLOATS);
+    float* p = base;
+    auto take = [&](int64_t floats) {
+        float* q = p;
+        p += up16(floats);
+        return q;
+    };
+    ConvWs w;
+    w.derived = take(DERIVED_W);
+    w.qp = take(n * cin);
+    w.t = take(n);
+    w.Z = take(n * cin);
+    w.aux = take(n * 4);
+    w.rec = take(n * recw);
+    w.dqp = take(n * cin);
+    w.dsdt = take(n * 2);
+    w.stats = take((int64_t)STAT_BLOCKS_MAX * STAT_FLOATS);
+    w.red = take(STAT_FLOATS);
+    if (end) *end = p;
+    return w;
 }
 
-ConvWs conv_ws_carve(float* base, int64_t n, int cin) {
-    const int64_t recw = cin == 16 ? REC_W : 8;
-    ConvWs w;
-    float* p = base;
-    w.derived = p; p += up16(DERIVED_W);
-    w.qp = p; p += up16(n * cin);
-    w.t = p; p += up16(n);
-    w.Z = p; p += up16(n * cin);
-    w.aux = p; p += up16(n * 4);
-    w.rec = p; p += up16(n * recw);
-    w.dqp = p; p += up16(n * cin);
-    w.dsdt = p; p += up16(n * 2);
-    w.stats = p; p += up16((int64_t)STAT_BLOCKS_MAX * STAT_FLOATS);
-    w.red = p;
-    return w;
+int64_t conv_ws_floats(int64_t n, int cin) {
+    float* end;
+    conv_ws_carve(nullptr, n, cin, &end);
+    return end - (float*)nullptr;
 }
 
 static int conv_forward(const mllp_graph* g, bool dst_is_var, int cin, const float* cp, const ConvWs& w,
@@ -40,7 +46,6 @@ static int conv_forward(const mllp_graph* g, bool dst_is_var, int cin, const flo
     return launch_attn_fwd(o, cin, cp, w, x_src, x_dst, h_out, o.scratch, s);
 }
 
-// dh is overwritten with the ReLU-masked gradient; dx_* may be null; acc bit0 -> dx_dst, bit1 -> dx_src
 // fork: work queued on `to` after this point waits for everything queued on `from` so far (capturable)
 static int fork_to(hipStream_t from, hipStream_t to, hipEvent_t ev) {
     MLLP_HIP_TRY(hipEventRecord(ev, from));
@@ -48,55 +53,20 @@ static int fork_to(hipStream_t from, hipStream_t to, hipEvent_t ev) {
     return MLLP_OK;
 }
 
-// fin: stream of the single-workgroup finalize kernel (s itself, or the graph's aux stream with event ev)
-static int conv_backward(const mllp_graph* g, bool dst_is_var, int cin, const float* cp, const ConvWs& w,
-                         const float* x_src, const float* x_dst, const float* h_out, float* dh, float* dx_dst,
-                         float* dx_src, int acc, float* param_grads, hipStream_t s, hipStream_t fin = nullptr,
-                         hipEvent_t ev = nullptr) {
-    const Orient& o = dst_is_var ? g->At : g->A;       // destination-major
-    const Orient& ot = dst_is_var ? g->A : g->At;      // source-major (rows = source nodes)
-    int rc;
-    if ((rc = launch_bwd_pre(o.n_dst, cin, cp, w, x_dst, h_out, dh, s))) return rc;
-    if ((rc = launch_attn_bwd_dst(o, cin, cp, w, x_src, dh, cin == 16 ? dx_dst : nullptr, acc & 1, o.scratch, s))) return rc;
-    if (cin == 16 && dx_src && (rc = launch_attn_bwd_src(ot, w, x_src, dx_src, (acc >> 1) & 1, ot.scratch, s))) return rc;
-    if ((rc = launch_param_stats(cin, o.n_dst, w, x_dst, dh, s))) return rc;
-    if (fin && fin != s) {
-        if ((rc = fork_to(s, fin, ev))) return rc;
-        return launch_finalize_conv(cin, cp, w.stats, stat_blocks_for(o.n_dst), param_grads, fin);
-    }
-    return launch_finalize_conv(cin, cp, w.stats, stat_blocks_for(o.n_dst), param_grads, s);
-}
-
 // ---- whole-model workspace ----------------------------------------------------------------------
-struct ModelWs {
-    ConvWs c1v, c1c, c2v, c2c, c3v;
-    float *h1v, *h1c, *h2v, *h2c, *h3v;
-    float *d3v, *d2v, *d2c, *d1v, *d1c;
-    float *d1v_b, *d1c_b;       // second contributions to dL/dh1 (fused path: separate buffers instead of +=)
-    float* head_partials;
-    int64_t total;
-};
 constexpr int HEAD_PART_FLOATS = 1024 * 18;
 
 static ModelWs model_ws(const mllp_graph* g, float* base) {
     const int64_t N = g->N, M = g->M;
     ModelWs w;
     float* p = base;
-    auto conv = [&](int64_t n, int cin) {
-        ConvWs c = conv_ws_carve(p, n, cin);
-        p += conv_ws_floats(n, cin);
-        return c;
-    };
     auto buf = [&](int64_t n) {
         float* q = p;
         p += up16(n);
         return q;
     };
-    w.c1v = conv(N, 1);
-    w.c1c = conv(M, 1);
-    w.c2v = conv(N, 16);
-    w.c2c = conv(M, 16);
-    w.c3v = conv(N, 16);
+    for (int c = 0; c < MODEL_CONVS; ++c)
+        w.c[c] = conv_ws_carve(p, MODEL_CONV[c].dst_is_var ? N : M, MODEL_CONV[c].cin, &p);
     w.h1v = buf(N * 16); w.h1c = buf(M * 16);
     w.h2v = buf(N * 16); w.h2c = buf(M * 16);
     w.h3v = buf(N * 16);
@@ -108,32 +78,52 @@ static ModelWs model_ws(const mllp_graph* g, float* base) {
     return w;
 }
 
-// offsets of the convs in GNNModel.state_dict() order
-constexpr int OFF_C1V = 0, OFF_C1C = 144, OFF_C2V = 288, OFF_C2C = 1392, OFF_C3V = 2496, OFF_C3C = 3600, OFF_FC = 4704;
+// folded weights of all five convs in one launch (they only depend on the parameters)
+int model_param_prep(const float* P, const ModelWs& w, hipStream_t s) {
+    const float* cps[MODEL_CONVS];
+    int cins[MODEL_CONVS];
+    float* ders[MODEL_CONVS];
+    for (int c = 0; c < MODEL_CONVS; ++c) { cps[c] = conv_at(P, c); cins[c] = MODEL_CONV[c].cin; ders[c] = w.c[c].derived; }
+    return launch_param_prep_batch(MODEL_CONVS, cps, cins, ders, s);
+}
+
+// the five single-workgroup finalize kernels (and the zero gradient of the never-used gconv3_s2w) as ONE launch, from the
+// per-workgroup partial statistics or (reduced: the fused path) from their sums
+int model_finalize(const mllp_graph* g, const float* P, const ModelWs& w, bool reduced, float* grads, hipStream_t s) {
+    const float* cps[MODEL_CONVS];
+    const float* sts[MODEL_CONVS];
+    float* grs[MODEL_CONVS];
+    int cins[MODEL_CONVS], nbs[MODEL_CONVS];
+    for (int c = 0; c < MODEL_CONVS; ++c) {
+        cps[c] = conv_at(P, c); cins[c] = MODEL_CONV[c].cin; grs[c] = conv_at(grads, c);
+        sts[c] = reduced ? w.c[c].red : w.c[c].stats;
+        nbs[c] = reduced ? 1 : stat_blocks_for((MODEL_CONV[c].dst_is_var ? g->At : g->A).n_dst);
+    }
+    return launch_finalize_batch(MODEL_CONVS, cps, cins, sts, nbs, grs, grads + OFF_UNUSED, LEN_UNUSED, s);
+}
 
 static int model_forward_body(const mllp_graph* g, const float* P, const float* x1, const float* x2, const ModelWs& w,
                               hipStream_t s) {
     int rc;
     hipStream_t a = g->aux;
-    {   // folded weights of all five convs in one launch (they only depend on the parameters)
-        const float* cps[MODEL_CONVS] = {P + OFF_C1V, P + OFF_C1C, P + OFF_C2V, P + OFF_C2C, P + OFF_C3V};
-        const int cins[MODEL_CONVS] = {1, 1, 16, 16, 16};
-        float* ders[MODEL_CONVS] = {w.c1v.derived, w.c1c.derived, w.c2v.derived, w.c2c.derived, w.c3v.derived};
-        if ((rc = launch_param_prep_batch(MODEL_CONVS, cps, cins, ders, s))) return rc;
-    }
+    auto conv = [&](int c, const float* x_src, const float* x_dst, float* h_out, hipStream_t st) {
+        return conv_forward(g, MODEL_CONV[c].dst_is_var, MODEL_CONV[c].cin, conv_at(P, c), w.c[c], x_src, x_dst, h_out, st,
+                            false);
+    };
+    if ((rc = model_param_prep(P, w, s))) return rc;
     // linear_program_methods.py:241-242  layer 1 (scalar inputs), both directions from the SAME inputs:
     // the w2s conv walks A^T, the s2w conv walks A -- independent, so they run on two streams
     if ((rc = fork_to(s, a, g->ev[0]))) return rc;
-    if ((rc = conv_forward(g, true, 1, P + OFF_C1V, w.c1v, x2, x1, w.h1v, s, false))) return rc;
-    if ((rc = conv_forward(g, false, 1, P + OFF_C1C, w.c1c, x1, x2, w.h1c, a, false))) return rc;
+    if ((rc = conv(CONV_1V, x2, x1, w.h1v, s))) return rc;
+    if ((rc = conv(CONV_1C, x1, x2, w.h1c, a))) return rc;
     if ((rc = fork_to(a, s, g->ev[1]))) return rc;       // join: layer 2 on s needs h1c
     if ((rc = fork_to(s, a, g->ev[2]))) return rc;       // ... and layer 2 on aux needs h1v
     // :244-245  layer 2 (simultaneous update: both read layer-1 outputs)
-    if ((rc = conv_forward(g, true, 16, P + OFF_C2V, w.c2v, w.h1c, w.h1v, w.h2v, s, false))) return rc;
-    if ((rc = conv_forward(g, false, 16, P + OFF_C2C, w.c2c, w.h1v, w.h1c, w.h2c, a, false))) return rc;
+    if ((rc = conv(CONV_2V, w.h1c, w.h1v, w.h2v, s))) return rc;
+    if ((rc = conv(CONV_2C, w.h1v, w.h1c, w.h2c, a))) return rc;
     if ((rc = fork_to(a, s, g->ev[3]))) return rc;       // join
     // :247  layer 3, variables only (gconv3_s2w is never called, :248)
-    return conv_forward(g, true, 16, P + OFF_C3V, w.c3v, w.h2c, w.h2v, w.h3v, s, false);
+    return conv(CONV_3V, w.h2c, w.h2v, w.h3v, s);
 }
 
 // One conv of the backward pass, cut at its dependency points so that the two streams can interleave convs:
@@ -142,6 +132,7 @@ static int model_forward_body(const mllp_graph* g, const float* P, const float* 
 //   src   source-major sweep             needs pre; writes dx_src                       (independent of dst)
 //   stat  parameter statistics           needs dst
 //   fin   single-workgroup finalize      needs stat
+// dh is overwritten with the ReLU-masked gradient; dx_* may be null; acc bit0 -> dx_dst, bit1 -> dx_src
 struct ConvBwd {
     const mllp_graph* g;
     bool dst_is_var;
@@ -182,11 +173,16 @@ static int model_backward_body(const mllp_graph* g, const float* P, const float*
                                const ModelWs& w, float* grads, hipStream_t s) {
     int rc;
     hipStream_t a = g->aux;
-    const ConvBwd c3{g, true, 16, P + OFF_C3V, w.c3v, w.h2c, w.h2v, w.h3v, w.d3v, w.d2v, w.d2c, 0, grads + OFF_C3V};
-    const ConvBwd c2v{g, true, 16, P + OFF_C2V, w.c2v, w.h1c, w.h1v, w.h2v, w.d2v, w.d1v, w.d1c, 0, grads + OFF_C2V};
-    const ConvBwd c2c{g, false, 16, P + OFF_C2C, w.c2c, w.h1v, w.h1c, w.h2c, w.d2c, w.d1c, w.d1v, 3, grads + OFF_C2C};
-    const ConvBwd c1v{g, true, 1, P + OFF_C1V, w.c1v, x2, x1, w.h1v, w.d1v, nullptr, nullptr, 0, grads + OFF_C1V};
-    const ConvBwd c1c{g, false, 1, P + OFF_C1C, w.c1c, x1, x2, w.h1c, w.d1c, nullptr, nullptr, 0, grads + OFF_C1C};
+    auto conv = [&](int c, const float* x_src, const float* x_dst, float* h_out, float* dh, float* dx_dst, float* dx_src,
+                    int acc) {
+        return ConvBwd{g, MODEL_CONV[c].dst_is_var, MODEL_CONV[c].cin, conv_at(P, c), w.c[c], x_src, x_dst, h_out, dh,
+                       dx_dst, dx_src, acc, conv_at(grads, c)};
+    };
+    const ConvBwd c3 = conv(CONV_3V, w.h2c, w.h2v, w.h3v, w.d3v, w.d2v, w.d2c, 0);
+    const ConvBwd c2v = conv(CONV_2V, w.h1c, w.h1v, w.h2v, w.d2v, w.d1v, w.d1c, 0);
+    const ConvBwd c2c = conv(CONV_2C, w.h1v, w.h1c, w.h2c, w.d2c, w.d1c, w.d1v, 3);
+    const ConvBwd c1v = conv(CONV_1V, x2, x1, w.h1v, w.d1v, nullptr, nullptr, 0);
+    const ConvBwd c1c = conv(CONV_1C, x1, x2, w.h1c, w.d1c, nullptr, nullptr, 0);
 #define TRY(x) if ((rc = (x))) return rc
 #define REC(e, st) TRY(hipEventRecord(g->ev[e], st) == hipSuccess ? MLLP_OK : fail(MLLP_EHIP, "event record"))
 #define WAIT(st, e) TRY(hipStreamWaitEvent(st, g->ev[e], 0) == hipSuccess ? MLLP_OK : fail(MLLP_EHIP, "stream wait"))
@@ -221,17 +217,7 @@ static int model_backward_body(const mllp_graph* g, const float* P, const float*
 #undef WAIT
     TRY(fork_to(a, s, g->ev[0]));            // join everything queued on aux
 #undef TRY
-    // the five single-workgroup finalize kernels (and the zero gradient of the never-used gconv3_s2w) as ONE launch
-    const ConvBwd* cs[MODEL_CONVS] = {&c1v, &c1c, &c2v, &c2c, &c3};
-    const float* cps[MODEL_CONVS];
-    const float* sts[MODEL_CONVS];
-    float* grs[MODEL_CONVS];
-    int cins[MODEL_CONVS], nbs[MODEL_CONVS];
-    for (int i = 0; i < MODEL_CONVS; ++i) {
-        cps[i] = cs[i]->cp; cins[i] = cs[i]->cin; sts[i] = cs[i]->w.stats;
-        nbs[i] = stat_blocks_for(cs[i]->o().n_dst); grs[i] = cs[i]->param_grads;
-    }
-    return launch_finalize_batch(MODEL_CONVS, cps, cins, sts, nbs, grs, grads + OFF_C3C, OFF_FC - OFF_C3C, s);
+    return model_finalize(g, P, w, false, grads, s);
 }
 
 // ---- fused latency-regime path ------------------------------------------------------------------------
@@ -241,26 +227,9 @@ static bool use_fused(const mllp_graph* g) {
     return g->nnz < ((int64_t)32 << 20);     // the throughput regime keeps the generic / LDS-tiled sweeps
 }
 
-static FusedModel fused_model(const mllp_graph* g, const float* P, const float* x1, const float* x2, const ModelWs& w,
-                              const float* labels, float inv_batch, float* logits) {
-    (void)g;
-    FusedModel m = {};
-    m.cp[0] = P + OFF_C1V; m.cp[1] = P + OFF_C1C; m.cp[2] = P + OFF_C2V; m.cp[3] = P + OFF_C2C; m.cp[4] = P + OFF_C3V;
-    m.c[0] = w.c1v; m.c[1] = w.c1c; m.c[2] = w.c2v; m.c[3] = w.c2c; m.c[4] = w.c3v;
-    m.x1 = x1; m.x2 = x2; m.fcw = P + OFF_FC; m.fcb = P + OFF_FC + 16; m.labels = labels; m.inv_batch = inv_batch;
-    m.h1v = w.h1v; m.h1c = w.h1c; m.h2v = w.h2v; m.h2c = w.h2c; m.h3v = w.h3v;
-    m.d3v = w.d3v; m.d2v = w.d2v; m.d2c = w.d2c; m.d1v = w.d1v; m.d1c = w.d1c; m.d1v_b = w.d1v_b; m.d1c_b = w.d1c_b;
-    m.logits = logits; m.head_part = w.head_partials;
-    m.have_head_part = true;
-    return m;
-}
-
 }  // namespace mllp
 
 using namespace mllp;
-
-#define REQUIRE(cond, msg) \
-    if (!(cond)) return fail(MLLP_EINVAL, std::string(__func__) + ": " + (msg))
 
 extern "C" int mllp_spmm_csr_f32(const mllp_graph_t* g, int transpose, const float* d_H, float* d_Y, void* stream) {
     REQUIRE(g && d_H && d_Y, "null argument");
@@ -395,8 +364,12 @@ extern "C" int mllp_tconv_bwd(const mllp_graph_t* g, int dst_is_var, int cin, co
     REQUIRE(g && d_conv_params && d_x_src && d_x_dst && d_h_out && d_ws && d_dh && d_param_grads, "null argument");
     REQUIRE(cin == 1 || cin == 16, "cin must be 1 or 16");
     ConvWs w = conv_ws_carve(d_ws, dst_is_var ? g->N : g->M, cin);
-    return conv_backward(g, dst_is_var != 0, cin, d_conv_params, w, d_x_src, d_x_dst, d_h_out, d_dh, d_dx_dst,
-                         d_dx_src, accumulate, d_param_grads, (hipStream_t)stream);
+    const ConvBwd c{g, dst_is_var != 0, cin, d_conv_params, w, d_x_src, d_x_dst, d_h_out, d_dh, d_dx_dst, d_dx_src, accumulate,
+                    d_param_grads};
+    hipStream_t s = (hipStream_t)stream;
+    int rc;
+    if ((rc = c.pre(s)) || (rc = c.dst(s)) || (rc = c.src(s)) || (rc = c.stat(s))) return rc;
+    return c.fin(s);
 }
 
 extern "C" int mllp_gnn_workspace_bytes(const mllp_graph_t* g, int64_t* bytes) {
@@ -416,9 +389,9 @@ extern "C" int mllp_gnn_forward(const mllp_graph_t* g, const float* d_params, co
     gm->ws_path = use_fused(g) ? 1 : 0;
     gm->folded_ws = gm->folded_params = nullptr;
     if (use_fused(g))
-        return fused_forward(gm, fused_model(g, d_params, d_x1, d_x2, w, nullptr, 0.0f, d_logits), 1, s);
+        return fused_forward(gm, FusedModel{d_params, w, d_x1, d_x2, nullptr, 0.0f, d_logits}, 1, s);
     if ((rc = model_forward_body(g, d_params, d_x1, d_x2, w, s))) return rc;
-    return launch_head(0, g->N, w.h3v, d_params + OFF_FC, d_params + OFF_FC + 16, g->inv_n, nullptr, 0.0f, nullptr,
+    return launch_head(0, g->N, w.h3v, d_params + OFF_FC, d_params + OFF_FC + FEAT, g->inv_n, nullptr, 0.0f, nullptr,
                        d_logits, nullptr, w.head_partials, s);
 }
 
@@ -433,12 +406,12 @@ extern "C" int mllp_gnn_backward(const mllp_graph_t* g, const float* d_params, c
     REQUIRE(g->ws_ptr == d_ws && g->ws_path == (use_fused(g) ? 1 : 0),
             "no mllp_gnn_forward on this workspace with the current path (mllp_graph_set_path between forward and backward?)");
     if (use_fused(g)) {      // (the node tensors of the fused path are in renumbered order: it has its own head kernel)
-        const FusedModel m = fused_model(g, d_params, d_x1, d_x2, w, nullptr, 0.0f, nullptr);
+        const FusedModel m{d_params, w, d_x1, d_x2, nullptr, 0.0f, nullptr};
         if ((rc = fused_bind(const_cast<mllp_graph*>(g), d_x1, d_x2, nullptr, s))) return rc;
         if ((rc = fused_head_backward(g, m, d_dlogits, s))) return rc;
         return fused_backward(g, m, false, d_grads, nullptr, s);
     }
-    if ((rc = launch_head(1, g->N, w.h3v, d_params + OFF_FC, d_params + OFF_FC + 16, g->inv_n, nullptr, 0.0f,
+    if ((rc = launch_head(1, g->N, w.h3v, d_params + OFF_FC, d_params + OFF_FC + FEAT, g->inv_n, nullptr, 0.0f,
                           d_dlogits, nullptr, w.d3v, w.head_partials, s))) return rc;
     if ((rc = fork_to(s, g->aux, g->ev[1]))) return rc;
     if ((rc = launch_head_finalize(w.head_partials, head_blocks_for(g->N), d_grads + OFF_FC, nullptr, g->aux))) return rc;
@@ -452,16 +425,19 @@ extern "C" int mllp_gnn_backward(const mllp_graph_t* g, const float* d_params, c
 static int input_grads_body(const mllp_graph* g, const float* x1, const float* x2, const ModelWs& w, float* dx1,
                             float* dx2, float* dval, hipStream_t s) {
     int rc;
-    if ((rc = launch_layer1_dst_grads(w.c1v, w.d1v, dx1, g->N, w.c1c, w.d1c, dx2, g->M, s))) return rc;
-    if (dx1 && (rc = launch_attn_bwd_src1(g->At, w.c1c, x1, dx1, 1, g->At.scratch, s))) return rc;
-    if (dx2 && (rc = launch_attn_bwd_src1(g->A, w.c1v, x2, dx2, 1, g->A.scratch, s))) return rc;
+    // dL/da of conv c from its destination-major walk: A in place, A^T through the position map
+    auto edge = [&](int c, const float* x_src, int accumulate) {
+        const bool t = MODEL_CONV[c].dst_is_var;
+        return launch_edge_grad(t ? g->At : g->A, g->nnz, MODEL_CONV[c].cin, w.c[c], x_src, t ? g->at_pos : nullptr, dval,
+                                accumulate, s);
+    };
+    if ((rc = launch_layer1_dst_grads(w.c[CONV_1V], w.d1v, dx1, g->N, w.c[CONV_1C], w.d1c, dx2, g->M, s))) return rc;
+    if (dx1 && (rc = launch_attn_bwd_src1(g->At, w.c[CONV_1C], x1, dx1, 1, g->At.scratch, s))) return rc;
+    if (dx2 && (rc = launch_attn_bwd_src1(g->A, w.c[CONV_1V], x2, dx2, 1, g->A.scratch, s))) return rc;
     if (!dval) return MLLP_OK;
-    const int* pos = g->at_pos;
-    if ((rc = launch_edge_grad(g->A, g->nnz, 1, w.c1c, x1, nullptr, dval, 0, s))) return rc;
-    if ((rc = launch_edge_grad(g->A, g->nnz, 16, w.c2c, w.h1v, nullptr, dval, 1, s))) return rc;
-    if ((rc = launch_edge_grad(g->At, g->nnz, 1, w.c1v, x2, pos, dval, 1, s))) return rc;
-    if ((rc = launch_edge_grad(g->At, g->nnz, 16, w.c2v, w.h1c, pos, dval, 1, s))) return rc;
-    return launch_edge_grad(g->At, g->nnz, 16, w.c3v, w.h2c, pos, dval, 1, s);
+    if ((rc = edge(CONV_1C, x1, 0)) || (rc = edge(CONV_2C, w.h1v, 1)) || (rc = edge(CONV_1V, x2, 1)) ||
+        (rc = edge(CONV_2V, w.h1c, 1))) return rc;
+    return edge(CONV_3V, w.h2c, 1);
 }
 
 extern "C" int mllp_gnn_loss_step(const mllp_graph_t* g, const float* d_params, const float* d_x1, const float* d_x2,
@@ -473,12 +449,12 @@ extern "C" int mllp_gnn_loss_step(const mllp_graph_t* g, const float* d_params, 
     int rc;
     const_cast<mllp_graph*>(g)->folded_ws = const_cast<mllp_graph*>(g)->folded_params = nullptr;
     if (use_fused(g)) {
-        const FusedModel m = fused_model(g, d_params, d_x1, d_x2, w, d_labels, inv_batch, d_logits);
+        const FusedModel m{d_params, w, d_x1, d_x2, d_labels, inv_batch, d_logits};
         if ((rc = fused_forward(const_cast<mllp_graph*>(g), m, 2, s))) return rc;
         return fused_backward(g, m, true, d_grads, d_loss, s);
     }
     if ((rc = model_forward_body(g, d_params, d_x1, d_x2, w, s))) return rc;
-    if ((rc = launch_head(2, g->N, w.h3v, d_params + OFF_FC, d_params + OFF_FC + 16, g->inv_n, d_labels, inv_batch,
+    if ((rc = launch_head(2, g->N, w.h3v, d_params + OFF_FC, d_params + OFF_FC + FEAT, g->inv_n, d_labels, inv_batch,
                           nullptr, d_logits, w.d3v, w.head_partials, s))) return rc;
     if ((rc = fork_to(s, g->aux, g->ev[1]))) return rc;
     if ((rc = launch_head_finalize(w.head_partials, head_blocks_for(g->N), d_grads + OFF_FC, d_loss, g->aux))) return rc;
@@ -521,7 +497,7 @@ extern "C" int mllp_gnn_train_step(const mllp_graph_t* g, float* d_params, const
     mllp_graph* gm = const_cast<mllp_graph*>(g);
     if (use_fused(g)) {
         ModelWs w = model_ws(g, (float*)d_ws);
-        const FusedModel m = fused_model(g, d_params, d_x1, d_x2, w, d_labels, inv_batch, d_logits);
+        const FusedModel m{d_params, w, d_x1, d_x2, d_labels, inv_batch, d_logits};
         // bit 0 is the caller's claim that the parameters are unchanged since the last call; the library checks on its
         // side that the last whole-model call on this graph was a fused train_step on this workspace and these parameters
         const bool skip = (flags & 1) != 0 && gm->folded_ws == d_ws && gm->folded_params == d_params;

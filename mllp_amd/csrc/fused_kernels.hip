@@ -1753,11 +1753,6 @@ extern "C" int mllp_timing_read_stamps1(unsigned long long* host, int n) {
 }
 #endif
 
-static int check_launch(const char* what) {
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MLLP_OK : hip_fail(e, what);
-}
-
 template <class T>
 static int dev_alloc(mllp_graph* g, size_t count, T** out, const T* host = nullptr, size_t room = 1) {
     void* p = nullptr;
@@ -1906,11 +1901,11 @@ int fused_bind(mllp_graph* g, const float* x1, const float* x2, const float* lab
 // one workgroup per CU, a multiple of the partition count (workgroup b works on partition b % NP)
 int fused_grid(const mllp_graph* g) { return std::max(std::min(g->n_cu, STAT_BLOCKS_MAX) / NP, 1) * NP; }
 
-static FwdJob16 fwd_job16(const FusedOrient& o, const float* cp, const ConvWs& w, const float* x_src, const float* x_dst,
-                          float* h) {
+static FwdJob16 fwd_job16(const FusedOrient& o, const FusedModel& m, int c, const float* x_src, const float* x_dst, float* h) {
+    const ConvWs& w = m.w.c[c];
     FwdJob16 J = {};
     J.s = items_dev(o, 0);
-    J.x_src = x_src; J.x_dst = x_dst; J.D = w.derived; J.p = conv_params_at(cp, 16);
+    J.x_src = x_src; J.x_dst = x_dst; J.D = w.derived; J.p = conv_params_at(conv_at(m.P, c), MODEL_CONV[c].cin);
     J.h = h; J.Z = w.Z; J.aux = w.aux;
     J.head = 0;
 #ifdef MLLP_TIMING_BUILD
@@ -1918,37 +1913,35 @@ static FwdJob16 fwd_job16(const FusedOrient& o, const float* cp, const ConvWs& w
 #endif
     return J;
 }
-static FwdJob1 fwd_job1(const FusedOrient& o, const float* cp, const ConvWs& w, const float* x_dst, float* h) {
+static FwdJob1 fwd_job1(const FusedOrient& o, const FusedModel& m, int c, const float* x_dst, float* h) {
+    const ConvWs& w = m.w.c[c];
     FwdJob1 J = {};
     J.s = items_dev(o, 1);
-    J.x_dst = x_dst; J.D = w.derived; J.p = conv_params_at(cp, 1);
+    J.x_dst = x_dst; J.D = w.derived; J.p = conv_params_at(conv_at(m.P, c), MODEL_CONV[c].cin);
     J.h = h; J.Z = w.Z; J.aux = w.aux;
     return J;
 }
 
 int fused_forward(mllp_graph* g, const FusedModel& m, int head_mode, hipStream_t s, bool skip_prep) {
     const int G = fused_grid(g);
+    const ModelWs& w = m.w;
     int rc;
     if ((rc = fused_bind(g, m.x1, m.x2, head_mode == 2 ? m.labels : nullptr, s))) return rc;
-    if (!skip_prep) {   // folded weights of all five convs (skipped when the previous step's tail left them in this workspace)
-        const float* cps[MODEL_CONVS] = {m.cp[0], m.cp[1], m.cp[2], m.cp[3], m.cp[4]};
-        const int cins[MODEL_CONVS] = {1, 1, 16, 16, 16};
-        float* ders[MODEL_CONVS] = {m.c[0].derived, m.c[1].derived, m.c[2].derived, m.c[3].derived, m.c[4].derived};
-        if ((rc = launch_param_prep_batch(MODEL_CONVS, cps, cins, ders, s))) return rc;
-    }
+    // folded weights of all five convs (skipped when the previous step's tail left them in this workspace)
+    if (!skip_prep && (rc = model_param_prep(m.P, w, s))) return rc;
     {   // linear_program_methods.py:241-242  layer 1, both directions
         FwdLaunch1 L = {};
         L.n_jobs = 2;
-        L.job[0] = fwd_job1(g->FAt, m.cp[0], m.c[0], g->x1_p, m.h1v);     // w2s: dst = variables
-        L.job[1] = fwd_job1(g->FA, m.cp[1], m.c[1], g->x2_p, m.h1c);      // s2w: dst = constraints
+        L.job[0] = fwd_job1(g->FAt, m, CONV_1V, g->x1_p, w.h1v);     // w2s: dst = variables
+        L.job[1] = fwd_job1(g->FA, m, CONV_1C, g->x2_p, w.h1c);      // s2w: dst = constraints
         hipLaunchKernelGGL(fused_fwd1_kernel, dim3(G), dim3(FT), 0, s, L);
         if ((rc = check_launch("fused_fwd1"))) return rc;
     }
     {   // :244-245  layer 2 (simultaneous update)
         FwdLaunch16 L = {};
         L.n_jobs = 2;
-        L.job[0] = fwd_job16(g->FAt, m.cp[2], m.c[2], m.h1c, m.h1v, m.h2v);
-        L.job[1] = fwd_job16(g->FA, m.cp[3], m.c[3], m.h1v, m.h1c, m.h2c);
+        L.job[0] = fwd_job16(g->FAt, m, CONV_2V, w.h1c, w.h1v, w.h2v);
+        L.job[1] = fwd_job16(g->FA, m, CONV_2C, w.h1v, w.h1c, w.h2c);
         L.job[0].perm = g->perm_v; L.job[1].perm = g->perm_c;      // read (unconditional prefetch), used by the head only
         hipLaunchKernelGGL(fused_fwd16_kernel, dim3(G), dim3(FT), 0, s, L);
         if ((rc = check_launch("fused_fwd16 layer 2"))) return rc;
@@ -1956,12 +1949,12 @@ int fused_forward(mllp_graph* g, const FusedModel& m, int head_mode, hipStream_t
     {   // :247 layer 3 (variables only) + :250 fc (+ loss)
         FwdLaunch16 L = {};
         L.n_jobs = 1;
-        L.job[0] = fwd_job16(g->FAt, m.cp[4], m.c[4], m.h2c, m.h2v, m.h3v);
+        L.job[0] = fwd_job16(g->FAt, m, CONV_3V, w.h2c, w.h2v, w.h3v);
         FwdJob16& J = L.job[0];
         J.head = head_mode;
-        J.fcw = m.fcw; J.fcb = m.fcb; J.inv_n = g->inv_n_p; J.labels = g->labels_p; J.perm = g->perm_v;
+        J.fcw = m.P + OFF_FC; J.fcb = m.P + OFF_FC + FEAT; J.inv_n = g->inv_n_p; J.labels = g->labels_p; J.perm = g->perm_v;
         J.inv_batch = m.inv_batch;
-        J.logits = m.logits; J.g_out = m.d3v; J.head_part = m.head_part;
+        J.logits = m.logits; J.g_out = w.d3v; J.head_part = w.head_partials;
         hipLaunchKernelGGL(fused_fwd16_kernel, dim3(G), dim3(FT), 0, s, L);
         if ((rc = check_launch("fused_fwd16 layer 3"))) return rc;
     }
@@ -1970,16 +1963,17 @@ int fused_forward(mllp_graph* g, const FusedModel& m, int head_mode, hipStream_t
 
 int fused_head_backward(const mllp_graph* g, const FusedModel& m, const float* dlogits, hipStream_t s) {
     const int G = fused_grid(g);
-    hipLaunchKernelGGL(fused_head_bwd_kernel, dim3(G), dim3(RT), 0, s, (int)g->N, m.h3v, m.fcw, dlogits, g->perm_v, m.d3v,
-                       m.head_part);
+    hipLaunchKernelGGL(fused_head_bwd_kernel, dim3(G), dim3(RT), 0, s, (int)g->N, m.w.h3v, m.P + OFF_FC, dlogits, g->perm_v,
+                       m.w.d3v, m.w.head_partials);
     return check_launch("fused_head_bwd");
 }
 
-static BwdJob16 bwd_job16(const FusedOrient& o, const float* cp, const ConvWs& w, const float* x_src, const float* x_dst,
+static BwdJob16 bwd_job16(const FusedOrient& o, const FusedModel& m, int c, const float* x_src, const float* x_dst,
                           const float* h, const float* dh_a, const float* dh_b, float* dx_dst, bool need_rec, bool mask_dx) {
+    const ConvWs& w = m.w.c[c];
     BwdJob16 J = {};
     J.s = items_dev(o, 0);
-    J.x_src = x_src; J.x_dst = x_dst; J.D = w.derived; J.p = conv_params_at(cp, 16);
+    J.x_src = x_src; J.x_dst = x_dst; J.D = w.derived; J.p = conv_params_at(conv_at(m.P, c), MODEL_CONV[c].cin);
     J.h = h; J.dh_a = dh_a; J.dh_b = dh_b; J.Z = w.Z; J.aux = w.aux;
     J.rec = need_rec ? w.rec : nullptr;
     J.dx_dst = dx_dst;
@@ -1997,10 +1991,11 @@ static SrcJob16 src_job16(const FusedOrient& o_src_major, const ConvWs& w, const
     J.addp = add ? add : x_rows; J.addw = add ? 1.0f : 0.0f; J.mask = 1;
     return J;
 }
-static BwdJob1 bwd_job1(const FusedOrient& o, const float* cp, const ConvWs& w, const float* x_dst, const float* g_masked) {
+static BwdJob1 bwd_job1(const FusedOrient& o, const FusedModel& m, int c, const float* x_dst, const float* g_masked) {
+    const ConvWs& w = m.w.c[c];
     BwdJob1 J = {};
     J.s = items_dev(o, 1);
-    J.x_dst = x_dst; J.D = w.derived; J.p = conv_params_at(cp, 1);
+    J.x_dst = x_dst; J.D = w.derived; J.p = conv_params_at(conv_at(m.P, c), MODEL_CONV[c].cin);
     J.g = g_masked; J.Z = w.Z; J.aux = w.aux; J.stats = w.stats;
     return J;
 }
@@ -2018,68 +2013,67 @@ static BwdJob1 bwd_job1(const FusedOrient& o, const float* cp, const ConvWs& w, 
 int fused_backward(const mllp_graph* g, const FusedModel& m, bool premasked, float* grads, float* loss, hipStream_t s,
                    const FusedAdam* adam) {
     const int G = fused_grid(g);
+    const ModelWs& w = m.w;
     int rc;
     const FusedOrient& A = g->FA;      // rows = constraints
     const FusedOrient& At = g->FAt;    // rows = variables
     {   // K1
         BwdLaunch16 L = {};
         L.n_jobs = 1;
-        L.job[0] = bwd_job16(At, m.cp[4], m.c[4], m.h2c, m.h2v, premasked ? nullptr : m.h3v, m.d3v, nullptr, m.d2v, true, true);
+        L.job[0] = bwd_job16(At, m, CONV_3V, w.h2c, w.h2v, premasked ? nullptr : w.h3v, w.d3v, nullptr, w.d2v, true, true);
         hipLaunchKernelGGL(fused_bwd16_kernel, dim3(G), dim3(FT), 0, s, L);
         if ((rc = check_launch("fused_bwd16 C3"))) return rc;
     }
     {   // K2: C3 source-major (rows = constraints) and C2V destination-major
         SrcLaunch16 S = {};
         S.n_jobs = 1;
-        S.job[0] = src_job16(A, m.c[4], m.h2c, m.d2c, nullptr);
+        S.job[0] = src_job16(A, w.c[CONV_3V], w.h2c, w.d2c, nullptr);
         hipLaunchKernelGGL(fused_src16_kernel, dim3(2 * G), dim3(FT), 0, s, S);   // 72 VGPRs: two workgroups per CU
         if ((rc = check_launch("fused_src16 C3"))) return rc;
         BwdLaunch16 L = {};
         L.n_jobs = 1;
-        L.job[0] = bwd_job16(At, m.cp[2], m.c[2], m.h1c, m.h1v, nullptr, m.d2v, nullptr, m.d1v, true, true);
+        L.job[0] = bwd_job16(At, m, CONV_2V, w.h1c, w.h1v, nullptr, w.d2v, nullptr, w.d1v, true, true);
         hipLaunchKernelGGL(fused_bwd16_kernel, dim3(G), dim3(FT), 0, s, L);
         if ((rc = check_launch("fused_bwd16 C2V"))) return rc;
     }
     {   // K3: C2C destination-major (rows = constraints) and C2V source-major (rows = constraints)
         BwdLaunch16 L = {};
         L.n_jobs = 1;
-        L.job[0] = bwd_job16(A, m.cp[3], m.c[3], m.h1v, m.h1c, nullptr, m.d2c, nullptr, m.d1c, true, true);
+        L.job[0] = bwd_job16(A, m, CONV_2C, w.h1v, w.h1c, nullptr, w.d2c, nullptr, w.d1c, true, true);
         hipLaunchKernelGGL(fused_bwd16_kernel, dim3(G), dim3(FT), 0, s, L);
         if ((rc = check_launch("fused_bwd16 C2C"))) return rc;
         SrcLaunch16 S = {};
         S.n_jobs = 2;
-        S.job[0] = src_job16(A, m.c[2], m.h1c, m.d1c_b, m.d1c);      // d1c_b = (h1c > 0) (dX + d1c): the whole gradient of h1c
-        S.job[1] = src_job16(At, m.c[3], m.h1v, m.d1v_b, m.d1v);     // K4: C2C source-major (rows = variables)
+        S.job[0] = src_job16(A, w.c[CONV_2V], w.h1c, w.d1c_b, w.d1c);    // d1c_b = (h1c > 0) (dX + d1c): the whole gradient of h1c
+        S.job[1] = src_job16(At, w.c[CONV_2C], w.h1v, w.d1v_b, w.d1v);    // K4: C2C source-major (rows = variables)
         hipLaunchKernelGGL(fused_src16_kernel, dim3(2 * G), dim3(FT), 0, s, S);   // 72 VGPRs: two workgroups per CU
         if ((rc = check_launch("fused_src16 C2V + C2C"))) return rc;
     }
     {   // K5: layer 1, both convs (inputs are data: no input gradients)
         BwdLaunch1 L = {};
         L.n_jobs = 2;
-        L.job[0] = bwd_job1(A, m.cp[1], m.c[1], g->x2_p, m.d1c_b);     // pre-masked, pre-summed by K3' / K4
-        L.job[1] = bwd_job1(At, m.cp[0], m.c[0], g->x1_p, m.d1v_b);
+        L.job[0] = bwd_job1(A, m, CONV_1C, g->x2_p, w.d1c_b);    // pre-masked, pre-summed by K3' / K4
+        L.job[1] = bwd_job1(At, m, CONV_1V, g->x1_p, w.d1v_b);
         hipLaunchKernelGGL(fused_bwd1_kernel, dim3(G), dim3(FT), 0, s, L);
         if ((rc = check_launch("fused_bwd1"))) return rc;
     }
     ReduceArgs R = {};
-    for (int i = 0; i < MODEL_CONVS; ++i) { R.stats[i] = m.c[i].stats; R.out[i] = m.c[i].red; }
+    for (int c = 0; c < MODEL_CONVS; ++c) { R.stats[c] = w.c[c].stats; R.out[c] = w.c[c].red; }
     R.nblk = G;
-    R.head_part = m.have_head_part ? m.head_part : nullptr;
-    R.head_out = grads + 4704;
+    R.head_part = w.head_partials;      // from fused_forward (head_mode 2) or fused_head_backward
+    R.head_out = grads + OFF_FC;
     R.loss_out = loss;
-    const int cins[MODEL_CONVS] = {1, 1, 16, 16, 16};
-    float* grs[MODEL_CONVS] = {grads + 0, grads + 144, grads + 288, grads + 1392, grads + 2496};
     if (adam) {     // K6 + K7 + Adam + the next step's folded weights in one launch (single-rank step)
         TailArgs T = {};
         T.R = R;
-        for (int i = 0; i < MODEL_CONVS; ++i) {
-            T.p[i] = conv_params_at(m.cp[i], cins[i]);
-            T.cin[i] = cins[i];
-            T.grads[i] = grs[i];
-            T.D[i] = m.c[i].derived;
+        for (int c = 0; c < MODEL_CONVS; ++c) {
+            T.p[c] = conv_params_at(conv_at(m.P, c), MODEL_CONV[c].cin);
+            T.cin[c] = MODEL_CONV[c].cin;
+            T.grads[c] = conv_at(grads, c);
+            T.D[c] = w.c[c].derived;
         }
-        T.zero = grads + 3600;
-        T.n_zero = 1104;
+        T.zero = grads + OFF_UNUSED;
+        T.n_zero = LEN_UNUSED;
         T.params = adam->params; T.grads_all = grads; T.m = adam->m; T.v = adam->v; T.state = adam->state;
         T.eps = adam->eps;
         T.n_params = adam->n;
@@ -2095,13 +2089,8 @@ int fused_backward(const mllp_graph* g, const FusedModel& m, bool premasked, flo
         hipLaunchKernelGGL(fused_reduce_kernel, dim3(MODEL_CONVS * STAT_TILES + 1), dim3(RT), 0, s, R, MODEL_CONVS);
         if ((rc = check_launch("fused_reduce"))) return rc;
     }
-    {   // K7: the 16x16 algebra of every conv, and the zero gradient of the never-used gconv3_s2w
-        const float* cps[MODEL_CONVS] = {m.cp[0], m.cp[1], m.cp[2], m.cp[3], m.cp[4]};
-        const float* sts[MODEL_CONVS] = {m.c[0].red, m.c[1].red, m.c[2].red, m.c[3].red, m.c[4].red};
-        const int nbs[MODEL_CONVS] = {1, 1, 1, 1, 1};
-        if ((rc = launch_finalize_batch(MODEL_CONVS, cps, cins, sts, nbs, grs, grads + 3600, 1104, s))) return rc;
-    }
-    return MLLP_OK;
+    // K7: the 16x16 algebra of every conv, and the zero gradient of the never-used gconv3_s2w
+    return model_finalize(g, m.P, w, true, grads, s);
 }
 
 }  // namespace mllp

@@ -28,6 +28,16 @@ int hip_fail(hipError_t e, const char* what);
         if (_e != hipSuccess) return ::mllp::hip_fail(_e, #expr);       \
     } while (0)
 
+// argument check of an extern "C" entry point: the message names the function
+#define REQUIRE(cond, msg) \
+    if (!(cond)) return ::mllp::fail(MLLP_EINVAL, std::string(__func__) + ": " + (msg))
+
+// after a kernel launch: the launch error, if any, under the kernel's name
+inline int check_launch(const char* what) {
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? MLLP_OK : hip_fail(e, what);
+}
+
 // scratch device buffer of a builder, freed when it goes out of scope
 template <class T>
 struct DevBuf {
@@ -202,7 +212,38 @@ namespace mllp {
 struct ConvParams {
     const float *Wk, *bk, *Wq, *bq, *Wv, *bv, *we, *Ws, *bs;
 };
-inline int conv_param_count(int cin) { return 4 * FEAT * cin + 5 * FEAT; }
+constexpr int conv_param_count(int cin) { return 4 * FEAT * cin + 5 * FEAT; }
+
+// ---- the model's layout: GNNModel.state_dict() order ---------------------
+// the five convs that are used, then the never-called gconv3_s2w (its gradient is zero), then fc (weight [16], bias)
+enum { CONV_1V, CONV_1C, CONV_2V, CONV_2C, CONV_3V };   // gconv1_w2s, gconv1_s2w, gconv2_w2s, gconv2_s2w, gconv3_w2s
+constexpr int MODEL_CONVS = CONV_3V + 1;
+struct ConvSpec {
+    bool dst_is_var;    // w2s: destinations are the variables (walks A^T); s2w: the constraints (walks A)
+    int cin;
+};
+constexpr ConvSpec MODEL_CONV[MODEL_CONVS] = {{true, 1}, {false, 1}, {true, 16}, {false, 16}, {true, 16}};
+struct ConvOffsets {
+    int at[MODEL_CONVS + 1];    // at[MODEL_CONVS]: the end of the used convs
+};
+constexpr ConvOffsets conv_offsets() {
+    ConvOffsets o = {};
+    for (int c = 0; c < MODEL_CONVS; ++c) o.at[c + 1] = o.at[c] + conv_param_count(MODEL_CONV[c].cin);
+    return o;
+}
+constexpr ConvOffsets CONV_OFF = conv_offsets();
+constexpr int OFF_UNUSED = CONV_OFF.at[MODEL_CONVS], LEN_UNUSED = conv_param_count(FEAT);   // gconv3_s2w
+constexpr int OFF_FC = OFF_UNUSED + LEN_UNUSED;
+constexpr int NUM_PARAMS = OFF_FC + FEAT + 1;
+static_assert(CONV_OFF.at[CONV_1V] == 0 && CONV_OFF.at[CONV_1C] == 144 && CONV_OFF.at[CONV_2V] == 288 &&
+                  CONV_OFF.at[CONV_2C] == 1392 && CONV_OFF.at[CONV_3V] == 2496,
+              "conv offsets differ from GNNModel.state_dict()");
+static_assert(OFF_UNUSED == 3600 && LEN_UNUSED == 1104 && OFF_FC == 4704, "gconv3_s2w / fc offsets differ from state_dict()");
+static_assert(NUM_PARAMS == MLLP_NUM_PARAMS, "the layout's total differs from MLLP_NUM_PARAMS");
+// conv c of a flat parameter or gradient buffer
+template <class T>
+inline T* conv_at(T* base, int c) { return base + CONV_OFF.at[c]; }
+
 inline ConvParams conv_params_at(const float* base, int cin) {
     ConvParams p;
     const float* q = base;
@@ -242,8 +283,20 @@ struct ConvWs {
     float* stats;    // [STAT_BLOCKS_MAX, STAT_FLOATS] per-workgroup partial statistics
     float* red;      // [STAT_FLOATS] the summed statistics (fused path)
 };
+// the one listing of the fields, each rounded up to 16 floats; *end: where the next workspace starts.  Carving from
+// nullptr measures: conv_ws_floats is what it advances by
+ConvWs conv_ws_carve(float* base, int64_t n_dst, int cin, float** end = nullptr);
 int64_t conv_ws_floats(int64_t n_dst, int cin);
-ConvWs conv_ws_carve(float* base, int64_t n_dst, int cin);
+
+// workspace of the whole model (api.cpp::model_ws carves it)
+struct ModelWs {
+    ConvWs c[MODEL_CONVS];      // by CONV_*
+    float *h1v, *h1c, *h2v, *h2c, *h3v;
+    float *d3v, *d2v, *d2c, *d1v, *d1c;
+    float *d1v_b, *d1c_b;       // second contributions to dL/dh1 (fused path: separate buffers instead of +=)
+    float* head_partials;
+    int64_t total;
+};
 
 // ---- launchers (sweep_kernels.hip / node_kernels.hip) -------------------------------------------
 int launch_spmm(const Orient& o, const float* H, float* Y, float* scratch, hipStream_t s);
@@ -280,7 +333,6 @@ int launch_bwdsrc16_tiled(const Tiled& tl, int n_rows, int n_cols, const float* 
                           int accumulate, hipStream_t s);
 int tiled_geometry(int variant, int* rows_per_tile, int* cols_per_block, int* bundle_capacity);
 int tiled_max_blocks_per_tile();
-constexpr int MODEL_CONVS = 5;   // convs of GNNModel that are used (gconv3_s2w is not)
 int launch_param_prep_batch(int n, const float* const* conv_params, const int* cin, float* const* derived, hipStream_t s);
 int launch_finalize_batch(int n, const float* const* conv_params, const int* cin, const float* const* stats,
                           const int* n_stat_blocks, float* const* grads, float* zero, int n_zero, hipStream_t s);
@@ -326,16 +378,17 @@ int launch_topm_select(const int* ptr_n, const int* ptr_m, int64_t n_seg, int n_
                        unsigned char* mask, int* index, float* stats, hipStream_t s);
 
 // ---- fused latency-regime path of the whole model (fused_kernels.hip) ---------------------------------
+// one whole-model call: the flat parameters, the carved workspace, the call's inputs (labels, logits: null where unused)
 struct FusedModel {
-    const float* cp[MODEL_CONVS];   // parameters of gconv1_w2s, gconv1_s2w, gconv2_w2s, gconv2_s2w, gconv3_w2s
-    ConvWs c[MODEL_CONVS];
-    const float *x1, *x2, *fcw, *fcb, *labels;
+    const float* P;
+    const ModelWs& w;
+    const float *x1, *x2, *labels;
     float inv_batch;
-    float *h1v, *h1c, *h2v, *h2c, *h3v;
-    float *d3v, *d2v, *d2c, *d1v, *d1c, *d1v_b, *d1c_b;
-    float *logits, *head_part;
-    bool have_head_part;         // fused_backward sums the fc partials (from fused_forward mode 2 or fused_head_backward)
+    float* logits;
 };
+// api.cpp: the per-conv launches of the whole model that both paths share (one launch each for the five convs)
+int model_param_prep(const float* P, const ModelWs& w, hipStream_t s);
+int model_finalize(const mllp_graph* g, const float* P, const ModelWs& w, bool reduced, float* grads, hipStream_t s);
 int fused_graph_build(mllp_graph* g, const int* h_csr_ptr, const int* h_csc_ptr);   // allocates: creation / set_path only
 int fused_grid(const mllp_graph* g);
 int fused_refill_values(mllp_graph* g, hipStream_t s);   // sent of both orientations from A.val / At.val again (launches only)

@@ -92,11 +92,6 @@ __global__ __launch_bounds__(BLOCK) void sv_scale_kernel(const int* __restrict__
 
 inline dim3 grid_for(int64_t n) { return dim3((unsigned)((n + BLOCK - 1) / BLOCK)); }
 
-int check_launch(const char* what) {
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MLLP_OK : hip_fail(e, what);
-}
-
 template <int L>
 int refresh(const int* map, const float* val, int64_t n, void* dst, hipStream_t s) {
     if (n == 0) return MLLP_OK;
@@ -220,8 +215,6 @@ int ensure_at_pos(mllp_graph* g, hipStream_t s) {
 
 using namespace mllp;
 
-#define REQUIRE(cond, msg) \
-    if (!(cond)) return fail(MLLP_EINVAL, std::string(__func__) + ": " + (msg))
 #define BORROWED_MSG                                                                                                    \
     "a caller-owned LDS-tiled copy is attached (mllp_graph_attach_tiled): its arrays are not the library's to write. " \
     "Drop it (n_tiles = 0) or build the copy with mllp_graph_build_tiled"

@@ -125,9 +125,6 @@ static int build_on_host(const Orient& o, int64_t nnz, const std::vector<int64_t
 
 using namespace mllp;
 
-#define REQUIRE(cond, msg) \
-    if (!(cond)) return fail(MLLP_EINVAL, std::string(__func__) + ": " + (msg))
-
 static bool valid_geom(int geom) {
     GeomInfo gi;
     return geom == STREAM_GEOM_LANE1 || geom_info(geom, &gi);

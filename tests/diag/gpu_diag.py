@@ -67,14 +67,14 @@ def main():
     sd_np = {k: v.numpy() for k, v in sd.items()}
     flat32 = o1.flatten_state(sd).float().cuda()
     # single layers
-    for name, dst_is_var, cin, off in (("gconv1_w2s", True, 1, 0), ("gconv1_s2w", False, 1, 144),
-                                       ("gconv2_w2s", True, 16, 288), ("gconv2_s2w", False, 16, 1392)):
+    for name, dst_is_var, cin in (("gconv1_w2s", True, 1), ("gconv1_s2w", False, 1), ("gconv2_w2s", True, 16),
+                                  ("gconv2_s2w", False, 16)):
         p = o2.conv_params(sd_np, name)
         ptr, idx, val, nd, ns = ob.orient(dst_is_var)
         xs = (rng.standard_normal((ns, cin)) * 0.7).astype(np.float32).astype(np.float64)
         xd = (rng.standard_normal((nd, cin)) * 0.7).astype(np.float32).astype(np.float64)
         h_ref, saved = o2.conv_fwd(p, ptr, idx, val, xs, xd)
-        cp = flat32[off:off + (144 if cin == 1 else 1104)].contiguous()
+        cp = flat32[_lib.conv_param_slice(name)].contiguous()
         ws = batch.tconv_workspace(dst_is_var, cin)
         xs_t = torch.tensor(xs, dtype=torch.float32, device="cuda").contiguous()
         xd_t = torch.tensor(xd, dtype=torch.float32, device="cuda").contiguous()

@@ -17,6 +17,7 @@ import torch
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 pytestmark = pytest.mark.gpu
 
+from mllp_amd._lib import conv_param_slice  # noqa: E402
 from mllp_amd.data import SUBSET5, LPInstance, load_packed, synthetic_instance  # noqa: E402
 from oracle import pyg_restatement as o1  # noqa: E402
 from oracle import spmm_form as o2  # noqa: E402
@@ -117,8 +118,9 @@ def test_spmm_both_orientations(LPBatch, subset5, tiers):
 
 
 @pytest.mark.parametrize("tiers", [(0, 0), (4, 16)])
-@pytest.mark.parametrize("name,dst_is_var,cin,off", [("gconv1_w2s", True, 1, 0), ("gconv1_s2w", False, 1, 144),
-                                                     ("gconv2_w2s", True, 16, 288), ("gconv2_s2w", False, 16, 1392)])
+@pytest.mark.parametrize("name,dst_is_var,cin,off", [          # (off: the conv's offset, part of the test id)
+    (n, v, c, conv_param_slice(n).start) for n, v, c in (("gconv1_w2s", True, 1), ("gconv1_s2w", False, 1),
+                                                         ("gconv2_w2s", True, 16), ("gconv2_s2w", False, 16))])
 def test_single_layer_forward_backward(LPBatch, subset5, weights, tiers, name, dst_is_var, cin, off):
     flat, sd, flat_gpu = weights
     b = LPBatch.from_instances(subset5, tier_wave=tiers[0], tier_block=tiers[1])
@@ -129,7 +131,7 @@ def test_single_layer_forward_backward(LPBatch, subset5, weights, tiers, name, d
     r32 = lambda a: a.astype(np.float32).astype(np.float64)
     xs, xd, dh = r32(rng.standard_normal((ns, cin))), r32(rng.standard_normal((nd, cin))), r32(rng.standard_normal((nd, 16)))
     h_ref, saved = o2.conv_fwd(p, ptr, idx, val, xs, xd)
-    cp = flat_gpu[off:off + (144 if cin == 1 else 1104)].contiguous()
+    cp = flat_gpu[conv_param_slice(name)].contiguous()
     ws = b.tconv_workspace(dst_is_var, cin)
     xs_t = torch.tensor(xs, dtype=torch.float32, device="cuda")
     xd_t = torch.tensor(xd, dtype=torch.float32, device="cuda")
@@ -273,7 +275,8 @@ def test_adam_and_trainer_follow_reference_loop(LPBatch, subset5, golden, weight
                                    rtol=1e-4, atol=1e-5)
         assert float(tr.opt.state[0]) == 3.0
     # gconv3_s2w is never called (reference methods.py:248): it receives zero gradient and never moves
-    np.testing.assert_array_equal(tr.params.cpu().numpy()[3600:4704], flat.astype(np.float32)[3600:4704])
+    unused = conv_param_slice("gconv3_s2w")
+    np.testing.assert_array_equal(tr.params.cpu().numpy()[unused], flat.astype(np.float32)[unused])
 
 
 def test_dropin_gnnmodel_autograd(subset5, golden, weights):
@@ -479,9 +482,9 @@ def test_tiled_attention_forward_equals_generic_and_oracle(LPBatch, weights):
     flat, sd, flat_gpu = weights
     sb = synthetic_batch(n_inst=4, m=600, n=1100, mean_row_nnz=30.0, seed=41, chunk=2)
     rng = np.random.default_rng(4)
-    for dst_is_var, off in ((False, 1392), (True, 288)):
+    for dst_is_var, name in ((False, "gconv2_s2w"), (True, "gconv2_w2s")):
         nd, ns = (sb.N, sb.M) if dst_is_var else (sb.M, sb.N)
-        cp = flat_gpu[off:off + 1104].contiguous()
+        cp = flat_gpu[conv_param_slice(name)].contiguous()
         xs = torch.tensor(rng.standard_normal((ns, 16)).astype(np.float32), device="cuda")
         xd = torch.tensor(rng.standard_normal((nd, 16)).astype(np.float32), device="cuda")
         ws_a, ws_b = sb.tconv_workspace(dst_is_var, 16), sb.tconv_workspace(dst_is_var, 16)
@@ -499,7 +502,7 @@ def test_tiled_attention_forward_equals_generic_and_oracle(LPBatch, weights):
         dh = torch.tensor(rng.standard_normal((nd, 16)).astype(np.float32), device="cuda")
         pg_b = sb.tconv_bwd(dst_is_var, 16, cp, xs, xd, h_til, ws_b, dh)[0].cpu().numpy()
         pg_a = sb.tconv_bwd(dst_is_var, 16, cp, xs, xd, h_ref, ws_a, dh)[0].cpu().numpy()
-        keep = np.ones(1104, bool)
+        keep = np.ones(cp.numel(), bool)
         keep[256:272] = False                                   # lin_key.bias
         close(pg_b[keep], pg_a[keep], 2e-5, "param grads after tiled forward")
     # whole model with both tiled attention copies attached
@@ -526,9 +529,9 @@ def test_tiled_attention_backward_src_equals_generic_and_oracle(LPBatch, weights
     flat, sd, flat_gpu = weights
     sb = synthetic_batch(n_inst=4, m=600, n=1100, mean_row_nnz=30.0, seed=43, chunk=2)
     rng = np.random.default_rng(5)
-    for dst_is_var, off in ((False, 1392), (True, 288)):
+    for dst_is_var, name in ((False, "gconv2_s2w"), (True, "gconv2_w2s")):
         nd, ns = (sb.N, sb.M) if dst_is_var else (sb.M, sb.N)
-        cp = flat_gpu[off:off + 1104].contiguous()
+        cp = flat_gpu[conv_param_slice(name)].contiguous()
         xs = torch.tensor(rng.standard_normal((ns, 16)).astype(np.float32), device="cuda")
         xd = torch.tensor(rng.standard_normal((nd, 16)).astype(np.float32), device="cuda")
         dh = torch.tensor(rng.standard_normal((nd, 16)).astype(np.float32), device="cuda")
@@ -546,7 +549,7 @@ def test_tiled_attention_backward_src_equals_generic_and_oracle(LPBatch, weights
         assert sb.enable_tiled(dst_is_var, variant=4) is not None
         pg_c, dxd_c, dxs_c, _ = sb.tconv_bwd(dst_is_var, 16, cp, xs, xd, h, ws, dh)
         close(dxd_c.cpu().numpy(), dxd_a.cpu().numpy(), 2e-6, "dx_dst tiled vs generic")
-        keep = np.ones(1104, bool)
+        keep = np.ones(cp.numel(), bool)
         keep[256:272] = False                                   # lin_key.bias
         close(pg_c.cpu().numpy()[keep], pg_a.cpu().numpy()[keep], 2e-5, "param grads, tiled destination sweep")
         assert torch.equal(dxs_c, dxs_b)
@@ -576,9 +579,9 @@ def test_tiled_layer1_sweeps_equal_generic_and_oracle(LPBatch, weights):
     sb = synthetic_batch(n_inst=4, m=600, n=1101, mean_row_nnz=30.0, seed=47, chunk=2)
     rng = np.random.default_rng(6)
     up16 = lambda v: (v + 15) // 16 * 16
-    for dst_is_var, off in ((False, 144), (True, 0)):
+    for dst_is_var, name in ((False, "gconv1_s2w"), (True, "gconv1_w2s")):
         nd, ns = (sb.N, sb.M) if dst_is_var else (sb.M, sb.N)
-        cp = flat_gpu[off:off + 144].contiguous()
+        cp = flat_gpu[conv_param_slice(name)].contiguous()
         xs = torch.tensor(rng.standard_normal(ns).astype(np.float32), device="cuda")
         xd = torch.tensor(rng.standard_normal(nd).astype(np.float32), device="cuda")
         dh = torch.tensor(rng.standard_normal((nd, 16)).astype(np.float32), device="cuda")
@@ -593,7 +596,7 @@ def test_tiled_layer1_sweeps_equal_generic_and_oracle(LPBatch, weights):
         o_ += up16(nd)
         close(ws_b[o_:o_ + nd * 4].cpu().numpy(), ws_a[o_:o_ + nd * 4].cpu().numpy(), 2e-6, "layer-1 aux tiled vs generic")
         pg_b = sb.tconv_bwd(dst_is_var, 1, cp, xs, xd, h_b, ws_b, dh)[0]
-        keep = np.ones(144, bool)
+        keep = np.ones(cp.numel(), bool)
         keep[16:32] = False                                     # lin_key.bias (cancels in the softmax)
         close(pg_b.cpu().numpy()[keep], pg_a.cpu().numpy()[keep], 2e-5, "layer-1 param grads tiled vs generic")
         assert torch.equal(sb.tconv_fwd(dst_is_var, 1, cp, xs, xd, ws_b), h_b)                  # run-to-run bitwise

@@ -12,6 +12,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+from mllp_amd._lib import conv_param_slice  # noqa: E402
 from mllp_amd.data import LPInstance, load_packed  # noqa: E402
 from oracle import pyg_restatement as o1  # noqa: E402
 from oracle import spmm_form as o2  # noqa: E402
@@ -129,7 +130,7 @@ def test_lane_copy_permutes_the_csr(LPBatch):
         assert b.stream_copy_info(transpose, GEOM)["n_tiles"] == 0
 
 
-def _layer1_case(LPBatch, insts, sd, name, dst_is_var, off, seed, what=""):
+def _layer1_case(LPBatch, insts, sd, name, dst_is_var, seed, what=""):
     b = LPBatch.from_instances(insts)
     ob = o2.BatchCSR(insts)
     rng = np.random.default_rng(seed)
@@ -140,7 +141,7 @@ def _layer1_case(LPBatch, insts, sd, name, dst_is_var, off, seed, what=""):
     xs, xd, dh = r32(rng.standard_normal((ns, 1))), r32(rng.standard_normal((nd, 1))), r32(rng.standard_normal((nd, 16)))
     h_ref, saved = o2.conv_fwd(p, ptr, idx, val, xs, xd)
     flat = o1.flatten_state({k: torch.tensor(v) for k, v in sd.items()}).float().cuda()
-    cp = flat[off:off + 144].contiguous()
+    cp = flat[conv_param_slice(name)].contiguous()
     xs_t = torch.tensor(xs[:, 0], dtype=torch.float32, device="cuda")
     xd_t = torch.tensor(xd[:, 0], dtype=torch.float32, device="cuda")
     dh_t = torch.tensor(dh, dtype=torch.float32, device="cuda")
@@ -172,7 +173,8 @@ def _layer1_case(LPBatch, insts, sd, name, dst_is_var, off, seed, what=""):
         o3 += ref.size
 
 
-@pytest.mark.parametrize("name,dst_is_var,off", [("gconv1_w2s", True, 0), ("gconv1_s2w", False, 144)])
+@pytest.mark.parametrize("name,dst_is_var,off", [          # (off: the conv's offset, part of the test id)
+    (n, v, conv_param_slice(n).start) for n, v in (("gconv1_w2s", True), ("gconv1_s2w", False))])
 def test_lane_layer1_ragged_and_wide_batches(LPBatch, sd9, name, dst_is_var, off):
     dense = {i: 30 + 7 * i for i in range(0, 60, 3)}
     cases = [
@@ -183,14 +185,14 @@ def test_lane_layer1_ragged_and_wide_batches(LPBatch, sd9, name, dst_is_var, off
         [_wide_instance(60, 700, 45011, 60), _ragged_instance(61, 90, 130)],
     ]
     for k, insts in enumerate(cases):
-        _layer1_case(LPBatch, insts, sd9, name, dst_is_var, off, seed=200 + k, what=f"case {k} {name}")
+        _layer1_case(LPBatch, insts, sd9, name, dst_is_var, seed=200 + k, what=f"case {k} {name}")
 
 
 def test_lane_layer1_full_netlib(LPBatch, sd9):
     """All 97 Netlib instances (rows of up to 6 184 entries next to rows of one), both orientations."""
     insts = load_packed()
-    _layer1_case(LPBatch, insts, sd9, "gconv1_w2s", True, 0, seed=7, what="netlib w2s")
-    _layer1_case(LPBatch, insts, sd9, "gconv1_s2w", False, 144, seed=8, what="netlib s2w")
+    _layer1_case(LPBatch, insts, sd9, "gconv1_w2s", True, seed=7, what="netlib w2s")
+    _layer1_case(LPBatch, insts, sd9, "gconv1_s2w", False, seed=8, what="netlib s2w")
 
 
 def test_skewed_batch_does_not_keep_a_padded_copy(LPBatch):

@@ -11,6 +11,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+from mllp_amd._lib import conv_param_slice  # noqa: E402
 from mllp_amd.data import LPInstance, load_packed  # noqa: E402
 from oracle import pyg_restatement as o1  # noqa: E402
 from oracle import spmm_form as o2  # noqa: E402
@@ -123,7 +124,7 @@ def test_attention_copies_device_equals_host_and_permute_the_csr(LPBatch, geom):
         assert b.stream_copy_info(transpose, geom)["n_tiles"] == 0
 
 
-def _layer_case(LPBatch, insts, sd, name, dst_is_var, off, seed, scale_q=1.0, geoms=(1, 2, 3), what="", rtol_grad=RTOL_GRAD):
+def _layer_case(LPBatch, insts, sd, name, dst_is_var, seed, scale_q=1.0, geoms=(1, 2, 3), what="", rtol_grad=RTOL_GRAD):
     """One 16-channel TransformerConv, forward and backward, with the streamed copies attached, against the fp64 oracle
     and against the generic sweeps (same library, no copies)."""
     b = LPBatch.from_instances(insts)
@@ -141,7 +142,7 @@ def _layer_case(LPBatch, insts, sd, name, dst_is_var, off, seed, scale_q=1.0, ge
     xs, xd, dh = r32(rng.standard_normal((ns, 16))), r32(rng.standard_normal((nd, 16))), r32(rng.standard_normal((nd, 16)))
     h_ref, saved = o2.conv_fwd(p, ptr, idx, val, xs, xd)
     flat = o1.flatten_state({k: torch.tensor(v) for k, v in sd.items()}).float().cuda()
-    cp = flat[off:off + 1104].contiguous()
+    cp = flat[conv_param_slice(name)].contiguous()
     xs_t = torch.tensor(xs, dtype=torch.float32, device="cuda")
     xd_t = torch.tensor(xd, dtype=torch.float32, device="cuda")
     dh_t = torch.tensor(dh, dtype=torch.float32, device="cuda")
@@ -182,7 +183,8 @@ def sd9():
     return {k: v.numpy() for k, v in o1.init_state(9, torch.float64).items()}
 
 
-@pytest.mark.parametrize("name,dst_is_var,off", [("gconv2_w2s", True, 288), ("gconv2_s2w", False, 1392)])
+@pytest.mark.parametrize("name,dst_is_var,off", [          # (off: the conv's offset, part of the test id)
+    (n, v, conv_param_slice(n).start) for n, v in (("gconv2_w2s", True), ("gconv2_s2w", False))])
 def test_streamed_layer_ragged_batches(LPBatch, sd9, name, dst_is_var, off):
     """Empty rows, rows of 1-3 entries, rows of dozens of entries inside one column block (longer than the register set
     of a pass: the compiled slow pass), tiny instances, an instance without nonzeros, tiles of exactly 480 / 481 rows."""
@@ -195,14 +197,14 @@ def test_streamed_layer_ragged_batches(LPBatch, sd9, name, dst_is_var, off):
          LPInstance("empty", np.zeros(6, np.int64), np.zeros(0, np.int32), np.zeros(0), np.zeros(4), np.zeros(5), np.zeros(4, np.int32))],
     ]
     for k, insts in enumerate(cases):
-        _layer_case(LPBatch, insts, sd9, name, dst_is_var, off, seed=100 + k, what=f"case {k} {name}")
+        _layer_case(LPBatch, insts, sd9, name, dst_is_var, seed=100 + k, what=f"case {k} {name}")
 
 
 def test_streamed_layer_full_netlib(LPBatch, sd9):
     """All 97 Netlib instances (rows of up to 6 184 entries), both orientations."""
     insts = load_packed()
-    _layer_case(LPBatch, insts, sd9, "gconv2_w2s", True, 288, seed=7, what="netlib w2s")
-    _layer_case(LPBatch, insts, sd9, "gconv2_s2w", False, 1392, seed=8, what="netlib s2w")
+    _layer_case(LPBatch, insts, sd9, "gconv2_w2s", True, seed=7, what="netlib w2s")
+    _layer_case(LPBatch, insts, sd9, "gconv2_s2w", False, seed=8, what="netlib s2w")
 
 
 def test_streamed_layer_logits_beyond_the_fast_window(LPBatch, sd9):
@@ -214,8 +216,8 @@ def test_streamed_layer_logits_beyond_the_fast_window(LPBatch, sd9):
     # gradients sum thousands of them -- the generic sweeps show the same deviation from the fp64 oracle there, which is
     # measured on the same input and bounds the streamed sweeps' deviation)
     for scale, rtol in ((8.0, RTOL_GRAD), (60.0, 4 * RTOL_GRAD)):
-        for name, dst_is_var, off, seed in (("gconv2_s2w", False, 1392, 9), ("gconv2_w2s", True, 288, 10)):
-            dev = _layer_case(LPBatch, insts, sd9, name, dst_is_var, off, seed=seed, scale_q=scale, what=f"scale {scale}",
+        for name, dst_is_var, seed in (("gconv2_s2w", False, 9), ("gconv2_w2s", True, 10)):
+            dev = _layer_case(LPBatch, insts, sd9, name, dst_is_var, seed=seed, scale_q=scale, what=f"scale {scale}",
                               rtol_grad=rtol)
             print(f"scale {scale} {name}: gradient deviation from the fp64 oracle, streamed {dev['streamed']:.3e}, "
                   f"generic {dev['generic']:.3e}")

@@ -9,6 +9,7 @@ sys.path.insert(0, ROOT)
 from mllp_amd import _lib
 _lib.LIB_PATH = os.path.join(ROOT, "mllp_amd", "csrc", os.environ.get("MLLP_LIB", "libmllp_hip_timing.so"))
 from mllp_amd.graph import synthetic_batch
+from mllp_amd._lib import conv_param_slice
 from mllp_amd.model import GNNModel, set_seed
 
 n_inst = int(sys.argv[1]) if len(sys.argv) > 1 else 64
@@ -16,9 +17,8 @@ dst_is_var = bool(int(sys.argv[2])) if len(sys.argv) > 2 else False
 b = synthetic_batch(n_inst)
 set_seed(42)
 params = GNNModel().flat_parameters().detach().float().cuda()
-off = 288 if dst_is_var else 1392
 nd, ns = (b.N, b.M) if dst_is_var else (b.M, b.N)
-cp = params[off:off + 1104].contiguous()
+cp = params[conv_param_slice("gconv2_w2s" if dst_is_var else "gconv2_s2w")].contiguous()
 g = torch.Generator(device="cuda").manual_seed(1)
 xs = torch.randn(ns, 16, device="cuda", generator=g); xd = torch.randn(nd, 16, device="cuda", generator=g)
 dh = torch.randn(nd, 16, device="cuda", generator=g)

@@ -10,6 +10,7 @@ if os.environ.get("MLLP_LIB"):              # experiments: a variant build of th
     from mllp_amd import _lib
     _lib.LIB_PATH = os.path.join(ROOT, "mllp_amd", "csrc", os.environ["MLLP_LIB"])
 from mllp_amd.graph import synthetic_batch
+from mllp_amd._lib import conv_param_slice
 from mllp_amd.model import GNNModel, set_seed
 
 n_inst = int(sys.argv[1]) if len(sys.argv) > 1 else 64
@@ -27,9 +28,9 @@ def timed(fn):
     e1.record(); torch.cuda.synchronize()
     return e0.elapsed_time(e1) / reps
 def rel(a, r): return (a - r).abs().max().item() / r.abs().max().item()
-for dst_is_var, off in ((False, 1392), (True, 288)):
+for dst_is_var, name in ((False, "gconv2_s2w"), (True, "gconv2_w2s")):
     nd, ns = (b.N, b.M) if dst_is_var else (b.M, b.N)
-    cp = params[off:off + 1104].contiguous()
+    cp = params[conv_param_slice(name)].contiguous()
     g = torch.Generator(device="cuda").manual_seed(1)
     xs = torch.randn(ns, 16, device="cuda", generator=g); xd = torch.randn(nd, 16, device="cuda", generator=g)
     dh = torch.randn(nd, 16, device="cuda", generator=g)

@@ -9,6 +9,7 @@ if os.environ.get("MLLP_LIB"):              # experiments: a variant build of th
     from mllp_amd import _lib
     _lib.LIB_PATH = os.path.join(ROOT, "mllp_amd", "csrc", os.environ["MLLP_LIB"])
 from mllp_amd.graph import synthetic_batch
+from mllp_amd._lib import conv_param_slice
 from mllp_amd.model import GNNModel, set_seed
 
 n_inst = int(sys.argv[1]) if len(sys.argv) > 1 else 64
@@ -23,9 +24,9 @@ def timed(fn):
     for _ in range(reps): fn()
     e1.record(); torch.cuda.synchronize()
     return e0.elapsed_time(e1) / reps
-for dst_is_var, off in ((False, 1392), (True, 288)):
+for dst_is_var, name in ((False, "gconv2_s2w"), (True, "gconv2_w2s")):
     nd, ns = (b.N, b.M) if dst_is_var else (b.M, b.N)
-    cp = params[off:off + 1104].contiguous()
+    cp = params[conv_param_slice(name)].contiguous()
     xs = torch.randn(ns, 16, device="cuda"); xd = torch.randn(nd, 16, device="cuda")
     ws = b.tconv_workspace(dst_is_var, 16)
     byt = b.nnz * 8 + 4 * (nd + 1) + ns * 64 + nd * 408
@@ -48,9 +49,9 @@ for dst_is_var, off in ((False, 1392), (True, 288)):
     print(f"dst_is_var={dst_is_var} conv bwd with tiled source AND destination sweeps {ms_d:.3f} ms  {info}")
     b.disable_tiled(not dst_is_var, variant=2); b.disable_tiled(dst_is_var, variant=1); b.disable_tiled(dst_is_var, variant=4)
 # layer-1 (one channel) convs: generic sweeps vs LDS-tiled (variant 3)
-for dst_is_var, off in ((False, 144), (True, 0)):
+for dst_is_var, name in ((False, "gconv1_s2w"), (True, "gconv1_w2s")):
     nd, ns = (b.N, b.M) if dst_is_var else (b.M, b.N)
-    cp = params[off:off + 144].contiguous()
+    cp = params[conv_param_slice(name)].contiguous()
     xs = torch.randn(ns, device="cuda"); xd = torch.randn(nd, device="cuda"); dh = torch.randn(nd, 16, device="cuda")
     ws = b.tconv_workspace(dst_is_var, 1)
     h = b.tconv_fwd(dst_is_var, 1, cp, xs, xd, ws).clone()

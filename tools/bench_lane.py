@@ -11,6 +11,7 @@ if os.environ.get("MLLP_LIB"):              # experiments: a variant build of th
     from mllp_amd import _lib
     _lib.LIB_PATH = os.path.join(ROOT, "mllp_amd", "csrc", os.environ["MLLP_LIB"])
 from mllp_amd.graph import synthetic_batch
+from mllp_amd._lib import conv_param_slice
 from mllp_amd.model import GNNModel, set_seed
 
 n_inst = int(sys.argv[1]) if len(sys.argv) > 1 else 64
@@ -26,9 +27,9 @@ def timed(fn):
     e1.record(); torch.cuda.synchronize()
     return e0.elapsed_time(e1) / reps
 def rel(a, r): return (a - r).abs().max().item() / r.abs().max().item()
-for dst_is_var, off in ((False, 144), (True, 0)):
+for dst_is_var, name in ((False, "gconv1_s2w"), (True, "gconv1_w2s")):
     nd, ns = (b.N, b.M) if dst_is_var else (b.M, b.N)
-    cp = params[off:off + 144].contiguous()
+    cp = params[conv_param_slice(name)].contiguous()
     g = torch.Generator(device="cuda").manual_seed(1)
     xs = torch.randn(ns, device="cuda", generator=g); xd = torch.randn(nd, device="cuda", generator=g)
     dh = torch.randn(nd, 16, device="cuda", generator=g)
@@ -44,7 +45,7 @@ for dst_is_var, off in ((False, 144), (True, 0)):
         msb = timed(lambda: b.tconv_bwd(dst_is_var, 1, cp, xs, xd, hh, ws, dh))
         pg = b.tconv_bwd(dst_is_var, 1, cp, xs, xd, hh, ws, dh)[0]
         if ref is None: ref, refb = h.clone(), pg.clone()
-        keep = torch.ones(144, dtype=torch.bool, device="cuda"); keep[16:32] = False
+        keep = torch.ones(cp.numel(), dtype=torch.bool, device="cuda"); keep[16:32] = False
         print(f"dst_is_var={dst_is_var} {kind:8s} fwd {msf:.3f} ms ({byt/msf/1e6/8000:.3f} of 8 TB/s at 6 B/nnz)  bwd (all kernels) {msb:.3f} ms"
               f"  maxrel h={rel(h, ref):.2e} pg={rel(pg[keep], refb[keep]):.2e}", flush=True)
         if kind == "tiled": b.disable_tiled(dst_is_var, variant=3)

@@ -7,6 +7,7 @@ import torch
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
 from mllp_amd.graph import synthetic_batch
+from mllp_amd._lib import conv_param_slice
 from mllp_amd.model import GNNModel, set_seed
 
 n_inst = int(sys.argv[1]) if len(sys.argv) > 1 else 256
@@ -14,9 +15,9 @@ reps = int(sys.argv[2]) if len(sys.argv) > 2 else 3
 b = synthetic_batch(n_inst)
 set_seed(42)
 params = GNNModel().flat_parameters().detach().float().cuda()
-for dst_is_var, off in ((False, 144), (True, 0)):
+for dst_is_var, name in ((False, "gconv1_s2w"), (True, "gconv1_w2s")):
     nd, ns = (b.N, b.M) if dst_is_var else (b.M, b.N)
-    cp = params[off:off + 144].contiguous()
+    cp = params[conv_param_slice(name)].contiguous()
     g = torch.Generator(device="cuda").manual_seed(1)
     xs = torch.randn(ns, device="cuda", generator=g); xd = torch.randn(nd, device="cuda", generator=g)
     dh = torch.randn(nd, 16, device="cuda", generator=g)

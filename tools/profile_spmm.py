@@ -9,6 +9,7 @@ import torch
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
 from mllp_amd.graph import synthetic_batch  # noqa: E402
+from mllp_amd._lib import conv_param_slice  # noqa: E402
 from mllp_amd.model import GNNModel, set_seed  # noqa: E402
 
 n_inst = int(sys.argv[1]) if len(sys.argv) > 1 else 32
@@ -24,7 +25,7 @@ for _ in range(reps):
     b.spmm(Ht, transpose=True, out=Yt)
 if which in ("conv", "all"):
     params = (set_seed(42), GNNModel().flat_parameters().detach().float().cuda())[1]
-    cp = params[1392:1392 + 1104].contiguous()
+    cp = params[conv_param_slice("gconv2_s2w")].contiguous()
     ws = b.tconv_workspace(False, 16)
     for _ in range(reps):
         h = b.tconv_fwd(False, 16, cp, H, Ht, ws)
