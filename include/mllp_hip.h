@@ -333,6 +333,29 @@ int mllp_gnn_train_step(const mllp_graph_t* g, float* d_params, const float* d_x
                         float* d_grads, float* d_exp_avg, float* d_exp_avg_sq, float* d_state, float eps, int flags,
                         void* stream);
 
+/* The training step of a SMALL batch as one launch of one workgroup (small_step.hip): weight fold, the five convs forward,
+ * fc + BCEWithLogits, the five convs backward, the parameter gradients and, with the three optimizer buffers given, Adam.
+ * It is the step of the reference's own loop -- one LP, one Adam step, the next LP (linear_program_experiment.py:123-144)
+ * -- for instances whose cost on the other paths is their launches.  The kernel reads the graph's plain arrays only
+ * (CSR(A), CSR(A^T), 1 / n_k), so it runs on any graph whatever mllp_graph_set_path selected, and leaves the path alone.
+ *   mllp_gnn_small_step_limits  limits = {max nodes M + N, max nonzeros, threads of the workgroup, LDS bytes}; needs no GPU.
+ *                               Every graph with M + N <= 2048 and nnz <= 8192 is within the limits.
+ *   mllp_gnn_small_step_fits    *fits = 1 when g is within the limits, else 0.
+ *   mllp_gnn_train_step_small   arguments as mllp_gnn_train_step (no flags).  d_exp_avg == d_exp_avg_sq == d_state == NULL
+ *                               selects the loss step: d_logits, d_loss, d_grads are written, d_params is not touched;
+ *                               one or two of the three NULL is MLLP_EINVAL.  A graph beyond the limits is refused with
+ *                               MLLP_EINVAL before any launch, nothing written; the message names the limit.  d_ws is the
+ *                               buffer of mllp_gnn_workspace_bytes().  One launch on `stream`, no allocation, hipGraph-
+ *                               capturable, bitwise reproducible.  The call forgets the forward and the folded weights the
+ *                               library remembered for g: a later mllp_gnn_backward asks for a forward first, and a later
+ *                               mllp_gnn_train_step folds its weights whatever flags bit 0 says.                       */
+int mllp_gnn_small_step_limits(int64_t limits[4]);
+int mllp_gnn_small_step_fits(const mllp_graph_t* g, int* fits);
+int mllp_gnn_train_step_small(const mllp_graph_t* g, float* d_params, const float* d_x1, const float* d_x2,
+                              const float* d_labels, float inv_batch, void* d_ws, float* d_logits, float* d_loss,
+                              float* d_grads, float* d_exp_avg, float* d_exp_avg_sq, float* d_state, float eps,
+                              void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Prediction + metrics (linear_program_experiment.py:146-151): per instance k, mark the m_k largest
  * logits, correct_k = |pred & basis|, f1_k = 2TP / (2TP + FP + FN).

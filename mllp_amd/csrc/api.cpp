@@ -516,6 +516,48 @@ extern "C" int mllp_gnn_train_step(const mllp_graph_t* g, float* d_params, const
     return launch_adam(d_params, d_grads, d_exp_avg, d_exp_avg_sq, d_state, eps, 1.0f, MLLP_NUM_PARAMS, s);
 }
 
+// ---- one-launch step of a small batch (small_step.hip) ---------------------------------------------------------------
+extern "C" int mllp_gnn_small_step_limits(int64_t limits[4]) {
+    REQUIRE(limits, "null argument");
+    limits[0] = SMALL_STEP_MAX_NODES; limits[1] = SMALL_STEP_MAX_NNZ;
+    limits[2] = SMALL_STEP_THREADS; limits[3] = SMALL_STEP_LDS_BYTES;
+    return MLLP_OK;
+}
+
+// empty when g is within the limits, else the sentence that names the limit it exceeds
+static std::string small_step_excess(const mllp_graph* g) {
+    if (g->M + g->N > SMALL_STEP_MAX_NODES)
+        return "the graph has " + std::to_string(g->M + g->N) + " nodes, the limit is " + std::to_string(SMALL_STEP_MAX_NODES);
+    if (g->nnz > SMALL_STEP_MAX_NNZ)
+        return "the graph has " + std::to_string(g->nnz) + " nonzeros, the limit is " + std::to_string(SMALL_STEP_MAX_NNZ);
+    return std::string();
+}
+
+extern "C" int mllp_gnn_small_step_fits(const mllp_graph_t* g, int* fits) {
+    REQUIRE(g && fits, "null argument");
+    *fits = small_step_excess(g).empty() ? 1 : 0;
+    return MLLP_OK;
+}
+
+extern "C" int mllp_gnn_train_step_small(const mllp_graph_t* g, float* d_params, const float* d_x1, const float* d_x2,
+                                         const float* d_labels, float inv_batch, void* d_ws, float* d_logits,
+                                         float* d_loss, float* d_grads, float* d_exp_avg, float* d_exp_avg_sq,
+                                         float* d_state, float eps, void* stream) {
+    REQUIRE(g && d_params && d_x1 && d_x2 && d_labels && d_ws && d_logits && d_loss && d_grads, "null argument");
+    const int n_opt = (d_exp_avg != nullptr) + (d_exp_avg_sq != nullptr) + (d_state != nullptr);
+    REQUIRE(n_opt == 0 || n_opt == 3, "optimizer state: give d_exp_avg, d_exp_avg_sq and d_state, or none of them (loss step)");
+    const std::string excess = small_step_excess(g);
+    REQUIRE(excess.empty(), excess + " (mllp_gnn_small_step_limits)");
+    // the kernel lays the workspace out as the generic path does but saves less: nothing the library remembers about
+    // this graph's workspace or folded weights holds afterwards
+    mllp_graph* gm = const_cast<mllp_graph*>(g);
+    gm->ws_ptr = nullptr;
+    gm->ws_path = -1;
+    gm->folded_ws = gm->folded_params = nullptr;
+    return launch_small_step(g, d_params, d_x1, d_x2, d_labels, inv_batch, model_ws(g, (float*)d_ws), d_logits, d_loss,
+                             d_grads, d_exp_avg, d_exp_avg_sq, d_state, eps, (hipStream_t)stream);
+}
+
 extern "C" int mllp_adam_step(float* d_params, const float* d_grads, float* d_exp_avg, float* d_exp_avg_sq,
                               float* d_state, float eps, float grad_scale, int64_t n, void* stream) {
     REQUIRE(d_params && d_grads && d_exp_avg && d_exp_avg_sq && d_state, "null argument");

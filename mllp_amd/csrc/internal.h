@@ -371,6 +371,14 @@ int head_blocks_for(int64_t n);
 int launch_adam(float* p, const float* g, float* m, float* v, float* state, float eps, float gscale, int64_t n,
                 hipStream_t s);
 int launch_fill_zero(float* p, int64_t n, hipStream_t s);
+
+// ---- one-launch step of a small batch (small_step.hip): one workgroup, the caller's workspace in model_ws layout ------
+// The limits of mllp_gnn_small_step_limits, stated once.  Floor of the ABI: M + N <= 2048 and nnz <= 8192 is eligible.
+constexpr int64_t SMALL_STEP_MAX_NODES = 8192, SMALL_STEP_MAX_NNZ = 16384;
+constexpr int SMALL_STEP_THREADS = 1024, SMALL_STEP_LDS_BYTES = 63296;
+int launch_small_step(const mllp_graph* g, float* params, const float* x1, const float* x2, const float* labels,
+                      float inv_batch, const ModelWs& w, float* logits, float* loss, float* grads, float* m, float* v,
+                      float* state, float eps, hipStream_t s);   // m == nullptr: gradients only
 int launch_topm_metrics(const mllp_graph* g, const float* logits, const float* labels, void* scratch, float* out,
                         hipStream_t s);
 // select.hip: ptr_n / ptr_m [n_seg + 1] device, or ptr_n == nullptr for ONE segment of n_dense logits, m_dense to select

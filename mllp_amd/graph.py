@@ -666,6 +666,30 @@ class LPBatch:
         self._folded = None if param_gen is None else (params.data_ptr(), params._version, param_gen + 1)
         return loss, logits, grads
 
+    def small_step_fits(self):
+        """Whether the batch is within the limits of the one-launch step (`small_step_limits`)."""
+        fits = ctypes.c_int()
+        _lib.check(_lib.lib().mllp_gnn_small_step_fits(self._h, ctypes.byref(fits)))
+        return bool(fits.value)
+
+    def train_step_small(self, params, exp_avg=None, exp_avg_sq=None, state=None, eps=1e-8, inv_batch=None, logits=None,
+                         loss=None, grads=None):
+        """The whole step as one launch of one workgroup (mllp_gnn_train_step_small), for a batch that `small_step_fits`.
+        With the three optimizer buffers: loss_step + Adam, as `train_step`.  Without them: the loss step, `params` stay."""
+        dev = params.device
+        logits = torch.empty(self.N, device=dev, dtype=torch.float32) if logits is None else logits
+        loss = torch.empty(1, device=dev, dtype=torch.float32) if loss is None else loss
+        grads = torch.empty(_lib.NUM_PARAMS, device=dev, dtype=torch.float32) if grads is None else grads
+        ib = (1.0 / self.n_inst) if inv_batch is None else float(inv_batch)
+        self._check_inputs()
+        self._folded = None          # (the library forgets the folded weights too)
+        _lib.check(_lib.lib().mllp_gnn_train_step_small(self._h, _lib.ptr(params), _lib.ptr(self.x1), _lib.ptr(self.x2),
+                                                        _lib.ptr(self.labels), ib, _lib.ptr(self.workspace()),
+                                                        _lib.ptr(logits), _lib.ptr(loss), _lib.ptr(grads),
+                                                        _lib.ptr(exp_avg), _lib.ptr(exp_avg_sq), _lib.ptr(state),
+                                                        float(eps), _lib.current_stream()))
+        return loss, logits, grads
+
     def topm_metrics(self, logits, out=None):
         """[n_inst, 2] = (correct_num, f1) per instance (reference experiment.py:146-151)."""
         if out is None:
@@ -743,6 +767,13 @@ def topm_select_dense(logits, m, want=("mask", "index", "stats")):
     _lib.check(_lib.lib().mllp_topm_select_dense(n, m, _lib.ptr(logits), *[_lib.ptr(b) for b in bufs], _lib.current_stream()))
     mask, index, stats = _select_views(bufs, n, m)
     return BasisPrediction(mask, index, stats, [n], [m])
+
+
+def small_step_limits():
+    """dict(max_nodes, max_nnz, threads, lds_bytes) of the one-launch step (mllp_gnn_small_step_limits); needs no GPU."""
+    out = (c_int64 * 4)()
+    _lib.check(_lib.lib().mllp_gnn_small_step_limits(out))
+    return dict(max_nodes=out[0], max_nnz=out[1], threads=out[2], lds_bytes=out[3])
 
 
 def adam_step(params, grads, exp_avg, exp_avg_sq, state, eps=1e-8, grad_scale=1.0):
