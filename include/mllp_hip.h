@@ -18,7 +18,7 @@
  *     stream); no entry point synchronises except mllp_graph_create_* / mllp_graph_export.
  *   - all launch functions are hipGraph-capturable (no malloc/free/sync inside).
  *   - the sparsity pattern of a mllp_graph_t is immutable after creation; its values change only through
- *     mllp_graph_set_values / mllp_graph_scale_values.  An internal scratch buffer is used by
+ *     mllp_graph_set_values / mllp_graph_scale_values / mllp_graph_normalize.  An internal scratch buffer is used by
  *     rows that are split over several workgroups: calls on ONE graph must be stream-ordered.
  *   - feature width is fixed at 16 (reference linear_program_methods.py:206-211), fp32 everywhere.
  *   - there is NO CPU fallback: without a HIP device every launch function fails with MLLP_EHIP.
@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MLLP_ABI_VERSION 6 /* 2: streamed SpMM copy, device-built tiled copies, mllp_gnn_train_step, mllp_graph_invalidate_inputs; 3: streamed copies of the attention sweeps (mllp_graph_*_stream_copy); 4: input gradients (mllp_gnn_backward_inputs); 5: AngleModel input gradients (mllp_angle_backward_inputs); 6: the predicted basis (mllp_topm_select, mllp_topm_select_dense); mllp_graph_set_values, _set_values_bytes and _scale_values arrived after 6 WITHOUT a bump: they are additions only (no existing export changed signature or meaning), so every caller built against 6 stays valid; a caller that needs them checks for the symbols */
+#define MLLP_ABI_VERSION 6 /* 2: streamed SpMM copy, device-built tiled copies, mllp_gnn_train_step, mllp_graph_invalidate_inputs; 3: streamed copies of the attention sweeps (mllp_graph_*_stream_copy); 4: input gradients (mllp_gnn_backward_inputs); 5: AngleModel input gradients (mllp_angle_backward_inputs); 6: the predicted basis (mllp_topm_select, mllp_topm_select_dense); mllp_graph_set_values, _set_values_bytes and _scale_values arrived after 6 WITHOUT a bump: they are additions only (no existing export changed signature or meaning), so every caller built against 6 stays valid; a caller that needs them checks for the symbols; mllp_graph_normalize and mllp_normalize_row_tier likewise */
 #define MLLP_FEAT 16
 #define MLLP_NUM_PARAMS 4721 /* GNNModel.state_dict(), SURVEY.md appendix A.2 */
 
@@ -144,6 +144,42 @@ int mllp_graph_invalidate_inputs(mllp_graph_t* g);
 int mllp_graph_set_values(mllp_graph_t* g, const float* d_val, void* stream);
 int mllp_graph_set_values_bytes(const mllp_graph_t* g, int64_t* bytes);
 int mllp_graph_scale_values(mllp_graph_t* g, const float* d_row_scale, const float* d_col_scale, void* stream);
+
+/* The reference's normalization of the resident batch, in place and on the device (mllp_amd/csrc/normalize.hip): the
+ * stage that made the tensors the reference's loader reads (linear_program_data.py:58-80, `netlib_mps_norm`), whose rule
+ * is restated in oracle/mps_norm.py `normalize`.  It puts a batch whose coefficients were made or changed on the device
+ * (mllp_graph_create_device, _set_values, _scale_values, a step along dL/da) back on the distribution the weights were
+ * trained on, without the host round trip and the rebuild.  In fp32:
+ *   rows       q_i = sum_j a_ij^2,  s_i = 1 / sqrt(q_i), or 1 for an empty or all-zero row; then, with the cap enabled,
+ *              where |b_i s_i| > rhs_cap:  s_i = rhs_cap / b_i -- SIGNED: a negative b_i flips the whole row, and every
+ *              capped row ends at right-hand side +rhs_cap (an empty row with b_i beyond the cap included).
+ *              rhs_cap <= 0, +inf or NaN disables the cap; the reference's value is 5.
+ *   objective  t_k = 1 / ||x1[instance k]||_2, or 1 for a zero or empty objective.
+ *   apply      x2_i <- b_i s_i,  x1_j <- c_j t_k,  a_ij <- s_i a_ij as mllp_graph_scale_values(g, s, NULL) does: every
+ *              value-holding array of the graph is refreshed with the guarantees of mllp_graph_set_values (byte for byte a
+ *              fresh build from the new values; the workspace record is cleared, so mllp_gnn_backward* needs a new
+ *              mllp_gnn_forward; the folded weights are kept), and the graph's copies of the inputs are invalidated as by
+ *              mllp_graph_invalidate_inputs, because d_x1 / d_x2 were just written.
+ *   d_x1 [N], d_x2 [M] : the batch's objective coefficients and right-hand sides (the inputs of mllp_gnn_*), caller-owned.
+ *   d_row_scale [M], d_obj_scale [n_inst] : receive the applied s_i and t_k (what carries duals or a solution back to the
+ *              original units); NULL = library-owned scratch (M + n_inst floats, allocated by the first call and counted by
+ *              mllp_graph_set_values_bytes from then on).
+ *   flags      bit 0 = compute only: the scales are written (both output pointers are then required) and nothing else is
+ *              written, invalidated or cleared.  Other bits must be 0.
+ * Deterministic and batch-independent: no atomics, and the order in which a row's squares are added depends on that
+ * row's nonzero count alone (mllp_normalize_row_tier: 0 = a 16-lane group up to 64 nonzeros, 1 = a wavefront up to 1024,
+ * 2 = a workgroup), an objective's on n_k alone -- an instance gets the same bits alone and inside any batch.
+ * A row whose |b_i| / ||row_i|| equals the cap to within fp32 rounding may fall on either side of the comparison; with
+ * b_i < 0 the two sides differ by the sign of the row.
+ * MLLP_EINVAL, before anything is written (d_x1 and d_x2 included): null g, d_x1 or d_x2; bit 0 with a null output;
+ * unknown flag bits; a caller-owned LDS-tiled copy is attached (the condition of mllp_graph_set_values).
+ * The FIRST call may allocate and synchronise like mllp_graph_set_values' (make it outside a capture); every later call
+ * is a launch function: `stream` only, no allocation, no synchronisation, hipGraph-capturable (a captured call
+ * invalidates and clears when it is captured, not when it is replayed).  Like _set_values it arrived after ABI 6 without
+ * a bump: an addition only.                                                                                       */
+int mllp_graph_normalize(mllp_graph_t* g, float* d_x1, float* d_x2, float rhs_cap, int flags, float* d_row_scale,
+                         float* d_obj_scale, void* stream);
+int mllp_normalize_row_tier(int64_t row_nnz, int* tier);
 
 /* ------------------------------------------------------------------------------------------------
  * Plain CSR SpMM (the roofline kernel named in BASELINE.json's metric):

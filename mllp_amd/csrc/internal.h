@@ -199,6 +199,8 @@ struct mllp_graph {
     // (mllp_graph_set_values refreshes At.val through the same map and builds it when it runs first)
     int* at_pos = nullptr;
     float* scale_buf = nullptr;  // [nnz] the scaled values of mllp_graph_scale_values, made on its first call (in `allocs`)
+    float* norm_scale = nullptr; // [M + n_inst] row and objective scales of mllp_graph_normalize calls that pass no output
+                                 // array, made on its first call (in `allocs`)
     // second stream + events: the two convs of a layer (one per orientation) and the single-workgroup
     // finalize kernels run beside the main stream (fork/join by events, also under hipGraph capture)
     hipStream_t aux = nullptr;
@@ -354,6 +356,12 @@ int launch_edge_grad(const Orient& o, int64_t nnz, int cin, const ConvWs& w, con
                      int accumulate, hipStream_t s);
 int build_csc_to_csr(const mllp_graph* g, int* pos, hipStream_t s);
 int ensure_at_pos(mllp_graph* g, hipStream_t s);   // set_values.hip: g->at_pos, built once per graph (allocates)
+// set_values.hip: a caller-owned LDS-tiled copy is attached; its values are in arrays the library may not write, so
+// mllp_graph_set_values, _scale_values and _normalize refuse with this message
+bool borrowed_tiled(const mllp_graph* g);
+#define MLLP_BORROWED_TILED_MSG                                                                                         \
+    "a caller-owned LDS-tiled copy is attached (mllp_graph_attach_tiled): its arrays are not the library's to write. " \
+    "Drop it (n_tiles = 0) or build the copy with mllp_graph_build_tiled"
 int launch_layer1_dst_grads(const ConvWs& wv, const float* gv, float* dx1, int64_t n, const ConvWs& wc, const float* gc,
                             float* dx2, int64_t m, hipStream_t s);
 int launch_param_stats(int cin, int64_t n_dst, const ConvWs& w, const float* x_dst, const float* g, hipStream_t s);

@@ -191,6 +191,8 @@ int refresh_copies(Orient& o, int64_t nnz, const float* val, hipStream_t s) {
     return MLLP_OK;
 }
 
+}  // namespace
+
 // a borrowed LDS-tiled copy holds values in arrays that are the caller's: nothing here may write them
 bool borrowed_tiled(const mllp_graph* g) {
     for (const Orient* o : {&g->A, &g->At})
@@ -198,8 +200,6 @@ bool borrowed_tiled(const mllp_graph* g) {
             if (tl.n_tiles > 0 && !tl.owned) return true;
     return false;
 }
-
-}  // namespace
 
 int ensure_at_pos(mllp_graph* g, hipStream_t s) {
     if (g->at_pos || g->nnz == 0) return MLLP_OK;
@@ -215,15 +215,12 @@ int ensure_at_pos(mllp_graph* g, hipStream_t s) {
 
 using namespace mllp;
 
-#define BORROWED_MSG                                                                                                    \
-    "a caller-owned LDS-tiled copy is attached (mllp_graph_attach_tiled): its arrays are not the library's to write. " \
-    "Drop it (n_tiles = 0) or build the copy with mllp_graph_build_tiled"
-
 extern "C" int mllp_graph_set_values_bytes(const mllp_graph_t* g, int64_t* bytes) {
     REQUIRE(g && bytes, "null argument");
     mllp_graph* gm = const_cast<mllp_graph*>(g);      // (the array tables take the copies by reference; nothing is written)
     int64_t words = g->nnz;                           // at_pos
     if (g->scale_buf) words += g->nnz;
+    if (g->norm_scale) words += g->M + g->n_inst;     // (normalize.hip: not a map, counted here with the other scratch)
     for (Orient* o : {&gm->A, &gm->At}) {
         for (int geom = 0; geom < STREAM_GEOMS; ++geom)
             if (o->stream[geom].n_tiles > 0) words += stream_words(o->stream[geom], geom);
@@ -237,7 +234,7 @@ extern "C" int mllp_graph_set_values_bytes(const mllp_graph_t* g, int64_t* bytes
 
 extern "C" int mllp_graph_set_values(mllp_graph_t* g, const float* d_val, void* stream) {
     REQUIRE(g && d_val, "null argument");
-    REQUIRE(!borrowed_tiled(g), BORROWED_MSG);
+    REQUIRE(!borrowed_tiled(g), MLLP_BORROWED_TILED_MSG);
     hipStream_t s = (hipStream_t)stream;
     g->ws_path = -1;            // the workspace holds activations of the old values: backward needs a new forward
     g->ws_ptr = nullptr;
@@ -263,7 +260,7 @@ extern "C" int mllp_graph_set_values(mllp_graph_t* g, const float* d_val, void* 
 
 extern "C" int mllp_graph_scale_values(mllp_graph_t* g, const float* d_row_scale, const float* d_col_scale, void* stream) {
     REQUIRE(g, "null graph");
-    REQUIRE(!borrowed_tiled(g), BORROWED_MSG);
+    REQUIRE(!borrowed_tiled(g), MLLP_BORROWED_TILED_MSG);
     hipStream_t s = (hipStream_t)stream;
     const int64_t nnz = g->nnz;
     if (nnz == 0) return mllp_graph_set_values(g, g->A.val, stream);

@@ -239,7 +239,8 @@ class LPBatch:
     def rescale(self, row_scale=None, col_scale=None):
         """a_ij <- (r_i a_ij) s_j, x2 <- x2 r, x1 <- x1 s, in place (mllp_graph_scale_values): for positive scales the
         same LP in other units, with the same optimal basis -- the label-preserving augmentation of this model's data.
-        `row_scale` [M] / `col_scale` [N] are cuda float32 tensors; None = ones."""
+        `row_scale` [M] / `col_scale` [N] are cuda float32 tensors; None = ones.  `normalize` brings the rescaled batch
+        back to the normalization the weights were trained on (it cancels a positive row scaling, a column scaling stays)."""
         for t, n, what in ((row_scale, self.M, "row_scale"), (col_scale, self.N, "col_scale")):
             if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n):
                 raise ValueError(f"rescale: {what} must be a contiguous cuda float32 tensor of {n} elements")
@@ -251,6 +252,30 @@ class LPBatch:
         if col_scale is not None:
             self.x1.mul_(col_scale.reshape(-1))
         return self.invalidate_inputs()
+
+    def normalize(self, rhs_cap=5.0, compute_only=False):
+        """The reference's normalization of the batch, in place on the device (mllp_graph_normalize): every constraint row
+        to unit 2-norm, or to right-hand side +rhs_cap where unit norm would leave |b_i| above it (signed: a negative b_i
+        flips the row), every instance's objective to unit 2-norm; `self.x1`, `self.x2` and every value-holding array of
+        the batch are rewritten, and a backward needs a new forward afterwards.  rhs_cap <= 0, inf or nan: no cap.
+        Returns (row_scale [M], obj_scale [n_inst]), the applied factors, as cuda tensors.  compute_only=True returns the
+        factors and writes nothing else.  The first call allocates and synchronises; later calls only launch."""
+        dev = self.x1.device
+        row_scale = torch.empty(self.M, dtype=torch.float32, device=dev)
+        obj_scale = torch.empty(self.n_inst, dtype=torch.float32, device=dev)
+        _lib.check(_lib.lib().mllp_graph_normalize(self._h, _lib.ptr(self.x1), _lib.ptr(self.x2), float(rhs_cap),
+                                                   1 if compute_only else 0, _lib.ptr(row_scale), _lib.ptr(obj_scale),
+                                                   _lib.current_stream()))
+        if not compute_only:        # (the library has invalidated its copies of x1 / x2 itself: _in_versions stays)
+            self._fwd_token = getattr(self, "_fwd_token", 0) + 1
+        return row_scale, obj_scale
+
+    @staticmethod
+    def normalize_row_tier(row_nnz):
+        """Which reduction of `normalize` a row of `row_nnz` nonzeros gets: 0 = 16-lane group, 1 = wavefront, 2 = workgroup."""
+        t = ctypes.c_int()
+        _lib.check(_lib.lib().mllp_normalize_row_tier(int(row_nnz), ctypes.byref(t)))
+        return t.value
 
     def set_path(self, path):
         """0 = by size, 1 = generic / LDS-tiled sweeps, 2 = fused latency-regime kernels (whole-model calls only)."""
