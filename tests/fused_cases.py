@@ -11,6 +11,8 @@
    C among its columns, so one constructor controls both orientations.
 4. `model_dt()`: the decomposition of oracle/spmm_form.py in a chosen floating-point type (spmm_form computes in fp64
    whatever it is given); the fp32 run against the fp64 run is the yardstick of the tolerances.
+5. Inputs that several test modules share: ragged random instances and the ragged batch of the copy compositions, the
+   inputs of the one-launch small step, the batches of degree grids with their per-tensor caps.
 """
 import math
 import os
@@ -19,7 +21,7 @@ import re
 import numpy as np
 import scipy.sparse as sp
 
-from mllp_amd.data import LPInstance
+from mllp_amd.data import SUBSET5, LPInstance
 from oracle import spmm_form as o2
 from oracle.pyg_restatement import CONV_CIN, state_dict_spec
 
@@ -496,3 +498,128 @@ def sharp_report(r, batch, rows, c=None):
                 a = np.exp(l - l.max())
                 out.append((orient, key, int(row), deg, tier, -(-deg // w), running_max_moves(l, w), float(a.max() / a.sum())))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 5. ragged instances and the inputs of the one-launch small step (shared by several test modules)
+# ---------------------------------------------------------------------------------------------------------------------
+def holes_instance(seed, m, n):
+    """Random LP with empty rows, empty columns and a few dense rows (ragged input for the tiled copies)."""
+    rng = np.random.default_rng(seed)
+    rows = []
+    for i in range(m):
+        u = rng.random()
+        k = 0 if u < 0.3 else (int(rng.integers(1, 4)) if u < 0.6 else (n // 2 if u > 0.98 else int(rng.poisson(12)) + 1))
+        cols = np.sort(rng.choice(n - n // 10, size=min(k, n - n // 10), replace=False)).astype(np.int32)   # last 10 % of the columns stay empty
+        rows.append(cols)
+    indptr = np.zeros(m + 1, np.int64)
+    indptr[1:] = np.cumsum([len(r) for r in rows])
+    indices = np.concatenate(rows).astype(np.int32) if indptr[-1] else np.zeros(0, np.int32)
+    values = rng.standard_normal(indptr[-1])
+    return LPInstance(f"holes{seed}", indptr, indices, values, rng.standard_normal(n), rng.random(m) * 5,
+                      (rng.random(n) < 0.37).astype(np.int32))
+
+
+def ragged_instance(seed, m, n, dense_rows=(), mean=14):
+    rng = np.random.default_rng(seed)
+    rows = []
+    for i in range(m):
+        u = rng.random()
+        k = 0 if u < 0.2 else (int(rng.integers(1, 4)) if u < 0.45 else int(rng.poisson(mean)) + 1)
+        if i in dense_rows:
+            k = dense_rows[i]
+        hi = max(1, n - n // 10)                               # the last 10 % of the columns stay empty
+        rows.append(np.sort(rng.choice(hi, size=min(k, hi), replace=False)).astype(np.int32))
+    indptr = np.zeros(m + 1, np.int64)
+    indptr[1:] = np.cumsum([len(r) for r in rows])
+    indices = np.concatenate(rows).astype(np.int32) if indptr[-1] else np.zeros(0, np.int32)
+    values = rng.standard_normal(indptr[-1])
+    return LPInstance(f"ragged{seed}", indptr, indices, values, rng.standard_normal(n), rng.random(m) * 5,
+                      (rng.random(n) < 0.37).astype(np.int32))
+
+
+def ragged_batch():
+    """Empty rows, a dense row block, an instance without nonzeros, a 3 x 5 instance, and instances of exactly 480 / 481
+    and 512 / 513 rows (tile boundaries of the copies)."""
+    empty = LPInstance("empty", np.zeros(6, np.int64), np.zeros(0, np.int32), np.zeros(0), np.zeros(4), np.zeros(5),
+                       np.zeros(4, np.int32))
+    return [ragged_instance(21, 400, 700, {i: 30 + 7 * i for i in range(0, 60, 3)}), holes_instance(1, 700, 900), empty,
+            ragged_instance(50, 480, 721), ragged_instance(51, 481, 1100), holes_instance(2, 3, 5),
+            ragged_instance(52, 512, 800), ragged_instance(53, 513, 640, mean=40)]
+
+
+def golden_state(golden):
+    import torch
+    from oracle import pyg_restatement as o1
+    return {k: v.numpy() for k, v in o1.unflatten_state(torch.tensor(golden["weights_flat"])).items()}
+
+
+def small_inst(A, name, seed):
+    A = sp.csr_matrix(A)
+    A.sort_indices()
+    rng = np.random.default_rng(seed)
+    m, n = A.shape
+    return LPInstance(name, A.indptr.astype(np.int64), A.indices.astype(np.int32), A.data.astype(np.float64),
+                      rng.standard_normal(n), rng.standard_normal(m), (rng.random(n) < 0.4).astype(np.int32))
+
+
+def small_grid(seed):
+    """rows AND columns of 0 .. 25 nonzeros (fused_cases.block_of / two_sided)"""
+    rng = np.random.default_rng(seed)
+    B = block_of(list(range(26)), 40, rng)
+    return two_sided(B, B, rng, f"grid25s{seed}")
+
+
+def small_long(as_column):
+    """one entry of 6 145 nonzeros (above every step of the other paths' tiers; this kernel gives each of its 64 groups a
+    chunk of 97 entries, the last one 34) beside rows of 0 .. 5"""
+    rng = np.random.default_rng(11)
+    B = block_of([6145] + [i % 6 for i in range(30)], 6200, rng)
+    return small_inst(B.T if as_column else B, "longcol" if as_column else "longrow", 12)
+
+
+def small_sharp():
+    """fused_cases' sharp case at this kernel's size: coefficients ascending (even rows) / descending (odd rows) along rows
+    on both sides of SM_LONG = 128 entries, in both orientations; the scores are doubled by the caller's weights"""
+    rng = np.random.default_rng(6)
+    degs = [40, 40, 128, 128, 129, 129, 700, 700, 1500, 1500]
+    B = block_of(degs, 1600, rng, values="updown")
+    C = block_of(degs, 1600, rng, values="updown")
+    inst = two_sided(B, C, rng, "sharp_small")
+    inst.coefs[:] = rng.uniform(-0.2, 0.2, inst.n)
+    inst.rhs[:] = rng.uniform(-0.2, 0.2, inst.m)
+    return inst
+
+
+def small_step_cases(golden, subset5):
+    sd = golden_state(golden)
+    cases = [(i.name, sd, [i]) for i in subset5]
+    by = {i.name: i for i in subset5}
+    cases += [("ragged3", sd, [by["afiro.mps"], empty_instance(3, 5), by["sc50a.mps"]]),
+              ("1x1", sd, [small_inst(np.array([[1.5]]), "one", 1)]),
+              ("nonz", sd, [empty_instance(7, 9), empty_instance(2, 1, seed=1)]),
+              ("grid25", sd, [small_grid(0)]),
+              ("grid25x2", sd, [small_grid(0), small_grid(1)]),
+              ("longrow", sd, [small_long(False)]),
+              ("longcol", sd, [small_long(True)]),
+              ("sharp", {k: v.numpy() for k, v in sharp_state(2.0).items()}, [small_sharp()])]
+    return cases
+
+
+SMALL_CASE_NAMES = SUBSET5 + ["ragged3", "1x1", "nonz", "grid25", "grid25x2", "longrow", "longcol", "sharp"]
+# Tensors that the fp32 reference itself cannot pin on their own scale (tests/grad_scales.py; counted by
+# tests/test_grad_scales.py on the CPU): gconv1_w2s.lin_query.weight, a cancellation, on three inputs.  The 1 x 1 instance is
+# no per-tensor input: with one nonzero per row every attention gradient is a cancellation to zero (three tensors exempt).
+SMALL_PER_TENSOR_CAPS = dict({n: 0 for n in SMALL_CASE_NAMES if n != "1x1"}, **{"kb2.mps": 1, "sc50a.mps": 1, "ragged3": 1})
+
+
+# test_fused_oracle.py's batches of n degree grids of different values, (variant, n) -> tensors that the fp32 restatement
+# alone exempts from the per-tensor check of tests/grad_scales.py on the loss step (always two large bias tensors of one
+# conv, lin_skip.bias and lin_value.bias at 1.3e-5 .. 1.8e-5: the restatement sums up to 10^6 terms one after the other);
+# None: more than two, no per-tensor input (grid1 x 8: four).  Asserted on the CPU by tests/test_grad_scales.py.
+GRID_BATCH_CAPS = {(0, 1): 0, (0, 2): 0, (0, 7): 2, (0, 8): 0, (0, 9): 2, (1, 1): 0, (1, 2): 0, (1, 7): 0, (1, 8): None, (1, 9): 2}
+GRID_BATCH_EXEMPT_STATED = {(1, 8): 4}
+
+
+def grid_batch(variant, n_inst):
+    return [degree_grid(variant, seed=s) for s in range(n_inst)]

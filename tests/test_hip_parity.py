@@ -618,21 +618,7 @@ def test_tiled_layer1_sweeps_equal_generic_and_oracle(LPBatch, weights):
     close(grads.cpu().numpy()[grad_mask()], r["grads"][grad_mask()], RTOL_GRAD, "grads with every tiled copy")
 
 
-def _holes_instance(seed, m, n):
-    """Random LP with empty rows, empty columns and a few dense rows (ragged input for the tiled copies)."""
-    rng = np.random.default_rng(seed)
-    rows = []
-    for i in range(m):
-        u = rng.random()
-        k = 0 if u < 0.3 else (int(rng.integers(1, 4)) if u < 0.6 else (n // 2 if u > 0.98 else int(rng.poisson(12)) + 1))
-        cols = np.sort(rng.choice(n - n // 10, size=min(k, n - n // 10), replace=False)).astype(np.int32)   # last 10 % of the columns stay empty
-        rows.append(cols)
-    indptr = np.zeros(m + 1, np.int64)
-    indptr[1:] = np.cumsum([len(r) for r in rows])
-    indices = np.concatenate(rows).astype(np.int32) if indptr[-1] else np.zeros(0, np.int32)
-    values = rng.standard_normal(indptr[-1])
-    return LPInstance(f"holes{seed}", indptr, indices, values, rng.standard_normal(n), rng.random(m) * 5,
-                      (rng.random(n) < 0.37).astype(np.int32))
+from fused_cases import holes_instance as _holes_instance  # noqa: E402
 
 
 def test_tiled_copies_edge_cases(LPBatch, weights):

@@ -14,6 +14,7 @@ ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import fused_cases as fc  # noqa: E402
+import grad_scales as gs  # noqa: E402
 from mllp_amd import _lib  # noqa: E402
 from mllp_amd._lib import conv_param_slice  # noqa: E402
 from mllp_amd.data import SUBSET5, LPInstance, load_packed  # noqa: E402
@@ -77,59 +78,11 @@ def _params(sd):
     return torch.tensor(flat, dtype=torch.float32, device="cuda")
 
 
-def _inst(A, name, seed):
-    A = sp.csr_matrix(A)
-    A.sort_indices()
-    rng = np.random.default_rng(seed)
-    m, n = A.shape
-    return LPInstance(name, A.indptr.astype(np.int64), A.indices.astype(np.int32), A.data.astype(np.float64),
-                      rng.standard_normal(n), rng.standard_normal(m), (rng.random(n) < 0.4).astype(np.int32))
-
-
-def _grid(seed):
-    """rows AND columns of 0 .. 25 nonzeros (fused_cases.block_of / two_sided)"""
-    rng = np.random.default_rng(seed)
-    B = fc.block_of(list(range(26)), 40, rng)
-    return fc.two_sided(B, B, rng, f"grid25s{seed}")
-
-
-def _long(as_column):
-    """one entry of 6 145 nonzeros (above every step of the other paths' tiers; this kernel gives each of its 64 groups a
-    chunk of 97 entries, the last one 34) beside rows of 0 .. 5"""
-    rng = np.random.default_rng(11)
-    B = fc.block_of([6145] + [i % 6 for i in range(30)], 6200, rng)
-    return _inst(B.T if as_column else B, "longcol" if as_column else "longrow", 12)
-
-
-def _sharp():
-    """fused_cases' sharp case at this kernel's size: coefficients ascending (even rows) / descending (odd rows) along rows
-    on both sides of SM_LONG = 128 entries, in both orientations; the scores are doubled by the caller's weights"""
-    rng = np.random.default_rng(6)
-    degs = [40, 40, 128, 128, 129, 129, 700, 700, 1500, 1500]
-    B = fc.block_of(degs, 1600, rng, values="updown")
-    C = fc.block_of(degs, 1600, rng, values="updown")
-    inst = fc.two_sided(B, C, rng, "sharp_small")
-    inst.coefs[:] = rng.uniform(-0.2, 0.2, inst.n)
-    inst.rhs[:] = rng.uniform(-0.2, 0.2, inst.m)
-    return inst
-
-
-def _cases(golden, subset5):
-    sd = _sd(golden)
-    cases = [(i.name, sd, [i]) for i in subset5]
-    by = {i.name: i for i in subset5}
-    cases += [("ragged3", sd, [by["afiro.mps"], fc.empty_instance(3, 5), by["sc50a.mps"]]),
-              ("1x1", sd, [_inst(np.array([[1.5]]), "one", 1)]),
-              ("nonz", sd, [fc.empty_instance(7, 9), fc.empty_instance(2, 1, seed=1)]),
-              ("grid25", sd, [_grid(0)]),
-              ("grid25x2", sd, [_grid(0), _grid(1)]),
-              ("longrow", sd, [_long(False)]),
-              ("longcol", sd, [_long(True)]),
-              ("sharp", {k: v.numpy() for k, v in fc.sharp_state(2.0).items()}, [_sharp()])]
-    return cases
-
-
-CASE_NAMES = SUBSET5 + ["ragged3", "1x1", "nonz", "grid25", "grid25x2", "longrow", "longcol", "sharp"]
+from fused_cases import SMALL_CASE_NAMES as CASE_NAMES  # noqa: E402
+from fused_cases import SMALL_PER_TENSOR_CAPS as PER_TENSOR_CAPS  # noqa: E402
+from fused_cases import small_inst as _inst  # noqa: E402
+from fused_cases import small_long as _long  # noqa: E402
+from fused_cases import small_step_cases as _cases  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -142,10 +95,11 @@ def dev():
 
 @pytest.fixture(scope="module")
 def oracle_cases(golden, subset5):
-    """name -> (sd, instances, oracle result): computed once, shared, never modified"""
+    """name -> (sd, instances, oracle result, per-tensor yardstick): computed once, shared, never modified"""
     out = {}
     for name, sd, insts in _cases(golden, subset5):
-        out[name] = (sd, insts, o2.gnn_forward_backward(sd, o2.BatchCSR(insts)))
+        ob = o2.BatchCSR(insts)
+        out[name] = (sd, insts, o2.gnn_forward_backward(sd, ob), gs.yardstick(sd, ob) if name in PER_TENSOR_CAPS else None)
     assert list(out) == CASE_NAMES
     return out
 
@@ -155,7 +109,7 @@ def oracle_cases(golden, subset5):
 def test_loss_step_against_oracle(dev, oracle_cases, name):
     """Loss-step mode (no optimizer buffers) against oracle.spmm_form.gnn_forward_backward in fp64: logits and loss at
     1e-5, gradients at 5e-5, max-norm relative (test_hip_parity's bars)."""
-    sd, insts, r = oracle_cases[name]
+    sd, insts, r, yard = oracle_cases[name]
     b = dev.from_instances(insts)
     assert b.small_step_fits(), f"{name}: M + N = {b.M + b.N}, nnz = {b.nnz} is beyond the limits"
     p = _params(sd)
@@ -170,6 +124,8 @@ def test_loss_step_against_oracle(dev, oracle_cases, name):
     close(lg, r["logits"], RTOL_ACT, f"{name} logits")
     assert abs(ls - r["loss"]) <= RTOL_ACT * abs(r["loss"]), f"{name} loss {ls} vs {r['loss']}"
     close(g, r["grads"], RTOL_GRAD, f"{name} grads")
+    if yard is not None:
+        gs.close_per_tensor(g, r["grads"], yard, f"{name} grads", max_exempt=PER_TENSOR_CAPS[name])
     unused = conv_param_slice("gconv3_s2w")
     assert not g[unused].any()
 

@@ -38,22 +38,7 @@ def LPBatch():
     cls.default_path = 0
 
 
-def _ragged_instance(seed, m, n, dense_rows=(), mean=14):
-    rng = np.random.default_rng(seed)
-    rows = []
-    for i in range(m):
-        u = rng.random()
-        k = 0 if u < 0.2 else (int(rng.integers(1, 4)) if u < 0.45 else int(rng.poisson(mean)) + 1)
-        if i in dense_rows:
-            k = dense_rows[i]
-        hi = max(1, n - n // 10)                               # the last 10 % of the columns stay empty
-        rows.append(np.sort(rng.choice(hi, size=min(k, hi), replace=False)).astype(np.int32))
-    indptr = np.zeros(m + 1, np.int64)
-    indptr[1:] = np.cumsum([len(r) for r in rows])
-    indices = np.concatenate(rows).astype(np.int32) if indptr[-1] else np.zeros(0, np.int32)
-    values = rng.standard_normal(indptr[-1])
-    return LPInstance(f"ragged{seed}", indptr, indices, values, rng.standard_normal(n), rng.random(m) * 5,
-                      (rng.random(n) < 0.37).astype(np.int32))
+from fused_cases import ragged_instance as _ragged_instance  # noqa: E402
 
 
 def _decode(copy, info, n_dst):

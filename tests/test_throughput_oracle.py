@@ -23,12 +23,13 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import grad_scales as gs  # noqa: E402
 from batch_slices import cut_instance  # noqa: E402
 from mllp_amd.data import LPInstance, load_packed  # noqa: E402
 from oracle import pyg_restatement as o1  # noqa: E402
 from oracle import spmm_form as o2  # noqa: E402
-from test_hip_parity import RTOL_ACT, RTOL_GRAD, _holes_instance, close, close_elementwise, grad_mask  # noqa: E402
-from test_stream_attn import _ragged_instance  # noqa: E402
+from fused_cases import ragged_batch as _ragged_batch  # noqa: E402
+from test_hip_parity import RTOL_ACT, RTOL_GRAD, close, close_elementwise, grad_mask  # noqa: E402
 
 REPLICAS = 32
 STREAM_COPIES = [(tr, g) for tr in (False, True) for g in (1, 2, 3, 4)]
@@ -292,16 +293,6 @@ COMPOSITIONS = ([("none", (), False), ("streamed_all", tuple(STREAM_COPIES), Fal
                 + [("tiled", (), True), ("streamed_and_tiled", tuple(STREAM_COPIES), True)])
 
 
-def _ragged_batch():
-    """Empty rows, a dense row block, an instance without nonzeros, a 3 x 5 instance, and instances of exactly 480 / 481
-    and 512 / 513 rows (tile boundaries of the copies)."""
-    empty = LPInstance("empty", np.zeros(6, np.int64), np.zeros(0, np.int32), np.zeros(0), np.zeros(4), np.zeros(5),
-                       np.zeros(4, np.int32))
-    return [_ragged_instance(21, 400, 700, {i: 30 + 7 * i for i in range(0, 60, 3)}), _holes_instance(1, 700, 900), empty,
-            _ragged_instance(50, 480, 721), _ragged_instance(51, 481, 1100), _holes_instance(2, 3, 5),
-            _ragged_instance(52, 512, 800), _ragged_instance(53, 513, 640, mean=40)]
-
-
 @pytest.fixture(scope="module")
 def small_batches(LPBatch, weights, netlib, netlib_oracle):
     cache = {}
@@ -315,7 +306,10 @@ def small_batches(LPBatch, weights, netlib, netlib_oracle):
             rd = o2.gnn_forward_backward(weights[1], ob, dlogits=dz.astype(np.float64))
             b = LPBatch.from_instances(insts)
             b.set_path(1)
-            cache[name] = (b, r, dz, rd["grads"])
+            # per-tensor yardsticks (tests/grad_scales.py) of the loss step and of dz; Netlib-97 stays on the global check (its
+            # fp32 restatement sums 8 M terms one after the other and is no yardstick)
+            yards = (gs.yardstick(weights[1], ob), gs.yardstick(weights[1], ob, dz.astype(np.float64))) if name == "ragged" else None
+            cache[name] = (b, r, dz, rd["grads"], yards)
         return cache[name]
     return get
 
@@ -324,7 +318,7 @@ def small_batches(LPBatch, weights, netlib, netlib_oracle):
 @pytest.mark.parametrize("batch", ["ragged", "netlib97"])
 def test_copy_composition_against_oracle(small_batches, weights, batch, comp):
     name, streams, tiled = comp
-    b, r, dz, grads_dz = small_batches(batch)
+    b, r, dz, grads_dz, yards = small_batches(batch)
     flat, sd, flat_gpu = weights
     _detach_copies(b)
     if streams == tuple(STREAM_COPIES):
@@ -346,6 +340,9 @@ def test_copy_composition_against_oracle(small_batches, weights, batch, comp):
     close(grads.cpu().numpy()[keep], r["grads"][keep], RTOL_GRAD, f"{batch} {name}: gradients")
     g = b.backward(flat_gpu, torch.tensor(dz, device="cuda")).clone()
     close(g.cpu().numpy()[keep], grads_dz[keep], RTOL_GRAD, f"{batch} {name}: gradients of a random dz")
+    if yards is not None:                       # every tensor on its own scale; the reference exempts none on this batch
+        gs.close_per_tensor(grads.cpu().numpy(), r["grads"], yards[0], f"{batch} {name}: gradients", max_exempt=0)
+        gs.close_per_tensor(g.cpu().numpy(), grads_dz, yards[1], f"{batch} {name}: gradients of a random dz", max_exempt=0)
     if streams and tiled:                       # the streamed copies take precedence: same bits as without the tiled ones
         for tr in (False, True):
             for v in (1, 2, 3, 4):
