@@ -345,6 +345,32 @@ int mllp_gnn_backward_inputs(const mllp_graph_t* g, const float* d_params, const
                              void* d_ws, const float* d_dlogits, float* d_grads, float* d_dx1, float* d_dx2,
                              float* d_dvalues, void* d_scratch, void* stream);
 
+/* Input gradients on EITHER path (symbols added without an ABI bump: callers check for them, as for mllp_graph_set_values).
+ * mllp_gnn_input_grads: call after mllp_gnn_forward on this workspace, on whichever path that forward used, with the
+ *   graph still selecting that path; MLLP_EINVAL with a message, before anything is written, when no forward ran on d_ws
+ *   (or mllp_graph_set_values has run since) or the path was switched in between.  Generic path: the call IS
+ *   mllp_gnn_backward_inputs (same code, same bits).  Fused latency-regime path (the default below 32 M nonzeros): the
+ *   fused backward, then a post-pass of four launches for the renumbered workspace (mllp_amd/csrc/fused_input_grads.hip).
+ *   Arguments as mllp_gnn_backward_inputs; d_grads is bit for bit what mllp_gnn_backward writes on that path, and with
+ *   d_grads == NULL the parameter gradients go to d_scratch (both NULL: MLLP_EINVAL).
+ * mllp_gnn_loss_step_inputs: mllp_gnn_loss_step followed by the post-pass of the path in use.  d_logits, d_loss and
+ *   d_grads are bit for bit those of mllp_gnn_loss_step on the same inputs and path; arguments as there.
+ * Both: d_dx1 [N], d_dx2 [M], d_dvalues [nnz] are in the caller's (original) node order, d_dvalues in the CSR order of A
+ *   (mllp_graph_export 2); overwritten, not accumulated; each may be NULL, then it is not computed and its kernels are not
+ *   launched (all three NULL: exactly mllp_gnn_backward / mllp_gnn_loss_step).  Bitwise reproducible: fixed launch
+ *   order, a fixed summation order for every sum, no float atomics.  A null graph, params, x1, x2, workspace, dlogits
+ *   or labels (loss step: also logits, loss, grads) is rejected with a message before any HIP call.  All work is queued on
+ *   `stream`.  Nothing is allocated, except that the first call on a graph with d_dvalues != NULL builds the graph-owned
+ *   map from A^T positions to A positions (one hipMalloc of 4 * nnz bytes): make that call outside a hipGraph capture;
+ *   every later call can be captured.  The records of which path wrote the workspace and of the folded weights are left
+ *   as mllp_gnn_backward / mllp_gnn_loss_step leave them.                                                           */
+int mllp_gnn_input_grads(const mllp_graph_t* g, const float* d_params, const float* d_x1, const float* d_x2,
+                         void* d_ws, const float* d_dlogits, float* d_grads, float* d_dx1, float* d_dx2,
+                         float* d_dvalues, void* d_scratch, void* stream);
+int mllp_gnn_loss_step_inputs(const mllp_graph_t* g, const float* d_params, const float* d_x1, const float* d_x2,
+                              const float* d_labels, float inv_batch, void* d_ws, float* d_logits, float* d_loss,
+                              float* d_grads, float* d_dx1, float* d_dx2, float* d_dvalues, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * torch.optim.Adam(lr, betas=(0.9, 0.999), eps=1e-8), no weight decay
  * (linear_program_experiment.py:119,143-144) on flat buffers.

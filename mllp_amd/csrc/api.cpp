@@ -485,6 +485,46 @@ extern "C" int mllp_gnn_backward_inputs(const mllp_graph_t* g, const float* d_pa
     return input_grads_body(g, d_x1, d_x2, model_ws(g, (float*)d_ws), d_dx1, d_dx2, d_dvalues, s);
 }
 
+// Input gradients on whichever path the forward on d_ws used.  Generic: mllp_gnn_backward_inputs itself.  Fused: the
+// fused backward, then the post-pass for a renumbered workspace (fused_input_grads.hip).
+extern "C" int mllp_gnn_input_grads(const mllp_graph_t* g, const float* d_params, const float* d_x1, const float* d_x2,
+                                    void* d_ws, const float* d_dlogits, float* d_grads, float* d_dx1, float* d_dx2,
+                                    float* d_dvalues, void* d_scratch, void* stream) {
+    REQUIRE(g && d_params && d_x1 && d_x2 && d_ws && d_dlogits, "null argument");
+    REQUIRE(d_grads || d_scratch, "d_grads and d_scratch are both null (mllp_gnn_input_grads_scratch_bytes)");
+    REQUIRE(g->ws_ptr == d_ws, "no mllp_gnn_forward on this workspace");
+    REQUIRE(g->ws_path == (use_fused(g) ? 1 : 0),
+            "the path was switched between the forward on this workspace and this call (mllp_graph_set_path)");
+    if (!use_fused(g))
+        return mllp_gnn_backward_inputs(g, d_params, d_x1, d_x2, d_ws, d_dlogits, d_grads, d_dx1, d_dx2, d_dvalues, d_scratch,
+                                        stream);
+    hipStream_t s = (hipStream_t)stream;
+    int rc;
+    if (d_dvalues && (rc = ensure_at_pos(const_cast<mllp_graph*>(g), s))) return rc;      // once per graph (allocates: make the first such call uncaptured)
+    float* grads = d_grads ? d_grads : (float*)d_scratch;
+    if ((rc = mllp_gnn_backward(g, d_params, d_x1, d_x2, d_ws, d_dlogits, grads, stream))) return rc;
+    const ModelWs w = model_ws(g, (float*)d_ws);
+    return fused_input_grads(g, FusedModel{d_params, w, d_x1, d_x2, nullptr, 0.0f, nullptr}, d_dx1, d_dx2, d_dvalues, s);
+}
+
+// mllp_gnn_loss_step, then the post-pass of the path in use
+extern "C" int mllp_gnn_loss_step_inputs(const mllp_graph_t* g, const float* d_params, const float* d_x1,
+                                         const float* d_x2, const float* d_labels, float inv_batch, void* d_ws,
+                                         float* d_logits, float* d_loss, float* d_grads, float* d_dx1, float* d_dx2,
+                                         float* d_dvalues, void* stream) {
+    REQUIRE(g && d_params && d_x1 && d_x2 && d_labels && d_ws && d_logits && d_loss && d_grads, "null argument");
+    hipStream_t s = (hipStream_t)stream;
+    int rc;
+    if (d_dvalues && (rc = ensure_at_pos(const_cast<mllp_graph*>(g), s))) return rc;      // once per graph, as above
+    if ((rc = mllp_gnn_loss_step(g, d_params, d_x1, d_x2, d_labels, inv_batch, d_ws, d_logits, d_loss, d_grads, stream)))
+        return rc;
+    const ModelWs w = model_ws(g, (float*)d_ws);
+    if (use_fused(g))
+        return fused_input_grads(g, FusedModel{d_params, w, d_x1, d_x2, d_labels, inv_batch, d_logits}, d_dx1, d_dx2,
+                                 d_dvalues, s);
+    return input_grads_body(g, d_x1, d_x2, w, d_dx1, d_dx2, d_dvalues, s);
+}
+
 extern "C" int mllp_gnn_train_step(const mllp_graph_t* g, float* d_params, const float* d_x1, const float* d_x2,
                                    const float* d_labels, float inv_batch, void* d_ws, float* d_logits, float* d_loss,
                                    float* d_grads, float* d_exp_avg, float* d_exp_avg_sq, float* d_state, float eps,

@@ -423,5 +423,8 @@ struct FusedAdam {
 };
 int fused_backward(const mllp_graph* g, const FusedModel& m, bool premasked, float* grads, float* loss, hipStream_t s,
                    const FusedAdam* adam = nullptr);
+// fused_input_grads.hip: dL/dx1, dL/dx2, dL/da_ij (caller's order; each may be null) from what fused_backward left in
+// m.w; m.x1 / m.x2 are the caller's inputs.  Launches only: g->at_pos must exist when dval is wanted (ensure_at_pos)
+int fused_input_grads(const mllp_graph* g, const FusedModel& m, float* dx1, float* dx2, float* dval, hipStream_t s);
 
 }  // namespace mllp

@@ -653,6 +653,45 @@ class LPBatch:
                                                        _lib.current_stream()))
         return grads, dx1, dx2, dv
 
+    def _input_grad_outputs(self, dev, x1, x2, values):
+        return (torch.empty(self.N, device=dev, dtype=torch.float32) if x1 else None,
+                torch.empty(self.M, device=dev, dtype=torch.float32) if x2 else None,
+                torch.empty(self.nnz, device=dev, dtype=torch.float32) if values else None)
+
+    def input_grads(self, params, dlogits, x1=True, x2=True, values=True, grads=None):
+        """`backward_inputs` on whichever path `forward` used (mllp_gnn_input_grads): after a forward on the fused
+        latency-regime path -- the default below 32 M nonzeros -- the fused backward and its own post-pass run, with no
+        `set_path`.  Returns (grads, dx1 [N], dx2 [M], dvalues [nnz]) with the conventions of `backward_inputs`."""
+        dev = params.device
+        if grads is None:
+            grads = torch.empty(_lib.NUM_PARAMS, device=dev, dtype=torch.float32)
+        dx1, dx2, dv = self._input_grad_outputs(dev, x1, x2, values)
+        dlogits = dlogits.contiguous().float()
+        _lib.check(_lib.lib().mllp_gnn_input_grads(self._h, _lib.ptr(params), _lib.ptr(self.x1), _lib.ptr(self.x2),
+                                                   _lib.ptr(self.workspace()), _lib.ptr(dlogits), _lib.ptr(grads),
+                                                   _lib.ptr(dx1), _lib.ptr(dx2), _lib.ptr(dv), c_void_p(0),
+                                                   _lib.current_stream()))
+        return grads, dx1, dx2, dv
+
+    def loss_step_inputs(self, params, inv_batch=None, logits=None, loss=None, grads=None, x1=True, x2=True, values=True):
+        """`loss_step` plus the gradients of that loss with respect to the inputs, on the path in use
+        (mllp_gnn_loss_step_inputs).  Returns (loss, logits, grads, dx1 [N], dx2 [M], dvalues [nnz]); dvalues is in the
+        CSR order of A (`export(2)`, what `set_values` takes), and an input whose flag is False gets None (and is not
+        computed).  The first call that asks for dvalues allocates: make it outside a graph capture."""
+        dev = params.device
+        logits = torch.empty(self.N, device=dev, dtype=torch.float32) if logits is None else logits
+        loss = torch.empty(1, device=dev, dtype=torch.float32) if loss is None else loss
+        grads = torch.empty(_lib.NUM_PARAMS, device=dev, dtype=torch.float32) if grads is None else grads
+        dx1, dx2, dv = self._input_grad_outputs(dev, x1, x2, values)
+        ib = (1.0 / self.n_inst) if inv_batch is None else float(inv_batch)
+        self._check_inputs()
+        self._folded = None          # (as loss_step)
+        _lib.check(_lib.lib().mllp_gnn_loss_step_inputs(self._h, _lib.ptr(params), _lib.ptr(self.x1), _lib.ptr(self.x2),
+                                                        _lib.ptr(self.labels), ib, _lib.ptr(self.workspace()),
+                                                        _lib.ptr(logits), _lib.ptr(loss), _lib.ptr(grads), _lib.ptr(dx1),
+                                                        _lib.ptr(dx2), _lib.ptr(dv), _lib.current_stream()))
+        return loss, logits, grads, dx1, dx2, dv
+
     def loss_step(self, params, inv_batch=None, logits=None, loss=None, grads=None):
         """forward + BCEWithLogits + backward.  loss = inv_batch * sum_k mean_i BCE; default 1/n_inst."""
         dev = params.device
