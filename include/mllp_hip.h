@@ -372,6 +372,47 @@ int mllp_gnn_loss_step_inputs(const mllp_graph_t* g, const float* d_params, cons
                               float* d_grads, float* d_dx1, float* d_dx2, float* d_dvalues, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Weighted loss head (symbols added without an ABI bump: callers check for them, as for mllp_graph_set_values).
+ * The reference's criterion is one unweighted nn.BCEWithLogitsLoss() per instance (linear_program_experiment.py:41,
+ * 139-141); these calls put torch's BCEWithLogitsLoss(pos_weight=...) and a weight per instance between
+ * mllp_gnn_forward and mllp_gnn_backward, in a kernel of their own (mllp_amd/csrc/weighted_loss.hip).  Per instance k of
+ * the graph with n_k columns, pw_k = d_pos_weight[k] and w_k = d_inst_weight[k] (NULL array = all ones):
+ *     sp_i = max(-z_i, 0) + log1p(exp(-|z_i|))
+ *     l_i  = (1 - y_i) z_i + (1 + (pw_k - 1) y_i) sp_i              any label y_i in [0, 1]
+ *     L_k  = (1 / n_k) sum_i l_i                                     0 for n_k = 0
+ *     dz_i = (w_k / n_k) ((1 - y_i) - (1 + (pw_k - 1) y_i) (1 - sigmoid(z_i)))
+ *     loss = sum_k w_k L_k
+ * L_k is NOT multiplied by w_k: an instance with w_k = 0 gets dz = 0 and still reports its loss, which makes a masked
+ * instance a held-out one.  w_k = inv_batch for every k and no pos_weight is the loss of mllp_gnn_loss_step (same value,
+ * another summation order).
+ * mllp_weighted_loss: d_logits, d_labels [N] in the caller's node order; d_inst_weight, d_pos_weight [n_inst] or NULL.
+ *   Outputs, each may be NULL (not computed) but not all three (MLLP_EINVAL): d_dlogits [N] (what mllp_gnn_backward and
+ *   mllp_gnn_input_grads take; must not overlap d_logits), d_inst_loss [n_inst] = L_k, d_loss [1].  One launch of one
+ *   workgroup per instance, plus one launch of one workgroup for d_loss.  With d_loss but no d_inst_loss ONE workgroup
+ *   takes the instances in turn -- same bits, slower: pass d_inst_loss where time matters.
+ * mllp_balanced_pos_weight: d_pos_weight [n_inst] = (n_k - P_k) / P_k with P_k = sum_i y_i, the weight that gives the
+ *   positives of an instance the total weight of its negatives; 1 where P_k = 0 or P_k = n_k (and for n_k = 0).  Labels
+ *   are constant for a batch's life: call it once, not per step.
+ * mllp_gnn_loss_step_weighted: mllp_gnn_forward, mllp_weighted_loss, mllp_gnn_backward on whichever path the graph
+ *   selects.  d_logits [N] and d_grads [MLLP_NUM_PARAMS] are bit for bit what those calls write; d_dlogits [N] is
+ *   required scratch and holds dz afterwards; d_loss, d_inst_loss, d_inst_weight, d_pos_weight may be NULL.  The
+ *   workspace record is left as mllp_gnn_forward / mllp_gnn_backward leave it, so mllp_gnn_input_grads may follow.
+ * All three: every sum has a fixed order that depends on n_k alone (loss: on n_inst alone, instance order), no float
+ * atomics, so an instance gives the same L_k and dz bits alone and inside any batch, whichever outputs are asked for,
+ * run after run.  A null graph, logits or labels (step: params, x1, x2, labels, workspace, logits, grads, dlogits;
+ * balanced: labels, pos_weight) is rejected with a message before any HIP call.  Nothing is allocated; all work is
+ * queued on `stream` (capturable).
+ * ---------------------------------------------------------------------------------------------- */
+int mllp_weighted_loss(const mllp_graph_t* g, const float* d_logits, const float* d_labels,
+                       const float* d_inst_weight, const float* d_pos_weight, float* d_dlogits,
+                       float* d_inst_loss, float* d_loss, void* stream);
+int mllp_balanced_pos_weight(const mllp_graph_t* g, const float* d_labels, float* d_pos_weight, void* stream);
+int mllp_gnn_loss_step_weighted(const mllp_graph_t* g, const float* d_params, const float* d_x1, const float* d_x2,
+                                const float* d_labels, const float* d_inst_weight, const float* d_pos_weight,
+                                void* d_ws, float* d_logits, float* d_loss, float* d_inst_loss, float* d_grads,
+                                float* d_dlogits, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * torch.optim.Adam(lr, betas=(0.9, 0.999), eps=1e-8), no weight decay
  * (linear_program_experiment.py:119,143-144) on flat buffers.
  *   d_state: 4 floats on the device {step (as float, incremented by the kernel), lr, beta1, beta2};

@@ -28,6 +28,10 @@ HOT_PATH_DEFAULTS = {
     "angle_feat_dim": 256,   # feat_dim of AngleModel for the 'angleNet' method (the reference hard-codes 256, experiment.py:83)
     "dtype": "f32",          # feature precision of the training step.  'f32' is the reference's arithmetic and the only one the
                              # step implements; 'bf16' exists for the plain SpMM only (LPBatch.spmm_bf16 / mllp_spmm_csr_bf16)
+    "pos_weight": None,      # weight of the positive labels in the loss: a float | 'balanced' (negatives / positives of each
+                             # instance); None == the reference's unweighted BCEWithLogitsLoss (experiment.py:41)
+    "holdout": None,         # instances evaluated every logging epoch and never trained on: a list of instance names, or a
+                             # fraction f in (0, 1) (mllp_amd.experiment.holdout_by_fraction); None == train on everything
 }
 
 

@@ -56,15 +56,59 @@ def plan_batches(instances, batch_size, rank, world):
     return plan
 
 
+def holdout_by_fraction(n, f):
+    """The held-out instances of a dataset of `n` for the yaml key `holdout: f`, 0 < f < 1: with the instances in dataset
+    order, instance i is held out iff floor((i + 1) f) > floor(i f) -- floor(n f) of them, evenly spread, the same ones
+    on every run and every rank."""
+    f = float(f)
+    if not 0.0 < f < 1.0:
+        raise ValueError(f"holdout: a fraction must lie in (0, 1), got {f!r}")
+    return [i for i in range(int(n)) if int(np.floor((i + 1) * f)) > int(np.floor(i * f))]
+
+
+def split_holdout(names, holdout):
+    """(trained ids, held-out ids) of the instances `names` (dataset order) for the yaml key `holdout`: None / an empty
+    list (nothing held out), a list of instance names (an unknown name raises), or a fraction (`holdout_by_fraction`)."""
+    names = list(names)
+    if holdout is None or (isinstance(holdout, (list, tuple)) and not holdout):
+        return list(range(len(names))), []
+    if isinstance(holdout, bool) or isinstance(holdout, str):
+        raise ValueError(f"holdout: expected a list of instance names or a fraction in (0, 1), got {holdout!r}")
+    if isinstance(holdout, (int, float)):
+        held = holdout_by_fraction(len(names), holdout)
+    else:
+        unknown = [h for h in holdout if h not in names]
+        if unknown:
+            raise ValueError(f"holdout: unknown instance name(s) {unknown} (the dataset has {names})")
+        held = sorted({names.index(h) for h in holdout})
+    heldset = set(held)
+    return [i for i in range(len(names)) if i not in heldset], held
+
+
+def plan_split_batches(instances, ids, batch_size, rank, world):
+    """`plan_batches` over the sub-list `ids` of `instances`, in GLOBAL ids."""
+    sub = [instances[i] for i in ids]
+    return [([ids[j] for j in mine], gcount) for mine, gcount in plan_batches(sub, batch_size, rank, world)]
+
+
 def run_epochs(cfg, instances, train_dict, trainer, batches, rank, world, device, start_epoch=0, out=print,
-               save_all=None):
+               save_all=None, holdout=(), n_holdout=0):
     """The epoch loop of reference linear_program_experiment.py:120-157 over prebuilt batches, for any trainer
     with `step(batch) -> (loss, logits)`, `step_empty()` and `metrics_of(batch) -> [n, 2]` (correct_num, f1).
 
     `batches` = [(global instance ids of THIS rank, batch or None, global instance count of the group)].
     With world > 1 the per-instance metrics of every rank are summed into one dense [n_instances, 2] tensor
     (each instance is owned by exactly one rank), so rank 0 prints and logs the complete epoch; the other
-    ranks print nothing and write no files."""
+    ranks print nothing and write no files.
+
+    `holdout` = [(global instance ids of THIS rank, batch)] of held-out instances, `n_holdout` their number over all
+    ranks: never passed to `step`; on every logging epoch `trainer.evaluate(batch)` -> dict(inst_loss [n], metrics
+    [n, 2]) gives their correct counts (logged under their names like everyone's) and `val_obj`, the mean of their
+    losses.  `obj` stays the mean over the trained instances."""
+    n_holdout = int(n_holdout)
+    if n_holdout and not hasattr(trainer, "evaluate"):
+        raise ValueError(f"holdout: {n_holdout} held-out instance(s), but {type(trainer).__name__} has no evaluate(batch)")
+    n_train = len(instances) - n_holdout
     dist = None
     if world > 1:
         import torch.distributed as dist
@@ -83,11 +127,21 @@ def run_epochs(cfg, instances, train_dict, trainer, batches, rank, world, device
             obj_sum += loss.to(device) * gcount     # loss is the batch mean over gcount instances (this rank's share)
             if logging:
                 table[torch.as_tensor(mine, device=device)] = trainer.metrics_of(b).to(device)
+        val_sum = torch.zeros(1, device=device) if logging and n_holdout else None
+        if val_sum is not None:
+            for mine, b in holdout:
+                if b is None:
+                    continue
+                ev = trainer.evaluate(b)
+                val_sum += ev["inst_loss"].to(device).sum()
+                table[torch.as_tensor(mine, device=device)] = ev["metrics"].to(device)
         if dist is not None:
             dist.all_reduce(obj_sum)
             if logging:
                 dist.all_reduce(table)
-        obj = float(obj_sum[0]) / len(instances)
+            if val_sum is not None:
+                dist.all_reduce(val_sum)
+        obj = float(obj_sum[0]) / n_train
         if logging:
             met = table.cpu().numpy()
             for gi, inst in enumerate(instances):      # groups are consecutive id ranges: this is the dataset order
@@ -96,10 +150,14 @@ def run_epochs(cfg, instances, train_dict, trainer, batches, rank, world, device
                     out("%8d, %8d, %8d, %5f" % (correct_num, inst.m, inst.n, f1))
                 train_dict[inst.name].append(correct_num)
         train_dict["obj"].append(obj)                  # plain float: the reference's numpy.float32 breaks json.dump
+        val_obj = None
+        if val_sum is not None:
+            val_obj = float(val_sum[0]) / n_holdout
+            train_dict.setdefault("val_obj", []).append(val_obj)
         if rank == 0:
             with open("train_log.json", "w") as json_file:                          # reference :155-156
                 json.dump(train_dict, json_file)
-            out(f"epoch {epoch}, obj={obj}")                                        # reference :157
+            out(f"epoch {epoch}, obj={obj}" + ("" if val_obj is None else f", val_obj={val_obj}"))    # reference :157
         if save_all is not None and save_every and (epoch + 1) % save_every == 0:
             save_all(epoch)
     return train_dict
@@ -129,11 +187,25 @@ def train_method(cfg, method_name, train_dataset, train_dict, out=print):
         dist.broadcast(flat0, src=0)
         model.load_flat(flat0)
     instances = [LPInstance.from_reference_tuple(t) for t in train_dataset]
-    batches = [(mine, LPBatch.from_instances([instances[i] for i in mine]) if mine else None, gcount)
-               for mine, gcount in plan_batches(instances, cfg.get_default("batch_size"), rank, world)]
+    make = lambda mine: LPBatch.from_instances([instances[i] for i in mine]) if mine else None  # noqa: E731
+    train_ids, held_ids = split_holdout([i.name for i in instances], cfg.get_default("holdout"))
+    extra = {}
+    if not held_ids:           # (no holdout: the calls of a build without the key)
+        batches = [(mine, make(mine), gcount)
+                   for mine, gcount in plan_batches(instances, cfg.get_default("batch_size"), rank, world)]
+    else:
+        if not train_ids:
+            raise ValueError("holdout: every instance is held out, nothing is left to train on")
+        batches = [(mine, make(mine), gcount)
+                   for mine, gcount in plan_split_batches(instances, train_ids, cfg.get_default("batch_size"), rank, world)]
+        extra = dict(n_holdout=len(held_ids),
+                     holdout=[(mine, make(mine)) for mine, _ in
+                              plan_split_batches(instances, held_ids, cfg.get_default("batch_size"), rank, world)])
+    pos_weight = cfg.get_default("pos_weight")
     trainer = LPTrainer(model.flat_parameters().detach(), lr=cfg.train_lr,
                         use_hip_graph=cfg.get_default("use_hip_graph"), with_metrics=True,
-                        tiled_copies=cfg.get_default("tiled_copies"))
+                        tiled_copies=cfg.get_default("tiled_copies"),
+                        **({} if pos_weight is None else dict(pos_weight=pos_weight)))
     start_epoch = 0
     if cfg.get_default("resume") and os.path.exists(ckpt_path):
         start_epoch = load_checkpoint(ckpt_path, trainer, train_dict, device)
@@ -147,7 +219,7 @@ def train_method(cfg, method_name, train_dataset, train_dict, out=print):
         torch.save(model.state_dict(), model_path)                                   # reference :176
         save_checkpoint(ckpt_path, trainer, train_dict, epoch)
 
-    run_epochs(cfg, instances, train_dict, trainer, batches, rank, world, device, start_epoch, out, save_all)
+    run_epochs(cfg, instances, train_dict, trainer, batches, rank, world, device, start_epoch, out, save_all, **extra)
     save_all(cfg.train_iter - 1)
     if rank == 0:
         out(f"Model saved to {model_path}.")

@@ -762,6 +762,105 @@ class LPBatch:
                                                 _lib.ptr(out), _lib.current_stream()))
         return out
 
+    # ---- weighted loss head (mllp_weighted_loss; csrc/weighted_loss.hip) ----------------------------------------
+    @property
+    def labels(self):
+        return self._labels
+
+    @labels.setter
+    def labels(self, t):
+        self._labels = t
+        self._balanced_pw = None          # (balanced_pos_weight: the weights of the labels bound before)
+
+    def balanced_pos_weight(self):
+        """[n_inst] cuda float32: pw_k = (n_k - P_k) / P_k with P_k the positives among the instance's labels, the
+        `pos_weight` that gives them the total weight of the negatives; 1 where an instance has no positive, no negative or
+        no column (mllp_balanced_pos_weight).  Computed once and kept: rebinding `labels`, or writing them in place, makes
+        the next call compute it again."""
+        key = (self._labels.data_ptr(), self._labels._version)
+        if self._balanced_pw is None or self._balanced_pw[0] != key:
+            out = torch.empty(max(self.n_inst, 1), device=self._labels.device, dtype=torch.float32)
+            y = self._labels if self.N else torch.zeros(1, device=out.device)       # (a batch without columns)
+            _lib.check(_lib.lib().mllp_balanced_pos_weight(self._h, _lib.ptr(y), _lib.ptr(out), _lib.current_stream()))
+            self._balanced_pw = (key, out[:self.n_inst])
+        return self._balanced_pw[1]
+
+    def _per_instance(self, v, what, allow_balanced=False):
+        """None, a float (broadcast), a tensor [n_inst] or (pos_weight only) 'balanced' -> None or a cuda float32 [n_inst]"""
+        if v is None:
+            return None
+        if isinstance(v, str):
+            if allow_balanced and v == "balanced":
+                return self.balanced_pos_weight()
+            raise ValueError(f"{what}: {v!r} is not understood" + (" (a float, a tensor [n_inst] or 'balanced')" if allow_balanced else ""))
+        if isinstance(v, torch.Tensor):
+            if not (v.is_cuda and v.dtype == torch.float32 and v.is_contiguous() and v.numel() == self.n_inst):
+                raise ValueError(f"{what} must be a contiguous cuda float32 tensor of {self.n_inst} elements")
+            return v
+        consts = self.__dict__.setdefault("_inst_consts", {})
+        if float(v) not in consts:
+            consts[float(v)] = torch.full((max(self.n_inst, 1),), float(v), device=self.x1.device, dtype=torch.float32)
+        return consts[float(v)]
+
+    def weighted_loss(self, logits, inst_weight=None, pos_weight=None, want=("loss", "inst_loss", "dlogits")):
+        """torch's BCEWithLogitsLoss(pos_weight) per instance with a weight per instance, from `logits` and the batch's
+        labels (mllp_weighted_loss): L_k = mean_i l_i (NOT multiplied by w_k: an instance of weight 0 still reports its
+        loss), loss = sum_k w_k L_k, dlogits = d loss / d logits (what `backward` / `input_grads` take).  `inst_weight`:
+        None (ones), a float or a tensor [n_inst]; `pos_weight`: None (ones), a float, a tensor [n_inst] or 'balanced'.
+        Returns dict(loss [1], inst_loss [n_inst], dlogits [N]) of device tensors; those not named in `want` are None and
+        cost nothing.  Bitwise reproducible, the same bits for an instance alone and inside any batch; no sync."""
+        want = (want,) if isinstance(want, str) else tuple(want)
+        bad = [w for w in want if w not in ("loss", "inst_loss", "dlogits")]
+        if bad or not want:
+            raise ValueError(f"weighted_loss: want must name some of 'loss', 'inst_loss', 'dlogits' (got {want!r})")
+        if not (logits.is_cuda and logits.dtype == torch.float32 and logits.is_contiguous() and logits.numel() == self.N):
+            raise ValueError(f"weighted_loss: logits must be a contiguous cuda float32 tensor of {self.N} elements")
+        dev = logits.device
+        iw = self._per_instance(inst_weight, "weighted_loss: inst_weight")
+        pw = self._per_instance(pos_weight, "weighted_loss: pos_weight", allow_balanced=True)
+        # (at least one element each: an empty torch tensor has a null pointer, which the library reads as "not wanted")
+        loss = torch.empty(1, device=dev, dtype=torch.float32) if "loss" in want else None
+        # (loss without inst_loss: the L_k still get a buffer -- without one the library walks the instances in ONE workgroup)
+        inst = torch.empty(max(self.n_inst, 1), device=dev, dtype=torch.float32) if {"inst_loss", "loss"} & set(want) else None
+        dz = torch.empty(max(self.N, 1), device=dev, dtype=torch.float32) if "dlogits" in want else None
+        z, y = (logits, self._labels) if self.N else (torch.zeros(1, device=dev),) * 2      # (a batch without columns)
+        _lib.check(_lib.lib().mllp_weighted_loss(self._h, _lib.ptr(z), _lib.ptr(y), _lib.ptr(iw), _lib.ptr(pw), _lib.ptr(dz),
+                                                 _lib.ptr(inst), _lib.ptr(loss), _lib.current_stream()))
+        return dict(loss=loss, inst_loss=inst[:self.n_inst] if "inst_loss" in want else None,
+                    dlogits=None if dz is None else dz[:self.N])
+
+    def loss_step_weighted(self, params, inst_weight=None, pos_weight=None, logits=None, loss=None, inst_loss=None,
+                           grads=None):
+        """`forward`, `weighted_loss`, `backward` in one library call on the path in use (mllp_gnn_loss_step_weighted).
+        Weights as in `weighted_loss`; inst_weight None is all ONES (loss = sum_k L_k) -- pass 1 / n_inst for the batch mean
+        that `loss_step` computes.  Returns (loss [1], logits [N], grads, inst_loss [n_inst]); logits are bit for bit those
+        of `forward`, and `input_grads` may follow with `self.last_dlogits`."""
+        dev = params.device
+        logits = torch.empty(self.N, device=dev, dtype=torch.float32) if logits is None else logits
+        loss = torch.empty(1, device=dev, dtype=torch.float32) if loss is None else loss
+        inst_loss = torch.empty(max(self.n_inst, 1), device=dev, dtype=torch.float32)[:self.n_inst] if inst_loss is None else inst_loss
+        grads = torch.empty(_lib.NUM_PARAMS, device=dev, dtype=torch.float32) if grads is None else grads
+        if getattr(self, "last_dlogits", None) is None:
+            self.last_dlogits = torch.empty(max(self.N, 1), device=dev, dtype=torch.float32)[:self.N]
+        iw = self._per_instance(inst_weight, "loss_step_weighted: inst_weight")
+        pw = self._per_instance(pos_weight, "loss_step_weighted: pos_weight", allow_balanced=True)
+        self._check_inputs()
+        self._folded = None          # (as forward)
+        _lib.check(_lib.lib().mllp_gnn_loss_step_weighted(self._h, _lib.ptr(params), _lib.ptr(self.x1), _lib.ptr(self.x2),
+                                                          _lib.ptr(self._labels), _lib.ptr(iw), _lib.ptr(pw),
+                                                          _lib.ptr(self.workspace()), _lib.ptr(logits), _lib.ptr(loss),
+                                                          _lib.ptr(inst_loss), _lib.ptr(grads), _lib.ptr(self.last_dlogits),
+                                                          _lib.current_stream()))
+        return loss, logits, grads, inst_loss
+
+    def evaluate(self, params, pos_weight=None):
+        """Held-out evaluation: `forward`, the per-instance losses L_k of `weighted_loss` (no dlogits) and `topm_metrics`.
+        Returns dict(logits [N], inst_loss [n_inst], metrics [n_inst, 2] = correct_num, f1) of device tensors.  No
+        gradient is computed, nothing but this batch's workspace is written, and nothing synchronises."""
+        logits = self.forward(params)
+        inst = self.weighted_loss(logits, None, pos_weight, want="inst_loss")["inst_loss"]
+        return dict(logits=logits, inst_loss=inst, metrics=self.topm_metrics(logits))
+
     def predict_basis(self, logits, want=("mask", "index", "stats")):
         """The predicted basis of every instance, on the device and without labels (mllp_topm_select): the m_k largest
         logits of instance k (m_k = its constraints), ordered and tie-broken as `topm_metrics` does -- by the key of the

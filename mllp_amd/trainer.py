@@ -113,7 +113,8 @@ class LPTrainer:
     TILED_NNZ_MIN = 32 << 20
 
     def __init__(self, params_flat: torch.Tensor, lr=1e-3, use_hip_graph="auto",
-                 global_instances: Optional[int] = None, with_metrics=False, tiled_copies="auto", stream_copies=True):
+                 global_instances: Optional[int] = None, with_metrics=False, tiled_copies="auto", stream_copies=True,
+                 pos_weight=None):
         assert params_flat.is_cuda and params_flat.numel() == NUM_PARAMS
         self.params = params_flat.detach().clone().float().contiguous()
         self.opt = FlatAdam(self.params, lr=lr)
@@ -122,6 +123,9 @@ class LPTrainer:
         self.with_metrics = with_metrics
         self.tiled_copies = tiled_copies
         self.stream_copies = stream_copies
+        # None: the unweighted loss of mllp_gnn_train_step / mllp_gnn_loss_step.  A float, a tensor [n_inst] or 'balanced':
+        # BCEWithLogitsLoss(pos_weight) through LPBatch.loss_step_weighted, per-instance losses in `inst_loss_of`
+        self.pos_weight = pos_weight
         self._plans = {}
         self._gen = 0                  # bumped at every library-side write of the parameters (LPBatch.train_step)
 
@@ -140,8 +144,19 @@ class LPTrainer:
             p = dict(batch=batch, logits=torch.empty(batch.N, device=dev), loss=torch.zeros(1, device=dev),
                      grads=torch.zeros(NUM_PARAMS, device=dev), metrics=torch.zeros(batch.n_inst, 2, device=dev),
                      g_fwd=None, g_opt=None, warm=0, graph=graph)
+            if self.pos_weight is not None:
+                p["inst_loss"] = torch.zeros(max(batch.n_inst, 1), device=dev)[:batch.n_inst]
             self._plans[key] = p
         return p
+
+    def inst_loss_of(self, batch: LPBatch) -> torch.Tensor:
+        """[n_inst] per-instance losses L_k of the last step on `batch` (trainers with a pos_weight); device tensor."""
+        return self._plans[batch.token]["inst_loss"]
+
+    def evaluate(self, batch: LPBatch):
+        """`LPBatch.evaluate` under this trainer's parameters and pos_weight: dict(logits, inst_loss, metrics).  No
+        gradient, no optimizer step, no sync; parameters and Adam state are not touched."""
+        return batch.evaluate(self.params, self.pos_weight)
 
     def metrics_of(self, batch: LPBatch) -> torch.Tensor:
         """[n_inst, 2] (correct_num, f1) of the last step on `batch` (with_metrics=True); device tensor."""
@@ -172,7 +187,10 @@ class LPTrainer:
     def _fwd_bwd(self, p):
         b = p["batch"]
         inv = 1.0 / float(self.global_instances or b.n_inst)
-        b.loss_step(self.params, inv, p["logits"], p["loss"], p["grads"])
+        if self.pos_weight is not None:
+            b.loss_step_weighted(self.params, inv, self.pos_weight, p["logits"], p["loss"], p["inst_loss"], p["grads"])
+        else:
+            b.loss_step(self.params, inv, p["logits"], p["loss"], p["grads"])
         if self.with_metrics:
             b.topm_metrics(p["logits"], p["metrics"])
 
@@ -195,7 +213,7 @@ class LPTrainer:
         multi = dist.is_available() and dist.is_initialized() and (
             dist.get_world_size() > 1 or os.environ.get("MLLP_BENCH_FORCE_DIST") == "1")
         if not p["graph"] or p["warm"] < 1:
-            if multi:
+            if multi or self.pos_weight is not None:      # (one rank: the all-reduce is a no-op)
                 self._fwd_bwd(p)
                 allreduce_sum_(p["grads"])
                 self._opt(p)
