@@ -310,6 +310,29 @@ int mllp_tconv_bwd(const mllp_graph_t* g, int dst_is_var, int cin, const float* 
  *   d_x1 [N] = objective coefficients (x1, methods.py:90), d_x2 [M] = right-hand sides (x2, :91)
  *   d_ws     : mllp_gnn_workspace_bytes() bytes, kept between forward and backward
  *   d_logits [N] : per-variable logits (methods.py:250-251)
+ * MEMORY CONTRACT of every mllp_gnn_*, mllp_tconv_*, mllp_spmm_*, mllp_weighted_loss, mllp_balanced_pos_weight, mllp_topm_*
+ * and mllp_graph_normalize call, for every buffer the caller owns (tests/test_memory_contract.py):
+ *   1. A call's outputs do not depend on any byte that d_ws, or any other scratch or output buffer, held before the call:
+ *      the buffers may be uninitialised, NaN included, and the same bits come out.  The only state carried between calls is
+ *      what this header names: mllp_gnn_forward -> mllp_gnn_backward / _backward_inputs / _input_grads on the same workspace
+ *      (mllp_gnn_loss_step_weighted leaves its forward's state likewise), mllp_gnn_train_step flags bit 0, and
+ *      mllp_tconv_fwd -> mllp_tconv_bwd on the same d_ws.
+ *   2. A call writes nothing outside the documented extent of the buffers it is given -- for d_ws exactly
+ *      mllp_gnn_workspace_bytes() (mllp_tconv_workspace_floats() floats) from the pointer -- and never writes an input:
+ *      d_params (except in the train steps), d_x1, d_x2, d_labels, d_dlogits where it is an input, d_inst_weight,
+ *      d_pos_weight, d_conv_params, d_x_src, d_x_dst, d_h_out in the backward, d_H.
+ *   3. A call's outputs do not depend on any byte outside those extents (a kernel may read past the end of an array
+ *      inside the caller's allocation only where what it reads cannot reach a result).
+ *   4. Between whole calls that carry nothing the caller may do anything to the workspace: after mllp_gnn_loss_step,
+ *      _loss_step_weighted (unless mllp_gnn_input_grads follows), _loss_step_inputs, _train_step_small, and after
+ *      mllp_gnn_train_step when the next call passes flags 0.
+ *   ALIGNMENT: d_ws, d_params, d_x1 and d_x2 of the mllp_gnn_* calls must be 16-byte aligned -- the workspace's fields,
+ *      fc.weight and (on the lane-per-row copy of the layer-1 sweeps) four neighbouring source values are accessed in 16-byte
+ *      pieces --, as must every pointer of mllp_tconv_fwd / _bwd except d_param_grads (rows of 16 floats; d_ws, d_conv_params)
+ *      and d_H, d_Y of mllp_spmm_csr_f32.  A misaligned one is refused with MLLP_EINVAL and a message before any HIP call,
+ *      nothing written.  d_logits, d_labels, d_loss, d_grads, d_dlogits, d_dx1, d_dx2, d_dvalues, d_scratch, the optimizer
+ *      buffers, the per-instance arrays and the buffers of the loss-head, top-m and normalize calls need only the natural
+ *      alignment of their element type.
  * mllp_gnn_backward: d_dlogits [N] -> d_grads [MLLP_NUM_PARAMS] (overwritten; the never-called
  *   gconv3_s2w block, methods.py:248, is written as zeros).
  * mllp_gnn_loss_step: forward + BCEWithLogitsLoss + backward in one call, loss =

@@ -8,6 +8,13 @@ namespace mllp {
 
 static inline int64_t up16(int64_t x) { return (x + 15) & ~int64_t(15); }
 
+// Caller pointers that the kernels read or write in 16-byte pieces (include/mllp_hip.h, "Memory contract"): the workspace
+// (every field is carved at a multiple of 16 floats), the parameters (the fused head reads fc.weight four floats at a time),
+// x1 / x2 (the lane-per-row copy of the layer-1 sweeps loads four source values at once) and every [n, 16] node array of the
+// single-conv and SpMM calls.  A null pointer is aligned: the null checks have their own message.
+static inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+#define REQUIRE_ALIGNED16(cond) REQUIRE(cond, "misaligned pointer: " #cond " (these are accessed in 16-byte pieces)")
+
 ConvWs conv_ws_carve(float* base, int64_t n, int cin, float** end) {
     const int64_t recw = cin == 16 ? REC_W : 8;
     float* p = base;
@@ -233,6 +240,7 @@ using namespace mllp;
 
 extern "C" int mllp_spmm_csr_f32(const mllp_graph_t* g, int transpose, const float* d_H, float* d_Y, void* stream) {
     REQUIRE(g && d_H && d_Y, "null argument");
+    REQUIRE_ALIGNED16(al16(d_H) && al16(d_Y));
     const Orient& o = transpose ? g->At : g->A;
     return launch_spmm(o, d_H, d_Y, o.scratch, (hipStream_t)stream);
 }
@@ -353,6 +361,7 @@ extern "C" int mllp_tconv_fwd(const mllp_graph_t* g, int dst_is_var, int cin, co
                               const float* d_x_src, const float* d_x_dst, float* d_h_out, float* d_ws, void* stream) {
     REQUIRE(g && d_conv_params && d_x_src && d_x_dst && d_h_out && d_ws, "null argument");
     REQUIRE(cin == 1 || cin == 16, "cin must be 1 or 16");
+    REQUIRE_ALIGNED16(al16(d_ws) && al16(d_conv_params) && al16(d_x_src) && al16(d_x_dst) && al16(d_h_out));
     ConvWs w = conv_ws_carve(d_ws, dst_is_var ? g->N : g->M, cin);
     return conv_forward(g, dst_is_var != 0, cin, d_conv_params, w, d_x_src, d_x_dst, d_h_out, (hipStream_t)stream);
 }
@@ -363,6 +372,8 @@ extern "C" int mllp_tconv_bwd(const mllp_graph_t* g, int dst_is_var, int cin, co
                               void* stream) {
     REQUIRE(g && d_conv_params && d_x_src && d_x_dst && d_h_out && d_ws && d_dh && d_param_grads, "null argument");
     REQUIRE(cin == 1 || cin == 16, "cin must be 1 or 16");
+    REQUIRE_ALIGNED16(al16(d_ws) && al16(d_conv_params) && al16(d_x_src) && al16(d_x_dst) && al16(d_h_out) && al16(d_dh) &&
+                      al16(d_dx_dst) && al16(d_dx_src));
     ConvWs w = conv_ws_carve(d_ws, dst_is_var ? g->N : g->M, cin);
     const ConvBwd c{g, dst_is_var != 0, cin, d_conv_params, w, d_x_src, d_x_dst, d_h_out, d_dh, d_dx_dst, d_dx_src, accumulate,
                     d_param_grads};
@@ -381,6 +392,7 @@ extern "C" int mllp_gnn_workspace_bytes(const mllp_graph_t* g, int64_t* bytes) {
 extern "C" int mllp_gnn_forward(const mllp_graph_t* g, const float* d_params, const float* d_x1, const float* d_x2,
                                 void* d_ws, float* d_logits, void* stream) {
     REQUIRE(g && d_params && d_x1 && d_x2 && d_ws && d_logits, "null argument");
+    REQUIRE_ALIGNED16(al16(d_ws) && al16(d_params) && al16(d_x1) && al16(d_x2));
     hipStream_t s = (hipStream_t)stream;
     ModelWs w = model_ws(g, (float*)d_ws);
     int rc;
@@ -398,6 +410,7 @@ extern "C" int mllp_gnn_forward(const mllp_graph_t* g, const float* d_params, co
 extern "C" int mllp_gnn_backward(const mllp_graph_t* g, const float* d_params, const float* d_x1, const float* d_x2,
                                  void* d_ws, const float* d_dlogits, float* d_grads, void* stream) {
     REQUIRE(g && d_params && d_x1 && d_x2 && d_ws && d_dlogits && d_grads, "null argument");
+    REQUIRE_ALIGNED16(al16(d_ws) && al16(d_params) && al16(d_x1) && al16(d_x2));
     hipStream_t s = (hipStream_t)stream;
     ModelWs w = model_ws(g, (float*)d_ws);
     int rc;
@@ -444,6 +457,7 @@ extern "C" int mllp_gnn_loss_step(const mllp_graph_t* g, const float* d_params, 
                                   const float* d_labels, float inv_batch, void* d_ws, float* d_logits, float* d_loss,
                                   float* d_grads, void* stream) {
     REQUIRE(g && d_params && d_x1 && d_x2 && d_labels && d_ws && d_logits && d_loss && d_grads, "null argument");
+    REQUIRE_ALIGNED16(al16(d_ws) && al16(d_params) && al16(d_x1) && al16(d_x2));
     hipStream_t s = (hipStream_t)stream;
     ModelWs w = model_ws(g, (float*)d_ws);
     int rc;
@@ -471,6 +485,7 @@ extern "C" int mllp_gnn_backward_inputs(const mllp_graph_t* g, const float* d_pa
                                         const float* d_x2, void* d_ws, const float* d_dlogits, float* d_grads,
                                         float* d_dx1, float* d_dx2, float* d_dvalues, void* d_scratch, void* stream) {
     REQUIRE(g && d_params && d_x1 && d_x2 && d_ws && d_dlogits, "null argument");
+    REQUIRE_ALIGNED16(al16(d_ws) && al16(d_params) && al16(d_x1) && al16(d_x2));
     REQUIRE(g->ws_ptr == d_ws, "no mllp_gnn_forward on this workspace");
     REQUIRE(g->ws_path == 0, "the forward on this workspace ran on the fused path: input gradients need the generic "
                              "sweeps (mllp_graph_set_path(g, 1) before mllp_gnn_forward)");
@@ -491,6 +506,7 @@ extern "C" int mllp_gnn_input_grads(const mllp_graph_t* g, const float* d_params
                                     void* d_ws, const float* d_dlogits, float* d_grads, float* d_dx1, float* d_dx2,
                                     float* d_dvalues, void* d_scratch, void* stream) {
     REQUIRE(g && d_params && d_x1 && d_x2 && d_ws && d_dlogits, "null argument");
+    REQUIRE_ALIGNED16(al16(d_ws) && al16(d_params) && al16(d_x1) && al16(d_x2));
     REQUIRE(d_grads || d_scratch, "d_grads and d_scratch are both null (mllp_gnn_input_grads_scratch_bytes)");
     REQUIRE(g->ws_ptr == d_ws, "no mllp_gnn_forward on this workspace");
     REQUIRE(g->ws_path == (use_fused(g) ? 1 : 0),
@@ -513,6 +529,7 @@ extern "C" int mllp_gnn_loss_step_inputs(const mllp_graph_t* g, const float* d_p
                                          float* d_logits, float* d_loss, float* d_grads, float* d_dx1, float* d_dx2,
                                          float* d_dvalues, void* stream) {
     REQUIRE(g && d_params && d_x1 && d_x2 && d_labels && d_ws && d_logits && d_loss && d_grads, "null argument");
+    REQUIRE_ALIGNED16(al16(d_ws) && al16(d_params) && al16(d_x1) && al16(d_x2));
     hipStream_t s = (hipStream_t)stream;
     int rc;
     if (d_dvalues && (rc = ensure_at_pos(const_cast<mllp_graph*>(g), s))) return rc;      // once per graph, as above
@@ -530,6 +547,7 @@ extern "C" int mllp_gnn_train_step(const mllp_graph_t* g, float* d_params, const
                                    float* d_grads, float* d_exp_avg, float* d_exp_avg_sq, float* d_state, float eps,
                                    int flags, void* stream) {
     REQUIRE(g && d_params && d_x1 && d_x2 && d_labels && d_ws && d_logits && d_loss && d_grads, "null argument");
+    REQUIRE_ALIGNED16(al16(d_ws) && al16(d_params) && al16(d_x1) && al16(d_x2));
     REQUIRE(d_exp_avg && d_exp_avg_sq && d_state, "null optimizer state");
     REQUIRE((flags & ~1) == 0, "flags: bit 0 = the folded weights in the workspace are current");
     hipStream_t s = (hipStream_t)stream;
@@ -584,6 +602,7 @@ extern "C" int mllp_gnn_train_step_small(const mllp_graph_t* g, float* d_params,
                                          float* d_loss, float* d_grads, float* d_exp_avg, float* d_exp_avg_sq,
                                          float* d_state, float eps, void* stream) {
     REQUIRE(g && d_params && d_x1 && d_x2 && d_labels && d_ws && d_logits && d_loss && d_grads, "null argument");
+    REQUIRE_ALIGNED16(al16(d_ws) && al16(d_params) && al16(d_x1) && al16(d_x2));
     const int n_opt = (d_exp_avg != nullptr) + (d_exp_avg_sq != nullptr) + (d_state != nullptr);
     REQUIRE(n_opt == 0 || n_opt == 3, "optimizer state: give d_exp_avg, d_exp_avg_sq and d_state, or none of them (loss step)");
     const std::string excess = small_step_excess(g);

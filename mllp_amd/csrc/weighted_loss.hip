@@ -182,6 +182,9 @@ extern "C" int mllp_gnn_loss_step_weighted(const mllp_graph_t* g, const float* d
                                            void* d_ws, float* d_logits, float* d_loss, float* d_inst_loss, float* d_grads,
                                            float* d_dlogits, void* stream) {
     REQUIRE(g && d_params && d_x1 && d_x2 && d_labels && d_ws && d_logits && d_grads, "null argument");
+    REQUIRE(((reinterpret_cast<uintptr_t>(d_ws) | reinterpret_cast<uintptr_t>(d_params) | reinterpret_cast<uintptr_t>(d_x1) |
+              reinterpret_cast<uintptr_t>(d_x2)) & 15) == 0,
+            "misaligned pointer: d_ws, d_params, d_x1 and d_x2 are accessed in 16-byte pieces");
     REQUIRE(d_dlogits, "null d_dlogits: the step needs [N] floats of scratch between its loss head and its backward");
     int rc;
     if ((rc = mllp_gnn_forward(g, d_params, d_x1, d_x2, d_ws, d_logits, stream))) return rc;
