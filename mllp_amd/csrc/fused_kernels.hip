@@ -4,9 +4,10 @@
 // step of the generic path is ~45 launches whose sweeps are bound by dependent memory round trips at low occupancy
 // (profiles/r01_netlib_kernel_stats.md: 91 us for a 1 M-nonzero attention sweep, 68 % of wave time in s_waitcnt), and
 // per conv it writes and re-reads q', t, dq', ds/dt and runs a separate statistics pass.  Here a conv is ONE sweep
-// launch forward (q' = Pq x, the attention sweep, the output GEMMs, ReLU -- and for the last conv fc +
-// BCEWithLogits + dL/dh) and TWO backward (destination-major: ReLU mask, gv = Wv^T g, record, sweep, input gradient,
-// parameter statistics on the MFMA; source-major: the transposed sweep); the two convs of a layer share a launch.
+// launch forward (q' = Pq x, the attention sweep, the output GEMMs, ReLU -- and for the last conv fc) and TWO
+// backward (destination-major: ReLU mask, gv = Wv^T g, record, sweep, input gradient, parameter statistics on the MFMA;
+// source-major: the transposed sweep); the two convs of a layer share a launch.  In a loss step the last conv's forward
+// launch, fc + BCEWithLogits and its destination-major backward launch are ONE launch (fused_l3_kernel).
 // reference: linear_program_methods.py:238-251, linear_program_experiment.py:139-141; formulas SURVEY.md appendix
 // A.3 / A.4 (oracle/spmm_form.py).
 //
@@ -344,10 +345,11 @@ struct FwdJob16 {
     const float* __restrict__ x_dst;   // [n_dst, 16]
     const float* __restrict__ D;       // folded weights (param_prep)
     ConvParams p;
-    float* __restrict__ h;             // [n_dst, 16]   (not written when head == 2)
+    float* __restrict__ h;             // [n_dst, 16]
     float* __restrict__ Z;             // [n_dst, 16]
     float* __restrict__ aux;           // [n_dst, 4]
-    int head;                          // 0: plain conv, 1: + logits, 2: + BCEWithLogits, dL/dh (masked) and fc partials
+    int head;                          // 0: plain conv, 1: + logits; 2 (fused_l3_kernel only: h, Z, aux unused): + BCEWithLogits,
+                                       // fc partials and the conv's destination-major backward
     const float* __restrict__ fcw;
     const float* __restrict__ fcb;
     const float* __restrict__ inv_n;   // [n_dst] renumbered
@@ -355,7 +357,6 @@ struct FwdJob16 {
     const int* __restrict__ perm;      // [n_dst] renumbered -> caller's variable id (where the logit goes)
     float inv_batch;
     float* __restrict__ logits;        // [n_dst] caller's order
-    float* __restrict__ g_out;         // [n_dst, 16]  dL/dh of the head, already ReLU-masked
     float* __restrict__ head_part;     // [grid, 18]   {dW_fc[16], db_fc, loss} per workgroup
 #ifdef MLLP_TIMING_BUILD
     int abl;
@@ -436,6 +437,35 @@ __device__ __forceinline__ void soft_merge(SoftState& st, int mode) {
     st.Z.w = shared_sum4(st.Z.w * f, mode);
 }
 
+// block tier: the wavefronts of the workgroup merge their states through LDS (fixed order); every lane ends with the row's
+// state.  UNROLL: FW in the sweeps that can afford it; 1 in fused_l3_kernel, where the unrolled loop (twelve slot
+// addresses and twelve factors in register pairs) was the kernel's register peak.  Same operations in the same order.
+template <int UNROLL>
+__device__ __forceinline__ void soft_merge_block(SoftState& st, float* merge_lds, int lane, int part) {
+    const int wave = threadIdx.x >> 6;
+    if (lane < 4) {
+        float* slot = merge_lds + wave * 20;
+        if (part == 0) *reinterpret_cast<float4*>(slot) = make_float4(st.m, st.L, st.u, 0.0f);
+        *reinterpret_cast<float4*>(slot + 4 + 4 * part) = st.Z;
+    }
+    __syncthreads();
+    float M = NEG_BIG;
+#pragma unroll UNROLL
+    for (int w = 0; w < FW; ++w) M = fmaxf(M, merge_lds[w * 20]);
+    float L = 0.0f, u = 0.0f;
+    float4 Z = f4zero();
+#pragma unroll UNROLL
+    for (int w = 0; w < FW; ++w) {
+        const float4 hd = lds4(merge_lds + w * 20);
+        const float f = exp_acc(hd.x - M);
+        L = fmaf(f, hd.y, L);
+        u = fmaf(f, hd.z, u);
+        fma4(f, lds4(merge_lds + w * 20 + 4 + 4 * part), Z);
+    }
+    st.m = M; st.L = L; st.u = u; st.Z = Z;
+    __syncthreads();     // the slots are free for the next block-tier row
+}
+
 struct HeadAcc {
     float4 w;      // dW_fc of this lane's four channels
     float b, l;    // db_fc, loss (part-0 lanes)
@@ -445,7 +475,7 @@ struct HeadAcc {
 // on their way at the loop's back edge, where the first use of the prefetched row data makes hipcc wait with vmcnt(0)
 // -- 1.3-1.6 k cycles per item waiting for store acknowledgements (in-kernel stamps, "between items").
 struct FwdPending {
-    float4 zn, hv, g, aux;
+    float4 zn, hv, aux;
     float z;
     int row, lrow;      // row < 0: nothing pending
 };
@@ -453,9 +483,8 @@ __device__ __forceinline__ void fwd16_flush(const FwdJob16& J, FwdPending& p, in
     if (p.row >= 0 && !FUSED_ABL(2048)) {
         *reinterpret_cast<float4*>(J.Z + (size_t)p.row * 16 + 4 * part) = p.zn;
         if (part == 0) reinterpret_cast<float4*>(J.aux)[p.row] = p.aux;
-        if (J.head != 2) *reinterpret_cast<float4*>(J.h + (size_t)p.row * 16 + 4 * part) = p.hv;
+        *reinterpret_cast<float4*>(J.h + (size_t)p.row * 16 + 4 * part) = p.hv;
         if (J.head && part == 0) J.logits[p.lrow] = p.z;
-        if (J.head == 2) *reinterpret_cast<float4*>(J.g_out + (size_t)p.row * 16 + 4 * part) = p.g;
     }
     p.row = -1;
 }
@@ -475,7 +504,7 @@ struct FwdNext {
 };
 __device__ __forceinline__ void fwd16_row(const FwdJob16& J, const FwdW16& W, const PartTiers& P, const RowSlot& r,
                                           const float4& xd, int2& en, int lrow, const SlotReq& q1, int it2, FwdNext& nx,
-                                          FwdPending& pend, int part, int lane, float* merge_lds, float* tiles, HeadAcc& ha
+                                          FwdPending& pend, int part, int lane, float* merge_lds, float* tiles
 #ifdef MLLP_TIMING_BUILD
                                           , unsigned long long (&stamp_sum)[8], unsigned long long& stamp_last
 #endif
@@ -520,28 +549,7 @@ __device__ __forceinline__ void fwd16_row(const FwdJob16& J, const FwdW16& W, co
     FUSED_STAMP(3)      // prefetch issue
 
     if (r.mode >= 1) soft_merge(st, r.mode);
-    if (r.mode == 3) {       // merge the 16 wavefronts of the workgroup through LDS (fixed order)
-        const int wave = threadIdx.x >> 6;
-        if (lane < 4) {
-            float* slot = merge_lds + wave * 20;
-            if (part == 0) *reinterpret_cast<float4*>(slot) = make_float4(st.m, st.L, st.u, 0.0f);
-            *reinterpret_cast<float4*>(slot + 4 + 4 * part) = st.Z;
-        }
-        __syncthreads();
-        float M = NEG_BIG;
-        for (int w = 0; w < FW; ++w) M = fmaxf(M, merge_lds[w * 20]);
-        float L = 0.0f, u = 0.0f;
-        float4 Z = f4zero();
-        for (int w = 0; w < FW; ++w) {
-            const float4 hd = lds4(merge_lds + w * 20);
-            const float f = exp_acc(hd.x - M);
-            L = fmaf(f, hd.y, L);
-            u = fmaf(f, hd.z, u);
-            fma4(f, lds4(merge_lds + w * 20 + 4 + 4 * part), Z);
-        }
-        st.m = M; st.L = L; st.u = u; st.Z = Z;
-        __syncthreads();     // the slots are free for the next block-tier row
-    }
+    if (r.mode == 3) soft_merge_block<FW>(st, merge_lds, lane, part);
     const bool writer = r.writer;
     // epilogue: o = Wv Zn + Ws x + (bs + S bv + un we)
     const float rinv = 1.0f / (st.L + 1e-16f);   // torch_geometric.utils.softmax: sum + 1e-16
@@ -566,26 +574,9 @@ __device__ __forceinline__ void fwd16_row(const FwdJob16& J, const FwdW16& W, co
     pend.row = writer ? r.row : -1;
     pend.zn = zn; pend.hv = hv; pend.lrow = lrow_cur;
     pend.aux = make_float4(un, st.L > 0.0f ? st.m : 0.0f, rinv, S);
-    pend.z = 0.0f; pend.g = f4zero();
-    if (J.head) {        // fc (16 -> 1) on the conv's output row, reference linear_program_methods.py:250
-        const float4 fw = lds4(W.fcw + 4 * part);
-        const float z = quad_sum(dot4(hv, fw)) + W.fcb;
-        pend.z = z;
-        if (J.head == 2 && writer) {      // BCEWithLogitsLoss, mean per instance / batch: linear_program_experiment.py:41,139-140
-            const float y = J.labels[r.row];
-            const float wn = J.inv_n[r.row] * J.inv_batch;
-            const float e = expf(-fabsf(z));
-            const float sig = z >= 0.0f ? 1.0f / (1.0f + e) : e / (1.0f + e);
-            const float dz = wn * (sig - y);
-            pend.g = make_float4(hv.x > 0.0f ? dz * fw.x : 0.0f, hv.y > 0.0f ? dz * fw.y : 0.0f,
-                                 hv.z > 0.0f ? dz * fw.z : 0.0f, hv.w > 0.0f ? dz * fw.w : 0.0f);
-            fma4(dz, hv, ha.w);
-            if (part == 0) {
-                ha.b += dz;
-                ha.l += wn * (fmaxf(z, 0.0f) - z * y + log1pf(e));
-            }
-        }
-    }
+    pend.z = 0.0f;
+    if (J.head)          // fc (16 -> 1) on the conv's output row, reference linear_program_methods.py:250
+        pend.z = quad_sum(dot4(hv, lds4(W.fcw + 4 * part))) + W.fcb;
     FUSED_STAMP(5)      // stores, head
 }
 
@@ -613,7 +604,6 @@ __device__ __forceinline__ void head_partials_store(HeadAcc& ha, float* head_lds
 __global__ __launch_bounds__(FT) void fused_fwd16_kernel(FwdLaunch16 A) {
     __shared__ FwdW16 Ws_[MAXJOBS];
     __shared__ float merge_lds[FW * 20];
-    __shared__ float head_lds[FW * 18];
     __shared__ float tiles_[FW * 3 * TILE];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, part = lane & 3;
     for (int j = 0; j < A.n_jobs; ++j) {
@@ -637,8 +627,6 @@ __global__ __launch_bounds__(FT) void fused_fwd16_kernel(FwdLaunch16 A) {
     }
     __syncthreads();
     float* tiles = tiles_ + wave * 3 * TILE;
-    HeadAcc ha;
-    ha.w = f4zero(); ha.b = 0.0f; ha.l = 0.0f;
 #ifdef MLLP_TIMING_BUILD
     unsigned long long stamp_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long stamp_last = __builtin_amdgcn_s_memtime();
@@ -650,11 +638,9 @@ __global__ __launch_bounds__(FT) void fused_fwd16_kernel(FwdLaunch16 A) {
     // this workgroup's partition of the instances, its rank among the partition's workgroups, their wavefronts
     const int px = blockIdx.x % NP, bi = blockIdx.x / NP, gp = gridDim.x / NP;
     const int gw = bi * FW + wave;
-    float* head_part = nullptr;
     for (int j = 0; j < A.n_jobs; ++j) {
         const FwdJob16& J = A.job[j];
         const PartTiers P = J.s.part[px];
-        if (J.head == 2) head_part = J.head_part;
         // block tier: the whole workgroup walks one long row at a time (longest rows first)
         const RowSlot none = empty_slot();
         FwdPending pend;
@@ -665,7 +651,7 @@ __global__ __launch_bounds__(FT) void fused_fwd16_kernel(FwdLaunch16 A) {
             int2 en = first_entries<4>(J.s, r, part);
             const int lrow = J.head ? J.perm[r.row] : 0;
             FwdNext nx;
-            fwd16_row(J, Ws_[j], P, r, xd, en, lrow, empty_request(), -1, nx, pend, part, lane, merge_lds, tiles, ha STAMP_ARGS);
+            fwd16_row(J, Ws_[j], P, r, xd, en, lrow, empty_request(), -1, nx, pend, part, lane, merge_lds, tiles STAMP_ARGS);
         }
         // wave loop: this wavefront's items (static assignment by estimated cost)
         WaveList wl = wave_list(J.s, px, gw);
@@ -685,7 +671,7 @@ __global__ __launch_bounds__(FT) void fused_fwd16_kernel(FwdLaunch16 A) {
             for (int k = 0; it >= 0; ++k) {
                 const int it2 = wave_list_get(wl, k + 2);
                 FwdNext nx;
-                fwd16_row(J, Ws_[j], P, r, xd, en, lrow, q1, it2, nx, pend, part, lane, merge_lds, tiles, ha STAMP_ARGS);
+                fwd16_row(J, Ws_[j], P, r, xd, en, lrow, q1, it2, nx, pend, part, lane, merge_lds, tiles STAMP_ARGS);
 #ifdef MLLP_TIMING_BUILD
                 stamp_sum[7] += 1;      // items
 #endif
@@ -702,7 +688,6 @@ __global__ __launch_bounds__(FT) void fused_fwd16_kernel(FwdLaunch16 A) {
         for (int k = 0; k < 8; ++k) d[k] = stamp_sum[k];
     }
 #endif
-    if (head_part) head_partials_store<FW>(ha, head_lds, head_part, tid);     // (uniform: one job at most has a head)
 }
 
 // ====================================================================================================
@@ -956,6 +941,60 @@ __device__ __forceinline__ void bwd16_step(const Gather4& g, int k0, int n_mine,
 #undef MLLP_BWD_SLOT
 }
 
+// tiles of a wavefront in the destination-major backward sweep
+constexpr int TB_G = 0, TB_X = 1, TB_Z = 2, TB_DQ = 3, TB_SC = 4, TB_E = 5, TB_N = 6;
+
+// block tier: sums of the workgroup's wavefronts through LDS, wave order (UNROLL as in soft_merge_block)
+template <int UNROLL>
+__device__ __forceinline__ void bwd_merge_block(BwdState& st, float* merge_lds, int lane, int part) {
+    const int wave = threadIdx.x >> 6;
+    if (lane < 4) {
+        float* slot = merge_lds + wave * 20;
+        if (part == 0) *reinterpret_cast<float4*>(slot) = make_float4(st.ds, st.dt, 0.0f, 0.0f);
+        *reinterpret_cast<float4*>(slot + 4 + 4 * part) = st.dq;
+    }
+    __syncthreads();
+    float ds = 0.0f, dt = 0.0f;
+    float4 dq = f4zero();
+#pragma unroll UNROLL
+    for (int w = 0; w < FW; ++w) {
+        ds += merge_lds[w * 20];
+        dt += merge_lds[w * 20 + 1];
+        dq = f4add(dq, lds4(merge_lds + w * 20 + 4 + 4 * part));
+    }
+    st.ds = ds; st.dt = dt; st.dq = dq;
+    __syncthreads();
+}
+// the record of a destination row (read by the source-major sweep and by fused_input_grads.hip)
+__device__ __forceinline__ void rec_store(float* __restrict__ rec, int row, int part, const float4& qp, const float4& gv,
+                                          float t, float m, float rinv, float ge, float cc) {
+    float* rr = rec + (size_t)row * REC_W;
+    *reinterpret_cast<float4*>(rr + 4 * part) = qp;
+    *reinterpret_cast<float4*>(rr + 16 + 4 * part) = gv;
+    if (part == 0) *reinterpret_cast<float4*>(rr + 32) = make_float4(t, m, rinv, ge);
+    if (part == 1) *reinterpret_cast<float4*>(rr + 36) = make_float4(cc, 0.0f, 0.0f, 0.0f);
+}
+// dx_i = Ws^T g_i + Pq^T dq'_i + ds_i Pb + dt_i Pt from the tiles G and DQ (through SC), times (x > 0) where `mask`
+template <class WT>
+__device__ __forceinline__ float4 dx_dst_row(const WT& W, float* tiles, const BwdState& st, bool mask, int xpos, int part,
+                                             int lane) {
+    float ag_[4], adq_[4];
+    tile_rows(tiles + TB_G * TILE, lane, ag_);
+    tile_rows(tiles + TB_DQ * TILE, lane, adq_);
+    tile_put_result(tiles + TB_SC * TILE,
+                    mat_apply(adq_, matB_lds(W.BPqT, lane), mat_apply(ag_, matB_lds(W.BWsT, lane), splat4(0.0f))), lane);
+    float4 v = tile_get(tiles + TB_SC * TILE, lane);
+    fma4(st.ds, lds4(W.Pb + 4 * part), v);
+    fma4(st.dt, lds4(W.Pt + 4 * part), v);
+    if (mask) {
+        if (!(xpos & 1)) v.x = 0.0f;
+        if (!(xpos & 2)) v.y = 0.0f;
+        if (!(xpos & 4)) v.z = 0.0f;
+        if (!(xpos & 8)) v.w = 0.0f;
+    }
+    return v;
+}
+
 // the row data of a destination-major backward item (fetched one item ahead)
 struct BwdRow {
     float4 ga, gb, h, x, Z, ax;
@@ -972,8 +1011,6 @@ __device__ __forceinline__ void bwd16_fetch(const BwdJob16& J, const RowSlot& r,
     d.ax = have ? reinterpret_cast<const float4*>(J.aux)[r.row] : z4;   // {u, rowmax, rinv, S}
 }
 
-// tiles of a wavefront in the destination-major backward sweep
-constexpr int TB_G = 0, TB_X = 1, TB_Z = 2, TB_DQ = 3, TB_SC = 4, TB_E = 5, TB_N = 6;
 
 // itn: the wavefront's next item (-1: none).  Its row pointers are requested BEHIND this item's first gathers: requested
 // in front of them (by the caller), they were the youngest loads when the first use of the prefetched row data made
@@ -1026,13 +1063,7 @@ __device__ __forceinline__ void bwd16_row(const BwdJob16& J, const BwdW16& W, co
     }
     // the record leaves behind the sweep: stored in front of it, the sweep's gather waits (vmcnt(0)) waited for the
     // stores' acknowledgements as well
-    if (writer && J.rec && !FUSED_ABL(8)) {
-        float* rr = J.rec + (size_t)r.row * REC_W;
-        *reinterpret_cast<float4*>(rr + 4 * part) = qp;
-        *reinterpret_cast<float4*>(rr + 16 + 4 * part) = gv;
-        if (part == 0) *reinterpret_cast<float4*>(rr + 32) = make_float4(t, m, rinv, ge);
-        if (part == 1) *reinterpret_cast<float4*>(rr + 36) = make_float4(cc, 0.0f, 0.0f, 0.0f);
-    }
+    if (writer && J.rec && !FUSED_ABL(8)) rec_store(J.rec, r.row, part, qp, gv, t, m, rinv, ge, cc);
     // the next item's row data and first entries travel while this one finishes
     rn = slot_make(qn);                // the next item's row pointers were requested when this item started
     bwd16_fetch(J, rn, part, rd);      // (rd and en are dead here: the next item's data land in the same registers)
@@ -1044,40 +1075,12 @@ __device__ __forceinline__ void bwd16_row(const BwdJob16& J, const BwdW16& W, co
         st.dq.z = shared_sum4(st.dq.z, r.mode); st.dq.w = shared_sum4(st.dq.w, r.mode);
     }
     if (r.mode == 3) {
-        const int wave = threadIdx.x >> 6;
-        if (lane < 4) {
-            float* slot = merge_lds + wave * 20;
-            if (part == 0) *reinterpret_cast<float4*>(slot) = make_float4(st.ds, st.dt, 0.0f, 0.0f);
-            *reinterpret_cast<float4*>(slot + 4 + 4 * part) = st.dq;
-        }
-        __syncthreads();
-        float ds = 0.0f, dt = 0.0f;
-        float4 dq = f4zero();
-        for (int w = 0; w < FW; ++w) {
-            ds += merge_lds[w * 20];
-            dt += merge_lds[w * 20 + 1];
-            dq = f4add(dq, lds4(merge_lds + w * 20 + 4 + 4 * part));
-        }
-        st.ds = ds; st.dt = dt; st.dq = dq;
-        __syncthreads();
+        bwd_merge_block<FW>(st, merge_lds, lane, part);
         if (threadIdx.x >= 64) return;      // wave-uniform: the row's outputs and statistics belong to wavefront 0
     }
     tile_put(tiles + TB_DQ * TILE, st.dq, lane);
-    if (J.dx_dst && !FUSED_ABL(4)) {          // dx_i = Ws^T g_i + Pq^T dq'_i + ds_i Pb + dt_i Pt
-        float ag_[4], adq_[4];
-        tile_rows(tiles + TB_G * TILE, lane, ag_);
-        tile_rows(tiles + TB_DQ * TILE, lane, adq_);
-        tile_put_result(tiles + TB_SC * TILE,
-                        mat_apply(adq_, matB_lds(W.BPqT, lane), mat_apply(ag_, matB_lds(W.BWsT, lane), splat4(0.0f))), lane);
-        float4 v = tile_get(tiles + TB_SC * TILE, lane);
-        fma4(st.ds, lds4(W.Pb + 4 * part), v);
-        fma4(st.dt, lds4(W.Pt + 4 * part), v);
-        if (J.mask_dx) {
-            if (!(xpos & 1)) v.x = 0.0f;
-            if (!(xpos & 2)) v.y = 0.0f;
-            if (!(xpos & 4)) v.z = 0.0f;
-            if (!(xpos & 8)) v.w = 0.0f;
-        }
+    if (J.dx_dst && !FUSED_ABL(4)) {
+        const float4 v = dx_dst_row(W, tiles, st, J.mask_dx != 0, xpos, part, lane);
         if (writer) *reinterpret_cast<float4*>(J.dx_dst + (size_t)r.row * 16 + 4 * part) = v;
     }
     // statistics (node_kernels.hip::param_stats16_kernel): operands with m / n = channel, k = row.  A row shared by
@@ -1191,6 +1194,298 @@ __global__ __launch_bounds__(FT) void fused_bwd16_kernel(BwdLaunch16 A) {
             __syncthreads();
         }
     }
+}
+
+// ====================================================================================================
+// layer 3 of a loss step: the forward item (head == 2) and the destination-major backward item of the SAME rows in one
+// kernel.  The two launches it replaces (fused_fwd16_kernel with the head, fused_bwd16_kernel job CONV_3V) walk the same
+// rows, the same entries and the same source rows through the same wavefront lists, and the backward item of a row
+// needs only what the forward item has just produced or loaded: x, q', t, Zn, {un, rowmax, rinv, S} and the masked head
+// gradient stay in registers, so Z, aux and d3v of CONV_3V are neither written nor read and h2v is read once.  Every
+// operation of fwd16_row and bwd16_row is kept, in its order, per row; the items per wavefront are the same lists:
+// the results are the bits of the two launches.
+// ====================================================================================================
+struct L3Job {
+    FwdJob16 f;                        // head == 2 (h, Z, aux unused)
+    float* __restrict__ rec;           // [n_dst, REC_W]
+    float* __restrict__ dx_dst;        // [n_dst, 16], stored times (x_dst > 0)
+    float* __restrict__ stats;         // [grid, STAT_FLOATS]
+};
+struct L3W {           // B operands of both halves, small vectors
+    float BPq[256], BWv[256], BWs[256], BWvT[256], BWsT[256], BPqT[256];
+    float pq0[16], Pt[16], Pb[16], bv[16], we[16], bs[16], fcw[16];
+    float pt0, fcb;
+};
+
+// The statistics tiles T2 .. T6 of a wavefront rest in its LDS region between items (20 VGPRs the two sweeps need):
+// each lane reads and writes its own float4, the sums and their order are those of register accumulators.
+constexpr int L3_REG_TILES = 2;
+constexpr int L3_PARK = (STAT_TILES - L3_REG_TILES) * 256;      // floats per wavefront
+__device__ __forceinline__ f32x4m park_get(const float* park, int i, int lane) {
+    const float4 v = lds4(park + ((i - L3_REG_TILES) * 64 + lane) * 4);
+    return (f32x4m){v.x, v.y, v.z, v.w};
+}
+__device__ __forceinline__ void park_put(float* park, int i, int lane, const f32x4m& a) {
+    *reinterpret_cast<float4*>(park + ((i - L3_REG_TILES) * 64 + lane) * 4) = make_float4(a[0], a[1], a[2], a[3]);
+}
+
+// Tiles as in bwd16_row.  The forward half keeps x in tile X, passes q' and Zn through tile Z and its output through SC.
+// The item pipeline is fwd16_row's (two deep); the backward half's first entries are the forward's, kept in registers,
+// and its first gathers leave in front of the forward epilogue.  All of an item's stores leave behind its second sweep.
+__device__ __forceinline__ void l3_row(const L3Job& JJ, const L3W& W, const PartTiers& P, const RowSlot& r, const float4& xd_in,
+                                       int2& en, int lrow, const SlotReq& q1, int it2, FwdNext& nx, int part, int lane,
+                                       float* merge_lds, float* tiles, float* park, HeadAcc& ha, f32x4m (&acc)[L3_REG_TILES]) {
+    const FwdJob16& J = JJ.f;
+    const bool have = r.row >= 0;
+    const bool writer = r.writer;
+    const int n_mine = slot_count(r);
+    const int2 en0 = en;      // the second sweep starts from the same entries
+    Gather4 gt;
+    gather4_issue(J.s, J.x_src, r, n_mine, 0, part, en, gt);      // the first gathers leave before anything else
+    nx.r = slot_make(q1);
+    nx.xd = ld4(J.x_dst + (size_t)max(nx.r.row, 0) * 16 + 4 * part);
+    nx.en = first_entries_any<4>(J.s, nx.r, part);
+    nx.lrow = J.perm[max(nx.r.row, 0)];
+    nx.q = item_request<4>(J.s, P, max(it2, 0), lane);
+    const float y = J.labels[max(r.row, 0)];                      // land during the sweep
+    const float wn = J.inv_n[max(r.row, 0)] * J.inv_batch;
+    // a quad without a row carries row 0's prefetch: zeros, as the backward's own fetch gave it
+    const float4 xd = have ? xd_in : f4zero();
+    const int xpos = (xd.x > 0.0f ? 1 : 0) | (xd.y > 0.0f ? 2 : 0) | (xd.z > 0.0f ? 4 : 0) | (xd.w > 0.0f ? 8 : 0);
+    float4 qp;
+    float t;
+    {
+        float ax_[4];
+        tile_put(tiles + TB_X * TILE, xd, lane);
+        tile_rows(tiles + TB_X * TILE, lane, ax_);
+        tile_put_result(tiles + TB_Z * TILE, mat_apply(ax_, matB_lds(W.BPq, lane), splat4(W.pq0[lane & 15])), lane);
+        qp = tile_get(tiles + TB_Z * TILE, lane);
+        t = quad_sum(dot4(lds4(W.Pt + 4 * part), xd)) + W.pt0;
+    }
+    SoftState st;
+    st.Z = f4zero(); st.m = NEG_BIG; st.L = 0.0f; st.u = 0.0f;
+    for (int k0 = 0;;) {
+        fwd16_step(gt, k0, n_mine, qp, t, st);
+        k0 += 4;
+        if (!__any(k0 < n_mine)) break;
+        gather4_issue(J.s, J.x_src, r, n_mine, k0, part, en, gt);
+    }
+    // the next item's data is taken where the sweep has drained the memory pipe (see fwd16_row)
+    asm volatile("" : "+v"(nx.xd.x), "+v"(nx.xd.y), "+v"(nx.xd.z), "+v"(nx.xd.w), "+v"(nx.en.x), "+v"(nx.en.y),
+                      "+v"(nx.lrow), "+v"(nx.q.sb), "+v"(nx.q.se));
+    // second sweep over the same row, from the same first entries: its first gathers travel during the forward epilogue
+    en = en0;
+    gather4_issue(J.s, J.x_src, r, n_mine, 0, part, en, gt);
+    if (r.mode >= 1) soft_merge(st, r.mode);
+    if (r.mode == 3) soft_merge_block<1>(st, merge_lds, lane, part);
+    // forward epilogue: o = Wv Zn + Ws x + (bs + S bv + un we), fc, BCEWithLogits
+    const float rinv = 1.0f / (st.L + 1e-16f);
+    const float S = st.L * rinv, un = st.u * rinv;
+    const float m = st.L > 0.0f ? st.m : 0.0f;
+    const float4 zn = f4scale(st.Z, rinv);
+    float4 o;
+    {
+        float ax_[4], az_[4];
+        tile_rows(tiles + TB_X * TILE, lane, ax_);
+        tile_put(tiles + TB_Z * TILE, zn, lane);
+        tile_rows(tiles + TB_Z * TILE, lane, az_);
+        tile_put_result(tiles + TB_SC * TILE,
+                        mat_apply(ax_, matB_lds(W.BWs, lane), mat_apply(az_, matB_lds(W.BWv, lane), splat4(0.0f))), lane);
+        o = tile_get(tiles + TB_SC * TILE, lane);
+    }
+    o = f4add(o, lds4(W.bs + 4 * part));
+    fma4(S, lds4(W.bv + 4 * part), o);
+    fma4(un, lds4(W.we + 4 * part), o);
+    const float4 hv = make_float4(fmaxf(o.x, 0.0f), fmaxf(o.y, 0.0f), fmaxf(o.z, 0.0f), fmaxf(o.w, 0.0f));
+    const float4 fw = lds4(W.fcw + 4 * part);
+    const float z = quad_sum(dot4(hv, fw)) + W.fcb;
+    float4 g = f4zero();
+    if (have) {        // BCEWithLogitsLoss, mean per instance / batch: linear_program_experiment.py:41,139-140.  Every quad of a
+                       // shared row holds the row's state: each computes the row's head gradient, the writer counts it
+        const float e = expf(-fabsf(z));
+        const float sig = z >= 0.0f ? 1.0f / (1.0f + e) : e / (1.0f + e);
+        const float dz = wn * (sig - y);
+        g = make_float4(hv.x > 0.0f ? dz * fw.x : 0.0f, hv.y > 0.0f ? dz * fw.y : 0.0f,
+                        hv.z > 0.0f ? dz * fw.z : 0.0f, hv.w > 0.0f ? dz * fw.w : 0.0f);
+        if (writer) {
+            fma4(dz, hv, ha.w);
+            if (part == 0) {
+                ha.b += dz;
+                ha.l += wn * (fmaxf(z, 0.0f) - z * y + log1pf(e));
+            }
+        }
+    }
+
+    // backward half (bwd16_row with dh_a = g, dh_b = none, no mask array); the first entries are the forward's
+    float4 gv;
+    float ge, cc;
+    {
+        g = f4add(g, f4zero());
+        const float4 Zn = have ? zn : f4zero();
+        const float Sx = have ? S : 0.0f, ux = have ? un : 0.0f;
+        float ag_[4];
+        tile_put(tiles + TB_G * TILE, g, lane);
+        tile_put(tiles + TB_Z * TILE, Zn, lane);
+        tile_put(tiles + TB_E * TILE, (have && part == 0) ? make_float4(1.0f, Sx, ux, 0.0f) : f4zero(), lane);
+        tile_rows(tiles + TB_G * TILE, lane, ag_);
+        tile_put_result(tiles + TB_DQ * TILE, mat_apply(ag_, matB_lds(W.BWvT, lane), splat4(0.0f)), lane);
+        gv = tile_get(tiles + TB_DQ * TILE, lane);
+        ge = quad_sum(dot4(g, lds4(W.we + 4 * part)));
+        const float gb = quad_sum(dot4(g, lds4(W.bv + 4 * part)));
+        const float Dn = quad_sum(dot4(gv, Zn)) + gb * Sx + ge * ux;
+        cc = gb - Dn;
+    }
+    const float mb = have ? m : 0.0f, rb = have ? rinv : 0.0f;
+    BwdState bs;
+    bs.dq = f4zero(); bs.ds = 0.0f; bs.dt = 0.0f;
+    for (int k0 = 0;;) {
+        bwd16_step(gt, k0, n_mine, qp, gv, t, mb, rb, ge, cc, bs);
+        k0 += 4;
+        if (!__any(k0 < n_mine)) break;
+        gather4_issue(J.s, J.x_src, r, n_mine, k0, part, en, gt);
+    }
+    // the item's stores leave behind its last sweep: no gather wait covers their acknowledgements
+    if (writer) {
+        if (part == 0) J.logits[lrow] = z;
+        rec_store(JJ.rec, r.row, part, qp, gv, t, mb, rb, ge, cc);
+    }
+    if (r.mode >= 1) {
+        bs.ds = shared_sum4(bs.ds, r.mode);
+        bs.dt = shared_sum4(bs.dt, r.mode);
+        bs.dq.x = shared_sum4(bs.dq.x, r.mode); bs.dq.y = shared_sum4(bs.dq.y, r.mode);
+        bs.dq.z = shared_sum4(bs.dq.z, r.mode); bs.dq.w = shared_sum4(bs.dq.w, r.mode);
+    }
+    if (r.mode == 3) {
+        bwd_merge_block<1>(bs, merge_lds, lane, part);
+        if (threadIdx.x >= 64) return;      // wave-uniform: the row's outputs and statistics belong to wavefront 0
+    }
+    tile_put(tiles + TB_DQ * TILE, bs.dq, lane);
+    {
+        const float4 v = dx_dst_row(W, tiles, bs, true, xpos, part, lane);
+        if (writer) *reinterpret_cast<float4*>(JJ.dx_dst + (size_t)r.row * 16 + 4 * part) = v;
+    }
+    if (r.mode >= 1 && !writer) {
+        const float4 z4 = f4zero();
+        tile_put(tiles + TB_G * TILE, z4, lane);
+        tile_put(tiles + TB_X * TILE, z4, lane);
+        tile_put(tiles + TB_Z * TILE, z4, lane);
+        tile_put(tiles + TB_E * TILE, z4, lane);
+        tile_put(tiles + TB_DQ * TILE, z4, lane);
+    }
+    tile_put(tiles + TB_SC * TILE, (writer && part == 0) ? make_float4(bs.ds, bs.dt, 0.0f, 0.0f) : f4zero(), lane);
+    float cg[4], cdq[4], csc[4], cx[4], cz[4], ce[4];
+    tile_cols(tiles + TB_G * TILE, lane, cg);
+    tile_cols(tiles + TB_DQ * TILE, lane, cdq);
+    tile_cols(tiles + TB_SC * TILE, lane, csc);
+    tile_cols(tiles + TB_X * TILE, lane, cx);
+    tile_cols(tiles + TB_Z * TILE, lane, cz);
+    tile_cols(tiles + TB_E * TILE, lane, ce);
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(cg[s], cx[s], acc[0], 0, 0, 0);    // T0 g x^T
+        acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(cg[s], cz[s], acc[1], 0, 0, 0);    // T1 g Z^T
+    }
+#define MLLP_L3_PARKED(I, A_, B_)                                                          \
+    {                                                                                      \
+        f32x4m a_ = park_get(park, I, lane);                                               \
+        for (int s = 0; s < 4; ++s) a_ = __builtin_amdgcn_mfma_f32_16x16x4f32(A_[s], B_[s], a_, 0, 0, 0); \
+        park_put(park, I, lane, a_);                                                       \
+    }
+    MLLP_L3_PARKED(2, cg, ce)      // T2 g e^T
+    MLLP_L3_PARKED(3, cdq, cx)     // T3 dq' x^T
+    MLLP_L3_PARKED(4, cdq, ce)     // T4 dq' e^T
+    MLLP_L3_PARKED(5, csc, cx)     // T5 sc x^T
+    MLLP_L3_PARKED(6, csc, ce)     // T6 sc e^T
+#undef MLLP_L3_PARKED
+}
+
+__global__ __launch_bounds__(FT) void fused_l3_kernel(L3Job JJ) {
+    __shared__ L3W W;
+    __shared__ float merge_lds[FW * 20];
+    __shared__ float head_lds[FW * 18];
+    __shared__ float tiles_[FW * TB_N * TILE];
+    __shared__ __attribute__((aligned(16))) float park_[FW * L3_PARK];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, part = lane & 3;
+    const FwdJob16& J = JJ.f;
+    if (wave == 0) matB_store(W.BPq, matB(J.D + OFF_PQ, 16, lane), lane);
+    if (wave == 1) matB_store(W.BWv, matB(J.p.Wv, 16, lane), lane);
+    if (wave == 2) matB_store(W.BWs, matB(J.p.Ws, 16, lane), lane);
+    if (wave == 3) matB_store(W.BWvT, matB_t(J.p.Wv, 16, lane), lane);
+    if (wave == 4) matB_store(W.BWsT, matB_t(J.p.Ws, 16, lane), lane);
+    if (wave == 5) matB_store(W.BPqT, matB_t(J.D + OFF_PQ, 16, lane), lane);
+    if (tid < 16) {
+        W.pq0[tid] = J.D[OFF_PQ0 + tid];
+        W.Pt[tid] = J.D[OFF_PT + tid];
+        W.Pb[tid] = J.D[OFF_PB + tid];
+        W.bv[tid] = J.p.bv[tid];
+        W.we[tid] = J.p.we[tid];
+        W.bs[tid] = J.p.bs[tid];
+        W.fcw[tid] = J.fcw[tid];
+    }
+    if (tid == 0) {
+        W.pt0 = J.D[OFF_PT0];
+        W.fcb = J.fcb[0];
+    }
+    __syncthreads();
+    float* tiles = tiles_ + wave * TB_N * TILE;
+    HeadAcc ha;
+    ha.w = f4zero(); ha.b = 0.0f; ha.l = 0.0f;
+    float* park = park_ + wave * L3_PARK;
+    f32x4m acc[L3_REG_TILES];
+#pragma unroll
+    for (int i = 0; i < L3_REG_TILES; ++i) acc[i] = splat4(0.0f);
+#pragma unroll
+    for (int i = L3_REG_TILES; i < STAT_TILES; ++i) park_put(park, i, lane, splat4(0.0f));
+    const int px = blockIdx.x % NP, bi = blockIdx.x / NP, gp = gridDim.x / NP;
+    const int gw = bi * FW + wave;
+    const PartTiers P = J.s.part[px];
+    const RowSlot none = empty_slot();
+    for (int k = bi; k < P.n_block; k += gp) {
+        const RowSlot r = block_slot<4>(J.s, P.row0 + k, tid);
+        const float4 xd = ld4(J.x_dst + (size_t)r.row * 16 + 4 * part);
+        int2 en = first_entries<4>(J.s, r, part);
+        const int lrow = J.perm[r.row];
+        FwdNext nx;
+        l3_row(JJ, W, P, r, xd, en, lrow, empty_request(), -1, nx, part, lane, merge_lds, tiles, park, ha, acc);
+    }
+    WaveList wl = wave_list(J.s, px, gw);
+    for (int c0 = 0; c0 < wl.L; c0 += 64) {
+        wave_list_chunk(wl, c0, lane);
+        int it = wave_list_get(wl, 0), it1 = wave_list_get(wl, 1);
+        RowSlot r = it >= 0 ? item_slot<4>(J.s, P, it, lane) : none;
+        float4 xd = r.row >= 0 ? ld4(J.x_dst + (size_t)r.row * 16 + 4 * part) : f4zero();
+        int2 en = first_entries<4>(J.s, r, part);
+        int lrow = r.row >= 0 ? J.perm[r.row] : 0;
+        SlotReq q1 = item_request<4>(J.s, P, max(it1, 0), lane);
+        if (it1 < 0) q1.row = -1;
+        // cold start: everything requested above is waited for here (see fused_fwd16_kernel)
+        asm volatile("" : "+v"(xd.x), "+v"(xd.y), "+v"(xd.z), "+v"(xd.w), "+v"(en.x), "+v"(en.y), "+v"(lrow),
+                          "+v"(q1.sb), "+v"(q1.se));
+        for (int k = 0; it >= 0; ++k) {
+            const int it2 = wave_list_get(wl, k + 2);
+            FwdNext nx;
+            l3_row(JJ, W, P, r, xd, en, lrow, q1, it2, nx, part, lane, merge_lds, tiles, park, ha, acc);
+            r = nx.r; xd = nx.xd; en = nx.en; lrow = nx.lrow; q1 = nx.q;
+            it = it1; it1 = it2;
+        }
+    }
+    // the workgroup's partial statistics, as fused_bwd16_kernel writes them; then the head partials
+    __syncthreads();
+    float* red = tiles_;                   // [FW][256]
+#pragma unroll
+    for (int i = 0; i < STAT_TILES; ++i) {
+        const f32x4m a = i < L3_REG_TILES ? acc[i < L3_REG_TILES ? i : 0] : park_get(park, max(i, L3_REG_TILES), lane);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) red[wave * 256 + ((lane >> 4) * 4 + q) * 16 + (lane & 15)] = a[q];
+        __syncthreads();
+        if (tid < 256) {
+            float v = 0.0f;
+            for (int w = 0; w < FW; ++w) v += red[w * 256 + tid];
+            JJ.stats[(size_t)blockIdx.x * STAT_FLOATS + i * 256 + tid] = v;
+        }
+        __syncthreads();
+    }
+    head_partials_store<FW>(ha, head_lds, J.head_part, tid);
 }
 
 // ====================================================================================================
@@ -1461,13 +1756,16 @@ __device__ __forceinline__ void bwd1_row(const BwdJob1& J, const BwdW1& W, const
     }
     FUSED_STAMP(3)      // merges, scalar sums
     // T[o][n] += sum over the 64 rows of the wavefront: 16 MFMA steps of 4 rows
-    const float* gt = tiles;
-    const float* rt = tiles + 64 * G1S;
+    // one base address per tile and a constant offset per step: written as (4 s + kq) * stride the sixteen steps kept
+    // thirty-two precomputed addresses in VGPRs across the sweeps (hipcc turns 4 s + kq into an OR and cannot fold it),
+    // four of which lived in scratch
     const int kq = lane >> 4, rr = lane & 15;
+    const float* gt = tiles + kq * G1S + rr;
+    const float* rt = tiles + 64 * G1S + kq * R1S + rr;
 #pragma unroll
     for (int s = 0; s < 16; ++s) {
-        const float a = gt[(4 * s + kq) * G1S + rr];
-        const float b = rr < 5 ? rt[(4 * s + kq) * R1S + rr] : 0.0f;
+        const float a = gt[4 * s * G1S];
+        const float b = rr < 5 ? rt[4 * s * R1S] : 0.0f;
         accT = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, accT, 0, 0, 0);
     }
     FUSED_STAMP(4)      // statistics on the MFMA
@@ -1922,6 +2220,17 @@ static FwdJob1 fwd_job1(const FusedOrient& o, const FusedModel& m, int c, const 
     return J;
 }
 
+// layer 3 (variables only) with the head
+static FwdJob16 l3_fwd_job(const mllp_graph* g, const FusedModel& m, int head_mode) {
+    const ModelWs& w = m.w;
+    FwdJob16 J = fwd_job16(g->FAt, m, CONV_3V, w.h2c, w.h2v, w.h3v);
+    J.head = head_mode;
+    J.fcw = m.P + OFF_FC; J.fcb = m.P + OFF_FC + FEAT; J.inv_n = g->inv_n_p; J.labels = g->labels_p; J.perm = g->perm_v;
+    J.inv_batch = m.inv_batch;
+    J.logits = m.logits; J.head_part = w.head_partials;
+    return J;
+}
+
 int fused_forward(mllp_graph* g, const FusedModel& m, int head_mode, hipStream_t s, bool skip_prep) {
     const int G = fused_grid(g);
     const ModelWs& w = m.w;
@@ -1946,15 +2255,11 @@ int fused_forward(mllp_graph* g, const FusedModel& m, int head_mode, hipStream_t
         hipLaunchKernelGGL(fused_fwd16_kernel, dim3(G), dim3(FT), 0, s, L);
         if ((rc = check_launch("fused_fwd16 layer 2"))) return rc;
     }
-    {   // :247 layer 3 (variables only) + :250 fc (+ loss)
+    if (head_mode == 2) return MLLP_OK;      // layer 3 + fc + loss run as the first launch of fused_backward (fused_l3_kernel)
+    {   // :247 layer 3 (variables only) + :250 fc
         FwdLaunch16 L = {};
         L.n_jobs = 1;
-        L.job[0] = fwd_job16(g->FAt, m, CONV_3V, w.h2c, w.h2v, w.h3v);
-        FwdJob16& J = L.job[0];
-        J.head = head_mode;
-        J.fcw = m.P + OFF_FC; J.fcb = m.P + OFF_FC + FEAT; J.inv_n = g->inv_n_p; J.labels = g->labels_p; J.perm = g->perm_v;
-        J.inv_batch = m.inv_batch;
-        J.logits = m.logits; J.g_out = w.d3v; J.head_part = w.head_partials;
+        L.job[0] = l3_fwd_job(g, m, head_mode);
         hipLaunchKernelGGL(fused_fwd16_kernel, dim3(G), dim3(FT), 0, s, L);
         if ((rc = check_launch("fused_fwd16 layer 3"))) return rc;
     }
@@ -2004,7 +2309,10 @@ static BwdJob1 bwd_job1(const FusedOrient& o, const FusedModel& m, int c, const 
 // stored already multiplied by the ReLU mask of that activation by the kernel that produces it (it has the activation
 // in registers as its own x), and the two parts of the layer-1 gradients are summed by the second producer: the
 // consumers read one array per node and no activations for masking.
-//   K1  C3  dst  (dh = d3v [premasked when it came from the fused head]) -> rec3, d2v (masked by h2v)
+//   K1  C3  dst  (dh = d3v, masked here by h3v) -> rec3, d2v (masked by h2v)
+//       premasked (loss step): fused_forward stopped after layer 2, and K1 is fused_l3_kernel -- layer 3's forward, fc,
+//       BCE and this sweep per item; Z / aux of C3, h3v and d3v are not written (no later call reads them: the input
+//       gradients read rec3 only, and a backward from dlogits needs its own forward for h3v)
 //   K2  C3  src  -> d2c (masked by h2c)                 K2' C2V dst (dh = d2v) -> rec2v, d1v (masked by h1v)
 //   K3  C2C dst  (dh = d2c) -> rec2c, d1c (masked)      K3' C2V src -> d1c_b = (h1c > 0) (dX + d1c)
 //   K4  C2C src  -> d1v_b = (h1v > 0) (dX + d1v)
@@ -2017,10 +2325,16 @@ int fused_backward(const mllp_graph* g, const FusedModel& m, bool premasked, flo
     int rc;
     const FusedOrient& A = g->FA;      // rows = constraints
     const FusedOrient& At = g->FAt;    // rows = variables
-    {   // K1
+    if (premasked) {   // K1 of a loss step: layer 3 forward, head and C3 dst in one launch
+        L3Job L = {};
+        L.f = l3_fwd_job(g, m, 2);
+        L.rec = w.c[CONV_3V].rec; L.dx_dst = w.d2v; L.stats = w.c[CONV_3V].stats;
+        hipLaunchKernelGGL(fused_l3_kernel, dim3(G), dim3(FT), 0, s, L);
+        if ((rc = check_launch("fused_l3"))) return rc;
+    } else {   // K1
         BwdLaunch16 L = {};
         L.n_jobs = 1;
-        L.job[0] = bwd_job16(At, m, CONV_3V, w.h2c, w.h2v, premasked ? nullptr : w.h3v, w.d3v, nullptr, w.d2v, true, true);
+        L.job[0] = bwd_job16(At, m, CONV_3V, w.h2c, w.h2v, w.h3v, w.d3v, nullptr, w.d2v, true, true);
         hipLaunchKernelGGL(fused_bwd16_kernel, dim3(G), dim3(FT), 0, s, L);
         if ((rc = check_launch("fused_bwd16 C3"))) return rc;
     }
@@ -2060,7 +2374,7 @@ int fused_backward(const mllp_graph* g, const FusedModel& m, bool premasked, flo
     ReduceArgs R = {};
     for (int c = 0; c < MODEL_CONVS; ++c) { R.stats[c] = w.c[c].stats; R.out[c] = w.c[c].red; }
     R.nblk = G;
-    R.head_part = w.head_partials;      // from fused_forward (head_mode 2) or fused_head_backward
+    R.head_part = w.head_partials;      // from fused_l3_kernel or fused_head_backward
     R.head_out = grads + OFF_FC;
     R.loss_out = loss;
     if (adam) {     // K6 + K7 + Adam + the next step's folded weights in one launch (single-rank step)

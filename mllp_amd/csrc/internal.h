@@ -409,12 +409,14 @@ int fused_graph_build(mllp_graph* g, const int* h_csr_ptr, const int* h_csc_ptr)
 int fused_grid(const mllp_graph* g);
 int fused_refill_values(mllp_graph* g, hipStream_t s);   // sent of both orientations from A.val / At.val again (launches only)
 int fused_bind(mllp_graph* g, const float* x1, const float* x2, const float* labels, hipStream_t s);
-// head_mode 1: logits (h3v kept), 2: logits + BCE + masked dL/dh3v in d3v + fc partials
+// head_mode 1: all three layers, logits (h3v kept).  2 (loss step): layers 1 and 2 only -- layer 3, the logits, BCE and the
+// fc partials come from the first launch of fused_backward(premasked = true), which must follow on the same workspace
 int fused_forward(mllp_graph* g, const FusedModel& m, int head_mode, hipStream_t s, bool skip_prep = false);
 // d3v = dlogits (original variable order) x fc weight in renumbered order, fc gradient partials
 int fused_head_backward(const mllp_graph* g, const FusedModel& m, const float* dlogits, hipStream_t s);
-// premasked: d3v and the fc partials come from fused_forward(head_mode 2); else d3v = dL/dh3v (unmasked) and the
-// caller has produced the fc gradient itself
+// premasked: after fused_forward(head_mode 2); the first launch runs layer 3's forward, the loss head and C3's
+// destination-major backward per item (Z / aux of C3, h3v and d3v are not written).  Else d3v = dL/dh3v (unmasked, from
+// fused_head_backward after a forward with head_mode 1) and the caller has produced the fc gradient itself
 // adam != nullptr: the single-rank tail (reduce + gradients + Adam + the next step's folded weights in one launch)
 struct FusedAdam {
     float *params, *m, *v, *state;
