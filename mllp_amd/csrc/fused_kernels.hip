@@ -19,14 +19,15 @@
 // inputs, its per-nonzero source feature is stored beside the value ({a_ij, x_j}): the layer-1 sweeps gather
 // nothing.  Only the logits leave in the caller's variable order.
 //
-// Mapping: persistent workgroups of 1024 threads, one per CU.  A WAVEFRONT takes an item = 16 rows, one QUAD of
-// lanes per row (lane `part` owns channels 4 part .. 4 part + 3; a gather of a 64-byte source row is one 16-byte
-// load per lane of the quad): 16 rows and 64 gathers in flight per wavefront, and the entries of the next four
-// nonzeros are fetched while the current four are gathered.  Rows longer than 16 nonzeros take 4 quads, longer than
-// 64 a whole wavefront, longer than 1024 the whole workgroup (states merged by DPP / shuffles / LDS).  Scalar
-// (layer-1) sweeps use one LANE per row.  The 16x16 per-node GEMMs and the parameter statistics run on the MFMA
-// (v_mfma_f32_16x16x4_f32, exact fp32) through LDS tiles that convert between the quad layout and the MFMA layouts.
-// Nothing here uses atomics: partial sums have a fixed owner and a fixed order, so two runs give identical bits.
+// Mapping: persistent workgroups of 768 threads (FT below says why not 1024), one per CU.  A WAVEFRONT takes an
+// item = 16 rows, one QUAD of lanes per row (lane `part` owns channels 4 part .. 4 part + 3; a gather of a 64-byte
+// source row is one 16-byte load per lane of the quad): 16 rows and 64 gathers in flight per wavefront, and the
+// entries of the next four nonzeros are fetched while the current four are gathered.  Rows longer than 16 nonzeros
+// take 4 quads, longer than 64 a whole wavefront, longer than 1024 the whole workgroup (states merged by DPP /
+// shuffles / LDS).  Scalar (layer-1) sweeps use one LANE per row.  The 16x16 per-node GEMMs and the parameter
+// statistics run on the MFMA (v_mfma_f32_16x16x4_f32, exact fp32) through LDS tiles that convert between the quad
+// layout and the MFMA layouts.  Nothing here uses atomics: partial sums have a fixed owner and a fixed order, so two
+// runs give identical bits.
 #include <algorithm>
 #include <vector>
 
@@ -39,9 +40,12 @@ namespace mllp {
 
 typedef float f32x4m __attribute__((ext_vector_type(4)));
 
-// Timing build only (`make timing`, libmllp_hip_timing.so): MLLP_FUSED_ABL masks parts of fused_bwd16_kernel out
-// (results WRONG): 1 = no sweep, 2 = no statistics, 4 = no input-gradient GEMMs, 8 = no record store, 16 = no
-// prologue GEMMs.  The product build compiles FUSED_ABL(bit) to false.
+// Timing build only (`make timing`, libmllp_hip_timing.so): MLLP_FUSED_ABL masks parts of the sweeps out (results
+// WRONG).  fused_bwd16_kernel: 1 = no sweep, 2 = no statistics at all, 4 = no input-gradient GEMMs, 8 = no record store,
+// 16 = no prologue GEMMs, 32 = statistics operands read but no statistics MFMAs, 64 = statistics MFMAs on made-up
+// operands (tiles not read).  fused_fwd16_kernel: 256 = no sweep, 512 = no epilogue GEMMs, 1024 = no prologue
+// GEMM, 2048 = no result stores.  The product build compiles FUSED_ABL(bit) to false; a row half shared between
+// kernels takes its bit as a bool argument.
 #ifdef MLLP_TIMING_BUILD
 static int g_fused_abl = [] {
     const char* e = getenv("MLLP_FUSED_ABL");
@@ -336,6 +340,33 @@ __device__ __forceinline__ float shared_max4(float v, int mode) {
 __device__ __forceinline__ float shared_sum1(float v, int mode) { return mode == 1 ? quad_sum(v) : wave_sum(v); }
 __device__ __forceinline__ float shared_max1(float v, int mode) { return mode == 1 ? quad_max(v) : group_max<64>(v); }
 
+// this workgroup's partition of the instances, its rank among the partition's workgroups, their number, and the rank
+// of this wavefront among the partition's wavefronts
+struct BlockPart {
+    int px, bi, gp, gw;
+};
+__device__ __forceinline__ BlockPart block_part() {
+    BlockPart b;
+    b.px = blockIdx.x % NP; b.bi = blockIdx.x / NP; b.gp = gridDim.x / NP;
+    b.gw = b.bi * FW + (threadIdx.x >> 6);
+    return b;
+}
+
+// The workgroup's partial of one 16 x 16 statistics tile: the wavefronts' tiles (MFMA result layout) summed in wave order
+// through red[FW][256] -> stats[blockIdx][i * 256 + ..].  Called by every thread; red is free again on return.
+__device__ __forceinline__ void stats_tile_store(const f32x4m& a, int i, float* red, float* __restrict__ stats, int tid) {
+    const int lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) red[wave * 256 + ((lane >> 4) * 4 + q) * 16 + (lane & 15)] = a[q];
+    __syncthreads();
+    if (tid < 256) {
+        float v = 0.0f;
+        for (int w = 0; w < FW; ++w) v += red[w * 256 + tid];
+        stats[(size_t)blockIdx.x * STAT_FLOATS + i * 256 + tid] = v;
+    }
+    __syncthreads();
+}
+
 // ====================================================================================================
 // forward, 16 source channels
 // ====================================================================================================
@@ -489,12 +520,17 @@ __device__ __forceinline__ void fwd16_flush(const FwdJob16& J, FwdPending& p, in
     p.row = -1;
 }
 
-// per-row prologue + sweep + epilogue of one job.  Two-deep pipeline over a wavefront's items: every item costs two
-// DEPENDENT round trips (row pointers -> first entries / row data), about 2.5 k cycles each, and with the second one
-// requested behind the sweep an item waited ~1.5 k cycles for it at its start (in-kernel stamps, "between items").
-// Now item i, right behind its own first gathers, turns the row pointers of item i + 1 (requested during item i - 1:
-// q1) into that item's slot and requests its row data and first entries (nx), and requests the row pointers of item
-// i + 2 (it2): both round trips have a whole item to complete.
+// ---- the halves of a forward row.  fwd16_row and l3_row are compositions of these; the weights are a template
+// parameter (FwdW16, L3W) and the LDS tiles a half works through are arguments: tiles + {0, 1, 2} TILE in
+// fused_fwd16_kernel, the TB_* tiles in fused_l3_kernel.  An ablation of the timing build reaches a half as a bool
+// that is the constant false in the product build.
+
+// Two-deep pipeline over a wavefront's items: every item costs two DEPENDENT round trips (row pointers -> first
+// entries / row data), about 2.5 k cycles each, and with the second one requested behind the sweep an item waited
+// ~1.5 k cycles for it at its start (in-kernel stamps, "between items").  Now item i, right behind its own first
+// gathers, turns the row pointers of item i + 1 (requested during item i - 1: q1) into that item's slot and requests
+// its row data and first entries (nx), and requests the row pointers of item i + 2 (it2): both round trips have a
+// whole item to complete.
 struct FwdNext {
     RowSlot r;
     float4 xd;
@@ -502,6 +538,87 @@ struct FwdNext {
     int lrow;
     SlotReq q;      // row pointers of the item after the next
 };
+__device__ __forceinline__ void fwd16_prefetch(const FwdJob16& J, const PartTiers& P, const SlotReq& q1, int it2, FwdNext& nx,
+                                               int part, int lane) {
+    nx.r = slot_make(q1);
+    nx.xd = ld4(J.x_dst + (size_t)max(nx.r.row, 0) * 16 + 4 * part);      // row 0 for a quad without a row: never stored
+    nx.en = first_entries_any<4>(J.s, nx.r, part);
+    nx.lrow = J.perm[max(nx.r.row, 0)];
+    nx.q = item_request<4>(J.s, P, max(it2, 0), lane);                     // it2 < 0: the item loop ends before it is used
+}
+// The sweep's last wait for gathers has just drained the memory pipe: the next item's data (requested at this item's
+// start) is TAKEN here, where waiting is free.  Left pending, hipcc waits for it at the register copies of the loop's
+// back edge with vmcnt(0), which also waits for the stores behind it (1.3 k cycles per item in the stamps).
+__device__ __forceinline__ void fwd16_take(FwdNext& nx) {
+    asm volatile("" : "+v"(nx.xd.x), "+v"(nx.xd.y), "+v"(nx.xd.z), "+v"(nx.xd.w), "+v"(nx.en.x), "+v"(nx.en.y),
+                      "+v"(nx.lrow), "+v"(nx.q.sb), "+v"(nx.q.se));
+}
+
+// q' = Pq x + pq0 on the MFMA (the rows of the wavefront through tile tx, where x stays; the result through tile tq),
+// t = Pt x + pt0
+template <class WT>
+__device__ __forceinline__ void row16_project(const WT& W, float* tx, float* tq, const float4& xd, bool no_gemm, int part,
+                                              int lane, float4& qp, float& t) {
+    float ax_[4];
+    tile_put(tx, xd, lane);
+    tile_rows(tx, lane, ax_);
+    if (!no_gemm) tile_put_result(tq, mat_apply(ax_, matB_lds(W.BPq, lane), splat4(W.pq0[lane & 15])), lane);
+    qp = tile_get(tq, lane);
+    t = quad_sum(dot4(lds4(W.Pt + 4 * part), xd)) + W.pt0;
+}
+
+// the attention sweep of a unit over its nonzeros; gt holds the gathers of slots 0 .. 3, issued by the caller
+__device__ __forceinline__ SoftState fwd16_sweep(const ItemsDev& s, const float* __restrict__ X, const RowSlot& r, int n_mine,
+                                                 int part, int2& en, Gather4& gt, const float4& qp, float t) {
+    SoftState st;
+    st.Z = f4zero(); st.m = NEG_BIG; st.L = 0.0f; st.u = 0.0f;
+    for (int k0 = 0;;) {
+        fwd16_step(gt, k0, n_mine, qp, t, st);
+        k0 += 4;
+        if (!__any(k0 < n_mine)) break;
+        gather4_issue(s, X, r, n_mine, k0, part, en, gt);
+    }
+    return st;
+}
+
+// every lane ends with the row's state (UNROLL: see soft_merge_block)
+template <int UNROLL>
+__device__ __forceinline__ void fwd16_merge(SoftState& st, int mode, float* merge_lds, int lane, int part) {
+    if (mode >= 1) soft_merge(st, mode);
+    if (mode == 3) soft_merge_block<UNROLL>(st, merge_lds, lane, part);
+}
+
+// epilogue: o = Wv Zn + Ws x + (bs + S bv + un we), ReLU.  x is read from tile tx (row16_project left it there), Zn goes
+// through tile tz, the output through tile to.
+struct FwdOut {
+    float4 zn, hv;
+    float rinv, S, un;
+};
+template <class WT>
+__device__ __forceinline__ FwdOut fwd16_epilogue(const WT& W, const float* tx, float* tz, float* to, const SoftState& st,
+                                                 bool no_gemm, int part, int lane) {
+    FwdOut f;
+    f.rinv = 1.0f / (st.L + 1e-16f);   // torch_geometric.utils.softmax: sum + 1e-16
+    f.S = st.L * f.rinv; f.un = st.u * f.rinv;
+    f.zn = f4scale(st.Z, f.rinv);
+    float4 o;
+    {
+        float ax_[4], az_[4];
+        tile_rows(tx, lane, ax_);
+        tile_put(tz, f.zn, lane);
+        tile_rows(tz, lane, az_);
+        if (!no_gemm)
+            tile_put_result(to, mat_apply(ax_, matB_lds(W.BWs, lane), mat_apply(az_, matB_lds(W.BWv, lane), splat4(0.0f))), lane);
+        o = tile_get(to, lane);
+    }
+    o = f4add(o, lds4(W.bs + 4 * part));
+    fma4(f.S, lds4(W.bv + 4 * part), o);
+    fma4(f.un, lds4(W.we + 4 * part), o);
+    f.hv = make_float4(fmaxf(o.x, 0.0f), fmaxf(o.y, 0.0f), fmaxf(o.z, 0.0f), fmaxf(o.w, 0.0f));
+    return f;
+}
+
+// per-row prologue + sweep + epilogue of one job
 __device__ __forceinline__ void fwd16_row(const FwdJob16& J, const FwdW16& W, const PartTiers& P, const RowSlot& r,
                                           const float4& xd, int2& en, int lrow, const SlotReq& q1, int it2, FwdNext& nx,
                                           FwdPending& pend, int part, int lane, float* merge_lds, float* tiles
@@ -513,70 +630,26 @@ __device__ __forceinline__ void fwd16_row(const FwdJob16& J, const FwdW16& W, co
     const int n_mine = FUSED_ABL(256) ? 0 : slot_count(r);
     Gather4 gt;
     gather4_issue(J.s, J.x_src, r, n_mine, 0, part, en, gt);      // the first gathers leave before anything else
-    nx.r = slot_make(q1);
-    nx.xd = ld4(J.x_dst + (size_t)max(nx.r.row, 0) * 16 + 4 * part);      // row 0 for a quad without a row: never stored
-    nx.en = first_entries_any<4>(J.s, nx.r, part);
-    nx.lrow = J.perm[max(nx.r.row, 0)];
-    nx.q = item_request<4>(J.s, P, max(it2, 0), lane);                     // it2 < 0: the item loop ends before it is used
+    fwd16_prefetch(J, P, q1, it2, nx, part, lane);
     float4 qp;
     float t;
-    {   // q' = Pq x + pq0 on the MFMA (rows of the wavefront through tile 0, kept for the epilogue; result through tile 1)
-        float ax_[4];
-        tile_put(tiles, xd, lane);
-        tile_rows(tiles, lane, ax_);
-        if (!FUSED_ABL(1024))
-        tile_put_result(tiles + TILE, mat_apply(ax_, matB_lds(W.BPq, lane), splat4(W.pq0[lane & 15])), lane);
-        qp = tile_get(tiles + TILE, lane);
-        t = quad_sum(dot4(lds4(W.Pt + 4 * part), xd)) + W.pt0;
-    }
+    row16_project(W, tiles, tiles + TILE, xd, FUSED_ABL(1024), part, lane, qp, t);
     FUSED_STAMP(1)      // first gathers issued, prologue GEMM
-    SoftState st;
-    st.Z = f4zero(); st.m = NEG_BIG; st.L = 0.0f; st.u = 0.0f;
-    for (int k0 = 0;;) {
-        fwd16_step(gt, k0, n_mine, qp, t, st);
-        k0 += 4;
-        if (!__any(k0 < n_mine)) break;
-        gather4_issue(J.s, J.x_src, r, n_mine, k0, part, en, gt);
-    }
+    SoftState st = fwd16_sweep(J.s, J.x_src, r, n_mine, part, en, gt, qp, t);
     FUSED_STAMP(2)      // sweep
-    // The sweep's last wait for gathers has just drained the memory pipe: the next item's data (requested at this item's
-    // start) is TAKEN here, where waiting is free.  Left pending, hipcc waits for it at the register copies of the loop's
-    // back edge with vmcnt(0), which also waits for the stores below (1.3 k cycles per item in the stamps).
-    asm volatile("" : "+v"(nx.xd.x), "+v"(nx.xd.y), "+v"(nx.xd.z), "+v"(nx.xd.w), "+v"(nx.en.x), "+v"(nx.en.y),
-                      "+v"(nx.lrow), "+v"(nx.q.sb), "+v"(nx.q.se));
+    fwd16_take(nx);
     fwd16_flush(J, pend, part);     // the previous item's results leave now: acknowledged long before the back edge
-    const int lrow_cur = lrow;      // where this row's logit goes (caller's variable order), fetched with the row
     FUSED_STAMP(3)      // prefetch issue
-
-    if (r.mode >= 1) soft_merge(st, r.mode);
-    if (r.mode == 3) soft_merge_block<FW>(st, merge_lds, lane, part);
-    const bool writer = r.writer;
-    // epilogue: o = Wv Zn + Ws x + (bs + S bv + un we)
-    const float rinv = 1.0f / (st.L + 1e-16f);   // torch_geometric.utils.softmax: sum + 1e-16
-    const float S = st.L * rinv, un = st.u * rinv;
-    const float4 zn = f4scale(st.Z, rinv);
-    float4 o;
-    {
-        float ax_[4], az_[4];
-        tile_rows(tiles, lane, ax_);
-        tile_put(tiles + TILE, zn, lane);
-        tile_rows(tiles + TILE, lane, az_);
-        if (!FUSED_ABL(512))
-        tile_put_result(tiles + 2 * TILE,
-                        mat_apply(ax_, matB_lds(W.BWs, lane), mat_apply(az_, matB_lds(W.BWv, lane), splat4(0.0f))), lane);
-        o = tile_get(tiles + 2 * TILE, lane);
-    }
-    o = f4add(o, lds4(W.bs + 4 * part));
-    fma4(S, lds4(W.bv + 4 * part), o);
-    fma4(un, lds4(W.we + 4 * part), o);
-    const float4 hv = make_float4(fmaxf(o.x, 0.0f), fmaxf(o.y, 0.0f), fmaxf(o.z, 0.0f), fmaxf(o.w, 0.0f));
+    fwd16_merge<FW>(st, r.mode, merge_lds, lane, part);
+    const FwdOut f = fwd16_epilogue(W, tiles, tiles + TILE, tiles + 2 * TILE, st, FUSED_ABL(512), part, lane);
     FUSED_STAMP(4)      // merges, epilogue GEMM
-    pend.row = writer ? r.row : -1;
-    pend.zn = zn; pend.hv = hv; pend.lrow = lrow_cur;
-    pend.aux = make_float4(un, st.L > 0.0f ? st.m : 0.0f, rinv, S);
+    pend.row = r.writer ? r.row : -1;
+    pend.zn = f.zn; pend.hv = f.hv;
+    pend.lrow = lrow;               // where this row's logit goes (caller's variable order), fetched with the row
+    pend.aux = make_float4(f.un, st.L > 0.0f ? st.m : 0.0f, f.rinv, f.S);
     pend.z = 0.0f;
     if (J.head)          // fc (16 -> 1) on the conv's output row, reference linear_program_methods.py:250
-        pend.z = quad_sum(dot4(hv, lds4(W.fcw + 4 * part))) + W.fcb;
+        pend.z = quad_sum(dot4(f.hv, lds4(W.fcw + 4 * part))) + W.fcb;
     FUSED_STAMP(5)      // stores, head
 }
 
@@ -601,6 +674,82 @@ __device__ __forceinline__ void head_partials_store(HeadAcc& ha, float* head_lds
     }
 }
 
+// Weight staging, before the workgroup's first barrier, for the three weight structs: FwdW16 (FWD), BwdW16 (BWD), L3W
+// (both).  One wavefront per B operand, and ONE block of loads per thread: filled by a function per half, each half's
+// small vectors were loaded, waited for and stored in turn, a round trip more per half at the top of the kernel
+// (fused_l3_kernel 0.4 - 0.8 us above its parent in the kernel trace: profiles/fused_shared_rows.md).  fcw / fcb: nullptr
+// without a head.
+template <bool FWD, bool BWD, class WT>
+__device__ __forceinline__ void stage_weights(WT& W, const float* __restrict__ D, const ConvParams& p,
+                                              const float* __restrict__ fcw, const float* __restrict__ fcb, int tid) {
+    const int lane = tid & 63, wave = tid >> 6;
+    if (wave == 0) matB_store(W.BPq, matB(D + OFF_PQ, 16, lane), lane);
+    if constexpr (FWD) {
+        if (wave == 1) matB_store(W.BWv, matB(p.Wv, 16, lane), lane);
+        if (wave == 2) matB_store(W.BWs, matB(p.Ws, 16, lane), lane);
+    }
+    if constexpr (BWD) {
+        constexpr int w0 = FWD ? 3 : 1;
+        if (wave == w0) matB_store(W.BWvT, matB_t(p.Wv, 16, lane), lane);
+        if (wave == w0 + 1) matB_store(W.BWsT, matB_t(p.Ws, 16, lane), lane);
+        if (wave == w0 + 2) matB_store(W.BPqT, matB_t(D + OFF_PQ, 16, lane), lane);
+    }
+    if (tid < 16) {
+        W.pq0[tid] = D[OFF_PQ0 + tid];
+        W.Pt[tid] = D[OFF_PT + tid];
+        W.bv[tid] = p.bv[tid];
+        W.we[tid] = p.we[tid];
+        if constexpr (BWD) W.Pb[tid] = D[OFF_PB + tid];
+        if constexpr (FWD) {
+            W.bs[tid] = p.bs[tid];
+            W.fcw[tid] = fcw ? fcw[tid] : 0.0f;
+        }
+    }
+    if (tid == 0) {
+        W.pt0 = D[OFF_PT0];
+        if constexpr (FWD) W.fcb = fcb ? fcb[0] : 0.0f;
+    }
+}
+
+// The walk of fused_fwd16_kernel and fused_l3_kernel over a job's rows: the block tier (the whole workgroup walks one
+// long row at a time, longest rows first), then this wavefront's items (static assignment by estimated cost) through
+// the two-deep pipeline.  row(r, xd, en, lrow, q1, it2, nx) works on one slot and leaves the next item's data in nx.
+template <class Row>
+__device__ __forceinline__ void walk_two_deep(const FwdJob16& J, const PartTiers& P, const BlockPart& B, int tid, Row&& row) {
+    const int lane = tid & 63, part = lane & 3;
+    const RowSlot none = empty_slot();
+    for (int k = B.bi; k < P.n_block; k += B.gp) {
+        const RowSlot r = block_slot<4>(J.s, P.row0 + k, tid);
+        const float4 xd = ld4(J.x_dst + (size_t)r.row * 16 + 4 * part);
+        int2 en = first_entries<4>(J.s, r, part);
+        const int lrow = J.perm[r.row];
+        FwdNext nx;
+        row(r, xd, en, lrow, empty_request(), -1, nx);
+    }
+    WaveList wl = wave_list(J.s, B.px, B.gw);
+    for (int c0 = 0; c0 < wl.L; c0 += 64) {
+        wave_list_chunk(wl, c0, lane);
+        int it = wave_list_get(wl, 0), it1 = wave_list_get(wl, 1);
+        RowSlot r = it >= 0 ? item_slot<4>(J.s, P, it, lane) : none;
+        float4 xd = r.row >= 0 ? ld4(J.x_dst + (size_t)r.row * 16 + 4 * part) : f4zero();
+        int2 en = first_entries<4>(J.s, r, part);
+        int lrow = r.row >= 0 ? J.perm[r.row] : 0;
+        SlotReq q1 = item_request<4>(J.s, P, max(it1, 0), lane);
+        if (it1 < 0) q1.row = -1;
+        // cold start: everything requested above is waited for HERE -- left pending into the loop, the copies at its
+        // header would wait with vmcnt(0) in every iteration (the waits of a loop header cover its entry path too)
+        asm volatile("" : "+v"(xd.x), "+v"(xd.y), "+v"(xd.z), "+v"(xd.w), "+v"(en.x), "+v"(en.y), "+v"(lrow),
+                          "+v"(q1.sb), "+v"(q1.se));
+        for (int k = 0; it >= 0; ++k) {
+            const int it2 = wave_list_get(wl, k + 2);
+            FwdNext nx;
+            row(r, xd, en, lrow, q1, it2, nx);
+            r = nx.r; xd = nx.xd; en = nx.en; lrow = nx.lrow; q1 = nx.q;
+            it = it1; it1 = it2;
+        }
+    }
+}
+
 __global__ __launch_bounds__(FT) void fused_fwd16_kernel(FwdLaunch16 A) {
     __shared__ FwdW16 Ws_[MAXJOBS];
     __shared__ float merge_lds[FW * 20];
@@ -608,22 +757,7 @@ __global__ __launch_bounds__(FT) void fused_fwd16_kernel(FwdLaunch16 A) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, part = lane & 3;
     for (int j = 0; j < A.n_jobs; ++j) {
         const FwdJob16& J = A.job[j];
-        FwdW16& W = Ws_[j];
-        if (wave == 0) matB_store(W.BPq, matB(J.D + OFF_PQ, 16, lane), lane);
-        if (wave == 1) matB_store(W.BWv, matB(J.p.Wv, 16, lane), lane);
-        if (wave == 2) matB_store(W.BWs, matB(J.p.Ws, 16, lane), lane);
-        if (tid < 16) {
-            W.pq0[tid] = J.D[OFF_PQ0 + tid];
-            W.Pt[tid] = J.D[OFF_PT + tid];
-            W.bv[tid] = J.p.bv[tid];
-            W.we[tid] = J.p.we[tid];
-            W.bs[tid] = J.p.bs[tid];
-            W.fcw[tid] = J.head ? J.fcw[tid] : 0.0f;
-        }
-        if (tid == 0) {
-            W.pt0 = J.D[OFF_PT0];
-            W.fcb = J.head ? J.fcb[0] : 0.0f;
-        }
+        stage_weights<true, false>(Ws_[j], J.D, J.p, J.head ? J.fcw : nullptr, J.head ? J.fcb : nullptr, tid);
     }
     __syncthreads();
     float* tiles = tiles_ + wave * 3 * TILE;
@@ -635,52 +769,23 @@ __global__ __launch_bounds__(FT) void fused_fwd16_kernel(FwdLaunch16 A) {
 #else
 #define STAMP_ARGS
 #endif
-    // this workgroup's partition of the instances, its rank among the partition's workgroups, their wavefronts
-    const int px = blockIdx.x % NP, bi = blockIdx.x / NP, gp = gridDim.x / NP;
-    const int gw = bi * FW + wave;
+    const BlockPart B = block_part();
     for (int j = 0; j < A.n_jobs; ++j) {
         const FwdJob16& J = A.job[j];
-        const PartTiers P = J.s.part[px];
-        // block tier: the whole workgroup walks one long row at a time (longest rows first)
-        const RowSlot none = empty_slot();
+        const FwdW16& W = Ws_[j];
+        const PartTiers P = J.s.part[B.px];
         FwdPending pend;
         pend.row = -1;
-        for (int k = bi; k < P.n_block; k += gp) {
-            const RowSlot r = block_slot<4>(J.s, P.row0 + k, tid);
-            const float4 xd = ld4(J.x_dst + (size_t)r.row * 16 + 4 * part);
-            int2 en = first_entries<4>(J.s, r, part);
-            const int lrow = J.head ? J.perm[r.row] : 0;
-            FwdNext nx;
-            fwd16_row(J, Ws_[j], P, r, xd, en, lrow, empty_request(), -1, nx, pend, part, lane, merge_lds, tiles STAMP_ARGS);
-        }
-        // wave loop: this wavefront's items (static assignment by estimated cost)
-        WaveList wl = wave_list(J.s, px, gw);
-        for (int c0 = 0; c0 < wl.L; c0 += 64) {
-            wave_list_chunk(wl, c0, lane);
-            int it = wave_list_get(wl, 0), it1 = wave_list_get(wl, 1);
-            RowSlot r = it >= 0 ? item_slot<4>(J.s, P, it, lane) : none;
-            float4 xd = r.row >= 0 ? ld4(J.x_dst + (size_t)r.row * 16 + 4 * part) : f4zero();
-            int2 en = first_entries<4>(J.s, r, part);
-            int lrow = (J.head && r.row >= 0) ? J.perm[r.row] : 0;
-            SlotReq q1 = item_request<4>(J.s, P, max(it1, 0), lane);
-            if (it1 < 0) q1.row = -1;
-            // cold start: everything requested above is waited for HERE -- left pending into the loop, the copies at its
-            // header would wait with vmcnt(0) in every iteration (the waits of a loop header cover its entry path too)
-            asm volatile("" : "+v"(xd.x), "+v"(xd.y), "+v"(xd.z), "+v"(xd.w), "+v"(en.x), "+v"(en.y), "+v"(lrow),
-                              "+v"(q1.sb), "+v"(q1.se));
-            for (int k = 0; it >= 0; ++k) {
-                const int it2 = wave_list_get(wl, k + 2);
-                FwdNext nx;
-                fwd16_row(J, Ws_[j], P, r, xd, en, lrow, q1, it2, nx, pend, part, lane, merge_lds, tiles STAMP_ARGS);
+        walk_two_deep(J, P, B, tid, [&](const RowSlot& r, const float4& xd, int2& en, int lrow, const SlotReq& q1, int it2,
+                                        FwdNext& nx) __attribute__((always_inline)) {
+            fwd16_row(J, W, P, r, xd, en, lrow, q1, it2, nx, pend, part, lane, merge_lds, tiles STAMP_ARGS);
 #ifdef MLLP_TIMING_BUILD
-                stamp_sum[7] += 1;      // items
+            if (r.mode != 3) stamp_sum[7] += 1;      // items: only the walk's block-tier rows (block_slot) have mode 3
 #endif
-                r = nx.r; xd = nx.xd; en = nx.en; lrow = nx.lrow; q1 = nx.q;
-                it = it1; it1 = it2;
-            }
-        }
+        });
         fwd16_flush(J, pend, part);
     }
+#undef STAMP_ARGS
 #ifdef MLLP_TIMING_BUILD
     if (lane == 0 && A.job[0].abl >= 0) {
         stamp_sum[6] = __builtin_amdgcn_s_memtime() - stamp_begin;      // whole kernel of this wavefront
@@ -844,7 +949,7 @@ __device__ __forceinline__ void fwd1_row(const FwdJob1& J, const FwdW1& W, const
 __global__ __launch_bounds__(FT) void fused_fwd1_kernel(FwdLaunch1 A) {
     __shared__ FwdW1 Ws_[MAXJOBS];
     __shared__ float merge_lds[FW * 4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
     for (int j = 0; j < A.n_jobs; ++j) {
         const FwdJob1& J = A.job[j];
         FwdW1& W = Ws_[j];
@@ -857,14 +962,13 @@ __global__ __launch_bounds__(FT) void fused_fwd1_kernel(FwdLaunch1 A) {
         }
     }
     __syncthreads();
-    const int px = blockIdx.x % NP, bi = blockIdx.x / NP, gp = gridDim.x / NP;
-    const int gw = bi * FW + wave;
+    const BlockPart B = block_part();
     for (int j = 0; j < A.n_jobs; ++j) {
         const FwdJob1& J = A.job[j];
-        const PartTiers P = J.s.part[px];
-        for (int k = bi; k < P.n_block; k += gp)
+        const PartTiers P = J.s.part[B.px];
+        for (int k = B.bi; k < P.n_block; k += B.gp)
             fwd1_row(J, Ws_[j], block_slot<1>(J.s, P.row0 + k, tid), lane, merge_lds);
-        WaveList wl = wave_list(J.s, px, gw);
+        WaveList wl = wave_list(J.s, B.px, B.gw);
         for (int c0 = 0; c0 < wl.L; c0 += 64) {
             wave_list_chunk(wl, c0, lane);
             // row pointers of item k + 1 requested before item k is worked on
@@ -974,27 +1078,6 @@ __device__ __forceinline__ void rec_store(float* __restrict__ rec, int row, int 
     if (part == 0) *reinterpret_cast<float4*>(rr + 32) = make_float4(t, m, rinv, ge);
     if (part == 1) *reinterpret_cast<float4*>(rr + 36) = make_float4(cc, 0.0f, 0.0f, 0.0f);
 }
-// dx_i = Ws^T g_i + Pq^T dq'_i + ds_i Pb + dt_i Pt from the tiles G and DQ (through SC), times (x > 0) where `mask`
-template <class WT>
-__device__ __forceinline__ float4 dx_dst_row(const WT& W, float* tiles, const BwdState& st, bool mask, int xpos, int part,
-                                             int lane) {
-    float ag_[4], adq_[4];
-    tile_rows(tiles + TB_G * TILE, lane, ag_);
-    tile_rows(tiles + TB_DQ * TILE, lane, adq_);
-    tile_put_result(tiles + TB_SC * TILE,
-                    mat_apply(adq_, matB_lds(W.BPqT, lane), mat_apply(ag_, matB_lds(W.BWsT, lane), splat4(0.0f))), lane);
-    float4 v = tile_get(tiles + TB_SC * TILE, lane);
-    fma4(st.ds, lds4(W.Pb + 4 * part), v);
-    fma4(st.dt, lds4(W.Pt + 4 * part), v);
-    if (mask) {
-        if (!(xpos & 1)) v.x = 0.0f;
-        if (!(xpos & 2)) v.y = 0.0f;
-        if (!(xpos & 4)) v.z = 0.0f;
-        if (!(xpos & 8)) v.w = 0.0f;
-    }
-    return v;
-}
-
 // the row data of a destination-major backward item (fetched one item ahead)
 struct BwdRow {
     float4 ga, gb, h, x, Z, ax;
@@ -1011,6 +1094,148 @@ __device__ __forceinline__ void bwd16_fetch(const BwdJob16& J, const RowSlot& r,
     d.ax = have ? reinterpret_cast<const float4*>(J.aux)[r.row] : z4;   // {u, rowmax, rinv, S}
 }
 
+// ---- the halves of a destination-major backward row, composed by bwd16_row and l3_row (weights: BwdW16, L3W; `tiles`
+// are the wavefront's TB_* tiles).  Tile X holds the row's x when they start: row16_project left it there.
+
+// From the masked output gradient g and the row's Zn, S, u: everything of the row that the sweep does not need goes to
+// the tiles G, Z, E and stays there until the statistics; gv = Wv^T g on the MFMA (the result comes back through the
+// still unused tile DQ), ge, c.  A quad without a row passes zeros.
+struct DstProj {
+    float4 gv;
+    float ge, cc;
+};
+template <class WT>
+__device__ __forceinline__ DstProj dst16_project(const WT& W, float* tiles, const float4& g, const float4& Zn, float S, float u,
+                                                 bool have, bool no_gemm, int part, int lane) {
+    DstProj p;
+    float ag_[4];
+    tile_put(tiles + TB_G * TILE, g, lane);
+    tile_put(tiles + TB_Z * TILE, Zn, lane);
+    tile_put(tiles + TB_E * TILE, (have && part == 0) ? make_float4(1.0f, S, u, 0.0f) : f4zero(), lane);
+    tile_rows(tiles + TB_G * TILE, lane, ag_);
+    if (!no_gemm) tile_put_result(tiles + TB_DQ * TILE, mat_apply(ag_, matB_lds(W.BWvT, lane), splat4(0.0f)), lane);
+    p.gv = tile_get(tiles + TB_DQ * TILE, lane);
+    p.ge = quad_sum(dot4(g, lds4(W.we + 4 * part)));
+    const float gb = quad_sum(dot4(g, lds4(W.bv + 4 * part)));
+    const float Dn = quad_sum(dot4(p.gv, Zn)) + gb * S + p.ge * u;
+    p.cc = gb - Dn;
+    return p;
+}
+
+// the sweep of a unit over its nonzeros; gt holds the gathers of slots 0 .. 3, issued by the caller
+__device__ __forceinline__ BwdState dst16_sweep(const ItemsDev& s, const float* __restrict__ X, const RowSlot& r, int n_mine,
+                                                int part, int2& en, Gather4& gt, const float4& qp, const DstProj& p, float t,
+                                                float m, float rinv) {
+    BwdState st;
+    st.dq = f4zero(); st.ds = 0.0f; st.dt = 0.0f;
+    for (int k0 = 0;;) {
+        bwd16_step(gt, k0, n_mine, qp, p.gv, t, m, rinv, p.ge, p.cc, st);
+        k0 += 4;
+        if (!__any(k0 < n_mine)) break;
+        gather4_issue(s, X, r, n_mine, k0, part, en, gt);
+    }
+    return st;
+}
+
+// The units that share a row add their sums up (UNROLL: see soft_merge_block).  false (wave-uniform) for the wavefronts
+// that are done with a block-tier row: its outputs and statistics belong to wavefront 0.  The others leave the row's dq'
+// in tile DQ for the tail.
+template <int UNROLL>
+__device__ __forceinline__ bool dst16_merge(BwdState& st, int mode, float* merge_lds, float* tiles, int lane, int part) {
+    if (mode >= 1) {
+        st.ds = shared_sum4(st.ds, mode);
+        st.dt = shared_sum4(st.dt, mode);
+        st.dq.x = shared_sum4(st.dq.x, mode); st.dq.y = shared_sum4(st.dq.y, mode);
+        st.dq.z = shared_sum4(st.dq.z, mode); st.dq.w = shared_sum4(st.dq.w, mode);
+    }
+    if (mode == 3) {
+        bwd_merge_block<UNROLL>(st, merge_lds, lane, part);
+        if (threadIdx.x >= 64) return false;
+    }
+    tile_put(tiles + TB_DQ * TILE, st.dq, lane);
+    return true;
+}
+
+// tail, first part: the input gradient dx_i = Ws^T g_i + Pq^T dq'_i + ds_i Pb + dt_i Pt from the tiles G and DQ (through
+// SC), times (x > 0) where `mask`, and its store
+template <class WT>
+__device__ __forceinline__ void dst16_dx(const WT& W, float* tiles, const BwdState& st, const RowSlot& r,
+                                         float* __restrict__ dx_dst, bool mask, int xpos, int part, int lane) {
+    float ag_[4], adq_[4];
+    tile_rows(tiles + TB_G * TILE, lane, ag_);
+    tile_rows(tiles + TB_DQ * TILE, lane, adq_);
+    tile_put_result(tiles + TB_SC * TILE,
+                    mat_apply(adq_, matB_lds(W.BPqT, lane), mat_apply(ag_, matB_lds(W.BWsT, lane), splat4(0.0f))), lane);
+    float4 v = tile_get(tiles + TB_SC * TILE, lane);
+    fma4(st.ds, lds4(W.Pb + 4 * part), v);
+    fma4(st.dt, lds4(W.Pt + 4 * part), v);
+    if (mask) {
+        if (!(xpos & 1)) v.x = 0.0f;
+        if (!(xpos & 2)) v.y = 0.0f;
+        if (!(xpos & 4)) v.z = 0.0f;
+        if (!(xpos & 8)) v.w = 0.0f;
+    }
+    if (r.writer) *reinterpret_cast<float4*>(dx_dst + (size_t)r.row * 16 + 4 * part) = v;
+}
+// tail, second part: the operands of the statistics (node_kernels.hip::param_stats16_kernel) with m / n = channel,
+// k = row.  A row shared by several quads is counted once: only its writer keeps it, the other rows of the tiles become
+// zeros
+struct StatCols {
+    float g[4], dq[4], sc[4], x[4], z[4], e[4];
+};
+__device__ __forceinline__ void dst16_stat_cols(float* tiles, const BwdState& st, const RowSlot& r, bool no_read, int part,
+                                                int lane, StatCols& c) {
+    if (r.mode >= 1 && !r.writer) {
+        const float4 z4 = f4zero();
+        tile_put(tiles + TB_G * TILE, z4, lane);
+        tile_put(tiles + TB_X * TILE, z4, lane);
+        tile_put(tiles + TB_Z * TILE, z4, lane);
+        tile_put(tiles + TB_E * TILE, z4, lane);
+        tile_put(tiles + TB_DQ * TILE, z4, lane);
+    }
+    tile_put(tiles + TB_SC * TILE, (r.writer && part == 0) ? make_float4(st.ds, st.dt, 0.0f, 0.0f) : f4zero(), lane);
+    if (no_read) {
+        for (int s = 0; s < 4; ++s) c.g[s] = c.dq[s] = c.sc[s] = c.x[s] = c.z[s] = c.e[s] = (float)lane;
+        return;
+    }
+    tile_cols(tiles + TB_G * TILE, lane, c.g);
+    tile_cols(tiles + TB_DQ * TILE, lane, c.dq);
+    tile_cols(tiles + TB_SC * TILE, lane, c.sc);
+    tile_cols(tiles + TB_X * TILE, lane, c.x);
+    tile_cols(tiles + TB_Z * TILE, lane, c.z);
+    tile_cols(tiles + TB_E * TILE, lane, c.e);
+}
+
+// Statistics accumulation: T0 g x^T, T1 g Z^T, T2 g e^T, T3 dq' x^T, T4 dq' e^T, T5 sc x^T, T6 sc e^T, four k-steps per
+// tile.  The first REG tiles are register accumulators; the others rest in the wavefront's LDS between items (park_get /
+// park_put below: each lane reads and writes its own float4, the sums and their order are those of registers).
+__device__ __forceinline__ const float (&stat_a(const StatCols& c, int i))[4] { return i < 3 ? c.g : i < 5 ? c.dq : c.sc; }
+__device__ __forceinline__ const float (&stat_b(const StatCols& c, int i))[4] {
+    return (i == 0 || i == 3 || i == 5) ? c.x : i == 1 ? c.z : c.e;
+}
+__device__ __forceinline__ f32x4m park_get(const float* park, int k, int lane) {
+    const float4 v = lds4(park + (k * 64 + lane) * 4);
+    return (f32x4m){v.x, v.y, v.z, v.w};
+}
+__device__ __forceinline__ void park_put(float* park, int k, int lane, const f32x4m& a) {
+    *reinterpret_cast<float4*>(park + (k * 64 + lane) * 4) = make_float4(a[0], a[1], a[2], a[3]);
+}
+template <int REG>
+__device__ __forceinline__ void stats_accumulate(const StatCols& c, f32x4m (&acc)[REG], float* park, int lane) {
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+#pragma unroll
+        for (int i = 0; i < REG; ++i)
+            acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(stat_a(c, i)[s], stat_b(c, i)[s], acc[i], 0, 0, 0);
+    }
+#pragma unroll
+    for (int i = REG; i < STAT_TILES; ++i) {
+        f32x4m a = park_get(park, i - REG, lane);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) a = __builtin_amdgcn_mfma_f32_16x16x4f32(stat_a(c, i)[s], stat_b(c, i)[s], a, 0, 0, 0);
+        park_put(park, i - REG, lane, a);
+    }
+}
 
 // itn: the wavefront's next item (-1: none).  Its row pointers are requested BEHIND this item's first gathers: requested
 // in front of them (by the caller), they were the youngest loads when the first use of the prefetched row data made
@@ -1019,107 +1244,39 @@ __device__ __forceinline__ void bwd16_row(const BwdJob16& J, const BwdW16& W, co
                                           BwdRow& rd, int2& en, int itn, RowSlot& rn, int part,
                                           int lane, float* merge_lds, float* tiles, f32x4m (&acc)[STAT_TILES]) {
     const bool have = r.row >= 0;
-    const bool writer = r.writer;
     const int n_mine = FUSED_ABL(1) ? 0 : slot_count(r);
     Gather4 gt;
     gather4_issue(J.s, J.x_src, r, n_mine, 0, part, en, gt);      // the first gathers leave before anything else
     SlotReq qn = item_request<4>(J.s, P, max(itn, 0), lane);       // consumed behind the sweep
     if (itn < 0) qn.row = -1;
     const int xpos = (rd.x.x > 0.0f ? 1 : 0) | (rd.x.y > 0.0f ? 2 : 0) | (rd.x.z > 0.0f ? 4 : 0) | (rd.x.w > 0.0f ? 8 : 0);
-    float4 qp, gv;
-    float t, m, rinv, ge, cc;
-    {   // everything of the row that the sweep does not need stays in the tiles G, X, Z, E until the statistics
-        float4 g = f4add(rd.ga, rd.gb);
-        g = make_float4(rd.h.x > 0.0f ? g.x : 0.0f, rd.h.y > 0.0f ? g.y : 0.0f, rd.h.z > 0.0f ? g.z : 0.0f, rd.h.w > 0.0f ? g.w : 0.0f);
-        const float4 xd = rd.x, Zn = rd.Z, ax = rd.ax;
-        // gv = Wv^T g and q' = Pq x + pq0 on the MFMA; the results come back through the (still unused) tiles DQ and SC
-        float ag_[4], ax_[4];
-        tile_put(tiles + TB_G * TILE, g, lane);
-        tile_put(tiles + TB_X * TILE, xd, lane);
-        tile_put(tiles + TB_Z * TILE, Zn, lane);
-        tile_put(tiles + TB_E * TILE, (have && part == 0) ? make_float4(1.0f, ax.w, ax.x, 0.0f) : f4zero(), lane);
-        tile_rows(tiles + TB_G * TILE, lane, ag_);
-        tile_rows(tiles + TB_X * TILE, lane, ax_);
-        if (!FUSED_ABL(16)) {
-            tile_put_result(tiles + TB_DQ * TILE, mat_apply(ag_, matB_lds(W.BWvT, lane), splat4(0.0f)), lane);
-            tile_put_result(tiles + TB_SC * TILE, mat_apply(ax_, matB_lds(W.BPq, lane), splat4(W.pq0[lane & 15])), lane);
-        }
-        gv = tile_get(tiles + TB_DQ * TILE, lane);
-        qp = tile_get(tiles + TB_SC * TILE, lane);
-        t = quad_sum(dot4(lds4(W.Pt + 4 * part), xd)) + W.pt0;
-        ge = quad_sum(dot4(g, lds4(W.we + 4 * part)));
-        const float gb = quad_sum(dot4(g, lds4(W.bv + 4 * part)));
-        const float Dn = quad_sum(dot4(gv, Zn)) + gb * ax.w + ge * ax.x;
-        cc = gb - Dn;
-        m = ax.y; rinv = ax.z;
-    }
-    BwdState st;
-    st.dq = f4zero(); st.ds = 0.0f; st.dt = 0.0f;
-    for (int k0 = 0;;) {
-        bwd16_step(gt, k0, n_mine, qp, gv, t, m, rinv, ge, cc, st);
-        k0 += 4;
-        if (!__any(k0 < n_mine)) break;
-        gather4_issue(J.s, J.x_src, r, n_mine, k0, part, en, gt);
-    }
+    // dL/dh = dh_a + dh_b (the sum also turns a -0.0 of dh_a into +0.0), times the ReLU mask
+    float4 g = f4add(rd.ga, rd.gb);
+    g = make_float4(rd.h.x > 0.0f ? g.x : 0.0f, rd.h.y > 0.0f ? g.y : 0.0f, rd.h.z > 0.0f ? g.z : 0.0f, rd.h.w > 0.0f ? g.w : 0.0f);
+    const float m = rd.ax.y, rinv = rd.ax.z;      // aux = {u, rowmax, rinv, S}
+    // q' = Pq x + pq0 comes back through the (still unused) tile SC
+    float4 qp;
+    float t;
+    row16_project(W, tiles + TB_X * TILE, tiles + TB_SC * TILE, rd.x, FUSED_ABL(16), part, lane, qp, t);
+    const DstProj p = dst16_project(W, tiles, g, rd.Z, rd.ax.w, rd.ax.x, have, FUSED_ABL(16), part, lane);
+    BwdState st = dst16_sweep(J.s, J.x_src, r, n_mine, part, en, gt, qp, p, t, m, rinv);
     // the record leaves behind the sweep: stored in front of it, the sweep's gather waits (vmcnt(0)) waited for the
     // stores' acknowledgements as well
-    if (writer && J.rec && !FUSED_ABL(8)) rec_store(J.rec, r.row, part, qp, gv, t, m, rinv, ge, cc);
+    if (r.writer && J.rec && !FUSED_ABL(8)) rec_store(J.rec, r.row, part, qp, p.gv, t, m, rinv, p.ge, p.cc);
     // the next item's row data and first entries travel while this one finishes
     rn = slot_make(qn);                // the next item's row pointers were requested when this item started
     bwd16_fetch(J, rn, part, rd);      // (rd and en are dead here: the next item's data land in the same registers)
     en = first_entries<4>(J.s, rn, part);
-    if (r.mode >= 1) {
-        st.ds = shared_sum4(st.ds, r.mode);
-        st.dt = shared_sum4(st.dt, r.mode);
-        st.dq.x = shared_sum4(st.dq.x, r.mode); st.dq.y = shared_sum4(st.dq.y, r.mode);
-        st.dq.z = shared_sum4(st.dq.z, r.mode); st.dq.w = shared_sum4(st.dq.w, r.mode);
-    }
-    if (r.mode == 3) {
-        bwd_merge_block<FW>(st, merge_lds, lane, part);
-        if (threadIdx.x >= 64) return;      // wave-uniform: the row's outputs and statistics belong to wavefront 0
-    }
-    tile_put(tiles + TB_DQ * TILE, st.dq, lane);
-    if (J.dx_dst && !FUSED_ABL(4)) {
-        const float4 v = dx_dst_row(W, tiles, st, J.mask_dx != 0, xpos, part, lane);
-        if (writer) *reinterpret_cast<float4*>(J.dx_dst + (size_t)r.row * 16 + 4 * part) = v;
-    }
-    // statistics (node_kernels.hip::param_stats16_kernel): operands with m / n = channel, k = row.  A row shared by
-    // several quads is counted once: only its writer keeps it, the other rows of the tiles become zeros
+    if (!dst16_merge<FW>(st, r.mode, merge_lds, tiles, lane, part)) return;
+    if (J.dx_dst && !FUSED_ABL(4)) dst16_dx(W, tiles, st, r, J.dx_dst, J.mask_dx != 0, xpos, part, lane);
     if (FUSED_ABL(2)) return;
-    if (r.mode >= 1 && !writer) {
-        const float4 z4 = f4zero();
-        tile_put(tiles + TB_G * TILE, z4, lane);
-        tile_put(tiles + TB_X * TILE, z4, lane);
-        tile_put(tiles + TB_Z * TILE, z4, lane);
-        tile_put(tiles + TB_E * TILE, z4, lane);
-        tile_put(tiles + TB_DQ * TILE, z4, lane);
-    }
-    tile_put(tiles + TB_SC * TILE, (writer && part == 0) ? make_float4(st.ds, st.dt, 0.0f, 0.0f) : f4zero(), lane);
-    float cg[4], cdq[4], csc[4], cx[4], cz[4], ce[4];
-    if (FUSED_ABL(64)) {
-        for (int s = 0; s < 4; ++s) { cg[s] = cdq[s] = csc[s] = cx[s] = cz[s] = ce[s] = (float)lane; }
-    } else {
-    tile_cols(tiles + TB_G * TILE, lane, cg);
-    tile_cols(tiles + TB_DQ * TILE, lane, cdq);
-    tile_cols(tiles + TB_SC * TILE, lane, csc);
-    tile_cols(tiles + TB_X * TILE, lane, cx);
-    tile_cols(tiles + TB_Z * TILE, lane, cz);
-    tile_cols(tiles + TB_E * TILE, lane, ce);
-    }
+    StatCols c;
+    dst16_stat_cols(tiles, st, r, FUSED_ABL(64), part, lane, c);
     if (FUSED_ABL(32)) {
-        asm volatile("" :: "v"(cg[0]), "v"(cdq[1]), "v"(csc[2]), "v"(cx[3]), "v"(cz[0]), "v"(ce[1]));
+        asm volatile("" :: "v"(c.g[0]), "v"(c.dq[1]), "v"(c.sc[2]), "v"(c.x[3]), "v"(c.z[0]), "v"(c.e[1]));
         return;
     }
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(cg[s], cx[s], acc[0], 0, 0, 0);    // T0 g x^T
-        acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(cg[s], cz[s], acc[1], 0, 0, 0);    // T1 g Z^T
-        acc[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(cg[s], ce[s], acc[2], 0, 0, 0);    // T2 g e^T
-        acc[3] = __builtin_amdgcn_mfma_f32_16x16x4f32(cdq[s], cx[s], acc[3], 0, 0, 0);   // T3 dq' x^T
-        acc[4] = __builtin_amdgcn_mfma_f32_16x16x4f32(cdq[s], ce[s], acc[4], 0, 0, 0);   // T4 dq' e^T
-        acc[5] = __builtin_amdgcn_mfma_f32_16x16x4f32(csc[s], cx[s], acc[5], 0, 0, 0);   // T5 sc x^T
-        acc[6] = __builtin_amdgcn_mfma_f32_16x16x4f32(csc[s], ce[s], acc[6], 0, 0, 0);   // T6 sc e^T
-    }
+    stats_accumulate(c, acc, nullptr, lane);
 }
 
 __global__ __launch_bounds__(FT) void fused_bwd16_kernel(BwdLaunch16 A) {
@@ -1127,34 +1284,18 @@ __global__ __launch_bounds__(FT) void fused_bwd16_kernel(BwdLaunch16 A) {
     __shared__ float merge_lds[FW * 20];
     __shared__ float tiles_[FW * TB_N * TILE];       // 6.5 KB per wavefront; reused for the tile reduction at the end
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, part = lane & 3;
-    for (int j = 0; j < A.n_jobs; ++j) {
-        const BwdJob16& J = A.job[j];
-        BwdW16& W = Ws_[j];
-        if (wave == 0) matB_store(W.BWvT, matB_t(J.p.Wv, 16, lane), lane);
-        if (wave == 1) matB_store(W.BPq, matB(J.D + OFF_PQ, 16, lane), lane);
-        if (wave == 2) matB_store(W.BWsT, matB_t(J.p.Ws, 16, lane), lane);
-        if (wave == 3) matB_store(W.BPqT, matB_t(J.D + OFF_PQ, 16, lane), lane);
-        if (tid < 16) {
-            W.pq0[tid] = J.D[OFF_PQ0 + tid];
-            W.Pt[tid] = J.D[OFF_PT + tid];
-            W.Pb[tid] = J.D[OFF_PB + tid];
-            W.bv[tid] = J.p.bv[tid];
-            W.we[tid] = J.p.we[tid];
-        }
-        if (tid == 0) W.pt0 = J.D[OFF_PT0];
-    }
+    for (int j = 0; j < A.n_jobs; ++j) stage_weights<false, true>(Ws_[j], A.job[j].D, A.job[j].p, nullptr, nullptr, tid);
     __syncthreads();
     float* tiles = tiles_ + wave * TB_N * TILE;
-    const int px = blockIdx.x % NP, bi = blockIdx.x / NP, gp = gridDim.x / NP;
-    const int gw = bi * FW + wave;
+    const BlockPart B = block_part();
     for (int j = 0; j < A.n_jobs; ++j) {
         const BwdJob16& J = A.job[j];
-        const PartTiers P = J.s.part[px];
+        const PartTiers P = J.s.part[B.px];
         f32x4m acc[STAT_TILES];
 #pragma unroll
         for (int i = 0; i < STAT_TILES; ++i) acc[i] = splat4(0.0f);
         const RowSlot none = empty_slot();
-        for (int k = bi; k < P.n_block; k += gp) {
+        for (int k = B.bi; k < P.n_block; k += B.gp) {
             const RowSlot r = block_slot<4>(J.s, P.row0 + k, tid);
             BwdRow rd;
             bwd16_fetch(J, r, part, rd);
@@ -1162,7 +1303,7 @@ __global__ __launch_bounds__(FT) void fused_bwd16_kernel(BwdLaunch16 A) {
             RowSlot rn;
             bwd16_row(J, Ws_[j], P, r, rd, en, -1, rn, part, lane, merge_lds, tiles, acc);
         }
-        WaveList wl = wave_list(J.s, px, gw);
+        WaveList wl = wave_list(J.s, B.px, B.gw);
         for (int c0 = 0; c0 < wl.L; c0 += 64) {
             wave_list_chunk(wl, c0, lane);
             int it = wave_list_get(wl, 0);
@@ -1178,21 +1319,10 @@ __global__ __launch_bounds__(FT) void fused_bwd16_kernel(BwdLaunch16 A) {
                 it = itn;
             }
         }
-        // the workgroup's partial statistics: the 16 wavefronts' tiles summed in wave order, one tile at a time
+        // the workgroup's partial statistics: the wavefronts' tiles summed in wave order, one tile at a time
         __syncthreads();
-        float* red = tiles_;                   // [FW][256]
 #pragma unroll
-        for (int i = 0; i < STAT_TILES; ++i) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) red[wave * 256 + ((lane >> 4) * 4 + q) * 16 + (lane & 15)] = acc[i][q];
-            __syncthreads();
-            if (tid < 256) {
-                float v = 0.0f;
-                for (int w = 0; w < FW; ++w) v += red[w * 256 + tid];
-                J.stats[(size_t)blockIdx.x * STAT_FLOATS + i * 256 + tid] = v;
-            }
-            __syncthreads();
-        }
+        for (int i = 0; i < STAT_TILES; ++i) stats_tile_store(acc[i], i, tiles_, J.stats, tid);
     }
 }
 
@@ -1201,9 +1331,9 @@ __global__ __launch_bounds__(FT) void fused_bwd16_kernel(BwdLaunch16 A) {
 // kernel.  The two launches it replaces (fused_fwd16_kernel with the head, fused_bwd16_kernel job CONV_3V) walk the same
 // rows, the same entries and the same source rows through the same wavefront lists, and the backward item of a row
 // needs only what the forward item has just produced or loaded: x, q', t, Zn, {un, rowmax, rinv, S} and the masked head
-// gradient stay in registers, so Z, aux and d3v of CONV_3V are neither written nor read and h2v is read once.  Every
-// operation of fwd16_row and bwd16_row is kept, in its order, per row; the items per wavefront are the same lists:
-// the results are the bits of the two launches.
+// gradient stay in registers, so Z, aux and d3v of CONV_3V are neither written nor read and h2v is read once.  l3_row
+// calls the halves that fwd16_row and bwd16_row are made of, in their order, and the kernel walks the same lists with
+// fused_fwd16_kernel's walk: the results are the bits of the two launches because it is the same code.
 // ====================================================================================================
 struct L3Job {
     FwdJob16 f;                        // head == 2 (h, Z, aux unused)
@@ -1217,17 +1347,9 @@ struct L3W {           // B operands of both halves, small vectors
     float pt0, fcb;
 };
 
-// The statistics tiles T2 .. T6 of a wavefront rest in its LDS region between items (20 VGPRs the two sweeps need):
-// each lane reads and writes its own float4, the sums and their order are those of register accumulators.
+// The statistics tiles T2 .. T6 of a wavefront rest in its LDS region between items (20 VGPRs the two sweeps need)
 constexpr int L3_REG_TILES = 2;
 constexpr int L3_PARK = (STAT_TILES - L3_REG_TILES) * 256;      // floats per wavefront
-__device__ __forceinline__ f32x4m park_get(const float* park, int i, int lane) {
-    const float4 v = lds4(park + ((i - L3_REG_TILES) * 64 + lane) * 4);
-    return (f32x4m){v.x, v.y, v.z, v.w};
-}
-__device__ __forceinline__ void park_put(float* park, int i, int lane, const f32x4m& a) {
-    *reinterpret_cast<float4*>(park + ((i - L3_REG_TILES) * 64 + lane) * 4) = make_float4(a[0], a[1], a[2], a[3]);
-}
 
 // Tiles as in bwd16_row.  The forward half keeps x in tile X, passes q' and Zn through tile Z and its output through SC.
 // The item pipeline is fwd16_row's (two deep); the backward half's first entries are the forward's, kept in registers,
@@ -1242,11 +1364,7 @@ __device__ __forceinline__ void l3_row(const L3Job& JJ, const L3W& W, const Part
     const int2 en0 = en;      // the second sweep starts from the same entries
     Gather4 gt;
     gather4_issue(J.s, J.x_src, r, n_mine, 0, part, en, gt);      // the first gathers leave before anything else
-    nx.r = slot_make(q1);
-    nx.xd = ld4(J.x_dst + (size_t)max(nx.r.row, 0) * 16 + 4 * part);
-    nx.en = first_entries_any<4>(J.s, nx.r, part);
-    nx.lrow = J.perm[max(nx.r.row, 0)];
-    nx.q = item_request<4>(J.s, P, max(it2, 0), lane);
+    fwd16_prefetch(J, P, q1, it2, nx, part, lane);
     const float y = J.labels[max(r.row, 0)];                      // land during the sweep
     const float wn = J.inv_n[max(r.row, 0)] * J.inv_batch;
     // a quad without a row carries row 0's prefetch: zeros, as the backward's own fetch gave it
@@ -1254,149 +1372,51 @@ __device__ __forceinline__ void l3_row(const L3Job& JJ, const L3W& W, const Part
     const int xpos = (xd.x > 0.0f ? 1 : 0) | (xd.y > 0.0f ? 2 : 0) | (xd.z > 0.0f ? 4 : 0) | (xd.w > 0.0f ? 8 : 0);
     float4 qp;
     float t;
-    {
-        float ax_[4];
-        tile_put(tiles + TB_X * TILE, xd, lane);
-        tile_rows(tiles + TB_X * TILE, lane, ax_);
-        tile_put_result(tiles + TB_Z * TILE, mat_apply(ax_, matB_lds(W.BPq, lane), splat4(W.pq0[lane & 15])), lane);
-        qp = tile_get(tiles + TB_Z * TILE, lane);
-        t = quad_sum(dot4(lds4(W.Pt + 4 * part), xd)) + W.pt0;
-    }
-    SoftState st;
-    st.Z = f4zero(); st.m = NEG_BIG; st.L = 0.0f; st.u = 0.0f;
-    for (int k0 = 0;;) {
-        fwd16_step(gt, k0, n_mine, qp, t, st);
-        k0 += 4;
-        if (!__any(k0 < n_mine)) break;
-        gather4_issue(J.s, J.x_src, r, n_mine, k0, part, en, gt);
-    }
-    // the next item's data is taken where the sweep has drained the memory pipe (see fwd16_row)
-    asm volatile("" : "+v"(nx.xd.x), "+v"(nx.xd.y), "+v"(nx.xd.z), "+v"(nx.xd.w), "+v"(nx.en.x), "+v"(nx.en.y),
-                      "+v"(nx.lrow), "+v"(nx.q.sb), "+v"(nx.q.se));
+    row16_project(W, tiles + TB_X * TILE, tiles + TB_Z * TILE, xd, false, part, lane, qp, t);
+    SoftState st = fwd16_sweep(J.s, J.x_src, r, n_mine, part, en, gt, qp, t);
+    fwd16_take(nx);
     // second sweep over the same row, from the same first entries: its first gathers travel during the forward epilogue
     en = en0;
     gather4_issue(J.s, J.x_src, r, n_mine, 0, part, en, gt);
-    if (r.mode >= 1) soft_merge(st, r.mode);
-    if (r.mode == 3) soft_merge_block<1>(st, merge_lds, lane, part);
-    // forward epilogue: o = Wv Zn + Ws x + (bs + S bv + un we), fc, BCEWithLogits
-    const float rinv = 1.0f / (st.L + 1e-16f);
-    const float S = st.L * rinv, un = st.u * rinv;
+    fwd16_merge<1>(st, r.mode, merge_lds, lane, part);
+    const FwdOut f = fwd16_epilogue(W, tiles + TB_X * TILE, tiles + TB_Z * TILE, tiles + TB_SC * TILE, st, false, part, lane);
     const float m = st.L > 0.0f ? st.m : 0.0f;
-    const float4 zn = f4scale(st.Z, rinv);
-    float4 o;
-    {
-        float ax_[4], az_[4];
-        tile_rows(tiles + TB_X * TILE, lane, ax_);
-        tile_put(tiles + TB_Z * TILE, zn, lane);
-        tile_rows(tiles + TB_Z * TILE, lane, az_);
-        tile_put_result(tiles + TB_SC * TILE,
-                        mat_apply(ax_, matB_lds(W.BWs, lane), mat_apply(az_, matB_lds(W.BWv, lane), splat4(0.0f))), lane);
-        o = tile_get(tiles + TB_SC * TILE, lane);
-    }
-    o = f4add(o, lds4(W.bs + 4 * part));
-    fma4(S, lds4(W.bv + 4 * part), o);
-    fma4(un, lds4(W.we + 4 * part), o);
-    const float4 hv = make_float4(fmaxf(o.x, 0.0f), fmaxf(o.y, 0.0f), fmaxf(o.z, 0.0f), fmaxf(o.w, 0.0f));
+    // fc, BCEWithLogits
     const float4 fw = lds4(W.fcw + 4 * part);
-    const float z = quad_sum(dot4(hv, fw)) + W.fcb;
+    const float z = quad_sum(dot4(f.hv, fw)) + W.fcb;
     float4 g = f4zero();
     if (have) {        // BCEWithLogitsLoss, mean per instance / batch: linear_program_experiment.py:41,139-140.  Every quad of a
                        // shared row holds the row's state: each computes the row's head gradient, the writer counts it
         const float e = expf(-fabsf(z));
         const float sig = z >= 0.0f ? 1.0f / (1.0f + e) : e / (1.0f + e);
         const float dz = wn * (sig - y);
-        g = make_float4(hv.x > 0.0f ? dz * fw.x : 0.0f, hv.y > 0.0f ? dz * fw.y : 0.0f,
-                        hv.z > 0.0f ? dz * fw.z : 0.0f, hv.w > 0.0f ? dz * fw.w : 0.0f);
+        g = make_float4(f.hv.x > 0.0f ? dz * fw.x : 0.0f, f.hv.y > 0.0f ? dz * fw.y : 0.0f,
+                        f.hv.z > 0.0f ? dz * fw.z : 0.0f, f.hv.w > 0.0f ? dz * fw.w : 0.0f);
         if (writer) {
-            fma4(dz, hv, ha.w);
+            fma4(dz, f.hv, ha.w);
             if (part == 0) {
                 ha.b += dz;
                 ha.l += wn * (fmaxf(z, 0.0f) - z * y + log1pf(e));
             }
         }
     }
-
-    // backward half (bwd16_row with dh_a = g, dh_b = none, no mask array); the first entries are the forward's
-    float4 gv;
-    float ge, cc;
-    {
-        g = f4add(g, f4zero());
-        const float4 Zn = have ? zn : f4zero();
-        const float Sx = have ? S : 0.0f, ux = have ? un : 0.0f;
-        float ag_[4];
-        tile_put(tiles + TB_G * TILE, g, lane);
-        tile_put(tiles + TB_Z * TILE, Zn, lane);
-        tile_put(tiles + TB_E * TILE, (have && part == 0) ? make_float4(1.0f, Sx, ux, 0.0f) : f4zero(), lane);
-        tile_rows(tiles + TB_G * TILE, lane, ag_);
-        tile_put_result(tiles + TB_DQ * TILE, mat_apply(ag_, matB_lds(W.BWvT, lane), splat4(0.0f)), lane);
-        gv = tile_get(tiles + TB_DQ * TILE, lane);
-        ge = quad_sum(dot4(g, lds4(W.we + 4 * part)));
-        const float gb = quad_sum(dot4(g, lds4(W.bv + 4 * part)));
-        const float Dn = quad_sum(dot4(gv, Zn)) + gb * Sx + ge * ux;
-        cc = gb - Dn;
-    }
-    const float mb = have ? m : 0.0f, rb = have ? rinv : 0.0f;
-    BwdState bs;
-    bs.dq = f4zero(); bs.ds = 0.0f; bs.dt = 0.0f;
-    for (int k0 = 0;;) {
-        bwd16_step(gt, k0, n_mine, qp, gv, t, mb, rb, ge, cc, bs);
-        k0 += 4;
-        if (!__any(k0 < n_mine)) break;
-        gather4_issue(J.s, J.x_src, r, n_mine, k0, part, en, gt);
-    }
+    // backward half (bwd16_row with dh_a = g, dh_b = none, no mask array); the first entries are the forward's.
+    // g + 0 is bwd16_row's dh_a + dh_b: it turns a -0.0 into +0.0, and the bits downstream depend on it
+    g = f4add(g, f4zero());
+    const DstProj p = dst16_project(W, tiles, g, have ? f.zn : f4zero(), have ? f.S : 0.0f, have ? f.un : 0.0f, have, false,
+                                    part, lane);
+    const float mb = have ? m : 0.0f, rb = have ? f.rinv : 0.0f;
+    BwdState bs = dst16_sweep(J.s, J.x_src, r, n_mine, part, en, gt, qp, p, t, mb, rb);
     // the item's stores leave behind its last sweep: no gather wait covers their acknowledgements
     if (writer) {
         if (part == 0) J.logits[lrow] = z;
-        rec_store(JJ.rec, r.row, part, qp, gv, t, mb, rb, ge, cc);
+        rec_store(JJ.rec, r.row, part, qp, p.gv, t, mb, rb, p.ge, p.cc);
     }
-    if (r.mode >= 1) {
-        bs.ds = shared_sum4(bs.ds, r.mode);
-        bs.dt = shared_sum4(bs.dt, r.mode);
-        bs.dq.x = shared_sum4(bs.dq.x, r.mode); bs.dq.y = shared_sum4(bs.dq.y, r.mode);
-        bs.dq.z = shared_sum4(bs.dq.z, r.mode); bs.dq.w = shared_sum4(bs.dq.w, r.mode);
-    }
-    if (r.mode == 3) {
-        bwd_merge_block<1>(bs, merge_lds, lane, part);
-        if (threadIdx.x >= 64) return;      // wave-uniform: the row's outputs and statistics belong to wavefront 0
-    }
-    tile_put(tiles + TB_DQ * TILE, bs.dq, lane);
-    {
-        const float4 v = dx_dst_row(W, tiles, bs, true, xpos, part, lane);
-        if (writer) *reinterpret_cast<float4*>(JJ.dx_dst + (size_t)r.row * 16 + 4 * part) = v;
-    }
-    if (r.mode >= 1 && !writer) {
-        const float4 z4 = f4zero();
-        tile_put(tiles + TB_G * TILE, z4, lane);
-        tile_put(tiles + TB_X * TILE, z4, lane);
-        tile_put(tiles + TB_Z * TILE, z4, lane);
-        tile_put(tiles + TB_E * TILE, z4, lane);
-        tile_put(tiles + TB_DQ * TILE, z4, lane);
-    }
-    tile_put(tiles + TB_SC * TILE, (writer && part == 0) ? make_float4(bs.ds, bs.dt, 0.0f, 0.0f) : f4zero(), lane);
-    float cg[4], cdq[4], csc[4], cx[4], cz[4], ce[4];
-    tile_cols(tiles + TB_G * TILE, lane, cg);
-    tile_cols(tiles + TB_DQ * TILE, lane, cdq);
-    tile_cols(tiles + TB_SC * TILE, lane, csc);
-    tile_cols(tiles + TB_X * TILE, lane, cx);
-    tile_cols(tiles + TB_Z * TILE, lane, cz);
-    tile_cols(tiles + TB_E * TILE, lane, ce);
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-        acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(cg[s], cx[s], acc[0], 0, 0, 0);    // T0 g x^T
-        acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(cg[s], cz[s], acc[1], 0, 0, 0);    // T1 g Z^T
-    }
-#define MLLP_L3_PARKED(I, A_, B_)                                                          \
-    {                                                                                      \
-        f32x4m a_ = park_get(park, I, lane);                                               \
-        for (int s = 0; s < 4; ++s) a_ = __builtin_amdgcn_mfma_f32_16x16x4f32(A_[s], B_[s], a_, 0, 0, 0); \
-        park_put(park, I, lane, a_);                                                       \
-    }
-    MLLP_L3_PARKED(2, cg, ce)      // T2 g e^T
-    MLLP_L3_PARKED(3, cdq, cx)     // T3 dq' x^T
-    MLLP_L3_PARKED(4, cdq, ce)     // T4 dq' e^T
-    MLLP_L3_PARKED(5, csc, cx)     // T5 sc x^T
-    MLLP_L3_PARKED(6, csc, ce)     // T6 sc e^T
-#undef MLLP_L3_PARKED
+    if (!dst16_merge<1>(bs, r.mode, merge_lds, tiles, lane, part)) return;
+    dst16_dx(W, tiles, bs, r, JJ.dx_dst, true, xpos, part, lane);
+    StatCols c;
+    dst16_stat_cols(tiles, bs, r, false, part, lane, c);
+    stats_accumulate(c, acc, park, lane);
 }
 
 __global__ __launch_bounds__(FT) void fused_l3_kernel(L3Job JJ) {
@@ -1407,25 +1427,7 @@ __global__ __launch_bounds__(FT) void fused_l3_kernel(L3Job JJ) {
     __shared__ __attribute__((aligned(16))) float park_[FW * L3_PARK];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, part = lane & 3;
     const FwdJob16& J = JJ.f;
-    if (wave == 0) matB_store(W.BPq, matB(J.D + OFF_PQ, 16, lane), lane);
-    if (wave == 1) matB_store(W.BWv, matB(J.p.Wv, 16, lane), lane);
-    if (wave == 2) matB_store(W.BWs, matB(J.p.Ws, 16, lane), lane);
-    if (wave == 3) matB_store(W.BWvT, matB_t(J.p.Wv, 16, lane), lane);
-    if (wave == 4) matB_store(W.BWsT, matB_t(J.p.Ws, 16, lane), lane);
-    if (wave == 5) matB_store(W.BPqT, matB_t(J.D + OFF_PQ, 16, lane), lane);
-    if (tid < 16) {
-        W.pq0[tid] = J.D[OFF_PQ0 + tid];
-        W.Pt[tid] = J.D[OFF_PT + tid];
-        W.Pb[tid] = J.D[OFF_PB + tid];
-        W.bv[tid] = J.p.bv[tid];
-        W.we[tid] = J.p.we[tid];
-        W.bs[tid] = J.p.bs[tid];
-        W.fcw[tid] = J.fcw[tid];
-    }
-    if (tid == 0) {
-        W.pt0 = J.D[OFF_PT0];
-        W.fcb = J.fcb[0];
-    }
+    stage_weights<true, true>(W, J.D, J.p, J.fcw, J.fcb, tid);
     __syncthreads();
     float* tiles = tiles_ + wave * TB_N * TILE;
     HeadAcc ha;
@@ -1435,55 +1437,19 @@ __global__ __launch_bounds__(FT) void fused_l3_kernel(L3Job JJ) {
 #pragma unroll
     for (int i = 0; i < L3_REG_TILES; ++i) acc[i] = splat4(0.0f);
 #pragma unroll
-    for (int i = L3_REG_TILES; i < STAT_TILES; ++i) park_put(park, i, lane, splat4(0.0f));
-    const int px = blockIdx.x % NP, bi = blockIdx.x / NP, gp = gridDim.x / NP;
-    const int gw = bi * FW + wave;
-    const PartTiers P = J.s.part[px];
-    const RowSlot none = empty_slot();
-    for (int k = bi; k < P.n_block; k += gp) {
-        const RowSlot r = block_slot<4>(J.s, P.row0 + k, tid);
-        const float4 xd = ld4(J.x_dst + (size_t)r.row * 16 + 4 * part);
-        int2 en = first_entries<4>(J.s, r, part);
-        const int lrow = J.perm[r.row];
-        FwdNext nx;
-        l3_row(JJ, W, P, r, xd, en, lrow, empty_request(), -1, nx, part, lane, merge_lds, tiles, park, ha, acc);
-    }
-    WaveList wl = wave_list(J.s, px, gw);
-    for (int c0 = 0; c0 < wl.L; c0 += 64) {
-        wave_list_chunk(wl, c0, lane);
-        int it = wave_list_get(wl, 0), it1 = wave_list_get(wl, 1);
-        RowSlot r = it >= 0 ? item_slot<4>(J.s, P, it, lane) : none;
-        float4 xd = r.row >= 0 ? ld4(J.x_dst + (size_t)r.row * 16 + 4 * part) : f4zero();
-        int2 en = first_entries<4>(J.s, r, part);
-        int lrow = r.row >= 0 ? J.perm[r.row] : 0;
-        SlotReq q1 = item_request<4>(J.s, P, max(it1, 0), lane);
-        if (it1 < 0) q1.row = -1;
-        // cold start: everything requested above is waited for here (see fused_fwd16_kernel)
-        asm volatile("" : "+v"(xd.x), "+v"(xd.y), "+v"(xd.z), "+v"(xd.w), "+v"(en.x), "+v"(en.y), "+v"(lrow),
-                          "+v"(q1.sb), "+v"(q1.se));
-        for (int k = 0; it >= 0; ++k) {
-            const int it2 = wave_list_get(wl, k + 2);
-            FwdNext nx;
-            l3_row(JJ, W, P, r, xd, en, lrow, q1, it2, nx, part, lane, merge_lds, tiles, park, ha, acc);
-            r = nx.r; xd = nx.xd; en = nx.en; lrow = nx.lrow; q1 = nx.q;
-            it = it1; it1 = it2;
-        }
-    }
+    for (int i = L3_REG_TILES; i < STAT_TILES; ++i) park_put(park, i - L3_REG_TILES, lane, splat4(0.0f));
+    const BlockPart B = block_part();
+    const PartTiers P = J.s.part[B.px];
+    walk_two_deep(J, P, B, tid, [&](const RowSlot& r, const float4& xd, int2& en, int lrow, const SlotReq& q1, int it2,
+                                    FwdNext& nx) __attribute__((always_inline)) {
+        l3_row(JJ, W, P, r, xd, en, lrow, q1, it2, nx, part, lane, merge_lds, tiles, park, ha, acc);
+    });
     // the workgroup's partial statistics, as fused_bwd16_kernel writes them; then the head partials
     __syncthreads();
-    float* red = tiles_;                   // [FW][256]
 #pragma unroll
     for (int i = 0; i < STAT_TILES; ++i) {
-        const f32x4m a = i < L3_REG_TILES ? acc[i < L3_REG_TILES ? i : 0] : park_get(park, max(i, L3_REG_TILES), lane);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) red[wave * 256 + ((lane >> 4) * 4 + q) * 16 + (lane & 15)] = a[q];
-        __syncthreads();
-        if (tid < 256) {
-            float v = 0.0f;
-            for (int w = 0; w < FW; ++w) v += red[w * 256 + tid];
-            JJ.stats[(size_t)blockIdx.x * STAT_FLOATS + i * 256 + tid] = v;
-        }
-        __syncthreads();
+        const f32x4m a = i < L3_REG_TILES ? acc[min(i, L3_REG_TILES - 1)] : park_get(park, max(i - L3_REG_TILES, 0), lane);
+        stats_tile_store(a, i, tiles_, JJ.stats, tid);
     }
     head_partials_store<FW>(ha, head_lds, J.head_part, tid);
 }
@@ -1574,21 +1540,20 @@ __device__ __forceinline__ void src16_row(const SrcJob16& J, const RowSlot& r, f
 
 __global__ __launch_bounds__(FT) void fused_src16_kernel(SrcLaunch16 A) {
     __shared__ float merge_lds[FW * 20];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, part = lane & 3;
-    const int px = blockIdx.x % NP, bi = blockIdx.x / NP, gp = gridDim.x / NP;
-    const int gw = bi * FW + wave;
+    const int tid = threadIdx.x, lane = tid & 63, part = lane & 3;
+    const BlockPart B = block_part();
     for (int j = 0; j < A.n_jobs; ++j) {
         const SrcJob16& J = A.job[j];
-        const PartTiers P = J.s.part[px];
+        const PartTiers P = J.s.part[B.px];
         const RowSlot none = empty_slot();
-        for (int k = bi; k < P.n_block; k += gp) {
+        for (int k = B.bi; k < P.n_block; k += B.gp) {
             const RowSlot r = block_slot<4>(J.s, P.row0 + k, tid);
             float4 xj = ld4(J.x + (size_t)r.row * 16 + 4 * part);
             int2 en = first_entries<2>(J.s, r, part);
             RowSlot rn;
             src16_row(J, r, xj, en, empty_request(), rn, part, lane, merge_lds);
         }
-        WaveList wl = wave_list(J.s, px, gw);
+        WaveList wl = wave_list(J.s, B.px, B.gw);
         for (int c0 = 0; c0 < wl.L; c0 += 64) {
             wave_list_chunk(wl, c0, lane);
             int it = wave_list_get(wl, 0);
@@ -1784,8 +1749,7 @@ __global__ __launch_bounds__(FT) void fused_bwd1_kernel(BwdLaunch1 A) {
     }
     __syncthreads();
     float* tiles = tiles_ + wave * TILE1;
-    const int px = blockIdx.x % NP, bi = blockIdx.x / NP, gp = gridDim.x / NP;
-    const int gw = bi * FW + wave;
+    const BlockPart B = block_part();
 #ifdef MLLP_TIMING_BUILD
     unsigned long long stamp_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long stamp_last = __builtin_amdgcn_s_memtime();
@@ -1796,12 +1760,12 @@ __global__ __launch_bounds__(FT) void fused_bwd1_kernel(BwdLaunch1 A) {
 #endif
     for (int j = 0; j < A.n_jobs; ++j) {
         const BwdJob1& J = A.job[j];
-        const PartTiers P = J.s.part[px];
+        const PartTiers P = J.s.part[B.px];
         f32x4m accT = splat4(0.0f);
         float accS[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-        for (int k = bi; k < P.n_block; k += gp)
+        for (int k = B.bi; k < P.n_block; k += B.gp)
             bwd1_row(J, Ws_[j], block_slot<1>(J.s, P.row0 + k, tid), lane, merge_lds, tiles, accT, accS STAMP_ARGS1);
-        WaveList wl = wave_list(J.s, px, gw);
+        WaveList wl = wave_list(J.s, B.px, B.gw);
         for (int c0 = 0; c0 < wl.L; c0 += 64) {
             wave_list_chunk(wl, c0, lane);
             int it = wave_list_get(wl, 0);

@@ -356,6 +356,23 @@ def tier_rows(inst, c=None):
     return out
 
 
+# The tier cases of the fused layer-3 launch (tests/test_fused_l3_pair.py; tools/fused_dump.py runs them too):
+# name -> (variable-side degrees that C's rows bring, width of C, the tier of the 16-channel lists they must reach)
+L3_TIER_CASES = {
+    "base": ([0, 1, 4, 5, 16] * 7 + [2, 3], 40, "base"),             # 37 rows: the last base item holds 5 + |B's columns| % 16
+    "group": ([17, 64, 33, 18, 17, 64, 0, 5], 80, "group"),           # six group rows: one full item of four and a partial one
+    "wave": ([65, 1024, 640, 0, 1, 16], 1100, "wave"),
+    "block": ([1025, 6145, 3, 0, 17, 65], 6200, "block"),
+}
+L3_B_DEGREES, L3_B_WIDTH = [2, 3, 1, 0, 2], 9                         # the constraint block: base-tier degrees on both sides
+
+
+def l3_tier_instance(name):
+    degs, width, _ = L3_TIER_CASES[name]
+    rng = np.random.default_rng(100 + sorted(L3_TIER_CASES).index(name))
+    return two_sided(block_of(L3_B_DEGREES, L3_B_WIDTH, rng), block_of(degs, width, rng), rng, f"l3{name}")
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # 4. the oracle's decomposition in a chosen floating-point type
 # ---------------------------------------------------------------------------------------------------------------------

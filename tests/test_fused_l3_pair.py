@@ -22,9 +22,12 @@ RTOL_ACT / RTOL_GRAD:
 The yardstick exempts no tensor on any of the four inputs (max_exempt = 0).
 
 No comparison with `forward` + `backward(dlogits)` bit for bit: the BCE gradient the library used is not readable without
-a new export (d3v is no longer stored, and a dlogits recomputed in torch differs from the kernel's expf by an ulp), so
-the equality with the two launches this one replaces rests on the by-hand comparison of `bench.py --dump-outputs`
-between the parent and this kernel (profiles/fused_l3_pair.md: loss, logits and parameters identical after 25 steps).
+a new export (d3v is no longer stored, and a dlogits recomputed in torch differs from the kernel's expf by an ulp).  The
+equality with the two launches this one replaces rests on the code: every half of a row (forward projection, sweep,
+merges, epilogue; destination-major projection, sweep, merge, tail, statistics) is one function that fwd16_row, bwd16_row
+and l3_row all call, and fused_l3_kernel uses fused_fwd16_kernel's item walk.  The by-hand comparisons against the parent
+builds are recorded in profiles/fused_l3_pair.md (bench.py --dump-outputs: loss, logits and parameters identical after 25
+steps) and profiles/fused_shared_rows.md (the same, and every output of tools/fused_dump.py).
 """
 import numpy as np
 import pytest
@@ -39,20 +42,8 @@ from test_input_grads import oracle_input_grads
 
 gpu = pytest.mark.gpu
 
-# name -> (variable-side degrees that C's rows bring, width of C, the tier of the 16-channel lists they must reach)
-CASES = {
-    "base": ([0, 1, 4, 5, 16] * 7 + [2, 3], 40, "base"),             # 37 rows: the last base item holds 5 + |B's columns| % 16
-    "group": ([17, 64, 33, 18, 17, 64, 0, 5], 80, "group"),           # six group rows: one full item of four and a partial one
-    "wave": ([65, 1024, 640, 0, 1, 16], 1100, "wave"),
-    "block": ([1025, 6145, 3, 0, 17, 65], 6200, "block"),
-}
-B_DEGREES, B_WIDTH = [2, 3, 1, 0, 2], 9                               # the constraint block: base-tier degrees on both sides
-
-
-def _instance(name):
-    degs, width, _ = CASES[name]
-    rng = np.random.default_rng(100 + sorted(CASES).index(name))
-    return fc.two_sided(fc.block_of(B_DEGREES, B_WIDTH, rng), fc.block_of(degs, width, rng), rng, f"l3{name}")
+CASES = fc.L3_TIER_CASES
+_instance = fc.l3_tier_instance
 
 
 def _assert_reach(name, inst, cus):
