@@ -18,7 +18,7 @@
  *     stream); no entry point synchronises except mllp_graph_create_* / mllp_graph_export.
  *   - all launch functions are hipGraph-capturable (no malloc/free/sync inside).
  *   - the sparsity pattern of a mllp_graph_t is immutable after creation; its values change only through
- *     mllp_graph_set_values / mllp_graph_scale_values / mllp_graph_normalize.  An internal scratch buffer is used by
+ *     mllp_graph_set_values / mllp_graph_scale_values / mllp_graph_normalize / mllp_graph_plant_basis.  An internal scratch buffer is used by
  *     rows that are split over several workgroups: calls on ONE graph must be stream-ordered.
  *   - feature width is fixed at 16 (reference linear_program_methods.py:206-211), fp32 everywhere.
  *   - there is NO CPU fallback: without a HIP device every launch function fails with MLLP_EHIP.
@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MLLP_ABI_VERSION 6 /* 2: streamed SpMM copy, device-built tiled copies, mllp_gnn_train_step, mllp_graph_invalidate_inputs; 3: streamed copies of the attention sweeps (mllp_graph_*_stream_copy); 4: input gradients (mllp_gnn_backward_inputs); 5: AngleModel input gradients (mllp_angle_backward_inputs); 6: the predicted basis (mllp_topm_select, mllp_topm_select_dense); mllp_graph_set_values, _set_values_bytes and _scale_values arrived after 6 WITHOUT a bump: they are additions only (no existing export changed signature or meaning), so every caller built against 6 stays valid; a caller that needs them checks for the symbols; mllp_graph_normalize and mllp_normalize_row_tier likewise */
+#define MLLP_ABI_VERSION 6 /* 2: streamed SpMM copy, device-built tiled copies, mllp_gnn_train_step, mllp_graph_invalidate_inputs; 3: streamed copies of the attention sweeps (mllp_graph_*_stream_copy); 4: input gradients (mllp_gnn_backward_inputs); 5: AngleModel input gradients (mllp_angle_backward_inputs); 6: the predicted basis (mllp_topm_select, mllp_topm_select_dense); mllp_graph_set_values, _set_values_bytes and _scale_values arrived after 6 WITHOUT a bump: they are additions only (no existing export changed signature or meaning), so every caller built against 6 stays valid; a caller that needs them checks for the symbols; mllp_graph_normalize and mllp_normalize_row_tier likewise; mllp_graph_plant_basis, mllp_lp_certificate and mllp_lp_certificate_scratch_bytes likewise */
 #define MLLP_FEAT 16
 #define MLLP_NUM_PARAMS 4721 /* GNNModel.state_dict(), SURVEY.md appendix A.2 */
 
@@ -181,6 +181,54 @@ int mllp_graph_normalize(mllp_graph_t* g, float* d_x1, float* d_x2, float rhs_ca
                          float* d_obj_scale, void* stream);
 int mllp_normalize_row_tier(int64_t row_nnz, int* tier);
 
+/* Planted-basis LPs: a labelled training batch made where the batch lives (mllp_amd/csrc/planted.hip).  The LP is that of
+ * the normalized tensors, min c'x, Ax = b, x >= 0 with slack columns as ordinary columns; x1 = c, x2 = b, labels = 1 on
+ * the m columns of the basis.  Given one pivot per row, a primal point, a dual point and dual slacks, the resident batch
+ * is rewritten so that the pivots' columns are its unique optimal basis, in fp32:
+ *   basic_j = 1 iff j is some row's pivot.
+ *   row i, over its entries in CSR order:  off_i = sum |a_ij| and rest_i = sum a_ij xstar_j over the basic j != pivot[i];
+ *              the pivot entry becomes copysign(dominance * off_i + floor, its old value);
+ *              b_i = fma(new pivot value, xstar[pivot[i]], rest_i).  No other value changes by a bit.
+ *   column j, over CSR(A^T) with the new values:  c_j = sum_i a_ij ystar_i + (basic_j ? 0 : slack_j);  labels_j = basic_j.
+ * The basis matrix is strictly row-diagonally dominant under the pivot ordering, hence nonsingular with
+ * ||B^-1||_inf <= 1 / min_i(|d_i| - off_i); with xstar > 0 on the basic and slack > 0 on the nonbasic columns the point
+ * (xstar * basic, ystar) is primal and dual feasible and strictly complementary, so the basis is the unique optimum.
+ * Nothing inspects xstar, ystar or slack: their signs are the caller's business (mllp_lp_certificate reports on them).
+ *   d_pivot [M] int32 : the global column id of every row's pivot; the entry (i, pivot[i]) must exist in the pattern (rows
+ *              ascending, as every builder of this library leaves them) and no column may be the pivot of two rows.
+ *   d_xstar [N], d_ystar [M], d_slack [N] : inputs, never written.   dominance > 1, floor > 0, both finite.
+ *   d_x1 [N], d_x2 [M], d_labels [N] : outputs, every element written; what they held does not matter.
+ * A SETUP call, not a launch function: d_pivot is validated on the device first and `stream` is synchronised; a bad pivot
+ * gives MLLP_EINVAL with a message before a byte of the caller's buffers or of the graph's values is written.  The new
+ * values go through the library's scratch of nnz floats (that of mllp_graph_scale_values) and every value-holding array
+ * of the graph is refreshed with the guarantees of mllp_graph_set_values; the graph's copies of the inputs are
+ * invalidated as by mllp_graph_normalize.  Library scratch of N + M + 2 int32 is allocated by the first call and counted
+ * by mllp_graph_set_values_bytes from then on.
+ * MLLP_EINVAL before any HIP call: a null argument; dominance <= 1, floor <= 0 or either not finite; a caller-owned
+ * LDS-tiled copy is attached (the condition of mllp_graph_set_values).
+ * Deterministic and batch-independent: the sums take mllp_graph_normalize's three tiers and order, which depend on the
+ * row's (column's) nonzero count alone; a term the rule leaves out is skipped in place.  No float atomics, one writer
+ * per word.  Under the MEMORY CONTRACT below.  Added after ABI 6 without a bump, as mllp_graph_set_values was.
+ *
+ * mllp_lp_certificate: what a claimed optimal solution (x, y, basis) of the resident batch is worth, per instance, from
+ * two sparse sweeps over the stored data -- the planted labels, Netlib's, or a solver's output.  A launch function:
+ * `stream` only, no allocation, no synchronisation, hipGraph-capturable.
+ *   d_x1 [N] = c, d_x2 [M] = b, d_x [N], d_y [M], d_basis [N] (0 = nonbasic, anything else = basic) : inputs.
+ *   d_scratch : mllp_lp_certificate_scratch_bytes() bytes.     d_cert [n_inst, 6], per instance:
+ *     0  max_i |sum_j a_ij x_j - b_i|             primal residual (0 without rows)
+ *     1  min x_j over basic j                      (+inf without basic columns)
+ *     2  max |x_j| over nonbasic j                 (0 without nonbasic columns)
+ *     3  min (c_j - sum_i a_ij y_i) over nonbasic j   the smallest reduced cost (+inf without nonbasic columns)
+ *     4  max |c_j - sum_i a_ij y_i| over basic j   complementarity (0 without basic columns)
+ *     5  sum_j basis_j
+ * The per-row and per-column sums take the fixed order above; the reductions over an instance are max / min.        */
+int mllp_graph_plant_basis(mllp_graph_t* g, const int* d_pivot, const float* d_xstar, const float* d_ystar,
+                           const float* d_slack, float dominance, float floor, float* d_x1, float* d_x2, float* d_labels,
+                           void* stream);
+int mllp_lp_certificate_scratch_bytes(const mllp_graph_t* g, int64_t* bytes);
+int mllp_lp_certificate(const mllp_graph_t* g, const float* d_x1, const float* d_x2, const float* d_x, const float* d_y,
+                        const float* d_basis, float* d_cert, void* d_scratch, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Plain CSR SpMM (the roofline kernel named in BASELINE.json's metric):
  *   transpose == 0:  Y[M,16] = A   * H[N,16]       transpose == 1:  Y[N,16] = A^T * H[M,16]
@@ -310,8 +358,8 @@ int mllp_tconv_bwd(const mllp_graph_t* g, int dst_is_var, int cin, const float* 
  *   d_x1 [N] = objective coefficients (x1, methods.py:90), d_x2 [M] = right-hand sides (x2, :91)
  *   d_ws     : mllp_gnn_workspace_bytes() bytes, kept between forward and backward
  *   d_logits [N] : per-variable logits (methods.py:250-251)
- * MEMORY CONTRACT of every mllp_gnn_*, mllp_tconv_*, mllp_spmm_*, mllp_weighted_loss, mllp_balanced_pos_weight, mllp_topm_*
- * and mllp_graph_normalize call, for every buffer the caller owns (tests/test_memory_contract.py):
+ * MEMORY CONTRACT of every mllp_gnn_*, mllp_tconv_*, mllp_spmm_*, mllp_weighted_loss, mllp_balanced_pos_weight, mllp_topm_*,
+ * mllp_graph_normalize, mllp_graph_plant_basis and mllp_lp_certificate call, for every buffer the caller owns (tests/test_memory_contract.py):
  *   1. A call's outputs do not depend on any byte that d_ws, or any other scratch or output buffer, held before the call:
  *      the buffers may be uninitialised, NaN included, and the same bits come out.  The only state carried between calls is
  *      what this header names: mllp_gnn_forward -> mllp_gnn_backward / _backward_inputs / _input_grads on the same workspace

@@ -63,6 +63,10 @@ _PROTOTYPES = {
     "mllp_graph_scale_values": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "mllp_graph_normalize": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_int, c_void_p, c_void_p, c_void_p]),
     "mllp_normalize_row_tier": (c_int, [c_int64, POINTER(c_int)]),
+    "mllp_graph_plant_basis": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p,
+                                       c_void_p, c_void_p]),
+    "mllp_lp_certificate_scratch_bytes": (c_int, [c_void_p, POINTER(c_int64)]),
+    "mllp_lp_certificate": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mllp_graph_build_spmm_copy": (c_int, [c_void_p, c_int, c_int, c_void_p]),
     "mllp_graph_drop_spmm_copy": (c_int, [c_void_p, c_int]),
     "mllp_graph_spmm_copy_info": (c_int, [c_void_p, c_int, POINTER(c_int64)]),

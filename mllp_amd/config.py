@@ -32,6 +32,8 @@ HOT_PATH_DEFAULTS = {
                              # instance); None == the reference's unweighted BCEWithLogitsLoss (experiment.py:41)
     "holdout": None,         # instances evaluated every logging epoch and never trained on: a list of instance names, or a
                              # fraction f in (0, 1) (mllp_amd.experiment.holdout_by_fraction); None == train on everything
+    "planted": None,         # with train_data_type: 'planted', the block {instances, m, n, row_nnz, seed} of the planted-basis
+                             # LPs built on the device (mllp_amd.planted.PLANTED_DEFAULTS); None == those defaults
 }
 
 

@@ -201,6 +201,8 @@ struct mllp_graph {
     float* scale_buf = nullptr;  // [nnz] the scaled values of mllp_graph_scale_values, made on its first call (in `allocs`)
     float* norm_scale = nullptr; // [M + n_inst] row and objective scales of mllp_graph_normalize calls that pass no output
                                  // array, made on its first call (in `allocs`)
+    int* plant_ws = nullptr;     // [N + M + 2] mllp_graph_plant_basis (planted.hip): owner row of every column (-1: nonbasic), CSR
+                                 // position of every row's pivot, the error words; made on its first call (in `allocs`)
     // second stream + events: the two convs of a layer (one per orientation) and the single-workgroup
     // finalize kernels run beside the main stream (fork/join by events, also under hipGraph capture)
     hipStream_t aux = nullptr;
@@ -356,6 +358,7 @@ int launch_edge_grad(const Orient& o, int64_t nnz, int cin, const ConvWs& w, con
                      int accumulate, hipStream_t s);
 int build_csc_to_csr(const mllp_graph* g, int* pos, hipStream_t s);
 int ensure_at_pos(mllp_graph* g, hipStream_t s);   // set_values.hip: g->at_pos, built once per graph (allocates)
+int ensure_scale_buf(mllp_graph* g);               // set_values.hip: g->scale_buf [nnz], made once per graph (allocates)
 // set_values.hip: a caller-owned LDS-tiled copy is attached; its values are in arrays the library may not write, so
 // mllp_graph_set_values, _scale_values and _normalize refuse with this message
 bool borrowed_tiled(const mllp_graph* g);

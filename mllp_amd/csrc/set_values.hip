@@ -211,6 +211,15 @@ int ensure_at_pos(mllp_graph* g, hipStream_t s) {
     return MLLP_OK;
 }
 
+int ensure_scale_buf(mllp_graph* g) {
+    if (g->scale_buf || g->nnz == 0) return MLLP_OK;
+    void* p = nullptr;
+    MLLP_HIP_TRY(hipMalloc(&p, (size_t)g->nnz * sizeof(float)));
+    g->allocs.push_back(p);
+    g->scale_buf = static_cast<float*>(p);
+    return MLLP_OK;
+}
+
 }  // namespace mllp
 
 using namespace mllp;
@@ -221,6 +230,7 @@ extern "C" int mllp_graph_set_values_bytes(const mllp_graph_t* g, int64_t* bytes
     int64_t words = g->nnz;                           // at_pos
     if (g->scale_buf) words += g->nnz;
     if (g->norm_scale) words += g->M + g->n_inst;     // (normalize.hip: not a map, counted here with the other scratch)
+    if (g->plant_ws) words += g->N + g->M + 2;        // (planted.hip: likewise)
     for (Orient* o : {&gm->A, &gm->At}) {
         for (int geom = 0; geom < STREAM_GEOMS; ++geom)
             if (o->stream[geom].n_tiles > 0) words += stream_words(o->stream[geom], geom);
@@ -264,12 +274,7 @@ extern "C" int mllp_graph_scale_values(mllp_graph_t* g, const float* d_row_scale
     hipStream_t s = (hipStream_t)stream;
     const int64_t nnz = g->nnz;
     if (nnz == 0) return mllp_graph_set_values(g, g->A.val, stream);
-    if (!g->scale_buf) {        // once per graph (allocates)
-        void* p = nullptr;
-        MLLP_HIP_TRY(hipMalloc(&p, (size_t)nnz * sizeof(float)));
-        g->allocs.push_back(p);
-        g->scale_buf = static_cast<float*>(p);
-    }
+    if (int rc = ensure_scale_buf(g)) return rc;       // once per graph (allocates)
     hipLaunchKernelGGL(sv_scale_kernel, grid_for(nnz), dim3(BLOCK), 0, s, g->A.ptr, g->A.idx, g->A.val, (int)g->M, nnz,
                        d_row_scale, d_col_scale, g->scale_buf);
     if (int rc = check_launch("scale_values")) return rc;

@@ -300,6 +300,13 @@ def main(argv=None):
             train_dataset, train_dict = get_netlib_dataset_dense(normalize=True, names=names)
         else:
             train_dataset, train_dict = get_netlib_dataset(normalize=True, names=names)
+    elif cfg.train_data_type == "planted":          # labelled LPs built on the device (mllp_amd/planted.py)
+        unsupported = [m for m in cfg.methods if m not in SPARSE_METHODS]
+        if unsupported:
+            raise ValueError(f"train_data_type 'planted' feeds the sparse bipartite methods {SPARSE_METHODS} only, "
+                             f"not {unsupported}")
+        from .planted import planted_dataset
+        train_dataset, train_dict = planted_dataset(cfg.get_default("planted"), cfg.get_default("device"))
     else:
         raise ValueError(f"Unknown training dataset {cfg.train_data_type}!")
     for method_name in cfg.methods:                                                 # reference :45

@@ -270,6 +270,52 @@ class LPBatch:
             self._fwd_token = getattr(self, "_fwd_token", 0) + 1
         return row_scale, obj_scale
 
+    def plant_basis(self, pivot, xstar, ystar, slack, dominance=1.25, floor=0.25):
+        """Make the batch an LP whose unique optimal basis is the set of pivot columns, in place on the device
+        (mllp_graph_plant_basis): `pivot` [M] int32 names one column of every row (global id; the entry must exist, no
+        column twice), its entry becomes copysign(dominance * off_i + floor, old) with off_i the row's absolute sum over the
+        other basic columns, and `self.x2` = b, `self.x1` = c, `self.labels` = the basis mask are rewritten so that
+        (xstar on the basis, ystar) is primal and dual feasible with reduced costs `slack` off the basis.  xstar [N],
+        ystar [M], slack [N]: cuda float32; positive xstar and slack give a unique optimum, nothing checks them
+        (`certificate` reports).  Every value-holding array of the batch is refreshed as by `set_values`; a backward needs
+        a new forward.  A setup call: validates the pivots on the device and synchronises; a bad pivot raises MllpError
+        with nothing written."""
+        if not (pivot.is_cuda and pivot.dtype == torch.int32 and pivot.is_contiguous() and pivot.numel() == self.M):
+            raise ValueError(f"plant_basis: pivot must be a contiguous cuda int32 tensor of {self.M} elements")
+        for t, n, what in ((xstar, self.N, "xstar"), (ystar, self.M, "ystar"), (slack, self.N, "slack")):
+            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n):
+                raise ValueError(f"plant_basis: {what} must be a contiguous cuda float32 tensor of {n} elements")
+        # (at least one element each: an empty torch tensor has a null pointer, which the library refuses)
+        pad = lambda t, dt: t if t.numel() else torch.zeros(1, dtype=dt, device=self.x1.device)   # noqa: E731
+        args = [pad(pivot, torch.int32)] + [pad(t, torch.float32) for t in (xstar, ystar, slack, self.x1, self.x2, self._labels)]
+        _lib.check(_lib.lib().mllp_graph_plant_basis(self._h, *[_lib.ptr(a) for a in args[:4]], float(dominance), float(floor),
+                                                     *[_lib.ptr(a) for a in args[4:]], _lib.current_stream()))
+        self._fwd_token = getattr(self, "_fwd_token", 0) + 1      # (as set_values; the library invalidated its input copies)
+        self._balanced_pw = None                                  # (the labels were written behind torch's version counter)
+        return self
+
+    def certificate(self, x, y, basis=None, out=None):
+        """[n_inst, 6] cuda float32: what (x [N], y [M], basis [N], default `self.labels`) is worth as an optimal solution
+        of every instance as the batch stores it now (mllp_lp_certificate): max |Ax - b|, min x over the basis, max |x| off
+        it, min reduced cost c - A'y off the basis, max |reduced cost| on it, the basis' size.  An optimal basic solution
+        has 0, >= 0, 0, >= 0, 0, m up to rounding; empty sets give +inf (min) and 0 (max).  No sync, no allocation in the
+        library."""
+        basis = self._labels if basis is None else basis
+        for t, n, what in ((x, self.N, "x"), (y, self.M, "y"), (basis, self.N, "basis")):
+            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n):
+                raise ValueError(f"certificate: {what} must be a contiguous cuda float32 tensor of {n} elements")
+        dev = self.x1.device
+        if getattr(self, "_cert_scratch", None) is None:
+            n = c_int64()
+            _lib.check(_lib.lib().mllp_lp_certificate_scratch_bytes(self._h, ctypes.byref(n)))
+            self._cert_scratch = torch.empty(n.value // 4, device=dev, dtype=torch.float32)
+        if out is None:
+            out = torch.empty(max(self.n_inst, 1), 6, device=dev, dtype=torch.float32)[:self.n_inst]
+        pad = lambda t: t if t.numel() else torch.zeros(1, device=dev)      # noqa: E731
+        _lib.check(_lib.lib().mllp_lp_certificate(self._h, *[_lib.ptr(pad(t)) for t in (self.x1, self.x2, x, y, basis)],
+                                                  _lib.ptr(out), _lib.ptr(self._cert_scratch), _lib.current_stream()))
+        return out
+
     @staticmethod
     def normalize_row_tier(row_nnz):
         """Which reduction of `normalize` a row of `row_nnz` nonzeros gets: 0 = 16-lane group, 1 = wavefront, 2 = workgroup."""
