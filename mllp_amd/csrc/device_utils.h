@@ -42,6 +42,14 @@ __device__ __forceinline__ float row16_max(float v) {
     return v;
 }
 
+__device__ __forceinline__ float row16_min(float v) {
+    v = fminf(v, dpp_mov<0xB1>(v));
+    v = fminf(v, dpp_mov<0x4E>(v));
+    v = fminf(v, dpp_mov<0x141>(v));
+    v = fminf(v, dpp_mov<0x140>(v));
+    return v;
+}
+
 // G = 16: one DPP row.  G = 64: the whole wavefront (two more butterfly steps through the LDS crossbar).
 template <int G>
 __device__ __forceinline__ float group_sum(float v) {
@@ -58,6 +66,16 @@ __device__ __forceinline__ float group_max(float v) {
     if (G == 64) {
         v = fmaxf(v, __shfl_xor(v, 16, 64));
         v = fmaxf(v, __shfl_xor(v, 32, 64));
+    }
+    return v;
+}
+
+template <int G>
+__device__ __forceinline__ float group_min(float v) {
+    v = row16_min(v);
+    if (G == 64) {
+        v = fminf(v, __shfl_xor(v, 16, 64));
+        v = fminf(v, __shfl_xor(v, 32, 64));
     }
     return v;
 }

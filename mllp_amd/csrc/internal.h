@@ -212,6 +212,18 @@ struct mllp_graph {
 
 namespace mllp {
 
+// a device array that a graph makes on the first call that needs it and frees with itself (in `allocs`): a no-op once `slot`
+// is set.  Allocates: the first such call is not for a capture
+template <class T>
+inline int graph_alloc_once(mllp_graph* g, T*& slot, size_t bytes) {
+    if (slot) return MLLP_OK;
+    void* p = nullptr;
+    MLLP_HIP_TRY(hipMalloc(&p, bytes));
+    g->allocs.push_back(p);
+    slot = static_cast<T*>(p);
+    return MLLP_OK;
+}
+
 // ---- per-conv parameter views into the flat state_dict-ordered buffer ---------------------------
 struct ConvParams {
     const float *Wk, *bk, *Wq, *bq, *Wv, *bv, *we, *Ws, *bs;

@@ -14,85 +14,18 @@
 //   certificate            row sweep |sum_j a_ij x_j - b_i| -> scratch[0, M), column sweep c_j - sum_i a_ij y_i ->
 //                          scratch[M, M + N), then one workgroup per instance takes the six figures
 //
-// SUMMATION ORDER.  normalize.hip's: three tiers by the row's (column's) nonzero count alone -- 16 lanes up to 64 terms, a
-// wavefront up to 1024, the workgroup beyond --, lane l of G adds terms l, l + G, ... in that order starting from 0 (a term
-// that the rule leaves out is skipped in place), the lanes are added by device_utils.h::group_sum's butterfly, the four
-// wavefronts of the block tier as (0 + 1) + (2 + 3).  So an instance gets the same bits alone and inside any batch.  No
-// float atomics; one writer per word.
+// The summation order of every sweep is ordered_sum.h's (a term that the rule leaves out is skipped in place), so an
+// instance gets the same bits alone and inside any batch.  No float atomics; one writer per word.
 #include <climits>
 #include <cmath>
 
-#include "device_utils.h"
-#include "internal.h"
+#include "ordered_sum.h"
 
 namespace mllp {
 
 namespace {
 
-constexpr int PL_ROWS = BLOCK / 16;         // rows per workgroup: one 16-lane group each
-constexpr int PL_GROUP_MAX = 64;            // longest row of the group tier (normalize.hip::NORM_GROUP_MAX)
-constexpr int PL_WAVE_MAX = 1024;           // ... of the wave tier
 constexpr int PL_ERR_ABSENT = 1, PL_ERR_TWICE = 2, PL_ERR_RANGE = 4;
-
-__host__ __device__ constexpr int pl_tier(int len) { return len <= PL_GROUP_MAX ? 0 : len <= PL_WAVE_MAX ? 1 : 2; }
-
-struct Sum2 {
-    float a, b;
-};
-
-template <int G>
-__device__ __forceinline__ Sum2 group_sum2(Sum2 v) {
-    return {group_sum<G>(v.a), group_sum<G>(v.b)};
-}
-
-// lane `l` of G over the row's terms l, l + G, ... in that order
-template <int G, class Op>
-__device__ __forceinline__ Sum2 strided_terms(const Op& op, const typename Op::Row& rc, int beg, int len, int l) {
-    Sum2 v = {0.0f, 0.0f};
-    for (int j = l; j < len; j += G) op.term(rc, beg + j, v);
-    return v;
-}
-
-// One sweep over a CSR orientation in the three tiers.  Op: Row row(r) (what a row's terms share), term(row, e, sums)
-// adds nonzero e, finish(r, row, sums) is run by ONE lane of the row
-template <class Op>
-__global__ __launch_bounds__(BLOCK) void tier_sweep_kernel(const int* __restrict__ ptr, int n_rows, Op op) {
-    __shared__ int s_ptr[PL_ROWS + 1];
-    __shared__ Sum2 part[BLOCK / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int row0 = blockIdx.x * PL_ROWS;
-    const int n_here = min(PL_ROWS, n_rows - row0);
-    if (tid <= PL_ROWS) s_ptr[tid] = ptr[row0 + min(tid, n_here)];         // (rows past the end: empty)
-    __syncthreads();
-    {   // group tier: row `tid / 16` (a row of another tier runs the same code over no terms)
-        const int k = tid >> 4, beg = s_ptr[k], len = s_ptr[k + 1] - beg;
-        const bool mine = k < n_here && pl_tier(len) == 0;
-        const typename Op::Row rc = op.row(row0 + (mine ? k : 0));
-        const Sum2 q = group_sum2<16>(strided_terms<16>(op, rc, beg, mine ? len : 0, tid & 15));
-        if (mine && (tid & 15) == 0) op.finish(row0 + k, rc, q);
-    }
-    for (int k = wave; k < n_here; k += BLOCK / 64) {       // wave tier (k is uniform in the wavefront)
-        const int beg = s_ptr[k], len = s_ptr[k + 1] - beg;
-        if (pl_tier(len) != 1) continue;
-        const typename Op::Row rc = op.row(row0 + k);
-        const Sum2 q = group_sum2<64>(strided_terms<64>(op, rc, beg, len, lane));
-        if (lane == 0) op.finish(row0 + k, rc, q);
-    }
-    for (int k = 0; k < n_here; ++k) {                      // block tier (k is uniform in the workgroup)
-        const int beg = s_ptr[k], len = s_ptr[k + 1] - beg;
-        if (pl_tier(len) != 2) continue;
-        const typename Op::Row rc = op.row(row0 + k);
-        const Sum2 q = group_sum2<64>(strided_terms<BLOCK>(op, rc, beg, len, tid));
-        if (lane == 0) part[wave] = q;
-        __syncthreads();
-        if (tid == 0) {
-            const Sum2 t = {__fadd_rn(__fadd_rn(part[0].a, part[1].a), __fadd_rn(part[2].a, part[3].a)),
-                            __fadd_rn(__fadd_rn(part[0].b, part[1].b), __fadd_rn(part[2].b, part[3].b))};
-            op.finish(row0 + k, rc, t);
-        }
-        __syncthreads();
-    }
-}
 
 // ---- planting -----------------------------------------------------------------------------------------------------------
 // err[0]: PL_ERR_* bits, err[1]: the lowest offending row
@@ -123,6 +56,7 @@ __global__ __launch_bounds__(BLOCK) void plant_validate_kernel(const int* __rest
 }
 
 struct PlantRows {
+    using Acc = Sum2;           // {off_i, rest_i}
     struct Row {
         int p, pos;
     };
@@ -153,6 +87,7 @@ struct PlantRows {
 };
 
 struct PlantCols {
+    using Acc = float;
     struct Row {};
     const int* __restrict__ idx;    // CSR(A^T): the constraint of every nonzero
     const float* __restrict__ val;
@@ -162,10 +97,10 @@ struct PlantCols {
     float* __restrict__ x1;
     float* __restrict__ labels;
     __device__ __forceinline__ Row row(int) const { return {}; }
-    __device__ __forceinline__ void term(const Row&, int e, Sum2& v) const { v.a = __fmaf_rn(val[e], ystar[idx[e]], v.a); }
-    __device__ __forceinline__ void finish(int j, const Row&, const Sum2& v) const {
+    __device__ __forceinline__ void term(const Row&, int e, float& v) const { v = __fmaf_rn(val[e], ystar[idx[e]], v); }
+    __device__ __forceinline__ void finish(int j, const Row&, float v) const {
         const bool basic = owner[j] >= 0;
-        x1[j] = basic ? v.a : __fadd_rn(v.a, slack[j]);
+        x1[j] = basic ? v : __fadd_rn(v, slack[j]);
         labels[j] = basic ? 1.0f : 0.0f;
     }
 };
@@ -173,6 +108,7 @@ struct PlantCols {
 // ---- certificate --------------------------------------------------------------------------------------------------------
 // out[r] = |sum_j a_rj x_j - b_r| (rows = 1: CSR(A)) or c_r - sum_i a_ir y_i (rows = 0: CSR(A^T))
 struct CertSweep {
+    using Acc = float;
     struct Row {};
     const int* __restrict__ idx;
     const float* __restrict__ val;
@@ -181,32 +117,24 @@ struct CertSweep {
     int rows;
     float* __restrict__ out;
     __device__ __forceinline__ Row row(int) const { return {}; }
-    __device__ __forceinline__ void term(const Row&, int e, Sum2& v) const { v.a = __fmaf_rn(val[e], x[idx[e]], v.a); }
-    __device__ __forceinline__ void finish(int r, const Row&, const Sum2& v) const {
-        out[r] = rows ? fabsf(__fsub_rn(v.a, rhs[r])) : __fsub_rn(rhs[r], v.a);
+    __device__ __forceinline__ void term(const Row&, int e, float& v) const { v = __fmaf_rn(val[e], x[idx[e]], v); }
+    __device__ __forceinline__ void finish(int r, const Row&, float v) const {
+        out[r] = rows ? fabsf(__fsub_rn(v, rhs[r])) : __fsub_rn(rhs[r], v);
     }
 };
 
-constexpr int CERT_FIELDS = 6;
-
-__device__ __forceinline__ float wave_min(float v) {
-    for (int d = 1; d < 64; d <<= 1) v = fminf(v, __shfl_xor(v, d, 64));
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-    for (int d = 1; d < 64; d <<= 1) v = fmaxf(v, __shfl_xor(v, d, 64));
-    return v;
-}
+constexpr int CERT_FIELDS = 6, CERT_EXTREMA = 5;    // five maxima / minima, then the basis count
 
 // one workgroup per instance.  The max / min are exact whatever the order; the sum of the mask takes the block tier's order
 __global__ __launch_bounds__(BLOCK) void cert_reduce_kernel(const int* __restrict__ inst_ptr_m, const int* __restrict__ inst_ptr_n,
                                                             const float* __restrict__ row_res, const float* __restrict__ red,
                                                             const float* __restrict__ x, const float* __restrict__ basis,
                                                             float* __restrict__ cert) {
-    __shared__ float part[BLOCK / 64][CERT_FIELDS];
+    __shared__ float part[BLOCK / 64][CERT_EXTREMA];
+    __shared__ float count_part[BLOCK / 64];
     const int k = blockIdx.x, tid = threadIdx.x;
     const float inf = __builtin_huge_valf();
-    float f[CERT_FIELDS] = {0.0f, inf, 0.0f, inf, 0.0f, 0.0f};
+    float f[CERT_EXTREMA] = {0.0f, inf, 0.0f, inf, 0.0f}, count = 0.0f;
     for (int i = inst_ptr_m[k] + tid, end = inst_ptr_m[k + 1]; i < end; i += BLOCK) f[0] = fmaxf(f[0], row_res[i]);
     for (int j = inst_ptr_n[k] + tid, end = inst_ptr_n[k + 1]; j < end; j += BLOCK) {
         const float m = basis[j], xj = x[j], rc = red[j];
@@ -217,27 +145,24 @@ __global__ __launch_bounds__(BLOCK) void cert_reduce_kernel(const int* __restric
             f[2] = fmaxf(f[2], fabsf(xj));
             f[3] = fminf(f[3], rc);
         }
-        f[5] = __fadd_rn(f[5], m);
+        count = __fadd_rn(count, m);
     }
-    f[0] = wave_max(f[0]);
-    f[1] = wave_min(f[1]);
-    f[2] = wave_max(f[2]);
-    f[3] = wave_min(f[3]);
-    f[4] = wave_max(f[4]);
-    f[5] = group_sum<64>(f[5]);
+    f[0] = group_max<64>(f[0]);
+    f[1] = group_min<64>(f[1]);
+    f[2] = group_max<64>(f[2]);
+    f[3] = group_min<64>(f[3]);
+    f[4] = group_max<64>(f[4]);
     if ((tid & 63) == 0)
-        for (int c = 0; c < CERT_FIELDS; ++c) part[tid >> 6][c] = f[c];
-    __syncthreads();
-    if (tid < CERT_FIELDS) {
+        for (int c = 0; c < CERT_EXTREMA; ++c) part[tid >> 6][c] = f[c];
+    count = block_tree_sum<BLOCK / 64>(count, count_part);      // (its barriers publish `part` as well)
+    if (tid < CERT_EXTREMA) {
         const float a = part[0][tid], b = part[1][tid], c = part[2][tid], d = part[3][tid];
         const bool is_min = tid == 1 || tid == 3;
-        cert[(int64_t)k * CERT_FIELDS + tid] = tid == 5  ? __fadd_rn(__fadd_rn(a, b), __fadd_rn(c, d))
-                                               : is_min ? fminf(fminf(a, b), fminf(c, d))
-                                                        : fmaxf(fmaxf(a, b), fmaxf(c, d));
+        cert[(int64_t)k * CERT_FIELDS + tid] = is_min ? fminf(fminf(a, b), fminf(c, d)) : fmaxf(fmaxf(a, b), fmaxf(c, d));
+    } else if (tid == CERT_EXTREMA) {
+        cert[(int64_t)k * CERT_FIELDS + tid] = count;
     }
 }
-
-inline dim3 sweep_grid(int64_t n_rows) { return dim3((unsigned)((n_rows + PL_ROWS - 1) / PL_ROWS)); }
 
 }  // namespace
 
@@ -255,12 +180,8 @@ extern "C" int mllp_graph_plant_basis(mllp_graph_t* g, const int* d_pivot, const
     hipStream_t s = (hipStream_t)stream;
     const int M = (int)g->M, N = (int)g->N;
     int rc;
-    if (!g->plant_ws) {         // once per graph (allocates): owner [N], ppos [M], the error words [2]
-        void* p = nullptr;
-        MLLP_HIP_TRY(hipMalloc(&p, (size_t)(g->N + g->M + 2) * sizeof(int)));
-        g->allocs.push_back(p);
-        g->plant_ws = static_cast<int*>(p);
-    }
+    // owner [N], ppos [M], the error words [2]
+    if ((rc = graph_alloc_once(g, g->plant_ws, (size_t)(g->N + g->M + 2) * sizeof(int)))) return rc;
     if ((rc = ensure_scale_buf(g))) return rc;
     int* owner = g->plant_ws;
     int* ppos = owner + N;
@@ -286,18 +207,12 @@ extern "C" int mllp_graph_plant_basis(mllp_graph_t* g, const int* d_pivot, const
                                      "; nothing was written");
     }
     // ---- rows: the new values into the scratch, b into d_x2
-    if (M > 0) {
-        const PlantRows op = {g->A.idx, g->A.val, d_pivot, ppos, owner, d_xstar, dominance, floor, g->scale_buf, d_x2};
-        hipLaunchKernelGGL(tier_sweep_kernel<PlantRows>, sweep_grid(M), dim3(BLOCK), 0, s, g->A.ptr, M, op);
-        if ((rc = check_launch("plant_basis rows"))) return rc;
-    }
+    const PlantRows rows = {g->A.idx, g->A.val, d_pivot, ppos, owner, d_xstar, dominance, floor, g->scale_buf, d_x2};
+    if ((rc = launch_tier_sweep(g->A.ptr, M, rows, s, "plant_basis rows"))) return rc;
     if ((rc = mllp_graph_set_values(g, g->nnz ? g->scale_buf : g->A.val, stream))) return rc;
     // ---- columns over the refreshed CSR(A^T): c into d_x1, the mask into d_labels
-    if (N > 0) {
-        const PlantCols op = {g->At.idx, g->At.val, owner, d_ystar, d_slack, d_x1, d_labels};
-        hipLaunchKernelGGL(tier_sweep_kernel<PlantCols>, sweep_grid(N), dim3(BLOCK), 0, s, g->At.ptr, N, op);
-        if ((rc = check_launch("plant_basis columns"))) return rc;
-    }
+    const PlantCols cols = {g->At.idx, g->At.val, owner, d_ystar, d_slack, d_x1, d_labels};
+    if ((rc = launch_tier_sweep(g->At.ptr, N, cols, s, "plant_basis columns"))) return rc;
     return mllp_graph_invalidate_inputs(g);     // x1 / x2 / labels were just written
 }
 
@@ -315,16 +230,9 @@ extern "C" int mllp_lp_certificate(const mllp_graph_t* g, const float* d_x1, con
     float* row_res = static_cast<float*>(d_scratch);
     float* red = row_res + M;
     int rc;
-    if (M > 0) {
-        const CertSweep op = {g->A.idx, g->A.val, d_x, d_x2, 1, row_res};
-        hipLaunchKernelGGL(tier_sweep_kernel<CertSweep>, sweep_grid(M), dim3(BLOCK), 0, s, g->A.ptr, M, op);
-        if ((rc = check_launch("lp_certificate rows"))) return rc;
-    }
-    if (N > 0) {
-        const CertSweep op = {g->At.idx, g->At.val, d_y, d_x1, 0, red};
-        hipLaunchKernelGGL(tier_sweep_kernel<CertSweep>, sweep_grid(N), dim3(BLOCK), 0, s, g->At.ptr, N, op);
-        if ((rc = check_launch("lp_certificate columns"))) return rc;
-    }
+    if ((rc = launch_tier_sweep(g->A.ptr, M, CertSweep{g->A.idx, g->A.val, d_x, d_x2, 1, row_res}, s, "lp_certificate rows"))) return rc;
+    if ((rc = launch_tier_sweep(g->At.ptr, N, CertSweep{g->At.idx, g->At.val, d_y, d_x1, 0, red}, s, "lp_certificate columns")))
+        return rc;
     if (g->n_inst > 0) {
         hipLaunchKernelGGL(cert_reduce_kernel, dim3((unsigned)g->n_inst), dim3(BLOCK), 0, s, g->inst_ptr_m, g->inst_ptr_n, row_res, red,
                            d_x, d_basis, d_cert);

@@ -203,21 +203,15 @@ bool borrowed_tiled(const mllp_graph* g) {
 
 int ensure_at_pos(mllp_graph* g, hipStream_t s) {
     if (g->at_pos || g->nnz == 0) return MLLP_OK;
-    int* pos = nullptr;
-    MLLP_HIP_TRY(hipMalloc((void**)&pos, (size_t)g->nnz * sizeof(int)));
-    g->allocs.push_back(pos);
+    int* pos = nullptr;         // (the graph takes it once it is filled)
+    if (int rc = graph_alloc_once(g, pos, (size_t)g->nnz * sizeof(int))) return rc;
     if (int rc = build_csc_to_csr(g, pos, s)) return rc;
     g->at_pos = pos;
     return MLLP_OK;
 }
 
 int ensure_scale_buf(mllp_graph* g) {
-    if (g->scale_buf || g->nnz == 0) return MLLP_OK;
-    void* p = nullptr;
-    MLLP_HIP_TRY(hipMalloc(&p, (size_t)g->nnz * sizeof(float)));
-    g->allocs.push_back(p);
-    g->scale_buf = static_cast<float*>(p);
-    return MLLP_OK;
+    return g->nnz == 0 ? MLLP_OK : graph_alloc_once(g, g->scale_buf, (size_t)g->nnz * sizeof(float));
 }
 
 }  // namespace mllp

@@ -16,17 +16,15 @@
 //   weighted_loss_total_kernel  loss: one workgroup, the products w_k L_k staged 256 at a time and added by one thread
 //   balanced_pos_weight_kernel  pw_k = (n_k - P_k) / P_k with P_k = sum_i y_i, 1 where P_k is 0 or n_k
 //
-// SUMMATION ORDER.  Thread t adds l_t, l_(t + 1024), ... in that order, starting from 0 (eight of them per round, their
-// loads issued together: the order is that of one per round); the 64 lanes of a wavefront are
-// added by the xor butterfly of device_utils.h::group_sum (symmetric pair sums: every lane holds the same bits), the
-// sixteen wavefronts by a fixed binary tree ((0 + 1) + (2 + 3)) + ...  All of it depends on n_k alone, so an instance
-// gives the same L_k and dz bits alone and inside any batch, whichever outputs are asked for.  loss starts from 0 and adds
-// w_k L_k (one rounded product, one rounded sum) for k = 0, 1, ... in instance order.  No atomics; one writer per word.
+// The summation order is ordered_sum.h's with all 1024 threads as the lanes: thread t adds l_t, l_(t + 1024), ... (eight of
+// them per round, their loads issued together: the order is that of one per round), then the butterfly and the tree over
+// the sixteen wavefronts.  All of it depends on n_k alone, so an instance gives the same L_k and dz bits alone and inside
+// any batch, whichever outputs are asked for.  loss starts from 0 and adds w_k L_k (one rounded product, one rounded sum)
+// for k = 0, 1, ... in instance order.  No atomics; one writer per word.
 //
 // sigma(-z) is formed as head_kernel (node_kernels.hip) forms sigma(z): from e = exp(-|z|) <= 1, so nothing overflows;
 // it is computed directly, not as 1 - sigma(z), which would lose it entirely above z = 17.
-#include "device_utils.h"
-#include "internal.h"
+#include "ordered_sum.h"
 
 namespace mllp {
 
@@ -35,23 +33,6 @@ namespace {
 constexpr int WL_T = 1024, WL_W = WL_T / 64;
 constexpr int WL_U = 8;                 // columns of a thread whose loads are in flight together
 constexpr int WL_TOTAL_T = 256;
-
-// the workgroup's sum of v, in every thread (two barriers; `part` is reusable afterwards)
-__device__ __forceinline__ float wl_block_sum(float v, float* part) {
-    v = group_sum<64>(v);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float t[WL_W];
-#pragma unroll
-    for (int w = 0; w < WL_W; ++w) t[w] = part[w];
-#pragma unroll
-    for (int s = 1; s < WL_W; s <<= 1) {
-#pragma unroll
-        for (int w = 0; w < WL_W; w += 2 * s) t[w] = __fadd_rn(t[w], t[w + s]);
-    }
-    __syncthreads();
-    return t[0];
-}
 
 // L_k of the segment [beg, beg + n) in every thread; dz (when given) written on the way
 __device__ __forceinline__ float wl_instance(int beg, int n, float w, float pw, const float* __restrict__ z,
@@ -83,7 +64,7 @@ __device__ __forceinline__ float wl_instance(int beg, int n, float w, float pw, 
             if (dz) dz[beg + i] = wn * (omy - c * sneg);
         }
     }
-    const float s = wl_block_sum(acc, part);
+    const float s = block_tree_sum<WL_W>(acc, part);
     return n > 0 ? __fdiv_rn(s, nf) : 0.0f;
 }
 
@@ -131,7 +112,7 @@ __global__ __launch_bounds__(WL_T) void balanced_pos_weight_kernel(const int* __
     const int k = blockIdx.x, beg = ptr_n[k], n = ptr_n[k + 1] - beg;
     float acc = 0.0f;
     for (int i = threadIdx.x; i < n; i += WL_T) acc = __fadd_rn(acc, y[beg + i]);
-    const float P = wl_block_sum(acc, part), nf = (float)n;
+    const float P = block_tree_sum<WL_W>(acc, part), nf = (float)n;
     if (threadIdx.x == 0) pos_w[k] = (P > 0.0f && P < nf) ? __fdiv_rn(nf - P, P) : 1.0f;
 }
 
