@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define MLLP_ABI_VERSION 6 /* 2: streamed SpMM copy, device-built tiled copies, mllp_gnn_train_step, mllp_graph_invalidate_inputs; 3: streamed copies of the attention sweeps (mllp_graph_*_stream_copy); 4: input gradients (mllp_gnn_backward_inputs); 5: AngleModel input gradients (mllp_angle_backward_inputs); 6: the predicted basis (mllp_topm_select, mllp_topm_select_dense); mllp_graph_set_values, _set_values_bytes and _scale_values arrived after 6 WITHOUT a bump: they are additions only (no existing export changed signature or meaning), so every caller built against 6 stays valid; a caller that needs them checks for the symbols; mllp_graph_normalize and mllp_normalize_row_tier likewise; mllp_graph_plant_basis, mllp_lp_certificate and mllp_lp_certificate_scratch_bytes likewise */
+#define MLLP_ABI_VERSION 6 /* 2: streamed SpMM copy, device-built tiled copies, mllp_gnn_train_step, mllp_graph_invalidate_inputs; 3: streamed copies of the attention sweeps (mllp_graph_*_stream_copy); 4: input gradients (mllp_gnn_backward_inputs); 5: AngleModel input gradients (mllp_angle_backward_inputs); 6: the predicted basis (mllp_topm_select, mllp_topm_select_dense); mllp_graph_set_values, _set_values_bytes and _scale_values arrived after 6 WITHOUT a bump: they are additions only (no existing export changed signature or meaning), so every caller built against 6 stays valid; a caller that needs them checks for the symbols; mllp_graph_normalize and mllp_normalize_row_tier likewise; mllp_graph_plant_basis, mllp_lp_certificate and mllp_lp_certificate_scratch_bytes likewise; mllp_basis_repair and mllp_basis_repair_scratch_bytes likewise */
 #define MLLP_FEAT 16
 #define MLLP_NUM_PARAMS 4721 /* GNNModel.state_dict(), SURVEY.md appendix A.2 */
 
@@ -229,6 +229,47 @@ int mllp_lp_certificate_scratch_bytes(const mllp_graph_t* g, int64_t* bytes);
 int mllp_lp_certificate(const mllp_graph_t* g, const float* d_x1, const float* d_x2, const float* d_x, const float* d_y,
                         const float* d_basis, float* d_cert, void* d_scratch, void* stream);
 
+/* Repair and solve a predicted basis (mllp_amd/csrc/basis.hip): per instance, a ranking of its columns ->
+ * the best-ranked NONSINGULAR basis and its basic solution, whose outputs mllp_lp_certificate takes unchanged.  Added
+ * after ABI 6 without a bump, as mllp_lp_certificate was.
+ * THE RULE.  Instance k has m rows, n columns and the matrix A_k as the batch stores it now.  Its candidate list is its
+ * segment of d_order: instance-local column ids, best first, ended by the first negative entry or by n entries.  Walk the
+ * list in order, keeping a set of accepted columns, each with a pivot row of its own.  For a candidate j, with a = column
+ * j of A_k:  amax = max_i |a_i|;  w = what is left of a in the rows not yet pivoted after eliminating the accepted columns
+ * (the Schur-complement column);  r = max |w_i| over those rows.  Accept j iff amax > 0 and r > tol * amax; its pivot row
+ * is the row attaining r, the lowest row index among equal values.  Stop after m acceptances or at the end of the list.
+ * Greedy selection over a linear matroid: every accepted column is the best-ranked column independent of the
+ * better-ranked accepted ones, so no nonsingular set is lexicographically better in the given ranking.  A repeated id
+ * is rejected by the rule itself (its residual is zero up to rounding).  An id >= n ends the instance with code 3;
+ * nothing out of bounds is read.  With rank == m:  x_j = (B^-1 b)_j on the accepted columns and 0 elsewhere,
+ * y = B^-T c_B; otherwise the instance's x and y are zeros.  All in fp32; tol is a parameter of the rule (the customary
+ * value is 2^-12, about sqrt(eps)).
+ *   d_x1 [N] = c, d_x2 [M] = b : inputs, read only when d_x / d_y are asked for.   d_order [N] int32 : input.
+ *   max_m     : instances with m > max_m are skipped (code 2, outputs defaulted); they cost no scratch.  Values above 8192
+ *             mean 8192: the kernel keeps four vectors of m words in LDS (and at that size the transform is 256 MB).
+ *   d_basis [N] float 0/1, d_col_of_row [M] int32 (the local id of the column whose pivot row this is, or -1),
+ *   d_x [N], d_y [M], d_quality [n_inst, 2] : outputs, each may be NULL (not computed); d_x and d_y come together.
+ *   d_status [n_inst, 4] int32, required : {rank, candidates examined, rejected among the first m candidates, code};
+ *             code 0: rank == m;  1: the list ended below m;  2: skipped, m > max_m;  3: bad id.
+ *   d_quality : {smallest accepted r / amax, largest rejected r / amax}; empty sets give +inf and 0 (the certificate's
+ *             convention); a zero column counts as ratio 0.
+ *   d_scratch : mllp_basis_repair_scratch_bytes(g, max_m) bytes: m^2 words for every instance with 192 < m <= max_m
+ *             (smaller ones keep their transform in LDS); may be NULL when that is 0.
+ * Every requested output is fully written for every instance, skipped ones included (zeros, -1, status).  A launch
+ * function: `stream` only, no allocation, no synchronisation, hipGraph-capturable; one workgroup per instance.  It reads
+ * the graph's plain CSR(A^T) only: paths and attached copies do not matter and are left alone.  No float atomics; every
+ * sum has an order that depends on the instance alone, so the result is bitwise reproducible and the same for an
+ * instance alone and inside any batch.  The transform is DENSE (m^2 words per instance): this is an evaluation and setup
+ * call for m up to a few thousand, not a sparse LU.  Under the MEMORY CONTRACT below.
+ * MLLP_EINVAL before any launch, nothing written: null g, d_order or d_status; one of d_x, d_y without the other; null
+ * d_x1 or d_x2 with d_x and d_y asked for; null d_scratch with a non-zero scratch size; tol not finite or < 0; max_m < 0. */
+int mllp_basis_repair_scratch_bytes(const mllp_graph_t* g, int64_t max_m, int64_t* bytes);
+int mllp_basis_repair(const mllp_graph_t* g, const float* d_x1 /*c [N]*/, const float* d_x2 /*b [M]*/,
+                      const int32_t* d_order /*[N], per instance segment, local ids*/, float tol, int64_t max_m,
+                      float* d_basis /*[N] 0/1*/, int32_t* d_col_of_row /*[M] local id or -1*/,
+                      float* d_x /*[N]*/, float* d_y /*[M]*/, int32_t* d_status /*[n_inst,4]*/,
+                      float* d_quality /*[n_inst,2]*/, void* d_scratch, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Plain CSR SpMM (the roofline kernel named in BASELINE.json's metric):
  *   transpose == 0:  Y[M,16] = A   * H[N,16]       transpose == 1:  Y[N,16] = A^T * H[M,16]
@@ -359,7 +400,7 @@ int mllp_tconv_bwd(const mllp_graph_t* g, int dst_is_var, int cin, const float* 
  *   d_ws     : mllp_gnn_workspace_bytes() bytes, kept between forward and backward
  *   d_logits [N] : per-variable logits (methods.py:250-251)
  * MEMORY CONTRACT of every mllp_gnn_*, mllp_tconv_*, mllp_spmm_*, mllp_weighted_loss, mllp_balanced_pos_weight, mllp_topm_*,
- * mllp_graph_normalize, mllp_graph_plant_basis and mllp_lp_certificate call, for every buffer the caller owns (tests/test_memory_contract.py):
+ * mllp_graph_normalize, mllp_graph_plant_basis, mllp_lp_certificate and mllp_basis_repair call, for every buffer the caller owns (tests/test_memory_contract.py):
  *   1. A call's outputs do not depend on any byte that d_ws, or any other scratch or output buffer, held before the call:
  *      the buffers may be uninitialised, NaN included, and the same bits come out.  The only state carried between calls is
  *      what this header names: mllp_gnn_forward -> mllp_gnn_backward / _backward_inputs / _input_grads on the same workspace
@@ -379,7 +420,7 @@ int mllp_tconv_bwd(const mllp_graph_t* g, int dst_is_var, int cin, const float* 
  *      pieces --, as must every pointer of mllp_tconv_fwd / _bwd except d_param_grads (rows of 16 floats; d_ws, d_conv_params)
  *      and d_H, d_Y of mllp_spmm_csr_f32.  A misaligned one is refused with MLLP_EINVAL and a message before any HIP call,
  *      nothing written.  d_logits, d_labels, d_loss, d_grads, d_dlogits, d_dx1, d_dx2, d_dvalues, d_scratch, the optimizer
- *      buffers, the per-instance arrays and the buffers of the loss-head, top-m and normalize calls need only the natural
+ *      buffers, the per-instance arrays and the buffers of the loss-head, top-m, normalize and basis-repair calls need only the natural
  *      alignment of their element type.
  * mllp_gnn_backward: d_dlogits [N] -> d_grads [MLLP_NUM_PARAMS] (overwritten; the never-called
  *   gconv3_s2w block, methods.py:248, is written as zeros).

@@ -67,6 +67,9 @@ _PROTOTYPES = {
                                        c_void_p, c_void_p]),
     "mllp_lp_certificate_scratch_bytes": (c_int, [c_void_p, POINTER(c_int64)]),
     "mllp_lp_certificate": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mllp_basis_repair_scratch_bytes": (c_int, [c_void_p, c_int64, POINTER(c_int64)]),
+    "mllp_basis_repair": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_void_p]),
     "mllp_graph_build_spmm_copy": (c_int, [c_void_p, c_int, c_int, c_void_p]),
     "mllp_graph_drop_spmm_copy": (c_int, [c_void_p, c_int]),
     "mllp_graph_spmm_copy_info": (c_int, [c_void_p, c_int, POINTER(c_int64)]),

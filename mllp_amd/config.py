@@ -34,6 +34,10 @@ HOT_PATH_DEFAULTS = {
                              # fraction f in (0, 1) (mllp_amd.experiment.holdout_by_fraction); None == train on everything
     "planted": None,         # with train_data_type: 'planted', the block {instances, m, n, row_nnz, seed} of the planted-basis
                              # LPs built on the device (mllp_amd.planted.PLANTED_DEFAULTS); None == those defaults
+    "report_solved": None,   # the block {feas_tol, opt_tol, max_m}: every logging epoch the predicted ranking of the held-out
+                             # instances (the trained ones without `holdout`) is repaired into a basis, solved and certified on
+                             # the device, and train_log.json gains the counts usable / feasible / optimal / skipped (m > max_m;
+                             # max_m absent == none skipped); None == not computed, the log as before
 }
 
 

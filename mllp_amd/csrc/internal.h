@@ -408,6 +408,15 @@ int launch_topm_metrics(const mllp_graph* g, const float* logits, const float* l
 int launch_topm_select(const int* ptr_n, const int* ptr_m, int64_t n_seg, int n_dense, int m_dense, const float* logits,
                        unsigned char* mask, int* index, float* stats, hipStream_t s);
 
+// ---- basis repair (basis.hip): one workgroup per instance keeps the m x m transform T and four vectors of m words ------
+// The threshold between T in LDS and T in the caller's scratch, stated once: 192^2 + 4 * 192 words = 150 528 bytes, beside
+// the kernel's 400 bytes of static LDS, within the 160 KB of a workgroup.  The vectors stay in LDS above it, which bounds
+// the instances the call runs: 4 * 8192 words = 128 KB.  (At m = 8192 T alone is 256 MB and the elimination 2.7e11 updates.)
+constexpr int BASIS_LDS_MAX_M = 192;
+constexpr int BASIS_MAX_M = 8192;
+__host__ __device__ constexpr int64_t basis_repair_vec_words(int64_t m) { return 4 * m; }       // w, prow, crow, piv
+__host__ __device__ constexpr int64_t basis_repair_words(int64_t m) { return m * m; }           // scratch of one instance: T
+
 // ---- fused latency-regime path of the whole model (fused_kernels.hip) ---------------------------------
 // one whole-model call: the flat parameters, the carved workspace, the call's inputs (labels, logits: null where unused)
 struct FusedModel {

@@ -113,17 +113,21 @@ def run_epochs(cfg, instances, train_dict, trainer, batches, rank, world, device
     if world > 1:
         import torch.distributed as dist
     log_every = max(int(cfg.get_default("log_every")), 1)
+    report = cfg.get_default("report_solved")
     save_every = int(cfg.get_default("save_every"))
     for epoch in range(start_epoch, cfg.train_iter):                                # reference :120
         obj_sum = torch.zeros(1, device=device)
         logging = epoch % log_every == 0
         table = torch.zeros(len(instances), 2, device=device) if logging else None
+        train_solved = torch.zeros(len(SOLVED_KEYS), device=device) if logging and report is not None and not n_holdout else None
         for mine, b, gcount in batches:
             if b is None:      # a rank without instances in this batch still joins the all-reduce
                 trainer.step_empty()
                 continue
             trainer.global_instances = gcount
-            loss, _ = trainer.step(b)                                               # reference :124-144
+            loss, step_logits = trainer.step(b)                                     # reference :124-144
+            if train_solved is not None:            # (the logits of the step's forward, valid until the next step)
+                train_solved += solved_counts(b, step_logits, report).to(device)
             obj_sum += loss.to(device) * gcount     # loss is the batch mean over gcount instances (this rank's share)
             if logging:
                 table[torch.as_tensor(mine, device=device)] = trainer.metrics_of(b).to(device)
@@ -135,10 +139,18 @@ def run_epochs(cfg, instances, train_dict, trainer, batches, rank, world, device
                 ev = trainer.evaluate(b)
                 val_sum += ev["inst_loss"].to(device).sum()
                 table[torch.as_tensor(mine, device=device)] = ev["metrics"].to(device)
+        solved = None
+        if logging and report is not None:      # held-out instances, or the trained ones without a holdout
+            solved = train_solved if train_solved is not None else torch.zeros(len(SOLVED_KEYS), device=device)
+            for _, b in (holdout if n_holdout else ()):
+                if b is not None:
+                    solved += solved_counts(b, trainer.evaluate(b)["logits"], report).to(device)
         if dist is not None:
             dist.all_reduce(obj_sum)
             if logging:
                 dist.all_reduce(table)
+            if solved is not None:
+                dist.all_reduce(solved)
             if val_sum is not None:
                 dist.all_reduce(val_sum)
         obj = float(obj_sum[0]) / n_train
@@ -149,6 +161,9 @@ def run_epochs(cfg, instances, train_dict, trainer, batches, rank, world, device
                 if rank == 0:
                     out("%8d, %8d, %8d, %5f" % (correct_num, inst.m, inst.n, f1))
                 train_dict[inst.name].append(correct_num)
+        if solved is not None:
+            for key, v in zip(SOLVED_KEYS, solved.cpu().tolist()):
+                train_dict.setdefault(key, []).append(int(v))
         train_dict["obj"].append(obj)                  # plain float: the reference's numpy.float32 breaks json.dump
         val_obj = None
         if val_sum is not None:
@@ -161,6 +176,21 @@ def run_epochs(cfg, instances, train_dict, trainer, batches, rank, world, device
         if save_all is not None and save_every and (epoch + 1) % save_every == 0:
             save_all(epoch)
     return train_dict
+
+
+SOLVED_KEYS = ("usable", "feasible", "optimal", "skipped")
+
+
+def solved_counts(batch, logits, report):
+    """[4] device counts over a batch's instances, by SOLVED_KEYS: the predicted ranking repaired into a nonsingular basis
+    and solved on the device (LPBatch.repair_basis), then certified (LPBatch.solved) under the yaml block `report_solved`
+    {feas_tol, opt_tol, max_m}.  Instances with m > max_m are `skipped` and in no other count.  No sync."""
+    for key in ("feas_tol", "opt_tol"):
+        if key not in report:
+            raise ValueError(f"report_solved: {key} is required")
+    rep = batch.repair_basis(logits, max_m=report.get("max_m"), want=("basis", "x", "y"))
+    got = batch.solved(rep, report["feas_tol"], report["opt_tol"])
+    return torch.stack([got["usable"].sum(), got["primal_feasible"].sum(), got["optimal"].sum(), got["skipped"].sum()]).float()
 
 
 def train_method(cfg, method_name, train_dataset, train_dict, out=print):

@@ -925,6 +925,100 @@ class LPBatch:
         mask, index, stats = _select_views(bufs, self.N, self.M)
         return BasisPrediction(mask, index, stats, self.inst_n, self.inst_m, self.names)
 
+    # ---- repair and solve a predicted basis (mllp_basis_repair; csrc/basis.hip) ---------------------------------
+    def _column_segments(self):
+        """(instance of every column [N] int64, the instance's first column [N] int64), made once"""
+        if getattr(self, "_col_seg", None) is None:
+            dev = self.x1.device
+            n = torch.tensor(self.inst_n, dtype=torch.int64, device=dev).reshape(-1)
+            inst = torch.repeat_interleave(torch.arange(self.n_inst, device=dev), n)
+            first = torch.repeat_interleave(torch.cumsum(n, 0) - n, n)
+            self._col_seg = (inst, first)
+        return self._col_seg
+
+    def ranking(self, logits):
+        """int32 [N]: the candidate list `repair_basis` walks -- per instance its LOCAL column ids by descending logit, in
+        the total order of `predict_basis` (the key of the bit pattern, -0.0 < +0.0), lowest index first among equal
+        logits.  Plain torch on the device: the key, then two stable sorts."""
+        if not (logits.is_cuda and logits.dtype == torch.float32 and logits.is_contiguous() and logits.numel() == self.N):
+            raise ValueError(f"ranking: logits must be a contiguous cuda float32 tensor of {self.N} elements")
+        inst, first = self._column_segments()
+        v = logits.reshape(-1).view(torch.int32)
+        key = torch.where(v >= 0, v, v ^ 0x7FFFFFFF)        # signed and monotone in the select kernels' unsigned key
+        by_key = torch.sort(key, stable=True, descending=True)[1]
+        by_inst = torch.sort(inst[by_key], stable=True)[1]
+        cols = by_key[by_inst]
+        return (cols - first).to(torch.int32)
+
+    def repair_basis(self, logits=None, order=None, tol=2.0 ** -12, max_m=None,
+                     want=("basis", "col_of_row", "x", "y", "quality")):
+        """The best-ranked nonsingular basis of every instance and its basic solution, on the device
+        (mllp_basis_repair; the rule is stated in include/mllp_hip.h).  `order`: int32 [N], per instance its local column
+        ids, best first, ended by the first negative entry -- or `logits`, ranked by `ranking`.  `tol`: a column is
+        accepted when its residual exceeds tol times its largest entry (2^-12: the customary sqrt(eps) of fp32).  `max_m`:
+        instances with more rows are skipped (status code 2); None = the batch's largest m.  Returns a `BasisRepair` of
+        device tensors; those not named in `want` are None and cost nothing (`x` and `y` come together, `status` always).
+        The scratch is asked for once per max_m and kept on the batch.  No sync."""
+        want = (want,) if isinstance(want, str) else tuple(want)
+        names = ("basis", "col_of_row", "x", "y", "quality")
+        if [w for w in want if w not in names] or ("x" in want) != ("y" in want):
+            raise ValueError(f"repair_basis: want names some of {names}, 'x' and 'y' together (got {want!r})")
+        if (logits is None) == (order is None):
+            raise ValueError("repair_basis: give logits or order, one of them")
+        if order is None:
+            order = self.ranking(logits)
+        if not (order.is_cuda and order.dtype == torch.int32 and order.is_contiguous() and order.numel() == self.N):
+            raise ValueError(f"repair_basis: order must be a contiguous cuda int32 tensor of {self.N} elements")
+        dev = self.x1.device
+        max_m = max(self.inst_m, default=0) if max_m is None else int(max_m)
+        kept = getattr(self, "_repair_scratch", None)
+        if kept is None or kept[0] != max_m:
+            n = c_int64()
+            _lib.check(_lib.lib().mllp_basis_repair_scratch_bytes(self._h, max_m, ctypes.byref(n)))
+            kept = self._repair_scratch = (max_m, torch.empty(n.value // 4, device=dev, dtype=torch.float32) if n.value else None)
+        # (at least one element each: an empty torch tensor has a null pointer, which the library reads as "not wanted")
+        new = lambda n, dt: torch.empty(max(n, 1), dtype=dt, device=dev)      # noqa: E731
+        out = dict(basis=new(self.N, torch.float32) if "basis" in want else None,
+                   col_of_row=new(self.M, torch.int32) if "col_of_row" in want else None,
+                   x=new(self.N, torch.float32) if "x" in want else None, y=new(self.M, torch.float32) if "y" in want else None,
+                   status=new(self.n_inst * 4, torch.int32), quality=new(self.n_inst * 2, torch.float32) if "quality" in want else None)
+        pad = lambda t, dt=torch.float32: t if t.numel() else torch.zeros(1, dtype=dt, device=dev)   # noqa: E731
+        _lib.check(_lib.lib().mllp_basis_repair(self._h, _lib.ptr(pad(self.x1)), _lib.ptr(pad(self.x2)), _lib.ptr(pad(order, torch.int32)),
+                                                float(tol), max_m, *[_lib.ptr(out[k]) for k in ("basis", "col_of_row", "x", "y", "status",
+                                                                                               "quality")],
+                                                _lib.ptr(kept[1]), _lib.current_stream()))
+        cut = lambda t, n: None if t is None else t[:n]      # noqa: E731
+        return BasisRepair(cut(out["basis"], self.N), cut(out["col_of_row"], self.M), cut(out["x"], self.N), cut(out["y"], self.M),
+                           out["status"][:self.n_inst * 4].view(self.n_inst, 4),
+                           None if out["quality"] is None else out["quality"][:self.n_inst * 2].view(self.n_inst, 2))
+
+    def solve_basis(self, basis, tol=2.0 ** -12, max_m=None, want=("basis", "col_of_row", "x", "y", "quality")):
+        """The basic solution of a GIVEN basis (labels, a solver's output; [N], nonzero = basic): `repair_basis` on the list
+        "the mask's columns ascending, then -1".  Status code 1 when the basis is singular or has fewer than m columns."""
+        if not (basis.is_cuda and basis.is_contiguous() and basis.numel() == self.N):
+            raise ValueError(f"solve_basis: basis must be a contiguous cuda tensor of {self.N} elements")
+        inst, first = self._column_segments()
+        off = basis.reshape(-1) == 0
+        cols = torch.sort(inst * 2 + off.to(torch.int64), stable=True)[1]
+        order = torch.where(off[cols], torch.full_like(cols, -1), cols - first[cols]).to(torch.int32)
+        return self.repair_basis(order=order, tol=tol, max_m=max_m, want=want)
+
+    def solved(self, rep, feas_tol, opt_tol):
+        """What a `BasisRepair` (with x, y and basis) is worth, per instance, as device booleans from its status and the six
+        figures of `certificate`: `usable` (rank m: a basic solution exists), `primal_feasible` (usable, |Ax - b| <=
+        feas_tol, x >= -feas_tol on the basis, |x| <= feas_tol off it, m basic columns), `optimal` (primal feasible, reduced
+        costs >= -opt_tol off the basis and within opt_tol of 0 on it); `skipped`: m > max_m, never a failure of the
+        basis.  Both tolerances are in the units of the stored LP and have no defaults.  No sync."""
+        if rep.x is None or rep.y is None or rep.basis is None:
+            raise ValueError("solved: the BasisRepair needs x, y and basis")
+        feas_tol, opt_tol = float(feas_tol), float(opt_tol)
+        cert = self.certificate(rep.x, rep.y, rep.basis)
+        m = torch.tensor(self.inst_m, dtype=torch.float32, device=cert.device).reshape(-1)
+        usable = rep.status[:, 3] == 0
+        feasible = (usable & (cert[:, 0] <= feas_tol) & (cert[:, 1] >= -feas_tol) & (cert[:, 2] <= feas_tol) & (cert[:, 5] == m))
+        optimal = feasible & (cert[:, 3] >= -opt_tol) & (cert[:, 4] <= opt_tol)
+        return dict(usable=usable, primal_feasible=feasible, optimal=optimal, skipped=rep.status[:, 3] == 2, certificate=cert)
+
 
 def _select_outputs(want, n, m, n_seg, dev):
     """(mask, index, stats) buffers of the select entry points, None where not wanted.  At least one element each: an
@@ -958,6 +1052,17 @@ class BasisPrediction:
         idx = self.index.cpu().numpy()
         off = np.concatenate([[0], np.cumsum(self.seg_m)])
         return [idx[off[k]:off[k] + min(self.seg_m[k], self.seg_n[k])] for k in range(len(self.seg_m))]
+
+
+class BasisRepair:
+    """What `LPBatch.repair_basis` / `solve_basis` return, all device tensors, nothing copied back: `.basis` (float32 [N],
+    1 = accepted: what `certificate` takes), `.col_of_row` (int32 [M]: the local column whose pivot row this is, or -1), `.x`
+    [N] and `.y` [M] (the basic solution, zeros where rank < m), `.status` (int32 [n_inst, 4] = rank, candidates examined,
+    rejected among the first m candidates, code: 0 rank == m, 1 list exhausted, 2 skipped, 3 bad id) and `.quality`
+    (float32 [n_inst, 2] = smallest accepted, largest rejected residual ratio)."""
+
+    def __init__(self, basis, col_of_row, x, y, status, quality):
+        self.basis, self.col_of_row, self.x, self.y, self.status, self.quality = basis, col_of_row, x, y, status, quality
 
 
 def topm_select_dense(logits, m, want=("mask", "index", "stats")):
