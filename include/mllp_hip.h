@@ -114,7 +114,10 @@ int mllp_graph_set_path(mllp_graph_t* g, int path);
  * their contents in place, or frees a buffer and gets the same address back for other data, must call
  * mllp_graph_invalidate_inputs before the next mllp_gnn_* call on this graph (the generic / tiled path reads the
  * pointers on every call and needs nothing).  Calls made while the stream is captured into a hipGraph re-make the
- * copies inside the capture and leave the cache empty.  mllp_gnn_backward must follow an mllp_gnn_forward on the same
+ * copies inside the capture and leave the cache empty.  A replay of such a hipGraph rewrites the graph's copies from ITS
+ * buffers whenever the caller launches it, unseen by the library: from the first captured call on, and until
+ * mllp_graph_destroy, every call on this graph re-makes the copies (up to five small launches) and the pointer cache is not
+ * trusted again, so eager calls and replays on different buffers may alternate freely.  mllp_gnn_backward must follow an mllp_gnn_forward on the same
  * workspace with the same path (MLLP_EINVAL otherwise: the two paths lay the workspace out differently).          */
 int mllp_graph_invalidate_inputs(mllp_graph_t* g);
 
@@ -362,7 +365,7 @@ int mllp_graph_attach_tiled(mllp_graph_t* g, int transpose, int variant, int64_t
  * library-owned: a later build / attach / detach of the same (orientation, variant) and mllp_graph_destroy free them.
  *   mllp_graph_tiled_info: info[0..4] = row tiles, (tile, block) pairs, most blocks in one tile, 1 if library-owned,
  *   longest (tile, block) segment in entries (0 for caller-built copies).
- *   mllp_graph_export_tiled (tests): device-to-device copy of array `which` = 0 tile_blk, 1 blk_id, 2 ptr2, 3 perm,
+ *   mllp_graph_export_tiled (tests; a setup call beside mllp_graph_build_tiled, not a launch function): device-to-device copy of array `which` = 0 tile_blk, 1 blk_id, 2 ptr2, 3 perm,
  *   4 ent ((nnz + 1) x 2 int32); `count` int32 elements must equal the array's length.                       */
 int mllp_graph_build_tiled(mllp_graph_t* g, int transpose, int variant, void* stream);
 int mllp_graph_tiled_info(const mllp_graph_t* g, int transpose, int variant, int64_t info[5]);

@@ -1012,6 +1012,13 @@ extern "C" int mllp_debug_angle_stamps(unsigned long long* host) {
 namespace mllp {
 namespace {
 
+// zeros by a launch of the stream's own: a hipMemsetAsync captured into a hipGraph was seen to run, at replay, ahead of
+// work queued on the launch stream in front of the graph (tests/test_stream_contract.py: the block came back holding what
+// the caller had just put there)
+__global__ void zero_fill_kernel(float* __restrict__ p, long long n) {
+    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) p[i] = 0.0f;
+}
+
 // mllp_angle_backward, and with dx / dcos the input gradients: the first layer's dX branch and the edge-attribute
 // gradient of the three BQ sweeps, stored by the first (layer 3) and added by the next two, in that order
 int angle_backward(int64_t N, int F, const float* d_cos, const float* d_x, const float* d_params, float* d_ws,
@@ -1025,7 +1032,8 @@ int angle_backward(int64_t N, int F, const float* d_cos, const float* d_x, const
     const float* fcw = d_params + ofc;
     int rc;
     // gconv3 is never called (reference :198 applies gconv2 twice): its gradient is zero
-    MLLP_HIP_TRY(hipMemsetAsync(d_grads + o3, 0, (size_t)conv_size(F, F) * sizeof(float), s));
+    const long long n3 = conv_size(F, F);
+    hipLaunchKernelGGL(zero_fill_kernel, dim3((unsigned)std::min<long long>((n3 + AT - 1) / AT, 1024)), dim3(AT), 0, s, d_grads + o3, n3);
     // fc: dW = sum_i dlogit_i H3_i, db = sum_i dlogit_i, dH3 = dlogit w (last node: 0)
     if ((rc = launch_wcolsum(s, (int)(N - 1), F, w.L[2].H, d_dlogits, nullptr, nullptr, 0.0f, d_grads + ofc, w.gpart))) return rc;
     hipLaunchKernelGGL(sum_kernel, dim3(1), dim3(AT), 0, s, N - 1, d_dlogits, d_grads + ofc + F);

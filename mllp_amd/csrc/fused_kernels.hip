@@ -2129,13 +2129,17 @@ int fused_graph_build(mllp_graph* g, const int* h_csr_ptr, const int* h_csc_ptr)
 // the pointers are: the model's inputs are data -- reference linear_program_methods.py:90-91; the contract and
 // mllp_graph_invalidate_inputs are in include/mllp_hip.h).  While the stream is being captured into a hipGraph the
 // copies are made inside the capture on every call and the cache is left empty: a captured launch has not run, so a
-// later eager call with the same pointers must not find the inputs "bound".
+// later eager call with the same pointers must not find the inputs "bound".  Nor may any eager call after that capture: a
+// replay of the captured hipGraph rewrites x1_p / x2_p / labels_p / sax from ITS buffers whenever the caller chooses, and
+// the library does not see it happen.  So from the first captured call to the graph's destruction every call binds anew
+// (g->bind_captured; tests/test_stream_contract.py::test_replay_between_eager_calls).
 int fused_bind(mllp_graph* g, const float* x1, const float* x2, const float* labels, hipStream_t s) {
     int rc;
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     (void)hipStreamIsCapturing(s, &cap);
     const bool capturing = cap != hipStreamCaptureStatusNone;
-    if (capturing) g->bound_x1 = g->bound_x2 = g->bound_labels = nullptr;
+    if (capturing) g->bind_captured = true;
+    if (g->bind_captured) g->bound_x1 = g->bound_x2 = g->bound_labels = nullptr;
     if (x1 != g->bound_x1 || x2 != g->bound_x2) {
         if (g->N > 0) hipLaunchKernelGGL(fused_permute_kernel, dim3(256), dim3(256), 0, s, (int)g->N, g->perm_v, x1, g->x1_p);
         if (g->M > 0) hipLaunchKernelGGL(fused_permute_kernel, dim3(256), dim3(256), 0, s, (int)g->M, g->perm_c, x2, g->x2_p);

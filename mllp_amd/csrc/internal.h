@@ -187,6 +187,7 @@ struct mllp_graph {
     const void* bound_x1 = nullptr;
     const void* bound_x2 = nullptr;
     const void* bound_labels = nullptr;
+    bool bind_captured = false;  // a hipGraph captured on this graph re-makes the copies at every replay: the cache is never trusted again
     int ws_path = -1;            // which whole-model path wrote the workspace last: 0 generic / tiled, 1 fused (backward checks it)
     const void* ws_ptr = nullptr;
     // which {workspace, parameters} hold the folded weights that fused_tail_kernel left behind for the NEXT step

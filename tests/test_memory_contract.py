@@ -266,11 +266,17 @@ class Ctx:
         self.pw = _f32(0.5 + 3.0 * rng.random(self.K))
 
 
+def case_flat(case):
+    """the parameters a case runs with: the golden ones; x 1.25 for the donor of the leavings and for the second data set
+    ("+b") of tests/test_stream_contract.py"""
+    flat = _golden_flat()
+    return flat * 1.25 if case == "donor" or case.endswith("+b") else flat
+
+
 def get_ctx(case, config):
     key = (case, config)
     if key not in _CTX:
-        flat = _golden_flat()
-        _CTX[key] = Ctx(case, config, flat * 1.25 if case == "donor" else flat)
+        _CTX[key] = Ctx(case, config, case_flat(case))
     c = _CTX[key]
     if c.skip:
         pytest.skip(c.skip)
@@ -281,7 +287,7 @@ def refs(case):
     """the fp64 references of a case: computed on first use, shared, never modified"""
     if case in _REFS:
         return _REFS[case]
-    insts, flat = case_instances(case), _golden_flat()
+    insts, flat = case_instances(case), case_flat(case)
     sd = fc.golden_state({"weights_flat": flat})
     ob = o2.BatchCSR(insts)
     seg_n, ib = [i.n for i in insts], 1.0 / len(insts)
@@ -710,23 +716,25 @@ def ep_topm(ctx, B):
     return {"metrics": met, "mask": mask, "index": index, "stats": stats}
 
 
-@gpu
-@pytest.mark.parametrize("case", CASES)
-def test_loss_head_metrics_and_selection(case):
-    ctx, r = get_ctx(case, "generic"), refs(case)
+def anchor_weighted_loss(ctx):
+    """bars of tests/test_weighted_loss.py: test_kernel_alone_against_oracle, test_balanced_pos_weight (one ulp)"""
+    r = refs(ctx.case)
 
     def check_wl(out):
-        """bars of tests/test_weighted_loss.py: test_kernel_alone_against_oracle, test_balanced_pos_weight (one ulp)"""
         close(fl(out["inst_loss"]), r.wl["inst_loss"], RTOL_ACT, "inst_loss")
         close(fl(out["loss"]), np.array([r.wl["loss"]]), RTOL_ACT, "loss")
         close(fl(out["dlogits"]), r.wl["dz"], 1e-5, "dlogits")
         want = oracle_balanced(r.ob.basis, r.seg_n).astype(np.float32)
         ulp = np.abs(out["balanced"].astype(np.int64) - want.view(np.int32).astype(np.int64))
         assert ulp.max() <= 1, ulp
-    contract(ctx, ep_weighted_loss, check_wl)
+    return check_wl
+
+
+def anchor_topm(ctx):
+    """metrics as tests/test_hip_parity.py::test_whole_model_against_golden checks them; selection: exact"""
+    r = refs(ctx.case)
 
     def check_topm(out):
-        """metrics as tests/test_hip_parity.py::test_whole_model_against_golden checks them; selection: exact"""
         z = _f32(r.step["logits"])
         met, off = fl(out["metrics"]).reshape(-1, 2), np.concatenate([[0], np.cumsum(r.seg_n)])
         for k, i in enumerate(ctx.insts):
@@ -739,7 +747,15 @@ def test_loss_head_metrics_and_selection(case):
         assert np.array_equal(out["mask"], mask) and np.array_equal(out["index"], index)
         assert np.array_equal(out["stats"], stats.reshape(-1).view(np.int32))
     assert all(i.m <= i.n for i in ctx.insts)
-    contract(ctx, ep_topm, check_topm, skip_finite=("stats", "index"))
+    return check_topm
+
+
+@gpu
+@pytest.mark.parametrize("case", CASES)
+def test_loss_head_metrics_and_selection(case):
+    ctx = get_ctx(case, "generic")
+    contract(ctx, ep_weighted_loss, anchor_weighted_loss(ctx))
+    contract(ctx, ep_topm, anchor_topm(ctx), skip_finite=("stats", "index"))
 
 
 TCONVS = {"cin1": ("gconv1_w2s", True, 1), "cin16": ("gconv2_s2w", False, 16)}
@@ -750,9 +766,10 @@ TCONV_KEYS = ("lin_key.weight", "lin_key.bias", "lin_query.weight", "lin_query.b
 def _tconv_inputs(ctx, which):
     name, dst_is_var, cin = TCONVS[which]
     nd, ns = (ctx.N, ctx.M) if dst_is_var else (ctx.M, ctx.N)
-    rng = np.random.default_rng(3)
+    seed = getattr(ctx, "data_seed", 0)     # the second data set of tests/test_stream_contract.py: other inputs, and dh x 0.25
+    rng = np.random.default_rng(3 + seed)   # beside its parameters x 1.25 (lin_key.bias's bar is absolute, its noise scales with dh)
     return name, dst_is_var, cin, nd, ns, _f32(rng.standard_normal((ns, cin))), _f32(rng.standard_normal((nd, cin))), \
-        _f32(rng.standard_normal((nd, 16)))
+        _f32(rng.standard_normal((nd, 16)) * (0.25 if seed else 1.0))
 
 
 def _tconv(which):
@@ -779,13 +796,10 @@ def _tconv(which):
     return ep
 
 
-@gpu
-@pytest.mark.parametrize("which", list(TCONVS))
-@pytest.mark.parametrize("config", CONFIGS[1:])
-@pytest.mark.parametrize("case", CASES)
-def test_single_conv(case, config, which):
-    """mllp_tconv_fwd + _bwd on one workspace; the bars of tests/test_hip_parity.py::test_single_layer_forward_backward"""
-    ctx, r = get_ctx(case, config), refs(case)
+def anchor_tconv(ctx, which, reads_h=True):
+    """the bars of tests/test_hip_parity.py::test_single_layer_forward_backward (reads_h: the entry point read h back
+    between the forward and the backward)"""
+    r = refs(ctx.case)
     name, dst_is_var, cin, nd, ns, xs, xd, dh = _tconv_inputs(ctx, which)
     p = o2.conv_params(r.sd, name)
     ptr, idx, val, _, _ = r.ob.orient(dst_is_var)
@@ -795,7 +809,8 @@ def test_single_conv(case, config, which):
 
     def check(out):
         close(fl(out["h"]).reshape(nd, 16), h_ref, RTOL_ACT, "h")
-        assert np.array_equal(out["h"], out["h_before_bwd"])            # d_h_out is an input of the backward
+        if reads_h:
+            assert np.array_equal(out["h"], out["h_before_bwd"])        # d_h_out is an input of the backward
         close(fl(out["dh"]).reshape(nd, 16), inter["g"], 1e-7, "masked dh")
         if cin == 16:
             close(fl(out["dx_dst"]).reshape(nd, 16), dxd, RTOL_GRAD, "dx_dst")
@@ -809,13 +824,23 @@ def test_single_conv(case, config, which):
                 close(pg[o3:o3 + ref.size], ref, RTOL_GRAD, key)
             o3 += ref.size
         assert o3 == pg.size
-    contract(ctx, _tconv(which), check)
+    return check
+
+
+@gpu
+@pytest.mark.parametrize("which", list(TCONVS))
+@pytest.mark.parametrize("config", CONFIGS[1:])
+@pytest.mark.parametrize("case", CASES)
+def test_single_conv(case, config, which):
+    """mllp_tconv_fwd + _bwd on one workspace"""
+    ctx = get_ctx(case, config)
+    contract(ctx, _tconv(which), anchor_tconv(ctx, which))
 
 
 def _spmm(transpose):
     def ep(ctx, B):
         n_in, n_out = (ctx.M, ctx.N) if transpose else (ctx.N, ctx.M)
-        H = B.ro("H", _f32(np.random.default_rng(1).standard_normal((n_in, 16))), wide=True)
+        H = B.ro("H", _f32(np.random.default_rng(1 + getattr(ctx, "data_seed", 0)).standard_normal((n_in, 16))), wide=True)
         Y = B.rw("Y", n_out * 16, wide=True)
         _lib.check(_lib.lib().mllp_spmm_csr_f32(ctx.h, int(transpose), H.ptr, Y.ptr, _stream()))
         return {"Y": Y}
@@ -823,17 +848,22 @@ def _spmm(transpose):
     return ep
 
 
+def anchor_spmm(ctx, transpose, rtol=1e-6):
+    """the bar of tests/test_hip_parity.py::test_spmm_both_orientations"""
+    ob = refs(ctx.case).ob
+    n_in = ctx.M if transpose else ctx.N
+    H = _f32(np.random.default_rng(1 + getattr(ctx, "data_seed", 0)).standard_normal((n_in, 16))).astype(np.float64)
+    ptr, idx, val = (ob.cp, ob.ri, ob.cv) if transpose else (ob.rp, ob.ci, ob.va)
+    want = o2.spmm(ptr, idx, val.astype(np.float32).astype(np.float64), H)
+    return lambda out: close(fl(out["Y"]).reshape(want.shape), want, rtol, "A H")
+
+
 @gpu
 @pytest.mark.parametrize("transpose", [False, True])
 @pytest.mark.parametrize("case", CASES)
 def test_spmm(case, transpose):
-    """the bar of tests/test_hip_parity.py::test_spmm_both_orientations"""
-    ctx, ob = get_ctx(case, "generic"), refs(case).ob
-    n_in = ctx.M if transpose else ctx.N
-    H = _f32(np.random.default_rng(1).standard_normal((n_in, 16))).astype(np.float64)
-    ptr, idx, val = (ob.cp, ob.ri, ob.cv) if transpose else (ob.rp, ob.ci, ob.va)
-    want = o2.spmm(ptr, idx, val.astype(np.float32).astype(np.float64), H)
-    contract(ctx, _spmm(transpose), lambda out: close(fl(out["Y"]).reshape(want.shape), want, 1e-6, "A H"))
+    ctx = get_ctx(case, "generic")
+    contract(ctx, _spmm(transpose), anchor_spmm(ctx, transpose))
 
 
 def ep_normalize(ctx, B):
