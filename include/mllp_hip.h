@@ -384,8 +384,10 @@ int mllp_graph_export_tiled(const mllp_graph_t* g, int transpose, int variant, i
  *          between forward and backward).
  * Backward: d_dh [N_dst,16] = dL/dh_out (overwritten with the ReLU-masked gradient);
  *   d_dx_dst [N_dst,cin], d_dx_src [N_src,cin] may be NULL (then not computed; with cin = 1 they are never
- *   computed here: the whole model's input gradients are mllp_gnn_backward_inputs); accumulate bit 0 / bit 1 = add into d_dx_dst / d_dx_src
- *   instead of overwriting; d_param_grads: same layout as d_conv_params (overwritten).
+ *   computed here and never written: the whole model's input gradients are mllp_gnn_backward_inputs); accumulate bit 0 / bit 1 = add into d_dx_dst / d_dx_src
+ *   instead of overwriting; d_param_grads: same layout as d_conv_params (overwritten).  An accumulate bit whose pointer is
+ *   NULL is ignored.  No other output depends on accumulate or on which of the two pointers are given
+ *   (tests/test_conv_options.py).
  * ---------------------------------------------------------------------------------------------- */
 int mllp_tconv_workspace_floats(const mllp_graph_t* g, int dst_is_var, int cin, int64_t* n_floats);
 int mllp_tconv_fwd(const mllp_graph_t* g, int dst_is_var, int cin, const float* d_conv_params,
