@@ -273,6 +273,67 @@ int mllp_basis_repair(const mllp_graph_t* g, const float* d_x1 /*c [N]*/, const 
                       float* d_x /*[N]*/, float* d_y /*[M]*/, int32_t* d_status /*[n_inst,4]*/,
                       float* d_quality /*[n_inst,2]*/, void* d_scratch, void* stream);
 
+/* Pivot a basis to optimality (mllp_amd/csrc/simplex.hip): per instance, a basis mask -> dual simplex
+ * pivots on shifted costs until the basis is primal feasible, then primal simplex pivots on the true costs until it is
+ * optimal.  What it measures is the NUMBER OF PIVOTS between a (repaired) predicted basis and the optimum.  Added after
+ * ABI 6 without a bump, as mllp_basis_repair was.
+ * THE RULE.  The LP of instance k is the one mllp_lp_certificate judges: min c'x, A_k x = b, x >= 0, c = d_x1, b = d_x2, A_k
+ * as the batch stores it now.  All arithmetic is fp32.
+ *   Start.  d_start [N] is a mask (nonzero = basic).  Its columns in ascending order are factorized by the rule of
+ *     mllp_basis_repair with `tol` (the list mllp_basis_repair gets from LPBatch.solve_basis).  A mask whose column count
+ *     differs from m: code 3.  Rank < m: code 1.  Nothing is pivoted in either case.  Otherwise T = B^-1, row i of T
+ *     belonging to the basic column col_of_row[i].
+ *   Every iteration recomputes from the current T:  x_B = T b;  y = T' g_B;  d_j = g_j - a_j.y for the nonbasic columns,
+ *     g the stage's cost vector.  Nothing is carried forward by updates except T itself.
+ *   Stage D (dual simplex on shifted costs).  Before the first iteration d0 is computed with g = c and
+ *     s_j = max(0, dshift - d0_j) for nonbasic j, 0 for basic j; ctilde = c + s stays fixed, so every nonbasic column starts
+ *     at a reduced cost >= dshift (not 0: the entering ratios would all be tied at 0).  Leaving row: p minimises x_B, the
+ *     lowest row among equal values.  x_B,p >= -ftol ends stage D; it is never re-entered.  With rho = row p of T and
+ *     alpha_j = rho.a_j over the nonbasic j, the candidates are alpha_j < -ptol; none: code 4 (primal infeasible), stop.
+ *     Entering: j minimises max(dtilde_j, 0) / (-alpha_j), the lowest j among equal ratios.
+ *   Stage P (primal simplex on the true c).  Entering: j minimises d_j, the lowest j among equals (Dantzig).
+ *     d_j >= -dtol: code 0 (optimal), stop.  w = T a_j; the candidates are the rows with w_i > ptol; none: code 5
+ *     (unbounded), stop.  Leaving row: p minimises max(x_B,i, 0) / w_i, the lowest row among equals.
+ *   Pivot, in either stage.  w = T a_j; row p of T is divided by w_p; T[i][:] -= w_i T[p][:] for i != p (the update of
+ *     mllp_basis_repair, over all m stored columns); col_of_row[p] = j.
+ *   Limits.  A pivot that would be number max_pivots + 1 ends the instance with code 6 (codes 0, 4 and 5 come first: they
+ *     need no pivot).  m > max_m: code 2, as in mllp_basis_repair; values of max_m above 4096 mean 4096.
+ *   Determinism.  Every argmin is ONE integer min over the keys {bits of the non-negative ratio, or the order-preserving
+ *     key of x_B / d; index}.  Every sum has an order that depends on the instance alone (a column's entries in ascending
+ *     row order; T b by ascending column; T' g_B by lanes, then the butterfly of the wavefront).  No float atomics.  An
+ *     instance gives the same bits alone and inside any batch, with T in LDS or in scratch.
+ * WHAT THE RULE DOES NOT CLAIM.  It has no anti-cycling device; pricing is Dantzig and there are no Harris ratios; T is
+ * updated in product form and never refactorized.  It is an evaluation tool for up to a few hundred pivots on instances of
+ * m up to a few thousand, not a production LP solver: degenerate LPs (most of Netlib) may stop with code 6.
+ *   tol                        : mllp_basis_repair's, finite and >= 0.
+ *   ftol, dtol, ptol, dshift   : finite and > 0; parameters of the rule in the units of the stored LP, like tol -- not
+ *             measured bars.  (The Python defaults: ftol = dtol = ptol = 2^-10, dshift = 2^-4.)
+ *   d_x1 [N] = c, d_x2 [M] = b, d_start [N] : inputs, never written; d_start must not overlap an output.
+ *   d_basis [N] float 0/1, required : the basis at the stop for codes 0, 4, 5 and 6 (the kernel keeps it current and reads
+ *             it back to tell basic from nonbasic columns).
+ *   d_col_of_row [M] int32 or NULL : the local id of the basic column that owns row i of T at the stop.
+ *   d_trace [n_inst, max_pivots, 2] int32 or NULL : {entering local column, leaving row} of every pivot, -1 past the end.
+ *   d_status [n_inst, 4] int32, required : {code, stage-D pivots, stage-P pivots, rank of the start}.
+ *             code 0: optimal;  1: the start is singular;  2: skipped, m > max_m;  3: the mask does not have m columns;
+ *             4: primal infeasible;  5: unbounded;  6: max_pivots reached.  For codes 1, 2 and 3 the outputs are basis
+ *             zeros, col_of_row -1, trace -1 (rank of the start: the rank found for code 1, 0 for codes 2 and 3).
+ *   d_scratch : mllp_basis_simplex_scratch_bytes(g, max_m) bytes: for every instance with m <= max_m, n words (the shifts)
+ *             and, with m > 192, m^2 words more (smaller ones keep T in LDS); may be NULL when that is 0.
+ * x and y are deliberately not outputs: mllp_basis_repair on the final basis (LPBatch.solve_basis) gives them from a FRESH
+ * factorization, which is also the refactorization the product-form T never gets.
+ * Every requested output is fully written for every instance.  A launch function: `stream` only, no allocation, no
+ * synchronisation, hipGraph-capturable; one workgroup per instance; six workgroup barriers per pivot.  It reads the
+ * graph's plain CSR(A^T) only.  The kernel's six vectors of m words stay in LDS (6 * 4096 words = 96 KB: the row limit);
+ * T is DENSE.  Under the MEMORY CONTRACT below.
+ * MLLP_EINVAL before any launch, nothing written: null g, d_x1, d_x2, d_start, d_basis or d_status; tol not finite or < 0;
+ * ftol, dtol, ptol or dshift not finite or <= 0; max_pivots < 0; max_m < 0; null d_scratch with a non-zero scratch size. */
+int mllp_basis_simplex_scratch_bytes(const mllp_graph_t* g, int64_t max_m, int64_t* bytes);
+int mllp_basis_simplex(const mllp_graph_t* g, const float* d_x1 /*c [N]*/, const float* d_x2 /*b [M]*/,
+                       const float* d_start /*[N] mask*/, float tol, float ftol, float dtol, float ptol, float dshift,
+                       int64_t max_pivots, int64_t max_m, float* d_basis /*[N] 0/1, required*/,
+                       int32_t* d_col_of_row /*[M] or NULL*/, int32_t* d_trace /*[n_inst, max_pivots, 2] or NULL*/,
+                       int32_t* d_status /*[n_inst, 4], required*/, void* d_scratch, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Plain CSR SpMM (the roofline kernel named in BASELINE.json's metric):
  *   transpose == 0:  Y[M,16] = A   * H[N,16]       transpose == 1:  Y[N,16] = A^T * H[M,16]
@@ -405,7 +466,7 @@ int mllp_tconv_bwd(const mllp_graph_t* g, int dst_is_var, int cin, const float* 
  *   d_ws     : mllp_gnn_workspace_bytes() bytes, kept between forward and backward
  *   d_logits [N] : per-variable logits (methods.py:250-251)
  * MEMORY CONTRACT of every mllp_gnn_*, mllp_tconv_*, mllp_spmm_*, mllp_weighted_loss, mllp_balanced_pos_weight, mllp_topm_*,
- * mllp_graph_normalize, mllp_graph_plant_basis, mllp_lp_certificate and mllp_basis_repair call, for every buffer the caller owns (tests/test_memory_contract.py):
+ * mllp_graph_normalize, mllp_graph_plant_basis, mllp_lp_certificate, mllp_basis_repair and mllp_basis_simplex call, for every buffer the caller owns (tests/test_memory_contract.py):
  *   1. A call's outputs do not depend on any byte that d_ws, or any other scratch or output buffer, held before the call:
  *      the buffers may be uninitialised, NaN included, and the same bits come out.  The only state carried between calls is
  *      what this header names: mllp_gnn_forward -> mllp_gnn_backward / _backward_inputs / _input_grads on the same workspace
@@ -425,7 +486,7 @@ int mllp_tconv_bwd(const mllp_graph_t* g, int dst_is_var, int cin, const float* 
  *      pieces --, as must every pointer of mllp_tconv_fwd / _bwd except d_param_grads (rows of 16 floats; d_ws, d_conv_params)
  *      and d_H, d_Y of mllp_spmm_csr_f32.  A misaligned one is refused with MLLP_EINVAL and a message before any HIP call,
  *      nothing written.  d_logits, d_labels, d_loss, d_grads, d_dlogits, d_dx1, d_dx2, d_dvalues, d_scratch, the optimizer
- *      buffers, the per-instance arrays and the buffers of the loss-head, top-m, normalize and basis-repair calls need only the natural
+ *      buffers, the per-instance arrays and the buffers of the loss-head, top-m, normalize, basis-repair and basis-simplex calls need only the natural
  *      alignment of their element type.
  * mllp_gnn_backward: d_dlogits [N] -> d_grads [MLLP_NUM_PARAMS] (overwritten; the never-called
  *   gconv3_s2w block, methods.py:248, is written as zeros).

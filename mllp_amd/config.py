@@ -38,6 +38,8 @@ HOT_PATH_DEFAULTS = {
                              # instances (the trained ones without `holdout`) is repaired into a basis, solved and certified on
                              # the device, and train_log.json gains the counts usable / feasible / optimal / skipped (m > max_m;
                              # max_m absent == none skipped); None == not computed, the log as before
+                             # `pivots: K` in the block adds optimal_after_pivots / pivots: the repaired prediction pivoted to
+                             # the optimum with at most K simplex pivots per instance (LPBatch.simplex), and their total
 }
 
 

@@ -418,6 +418,17 @@ constexpr int BASIS_MAX_M = 8192;
 __host__ __device__ constexpr int64_t basis_repair_vec_words(int64_t m) { return 4 * m; }       // w, prow, crow, piv
 __host__ __device__ constexpr int64_t basis_repair_words(int64_t m) { return m * m; }           // scratch of one instance: T
 
+// ---- basis simplex (simplex.hip): the same transform, pivoted on; six vectors of m words, all in LDS ---------------------
+// Constants of this kernel alone (basis repair keeps its own).  T in LDS up to 192 rows: 192^2 + 6 * 192 words = 152 064
+// bytes, beside under 1 KB of static LDS, within the 160 KB of a workgroup.  Above it T is in the caller's scratch and the
+// vectors bound the rows: 6 * 4096 words = 96 KB.  Every instance that runs also takes n words of scratch (the shifts).
+constexpr int SIMPLEX_LDS_MAX_M = 192;
+constexpr int SIMPLEX_MAX_M = 4096;
+__host__ __device__ constexpr int64_t simplex_vec_words(int64_t m) { return 6 * m; }    // w, staged row / rho, col of row, x_B, y, g_B
+__host__ __device__ constexpr int64_t simplex_words(int64_t m, int64_t n) {              // scratch of one instance: T, shifts
+    return (m > SIMPLEX_LDS_MAX_M ? m * m : 0) + n;
+}
+
 // ---- fused latency-regime path of the whole model (fused_kernels.hip) ---------------------------------
 // one whole-model call: the flat parameters, the carved workspace, the call's inputs (labels, logits: null where unused)
 struct FusedModel {

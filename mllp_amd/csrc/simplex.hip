@@ -1,0 +1,464 @@
+// simplex.hip -- a basis mask -> the optimal basis by dual, then primal simplex pivots on the explicit inverse
+// (mllp_basis_simplex; the rule is stated in include/mllp_hip.h, the design in DESIGN.md 4.15).
+//
+// One workgroup per instance.  The start is factorized exactly as basis.hip does it (the same gather, keys, staged row and
+// update, duplicated here so that basis_repair_kernel stays what it is); with rank m every column of T has been pivoted, so
+// from then on T = B^-1 is a full m x m matrix, row i belonging to the basic column crow[i].  An iteration:
+//   S1  g_B[i] = g[crow[i]];  x_B[p] = sum_c T[p][c] b_c, c ascending, a thread per p; stage D: the leaving row is the
+//       integer min over {order key of x_B[p], p}.                                                             barrier
+//   S2  y_c = sum_p T[p][c] g_B[p], a wavefront per c: lane l adds p = l, l + 64, ..., then group_sum<64>; stage D: rho =
+//       row p of T, into the staged row's storage.                                                             barrier
+//   S3  pricing, a thread per nonbasic column over its CSR(A^T) entries (ascending row): d_j = g_j - a_j.y and, stage D,
+//       alpha_j = a_j.rho; the key {bits of the ratio | order key of d_j, j} reduced by wave shuffles, one LDS word per
+//       wavefront.  No per-column array.                                                                       barrier
+//   S4  w = T a_j, a thread per row (repair's gather); stage P: the ratio test, key {bits of max(x_B,i, 0) / w_i, i}.
+//                                                                                                              barrier
+//   S5  the staged row: row p of T (stage D: rho) divided by w_p.                                              barrier
+//   S6  T[i][:] -= w_i * staged row for i != p, row p = the staged row: a column per wavefront, rows over the lanes; then
+//       crow[p] = j, d_basis and the trace follow (one thread).                                                barrier
+// Six barriers per pivot in either stage.  T is COLUMN-MAJOR (element (i, c) at c * m + i): S1, S4 and S6 walk i with the
+// lanes.  IN_LDS: T in LDS up to SIMPLEX_LDS_MAX_M rows, in the caller's scratch above -- the same code, instantiated twice,
+// each with one address space for T.  The six vectors are in LDS in both.  The shifts s [n] are in scratch: read once per
+// iteration, coalesced.  Whether a column is basic is read from d_basis, which the kernel keeps current.
+// No float atomics; every sum has an order that depends on the instance alone: the same bits alone and inside any batch.
+#include <cmath>
+
+#include "device_utils.h"
+#include "internal.h"
+
+namespace mllp {
+
+namespace {
+
+constexpr int SX_T_LDS = 256, SX_T_GLB = 1024;      // threads of a workgroup, T in LDS / in scratch
+constexpr int SX_UNROLL = 4;
+constexpr int SX_OPTIMAL = 0, SX_SINGULAR = 1, SX_SKIPPED = 2, SX_BAD_MASK = 3, SX_INFEASIBLE = 4, SX_UNBOUNDED = 5, SX_LIMIT = 6;
+constexpr unsigned long long SX_NONE = ~0ull;       // the key of an empty candidate set
+
+__device__ __forceinline__ unsigned long long sx_wave_max(unsigned long long v) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned long long u = (unsigned long long)__shfl_xor((long long)v, o, 64);
+        v = u > v ? u : v;
+    }
+    return v;
+}
+__device__ __forceinline__ unsigned long long sx_wave_min(unsigned long long v) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned long long u = (unsigned long long)__shfl_xor((long long)v, o, 64);
+        v = u < v ? u : v;
+    }
+    return v;
+}
+// min over the workgroup, the same word in every thread.  One barrier; `slot` [NW] is free again after the NEXT barrier.
+template <int NW>
+__device__ __forceinline__ unsigned long long sx_block_min(unsigned long long v, unsigned long long* slot) {
+    v = sx_wave_min(v);
+    if ((threadIdx.x & 63) == 0) slot[threadIdx.x >> 6] = v;
+    __syncthreads();
+    v = SX_NONE;
+#pragma unroll
+    for (int q = 0; q < NW; ++q) v = slot[q] < v ? slot[q] : v;
+    return v;
+}
+// unsigned keys in the order of the floats (-0.0 below +0.0), and back
+__device__ __forceinline__ unsigned sx_order_key(float d) {
+    const unsigned u = __float_as_uint(d);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float sx_key_value(unsigned k) {
+    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+
+struct SimplexArgs {
+    const int* __restrict__ ptr_m;
+    const int* __restrict__ ptr_n;
+    const int* __restrict__ at_ptr;     // CSR(A^T)
+    const int* __restrict__ at_idx;
+    const float* __restrict__ at_val;
+    const float* __restrict__ c;
+    const float* __restrict__ b;
+    const float* __restrict__ start;
+    float tol, ftol, dtol, ptol, dshift;
+    long long max_pivots, max_m;
+    float* basis;
+    int* col_of_row;
+    int* trace;
+    int* status;
+    float* scratch;
+};
+
+template <bool IN_LDS, int NT>
+__global__ __launch_bounds__(NT) void basis_simplex_kernel(const SimplexArgs A) {
+    constexpr int NW = NT / 64;
+    extern __shared__ float sx_lds[];
+    __shared__ unsigned long long s_fkey[2][NW];    // the factorization's pivot search
+    __shared__ unsigned long long s_key[3][NW];     // leaving row (D), pricing, ratio test (P)
+    __shared__ long long s_off[NW];
+    __shared__ int s_cnt[NW];
+    const int k = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int row0 = A.ptr_m[k], m = A.ptr_m[k + 1] - row0;
+    const int col0 = A.ptr_n[k], n = A.ptr_n[k + 1] - col0;
+    if ((m <= SIMPLEX_LDS_MAX_M) != IN_LDS) return;     // the other launch's instance
+    int* st = A.status + 4 * (size_t)k;
+    // defaults of the outputs; a running instance writes them again behind at least one barrier
+    for (int j = tid; j < n; j += NT) A.basis[col0 + j] = 0.0f;
+    if (A.trace) {
+        int* tr = A.trace + 2 * (size_t)k * (size_t)A.max_pivots;
+        for (long long q = tid; q < 2 * A.max_pivots; q += NT) tr[q] = -1;
+    }
+    int count = 0;
+    if ((long long)m <= A.max_m) {
+        for (int j = tid; j < n; j += NT) count += A.start[col0 + j] != 0.0f;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) count += __shfl_xor(count, o, 64);
+        if (lane == 0) s_cnt[wave] = count;
+        __syncthreads();
+        count = 0;
+#pragma unroll
+        for (int v = 0; v < NW; ++v) count += s_cnt[v];
+    }
+    if ((long long)m > A.max_m || count != m) {
+        for (int i = tid; i < m; i += NT)
+            if (A.col_of_row) A.col_of_row[row0 + i] = -1;
+        if (tid == 0) { st[0] = (long long)m > A.max_m ? SX_SKIPPED : SX_BAD_MASK; st[1] = 0; st[2] = 0; st[3] = 0; }
+        return;
+    }
+    // this instance's piece of the scratch: behind those of the earlier instances that may run (integer sum: exact)
+    long long off = 0;
+    for (int j = tid; j < k; j += NT) {
+        const long long mj = A.ptr_m[j + 1] - A.ptr_m[j], nj = A.ptr_n[j + 1] - A.ptr_n[j];
+        if (mj <= A.max_m) off += simplex_words(mj, nj);
+    }
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) off += __shfl_xor(off, o, 64);
+    if (lane == 0) s_off[wave] = off;
+    __syncthreads();
+    off = 0;
+#pragma unroll
+    for (int v = 0; v < NW; ++v) off += s_off[v];
+    float* T;                                       // [m][m] column-major
+    float* w;                                       // [m] T a_j
+    float* sh;                                      // [n] the shifts of stage D
+    if constexpr (IN_LDS) {
+        T = sx_lds;
+        w = sx_lds + (size_t)m * m;
+        sh = A.scratch + off;
+    } else {
+        T = A.scratch + off;
+        w = sx_lds;
+        sh = A.scratch + off + (size_t)m * m;
+    }
+    float* prow = w + m;                            // [m] the staged pivot row; rho (row p of T) before it in stage D
+    int* crow = reinterpret_cast<int*>(prow + m);   // [m] local column whose row this is, or -1
+    float* xB = reinterpret_cast<float*>(crow + m); // [m] T b
+    int* piv = reinterpret_cast<int*>(xB);          //     (the factorization's pivoted rows in order, before there is an x_B)
+    float* yv = xB + m;                             // [m] T' g_B
+    float* gB = yv + m;                             // [m] the stage's costs of the basic columns
+    for (int i = tid; i < m; i += NT) crow[i] = -1;
+    __syncthreads();
+
+    // ---- the start: the rule of mllp_basis_repair on the mask's columns in ascending order (basis.hip) ------------------
+    int rank = 0, par = 0;
+    for (int j = 0; j < n && rank < m; ++j) {
+        if (A.start[col0 + j] == 0.0f) continue;
+        const int beg = A.at_ptr[col0 + j], end = A.at_ptr[col0 + j + 1];
+        float amax = 0.0f;
+        for (int e = beg; e < end; ++e) amax = fmaxf(amax, fabsf(A.at_val[e]));
+        unsigned long long best = 0ull;             // (every row that is not pivoted has a key above 0)
+        for (int i = tid; i < m; i += NT) {
+            float acc = 0.0f;
+            for (int e = beg; e < end; ++e) {
+                const int r = A.at_idx[e] - row0;
+                const float a = A.at_val[e];
+                if (crow[r] >= 0) acc = __fmaf_rn(a, T[(size_t)r * m + i], acc);
+                else if (r == i) acc = __fadd_rn(acc, a);
+            }
+            w[i] = acc;
+            if (crow[i] < 0) {
+                const unsigned long long key = ((unsigned long long)__float_as_uint(fabsf(acc)) << 32) | (unsigned)(0x7fffffff - i);
+                best = key > best ? key : best;
+            }
+        }
+        best = sx_wave_max(best);
+        if (lane == 0) s_fkey[par][wave] = best;
+        __syncthreads();        // (also: every w_i is written)
+        best = 0ull;
+#pragma unroll
+        for (int v = 0; v < NW; ++v) best = s_fkey[par][v] > best ? s_fkey[par][v] : best;
+        par ^= 1;               // (this buffer is written again two candidates on: a barrier lies between)
+        const float r = __uint_as_float((unsigned)(best >> 32));
+        const int p = 0x7fffffff - (int)(unsigned)(best & 0xffffffffull);
+        if (!(amax > 0.0f && r > __fmul_rn(A.tol, amax))) continue;     // (no barrier: nobody reads another thread's w_i)
+        const float wp = w[p];
+        for (int q = tid; q <= rank; q += NT)
+            prow[q] = q < rank ? __fdiv_rn(T[(size_t)piv[q] * m + p], wp) : __fdiv_rn(1.0f, wp);
+        __syncthreads();
+        for (int q = wave; q <= rank; q += NW) {    // a column per wavefront, the rows over its lanes
+            const float pc = prow[q];
+            const bool fresh = q == rank;           // column p was e_p until now
+            if (!fresh && pc == 0.0f) continue;
+            float* col = T + (size_t)(fresh ? p : piv[q]) * m;
+            for (int i0 = lane; i0 < m; i0 += 64 * SX_UNROLL) {
+                float tv[SX_UNROLL], wv[SX_UNROLL];
+#pragma unroll
+                for (int u = 0; u < SX_UNROLL; ++u) {
+                    const int i = i0 + 64 * u;
+                    wv[u] = i < m ? w[i] : 0.0f;
+                    tv[u] = (i < m && !fresh) ? col[i] : 0.0f;
+                }
+#pragma unroll
+                for (int u = 0; u < SX_UNROLL; ++u) {
+                    const int i = i0 + 64 * u;
+                    if (i >= m) continue;
+                    if (i == p) col[i] = pc;
+                    else if (fresh || wv[u] != 0.0f) col[i] = __fmaf_rn(-wv[u], pc, tv[u]);
+                }
+            }
+        }
+        if (tid == 0) {
+            piv[rank] = p;
+            crow[p] = j;
+        }
+        ++rank;
+        __syncthreads();
+    }
+    if (rank < m) {
+        for (int i = tid; i < m; i += NT)
+            if (A.col_of_row) A.col_of_row[row0 + i] = -1;
+        if (tid == 0) { st[0] = SX_SINGULAR; st[1] = 0; st[2] = 0; st[3] = rank; }
+        return;
+    }
+    for (int i = tid; i < m; i += NT) A.basis[col0 + crow[i]] = 1.0f;
+
+    // y = T' g_B: a wavefront per column of T
+    auto dual = [&]() {
+        for (int cc = wave; cc < m; cc += NW) {
+            const float* col = T + (size_t)cc * m;
+            float acc = 0.0f;
+            for (int p = lane; p < m; p += 64) acc = __fmaf_rn(col[p], gB[p], acc);
+            acc = group_sum<64>(acc);
+            if (lane == 0) yv[cc] = acc;
+        }
+    };
+
+    // ---- the shifts: s_j = max(0, dshift - d0_j) off the basis, 0 on it, d0 the reduced costs of c ------------------------
+    for (int i = tid; i < m; i += NT) gB[i] = A.c[col0 + crow[i]];
+    __syncthreads();            // (also: d_basis holds the start)
+    dual();
+    __syncthreads();
+    for (int j = tid; j < n; j += NT) {
+        float s = 0.0f;
+        if (A.basis[col0 + j] == 0.0f) {
+            float ay = 0.0f;
+            for (int e = A.at_ptr[col0 + j]; e < A.at_ptr[col0 + j + 1]; ++e) ay = __fmaf_rn(A.at_val[e], yv[A.at_idx[e] - row0], ay);
+            const float t = __fsub_rn(A.dshift, __fsub_rn(A.c[col0 + j], ay));
+            s = t > 0.0f ? t : 0.0f;
+        }
+        sh[j] = s;
+    }
+    __syncthreads();
+
+    // ---- the pivots ---------------------------------------------------------------------------------------------------------
+    int stage = 0, code = SX_LIMIT;
+    long long nD = 0, nP = 0;
+    int* tr = A.trace ? A.trace + 2 * (size_t)k * (size_t)A.max_pivots : nullptr;
+    while (true) {
+        // S1
+        for (int i = tid; i < m; i += NT) {
+            const int j = crow[i];
+            const float g = A.c[col0 + j];
+            gB[i] = stage == 0 ? __fadd_rn(g, sh[j]) : g;
+        }
+        unsigned long long best = SX_NONE;
+        for (int p = tid; p < m; p += NT) {
+            float acc = 0.0f;
+#pragma unroll 8
+            for (int cc = 0; cc < m; ++cc) acc = __fmaf_rn(T[(size_t)cc * m + p], A.b[row0 + cc], acc);
+            xB[p] = acc;
+            const unsigned long long key = ((unsigned long long)sx_order_key(acc) << 32) | (unsigned)p;
+            best = key < best ? key : best;
+        }
+        int p = -1;
+        if (stage == 0) {
+            best = sx_block_min<NW>(best, s_key[0]);
+            if (best == SX_NONE || !(sx_key_value((unsigned)(best >> 32)) < -A.ftol)) {
+                stage = 1;          // primal feasible: stage D is over for good; S1 once more with the true costs
+                continue;           // (nothing S1 writes is read before its barrier, and s_key[0] is not written again)
+            }
+            p = (int)(unsigned)(best & 0xffffffffull);
+        } else {
+            __syncthreads();
+        }
+        // S2
+        dual();
+        if (stage == 0)
+            for (int cc = tid; cc < m; cc += NT) prow[cc] = T[(size_t)cc * m + p];
+        __syncthreads();
+        // S3
+        best = SX_NONE;
+        for (int j = tid; j < n; j += NT) {
+            if (A.basis[col0 + j] != 0.0f) continue;
+            const int beg = A.at_ptr[col0 + j], end = A.at_ptr[col0 + j + 1];
+            float ay = 0.0f, ar = 0.0f;
+            for (int e = beg; e < end; ++e) {
+                const int r = A.at_idx[e] - row0;
+                const float a = A.at_val[e];
+                ay = __fmaf_rn(a, yv[r], ay);
+                if (stage == 0) ar = __fmaf_rn(a, prow[r], ar);
+            }
+            float g = A.c[col0 + j];
+            if (stage == 0) g = __fadd_rn(g, sh[j]);
+            const float d = __fsub_rn(g, ay);
+            unsigned long long key = SX_NONE;
+            if (stage == 0) {
+                if (ar < -A.ptol) key = ((unsigned long long)__float_as_uint(__fdiv_rn(d > 0.0f ? d : 0.0f, -ar)) << 32) | (unsigned)j;
+            } else {
+                key = ((unsigned long long)sx_order_key(d) << 32) | (unsigned)j;
+            }
+            best = key < best ? key : best;
+        }
+        best = sx_block_min<NW>(best, s_key[1]);
+        if (stage == 0 && best == SX_NONE) { code = SX_INFEASIBLE; break; }
+        if (stage == 1 && (best == SX_NONE || !(sx_key_value((unsigned)(best >> 32)) < -A.dtol))) { code = SX_OPTIMAL; break; }
+        const int j = (int)(unsigned)(best & 0xffffffffull);
+        // S4
+        const int beg = A.at_ptr[col0 + j], end = A.at_ptr[col0 + j + 1];
+        best = SX_NONE;
+        for (int i = tid; i < m; i += NT) {
+            float acc = 0.0f;
+            for (int e = beg; e < end; ++e) acc = __fmaf_rn(A.at_val[e], T[(size_t)(A.at_idx[e] - row0) * m + i], acc);
+            w[i] = acc;
+            if (stage == 1 && acc > A.ptol) {
+                const float x = xB[i];
+                const unsigned long long key = ((unsigned long long)__float_as_uint(__fdiv_rn(x > 0.0f ? x : 0.0f, acc)) << 32) | (unsigned)i;
+                best = key < best ? key : best;
+            }
+        }
+        if (stage == 1) {
+            best = sx_block_min<NW>(best, s_key[2]);
+            if (best == SX_NONE) { code = SX_UNBOUNDED; break; }
+            p = (int)(unsigned)(best & 0xffffffffull);
+        } else {
+            __syncthreads();
+        }
+        if (nD + nP >= A.max_pivots) { code = SX_LIMIT; break; }
+        // S5
+        const float wp = w[p];
+        for (int cc = tid; cc < m; cc += NT) prow[cc] = __fdiv_rn(stage == 0 ? prow[cc] : T[(size_t)cc * m + p], wp);
+        __syncthreads();
+        // S6
+        for (int cc = wave; cc < m; cc += NW) {     // a column per wavefront, the rows over its lanes
+            const float pc = prow[cc];
+            if (pc == 0.0f) continue;               // (row p holds a zero here already; every other row keeps its bits)
+            float* col = T + (size_t)cc * m;
+            for (int i0 = lane; i0 < m; i0 += 64 * SX_UNROLL) {
+                float tv[SX_UNROLL], wv[SX_UNROLL];
+#pragma unroll
+                for (int u = 0; u < SX_UNROLL; ++u) {
+                    const int i = i0 + 64 * u;
+                    wv[u] = i < m ? w[i] : 0.0f;
+                    tv[u] = i < m ? col[i] : 0.0f;
+                }
+#pragma unroll
+                for (int u = 0; u < SX_UNROLL; ++u) {
+                    const int i = i0 + 64 * u;
+                    if (i >= m) continue;
+                    if (i == p) col[i] = pc;
+                    else if (wv[u] != 0.0f) col[i] = __fmaf_rn(-wv[u], pc, tv[u]);
+                }
+            }
+        }
+        if (tid == 0) {
+            A.basis[col0 + crow[p]] = 0.0f;
+            A.basis[col0 + j] = 1.0f;
+            crow[p] = j;
+            if (tr) { tr[2 * (nD + nP)] = j; tr[2 * (nD + nP) + 1] = p; }
+        }
+        if (stage == 0) ++nD;
+        else ++nP;
+        __syncthreads();
+    }
+    for (int i = tid; i < m; i += NT)
+        if (A.col_of_row) A.col_of_row[row0 + i] = crow[i];
+    if (tid == 0) { st[0] = code; st[1] = (int)nD; st[2] = (int)nP; st[3] = m; }
+}
+
+// what a call needs, from the host copy of the instance offsets
+struct SimplexPlan {
+    int64_t words = 0;      // scratch, in 4-byte words
+    int64_t lds_m = 0;      // the largest m that runs with T in LDS
+    int64_t glb_m = 0;      // ... with T in scratch
+    bool any_lds = false, any_glb = false;      // which launches have an instance (a skipped one included)
+};
+SimplexPlan simplex_plan(const mllp_graph_t* g, int64_t max_m) {
+    SimplexPlan p;
+    max_m = std::min<int64_t>(max_m, SIMPLEX_MAX_M);
+    for (int64_t k = 0; k < g->n_inst && k + 1 < (int64_t)g->h_inst_ptr_m.size() && k + 1 < (int64_t)g->h_inst_ptr_n.size(); ++k) {
+        const int64_t m = g->h_inst_ptr_m[k + 1] - g->h_inst_ptr_m[k], n = g->h_inst_ptr_n[k + 1] - g->h_inst_ptr_n[k];
+        (m <= SIMPLEX_LDS_MAX_M ? p.any_lds : p.any_glb) = true;
+        if (m > max_m) continue;
+        p.words += simplex_words(m, n);
+        if (m <= SIMPLEX_LDS_MAX_M) p.lds_m = std::max(p.lds_m, m);
+        else p.glb_m = std::max(p.glb_m, m);
+    }
+    return p;
+}
+
+}  // namespace
+
+}  // namespace mllp
+
+using namespace mllp;
+
+extern "C" int mllp_basis_simplex_scratch_bytes(const mllp_graph_t* g, int64_t max_m, int64_t* bytes) {
+    REQUIRE(g && bytes, "null argument");
+    REQUIRE(max_m >= 0, "max_m must not be negative");
+    *bytes = simplex_plan(g, max_m).words * (int64_t)sizeof(float);
+    return MLLP_OK;
+}
+
+extern "C" int mllp_basis_simplex(const mllp_graph_t* g, const float* d_x1, const float* d_x2, const float* d_start, float tol,
+                                  float ftol, float dtol, float ptol, float dshift, int64_t max_pivots, int64_t max_m,
+                                  float* d_basis, int32_t* d_col_of_row, int32_t* d_trace, int32_t* d_status, void* d_scratch,
+                                  void* stream) {
+    REQUIRE(g && d_x1 && d_x2 && d_start && d_basis && d_status,
+            "null argument (g, d_x1, d_x2, d_start, d_basis and d_status are required)");
+    REQUIRE(std::isfinite(tol) && tol >= 0.0f, "tol must be finite and not negative");
+    REQUIRE(std::isfinite(ftol) && ftol > 0.0f && std::isfinite(dtol) && dtol > 0.0f && std::isfinite(ptol) && ptol > 0.0f &&
+                std::isfinite(dshift) && dshift > 0.0f,
+            "ftol, dtol, ptol and dshift must be finite and positive");
+    REQUIRE(max_pivots >= 0, "max_pivots must not be negative");
+    REQUIRE(max_m >= 0, "max_m must not be negative");
+    const SimplexPlan plan = simplex_plan(g, max_m);
+    REQUIRE(plan.words == 0 || d_scratch, "null d_scratch (mllp_basis_simplex_scratch_bytes is not 0)");
+    if (g->n_inst <= 0) return MLLP_OK;
+    hipStream_t s = (hipStream_t)stream;
+    max_m = std::min<int64_t>(max_m, SIMPLEX_MAX_M);
+    const SimplexArgs args = {g->inst_ptr_m, g->inst_ptr_n, g->At.ptr, g->At.idx, g->At.val, d_x1, d_x2, d_start, tol, ftol, dtol, ptol,
+                              dshift, (long long)max_pivots, (long long)max_m, d_basis, d_col_of_row, d_trace, d_status,
+                              static_cast<float*>(d_scratch)};
+    int rc;
+    if (plan.any_lds) {
+        // once per process: the kernel may take more dynamic LDS than the default limit (no stream operation)
+        static const hipError_t attr =
+            hipFuncSetAttribute(reinterpret_cast<const void*>(basis_simplex_kernel<true, SX_T_LDS>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)((SIMPLEX_LDS_MAX_M * SIMPLEX_LDS_MAX_M + simplex_vec_words(SIMPLEX_LDS_MAX_M)) * sizeof(float)));
+        if (attr != hipSuccess) return hip_fail(attr, "basis_simplex: hipFuncSetAttribute");
+        const size_t lds = (size_t)std::max<int64_t>(plan.lds_m * plan.lds_m + simplex_vec_words(plan.lds_m), 1) * sizeof(float);
+        hipLaunchKernelGGL((basis_simplex_kernel<true, SX_T_LDS>), dim3((unsigned)g->n_inst), dim3(SX_T_LDS), lds, s, args);
+        if ((rc = check_launch("basis_simplex (LDS)"))) return rc;
+    }
+    if (plan.any_glb) {
+        static const hipError_t attr =
+            hipFuncSetAttribute(reinterpret_cast<const void*>(basis_simplex_kernel<false, SX_T_GLB>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)(simplex_vec_words(SIMPLEX_MAX_M) * sizeof(float)));
+        if (attr != hipSuccess) return hip_fail(attr, "basis_simplex: hipFuncSetAttribute");
+        const size_t lds = (size_t)std::max<int64_t>(simplex_vec_words(plan.glb_m), 1) * sizeof(float);
+        hipLaunchKernelGGL((basis_simplex_kernel<false, SX_T_GLB>), dim3((unsigned)g->n_inst), dim3(SX_T_GLB), lds, s, args);
+        if ((rc = check_launch("basis_simplex (scratch)"))) return rc;
+    }
+    return MLLP_OK;
+}

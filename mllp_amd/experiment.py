@@ -119,7 +119,7 @@ def run_epochs(cfg, instances, train_dict, trainer, batches, rank, world, device
         obj_sum = torch.zeros(1, device=device)
         logging = epoch % log_every == 0
         table = torch.zeros(len(instances), 2, device=device) if logging else None
-        train_solved = torch.zeros(len(SOLVED_KEYS), device=device) if logging and report is not None and not n_holdout else None
+        train_solved = torch.zeros(len(report_keys(report)), device=device) if logging and report is not None and not n_holdout else None
         for mine, b, gcount in batches:
             if b is None:      # a rank without instances in this batch still joins the all-reduce
                 trainer.step_empty()
@@ -127,7 +127,7 @@ def run_epochs(cfg, instances, train_dict, trainer, batches, rank, world, device
             trainer.global_instances = gcount
             loss, step_logits = trainer.step(b)                                     # reference :124-144
             if train_solved is not None:            # (the logits of the step's forward, valid until the next step)
-                train_solved += solved_counts(b, step_logits, report).to(device)
+                train_solved += report_counts(b, step_logits, report).to(device)
             obj_sum += loss.to(device) * gcount     # loss is the batch mean over gcount instances (this rank's share)
             if logging:
                 table[torch.as_tensor(mine, device=device)] = trainer.metrics_of(b).to(device)
@@ -141,10 +141,10 @@ def run_epochs(cfg, instances, train_dict, trainer, batches, rank, world, device
                 table[torch.as_tensor(mine, device=device)] = ev["metrics"].to(device)
         solved = None
         if logging and report is not None:      # held-out instances, or the trained ones without a holdout
-            solved = train_solved if train_solved is not None else torch.zeros(len(SOLVED_KEYS), device=device)
+            solved = train_solved if train_solved is not None else torch.zeros(len(report_keys(report)), device=device)
             for _, b in (holdout if n_holdout else ()):
                 if b is not None:
-                    solved += solved_counts(b, trainer.evaluate(b)["logits"], report).to(device)
+                    solved += report_counts(b, trainer.evaluate(b)["logits"], report).to(device)
         if dist is not None:
             dist.all_reduce(obj_sum)
             if logging:
@@ -162,7 +162,7 @@ def run_epochs(cfg, instances, train_dict, trainer, batches, rank, world, device
                     out("%8d, %8d, %8d, %5f" % (correct_num, inst.m, inst.n, f1))
                 train_dict[inst.name].append(correct_num)
         if solved is not None:
-            for key, v in zip(SOLVED_KEYS, solved.cpu().tolist()):
+            for key, v in zip(report_keys(report), solved.cpu().tolist()):
                 train_dict.setdefault(key, []).append(int(v))
         train_dict["obj"].append(obj)                  # plain float: the reference's numpy.float32 breaks json.dump
         val_obj = None
@@ -191,6 +191,32 @@ def solved_counts(batch, logits, report):
     rep = batch.repair_basis(logits, max_m=report.get("max_m"), want=("basis", "x", "y"))
     got = batch.solved(rep, report["feas_tol"], report["opt_tol"])
     return torch.stack([got["usable"].sum(), got["primal_feasible"].sum(), got["optimal"].sum(), got["skipped"].sum()]).float()
+
+
+PIVOT_KEYS = ("optimal_after_pivots", "pivots")
+
+
+def pivot_counts(batch, logits, report):
+    """[2] device counts over a batch's instances, by PIVOT_KEYS, under `report_solved` {..., pivots: K}: the repaired
+    prediction pivoted to the optimum on the device (LPBatch.simplex, at most K pivots per instance), the final basis
+    factorized afresh and certified (LPBatch.simplex_solved) -- the instances certified optimal, and the pivots they took
+    in all.  No sync."""
+    max_m = report.get("max_m")
+    rep = batch.repair_basis(logits, max_m=max_m, want=("basis",))
+    res = batch.simplex(rep, int(report["pivots"]), max_m=max_m, want=())
+    got = batch.simplex_solved(res, report["feas_tol"], report["opt_tol"], max_m=max_m)
+    done = got["optimal"] & (res.status[:, 0] == 0)
+    return torch.stack([done.sum(), (got["pivots"] * done).sum()]).float()
+
+
+def report_keys(report):
+    """the keys `report_solved` adds to the log: SOLVED_KEYS, and PIVOT_KEYS when the block has `pivots`"""
+    return SOLVED_KEYS + (PIVOT_KEYS if report.get("pivots") is not None else ())
+
+
+def report_counts(batch, logits, report):
+    counts = solved_counts(batch, logits, report)
+    return counts if report.get("pivots") is None else torch.cat([counts, pivot_counts(batch, logits, report)])
 
 
 def train_method(cfg, method_name, train_dataset, train_dict, out=print):

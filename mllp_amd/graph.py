@@ -1019,6 +1019,57 @@ class LPBatch:
         optimal = feasible & (cert[:, 3] >= -opt_tol) & (cert[:, 4] <= opt_tol)
         return dict(usable=usable, primal_feasible=feasible, optimal=optimal, skipped=rep.status[:, 3] == 2, certificate=cert)
 
+    # ---- pivot a basis to optimality (mllp_basis_simplex; csrc/simplex.hip) ----------------------------------------
+    def simplex(self, start, max_pivots, tol=2.0 ** -12, ftol=2.0 ** -10, dtol=2.0 ** -10, ptol=2.0 ** -10, dshift=2.0 ** -4,
+                max_m=None, want=("basis", "col_of_row", "trace")):
+        """Dual, then primal simplex pivots from a basis to the optimum, on the device (mllp_basis_simplex; the rule is
+        stated in include/mllp_hip.h).  `start`: a mask tensor [N] (nonzero = basic) or a `BasisRepair`, whose `.basis` is
+        used.  `max_pivots`: the limit per instance (code 6 beyond it).  `tol` is `repair_basis`'; `ftol`, `dtol`, `ptol`,
+        `dshift` are the rule's feasibility, optimality and pivot tolerances and its cost shift, in the units of the stored
+        LP.  `max_m`: instances with more rows are skipped (code 2); None = the batch's largest m.  Returns a `BasisSimplex`
+        of device tensors; `col_of_row` and `trace` are None unless named in `want` (`basis` and `status` always come).  The
+        scratch is asked for once per max_m and kept on the batch.  No sync."""
+        want = (want,) if isinstance(want, str) else tuple(want)
+        names = ("basis", "col_of_row", "trace")
+        if [w for w in want if w not in names]:
+            raise ValueError(f"simplex: want names some of {names} (got {want!r})")
+        if isinstance(start, BasisRepair):
+            start = start.basis
+        if start is None or not (start.is_cuda and start.numel() == self.N):
+            raise ValueError(f"simplex: start must be a cuda tensor of {self.N} elements (or a BasisRepair with its basis)")
+        start = start.reshape(-1).to(torch.float32).contiguous()
+        max_pivots = int(max_pivots)
+        if max_pivots < 0:
+            raise ValueError("simplex: max_pivots must not be negative")
+        dev = self.x1.device
+        max_m = max(self.inst_m, default=0) if max_m is None else int(max_m)
+        kept = getattr(self, "_simplex_scratch", None)
+        if kept is None or kept[0] != max_m:
+            n = c_int64()
+            _lib.check(_lib.lib().mllp_basis_simplex_scratch_bytes(self._h, max_m, ctypes.byref(n)))
+            kept = self._simplex_scratch = (max_m, torch.empty(n.value // 4, device=dev, dtype=torch.float32) if n.value else None)
+        # (at least one element each: an empty torch tensor has a null pointer, which the library reads as "not wanted")
+        new = lambda n, dt: torch.empty(max(n, 1), dtype=dt, device=dev)      # noqa: E731
+        basis, status = new(self.N, torch.float32), new(self.n_inst * 4, torch.int32)
+        col_of_row = new(self.M, torch.int32) if "col_of_row" in want else None
+        trace = new(self.n_inst * max_pivots * 2, torch.int32) if "trace" in want else None
+        pad = lambda t: t if t.numel() else torch.zeros(1, dtype=torch.float32, device=dev)   # noqa: E731
+        _lib.check(_lib.lib().mllp_basis_simplex(self._h, _lib.ptr(pad(self.x1)), _lib.ptr(pad(self.x2)), _lib.ptr(pad(start)),
+                                                 float(tol), float(ftol), float(dtol), float(ptol), float(dshift), max_pivots, max_m,
+                                                 _lib.ptr(basis), _lib.ptr(col_of_row), _lib.ptr(trace), _lib.ptr(status),
+                                                 _lib.ptr(kept[1]), _lib.current_stream()))
+        return BasisSimplex(basis[:self.N], None if col_of_row is None else col_of_row[:self.M],
+                            None if trace is None else trace[:self.n_inst * max_pivots * 2].view(self.n_inst, max_pivots, 2),
+                            status[:self.n_inst * 4].view(self.n_inst, 4))
+
+    def simplex_solved(self, res, feas_tol, opt_tol, tol=2.0 ** -12, max_m=None):
+        """What a `BasisSimplex` is worth: `solve_basis(res.basis)` -- a FRESH factorization of the final basis, which the
+        product-form pivots never got -- then `solved` (the certificate).  The dict of `solved`, and `pivots`: stage-D +
+        stage-P pivots per instance (int32 [n_inst]).  No sync."""
+        got = self.solved(self.solve_basis(res.basis, tol=tol, max_m=max_m, want=("basis", "x", "y")), feas_tol, opt_tol)
+        got["pivots"] = res.status[:, 1] + res.status[:, 2]
+        return got
+
 
 def _select_outputs(want, n, m, n_seg, dev):
     """(mask, index, stats) buffers of the select entry points, None where not wanted.  At least one element each: an
@@ -1063,6 +1114,17 @@ class BasisRepair:
 
     def __init__(self, basis, col_of_row, x, y, status, quality):
         self.basis, self.col_of_row, self.x, self.y, self.status, self.quality = basis, col_of_row, x, y, status, quality
+
+
+class BasisSimplex:
+    """What `LPBatch.simplex` returns, all device tensors, nothing copied back: `.basis` (float32 [N], the basis at the
+    stop; zeros for codes 1, 2, 3), `.col_of_row` (int32 [M]: the local basic column that owns this row of the inverse, or
+    -1), `.trace` (int32 [n_inst, max_pivots, 2] = entering local column, leaving row of every pivot; -1 past the end) and
+    `.status` (int32 [n_inst, 4] = code, stage-D pivots, stage-P pivots, rank of the start; code 0 optimal, 1 singular
+    start, 2 skipped, 3 the mask does not have m columns, 4 primal infeasible, 5 unbounded, 6 max_pivots reached)."""
+
+    def __init__(self, basis, col_of_row, trace, status):
+        self.basis, self.col_of_row, self.trace, self.status = basis, col_of_row, trace, status
 
 
 def topm_select_dense(logits, m, want=("mask", "index", "stats")):
