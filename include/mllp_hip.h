@@ -334,6 +334,48 @@ int mllp_basis_simplex(const mllp_graph_t* g, const float* d_x1 /*c [N]*/, const
                        int32_t* d_col_of_row /*[M] or NULL*/, int32_t* d_trace /*[n_inst, max_pivots, 2] or NULL*/,
                        int32_t* d_status /*[n_inst, 4], required*/, void* d_scratch, void* stream);
 
+/* The same pivots with two guards (mllp_amd/csrc/simplex.hip): Bland's rule once a stage stalls, and a fresh
+ * factorization of the basis every refactor_every pivots.  Added after ABI 6 without a bump, as mllp_basis_simplex was.
+ * Everything not named here is mllp_basis_simplex's: the arguments and their checks, codes 0-6 and the status words, the
+ * scratch (mllp_basis_simplex_scratch_bytes; nothing more, and no LDS vector more), the limits 192 / 4096, one workgroup
+ * per instance, the launch-function, memory and determinism contracts.
+ * THE RULE is mllp_basis_simplex's with these additions.
+ *   Degenerate pivot.  A stage-P pivot is degenerate iff the leaving row's x_B,p <= ftol; a stage-D pivot iff the entering
+ *     column's shifted reduced cost dtilde_j <= dtol.  `stall` counts the consecutive degenerate pivots of the current
+ *     stage: 0 at the start, 0 again after a pivot that is not degenerate and when stage D ends.
+ *   Bland mode.  An iteration runs in Bland mode iff stall_pivots > 0 and stall >= stall_pivots when it begins.  Then
+ *     Stage D, leaving row: among the rows with x_B,i < -ftol, the one whose basic column col_of_row[i] is lowest; none
+ *       ends the stage (the same condition as outside Bland mode).
+ *     Stage D, entering column: the candidates as always (alpha_j < -ptol); j minimises
+ *       (dtilde_j > dtol ? dtilde_j : 0) / (-alpha_j), the lowest j among equal ratios.
+ *     Stage P, entering column: the lowest j with d_j < -dtol; none: code 0 (the same condition).
+ *     Stage P, leaving row: the candidates as always (w_i > ptol); the ratio is (x_B,i > ftol ? x_B,i : 0) / w_i, and among
+ *       the rows whose ratio has the bits of the smallest one, the row whose col_of_row[i] is lowest.
+ *     The clipping makes every degenerate candidate tie at an exact 0, in any precision; the ties are then broken by the
+ *     index of the variable, which is Bland's rule.  Outside Bland mode every choice is mllp_basis_simplex's, bit for bit.
+ *   Refactorization (refactor_every = R > 0).  After every pivot whose running number (stage-D + stage-P pivots so far) is
+ *     a multiple of R, and before the next iteration, T is discarded and the current basis is factorized as the start was:
+ *     its columns in ascending order, the rule of mllp_basis_repair with `tol`.  col_of_row becomes what that factorization
+ *     assigns: rows change owners, so a later "lowest row among equals" may differ from the run that was not refactorized;
+ *     that is part of the rule.  The shifts stay as they are.  Rank < m: code 7 (the basis could not be refactorized), stop:
+ *     d_basis keeps that basis, d_col_of_row is -1, the trace keeps the pivots taken, status words 1-3 as for any stop.
+ *   Equivalence.  With refactor_every == 0 and stall_pivots == 0 every output has the bits of mllp_basis_simplex's, and
+ *     d_guard is zeros.
+ * WHAT IT DOES NOT CLAIM.  No proof of termination in fp32 (Bland's argument needs exact ties, which the clipping gives
+ * only up to the tolerances); no Harris ratio test, no steepest-edge pricing; T is still dense and explicit.
+ *   refactor_every, stall_pivots : >= 0; 0 switches the guard off.
+ *   d_guard [n_inst, 2] int32 or NULL : {refactorizations completed (one that ends in code 7 is not counted), pivots chosen
+ *             in Bland mode}; fully written for every instance, zeros for codes 1, 2 and 3.
+ * A pivot in Bland mode whose stage is P costs one workgroup barrier more (seven); every other pivot six; a
+ * refactorization costs what the start's factorization costs.
+ * MLLP_EINVAL before any launch, nothing written: what mllp_basis_simplex refuses; refactor_every < 0; stall_pivots < 0.   */
+int mllp_basis_simplex_guarded(const mllp_graph_t* g, const float* d_x1 /*c [N]*/, const float* d_x2 /*b [M]*/,
+                               const float* d_start /*[N] mask*/, float tol, float ftol, float dtol, float ptol, float dshift,
+                               int64_t max_pivots, int64_t max_m, int64_t refactor_every, int64_t stall_pivots,
+                               float* d_basis /*[N] 0/1, required*/, int32_t* d_col_of_row /*[M] or NULL*/,
+                               int32_t* d_trace /*[n_inst, max_pivots, 2] or NULL*/, int32_t* d_status /*[n_inst, 4], required*/,
+                               int32_t* d_guard /*[n_inst, 2] or NULL*/, void* d_scratch, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Plain CSR SpMM (the roofline kernel named in BASELINE.json's metric):
  *   transpose == 0:  Y[M,16] = A   * H[N,16]       transpose == 1:  Y[N,16] = A^T * H[M,16]

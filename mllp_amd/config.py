@@ -39,7 +39,9 @@ HOT_PATH_DEFAULTS = {
                              # the device, and train_log.json gains the counts usable / feasible / optimal / skipped (m > max_m;
                              # max_m absent == none skipped); None == not computed, the log as before
                              # `pivots: K` in the block adds optimal_after_pivots / pivots: the repaired prediction pivoted to
-                             # the optimum with at most K simplex pivots per instance (LPBatch.simplex), and their total
+                             # the optimum with at most K simplex pivots per instance (LPBatch.simplex), and their total;
+                             # `refactor: R` / `stall: S` beside it are that call's refactor_every / stall_pivots (a fresh
+                             # factorization every R pivots, Bland's rule after S degenerate pivots); absent == the plain call
 }
 
 

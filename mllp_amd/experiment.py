@@ -200,10 +200,12 @@ def pivot_counts(batch, logits, report):
     """[2] device counts over a batch's instances, by PIVOT_KEYS, under `report_solved` {..., pivots: K}: the repaired
     prediction pivoted to the optimum on the device (LPBatch.simplex, at most K pivots per instance), the final basis
     factorized afresh and certified (LPBatch.simplex_solved) -- the instances certified optimal, and the pivots they took
-    in all.  No sync."""
+    in all.  `refactor: R` and `stall: S` in the block are LPBatch.simplex's refactor_every and stall_pivots; without them
+    the call is the one it was.  No sync."""
     max_m = report.get("max_m")
     rep = batch.repair_basis(logits, max_m=max_m, want=("basis",))
-    res = batch.simplex(rep, int(report["pivots"]), max_m=max_m, want=())
+    guards = {key: int(report[name]) for name, key in (("refactor", "refactor_every"), ("stall", "stall_pivots")) if report.get(name) is not None}
+    res = batch.simplex(rep, int(report["pivots"]), max_m=max_m, want=(), **guards)
     got = batch.simplex_solved(res, report["feas_tol"], report["opt_tol"], max_m=max_m)
     done = got["optimal"] & (res.status[:, 0] == 0)
     return torch.stack([done.sum(), (got["pivots"] * done).sum()]).float()

@@ -1021,14 +1021,17 @@ class LPBatch:
 
     # ---- pivot a basis to optimality (mllp_basis_simplex; csrc/simplex.hip) ----------------------------------------
     def simplex(self, start, max_pivots, tol=2.0 ** -12, ftol=2.0 ** -10, dtol=2.0 ** -10, ptol=2.0 ** -10, dshift=2.0 ** -4,
-                max_m=None, want=("basis", "col_of_row", "trace")):
+                max_m=None, want=("basis", "col_of_row", "trace"), refactor_every=0, stall_pivots=0):
         """Dual, then primal simplex pivots from a basis to the optimum, on the device (mllp_basis_simplex; the rule is
         stated in include/mllp_hip.h).  `start`: a mask tensor [N] (nonzero = basic) or a `BasisRepair`, whose `.basis` is
         used.  `max_pivots`: the limit per instance (code 6 beyond it).  `tol` is `repair_basis`'; `ftol`, `dtol`, `ptol`,
         `dshift` are the rule's feasibility, optimality and pivot tolerances and its cost shift, in the units of the stored
         LP.  `max_m`: instances with more rows are skipped (code 2); None = the batch's largest m.  Returns a `BasisSimplex`
         of device tensors; `col_of_row` and `trace` are None unless named in `want` (`basis` and `status` always come).  The
-        scratch is asked for once per max_m and kept on the batch.  No sync."""
+        scratch is asked for once per max_m and kept on the batch.  No sync.
+        `refactor_every` = R > 0: the basis is factorized afresh after every R pivots; `stall_pivots` = S > 0: Bland's rule
+        after S consecutive degenerate pivots of a stage.  With both 0 this is mllp_basis_simplex as ever; otherwise
+        mllp_basis_simplex_guarded (code 7: a basis could not be refactorized), and the result has `.guard`."""
         want = (want,) if isinstance(want, str) else tuple(want)
         names = ("basis", "col_of_row", "trace")
         if [w for w in want if w not in names]:
@@ -1041,6 +1044,9 @@ class LPBatch:
         max_pivots = int(max_pivots)
         if max_pivots < 0:
             raise ValueError("simplex: max_pivots must not be negative")
+        refactor_every, stall_pivots = int(refactor_every), int(stall_pivots)
+        if refactor_every < 0 or stall_pivots < 0:
+            raise ValueError("simplex: refactor_every and stall_pivots must not be negative")
         dev = self.x1.device
         max_m = max(self.inst_m, default=0) if max_m is None else int(max_m)
         kept = getattr(self, "_simplex_scratch", None)
@@ -1054,13 +1060,22 @@ class LPBatch:
         col_of_row = new(self.M, torch.int32) if "col_of_row" in want else None
         trace = new(self.n_inst * max_pivots * 2, torch.int32) if "trace" in want else None
         pad = lambda t: t if t.numel() else torch.zeros(1, dtype=torch.float32, device=dev)   # noqa: E731
-        _lib.check(_lib.lib().mllp_basis_simplex(self._h, _lib.ptr(pad(self.x1)), _lib.ptr(pad(self.x2)), _lib.ptr(pad(start)),
-                                                 float(tol), float(ftol), float(dtol), float(ptol), float(dshift), max_pivots, max_m,
-                                                 _lib.ptr(basis), _lib.ptr(col_of_row), _lib.ptr(trace), _lib.ptr(status),
-                                                 _lib.ptr(kept[1]), _lib.current_stream()))
+        guard = None
+        if refactor_every == 0 and stall_pivots == 0:
+            _lib.check(_lib.lib().mllp_basis_simplex(self._h, _lib.ptr(pad(self.x1)), _lib.ptr(pad(self.x2)), _lib.ptr(pad(start)),
+                                                     float(tol), float(ftol), float(dtol), float(ptol), float(dshift), max_pivots, max_m,
+                                                     _lib.ptr(basis), _lib.ptr(col_of_row), _lib.ptr(trace), _lib.ptr(status),
+                                                     _lib.ptr(kept[1]), _lib.current_stream()))
+        else:
+            guard = new(self.n_inst * 2, torch.int32)
+            _lib.check(_lib.lib().mllp_basis_simplex_guarded(
+                self._h, _lib.ptr(pad(self.x1)), _lib.ptr(pad(self.x2)), _lib.ptr(pad(start)), float(tol), float(ftol), float(dtol),
+                float(ptol), float(dshift), max_pivots, max_m, refactor_every, stall_pivots, _lib.ptr(basis), _lib.ptr(col_of_row),
+                _lib.ptr(trace), _lib.ptr(status), _lib.ptr(guard), _lib.ptr(kept[1]), _lib.current_stream()))
+            guard = guard[:self.n_inst * 2].view(self.n_inst, 2)
         return BasisSimplex(basis[:self.N], None if col_of_row is None else col_of_row[:self.M],
                             None if trace is None else trace[:self.n_inst * max_pivots * 2].view(self.n_inst, max_pivots, 2),
-                            status[:self.n_inst * 4].view(self.n_inst, 4))
+                            status[:self.n_inst * 4].view(self.n_inst, 4), guard)
 
     def simplex_solved(self, res, feas_tol, opt_tol, tol=2.0 ** -12, max_m=None):
         """What a `BasisSimplex` is worth: `solve_basis(res.basis)` -- a FRESH factorization of the final basis, which the
@@ -1121,10 +1136,12 @@ class BasisSimplex:
     stop; zeros for codes 1, 2, 3), `.col_of_row` (int32 [M]: the local basic column that owns this row of the inverse, or
     -1), `.trace` (int32 [n_inst, max_pivots, 2] = entering local column, leaving row of every pivot; -1 past the end) and
     `.status` (int32 [n_inst, 4] = code, stage-D pivots, stage-P pivots, rank of the start; code 0 optimal, 1 singular
-    start, 2 skipped, 3 the mask does not have m columns, 4 primal infeasible, 5 unbounded, 6 max_pivots reached)."""
+    start, 2 skipped, 3 the mask does not have m columns, 4 primal infeasible, 5 unbounded, 6 max_pivots reached, 7 a basis
+    could not be refactorized) and `.guard` (int32 [n_inst, 2] = refactorizations, pivots chosen by Bland's rule; None unless
+    `refactor_every` or `stall_pivots` was given)."""
 
-    def __init__(self, basis, col_of_row, trace, status):
-        self.basis, self.col_of_row, self.trace, self.status = basis, col_of_row, trace, status
+    def __init__(self, basis, col_of_row, trace, status, guard=None):
+        self.basis, self.col_of_row, self.trace, self.status, self.guard = basis, col_of_row, trace, status, guard
 
 
 def topm_select_dense(logits, m, want=("mask", "index", "stats")):

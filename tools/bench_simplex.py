@@ -2,7 +2,11 @@
 something: pivots from a WARM start (the optimal basis with k columns swapped, repaired) against pivots from the same LP's
 COLD start (the repair of a seeded random ranking).  Prints one JSON line (profiles/simplex_bench.json).
 
-    python tools/bench_simplex.py [--calls 8] [--windows 7] [--swap 10] [--max-pivots 2000]
+    python tools/bench_simplex.py [--calls 8] [--windows 7] [--swap 10] [--max-pivots 2000] [--refactor R] [--stall S]
+
+--refactor R / --stall S (either above 0) measure mllp_basis_simplex_guarded instead: a fresh factorization every R pivots,
+Bland's rule after S degenerate pivots of a stage; every row then has `refactorizations_per_call` and `bland_pivots_per_call`,
+the sums of d_guard over the batch (0 and 0 on the plain entry point).  (profiles/simplex_guarded_bench.json)
 
 Batches:  planted 64 and 1024 x (50 x 120);  one planted batch across the LDS threshold (32 x (160 x 400) with T in LDS, 32 x
 (256 x 600) with T in scratch);  the Netlib batch with max_m at the threshold, from a seeded random ranking, with the
@@ -31,9 +35,10 @@ from bench_basis_repair import device_window  # noqa: E402
 class Call:
     """mllp_basis_simplex on one batch and one start mask, outputs and scratch allocated once"""
 
-    def __init__(self, b, start, max_pivots, max_m=None):
+    def __init__(self, b, start, max_pivots, max_m=None, refactor=0, stall=0):
         from mllp_amd import _lib
         self.lib, self.b, self.start, self.max_pivots = _lib, b, start.to(torch.float32).contiguous(), int(max_pivots)
+        self.refactor, self.stall = int(refactor), int(stall)
         self.max_m = max(b.inst_m) if max_m is None else int(max_m)
         n = ctypes.c_int64()
         _lib.check(_lib.lib().mllp_basis_simplex_scratch_bytes(b._h, self.max_m, ctypes.byref(n)))
@@ -42,9 +47,16 @@ class Call:
         self.scratch = torch.empty(max(n.value // 4, 1), device=dev)
         self.basis = torch.empty(b.N, device=dev)
         self.status = torch.empty(b.n_inst, 4, device=dev, dtype=torch.int32)
+        self.guard = torch.zeros(b.n_inst, 2, device=dev, dtype=torch.int32)
 
     def __call__(self):
         p = self.lib.ptr
+        if self.refactor or self.stall:     # the guarded entry point; with both 0 the plain one, as ever
+            self.lib.check(self.lib.lib().mllp_basis_simplex_guarded(
+                self.b._h, p(self.b.x1), p(self.b.x2), p(self.start), 2.0 ** -12, 2.0 ** -10, 2.0 ** -10, 2.0 ** -10, 2.0 ** -4,
+                self.max_pivots, self.max_m, self.refactor, self.stall, p(self.basis), None, None, p(self.status), p(self.guard),
+                p(self.scratch), self.lib.current_stream()))
+            return
         self.lib.check(self.lib.lib().mllp_basis_simplex(self.b._h, p(self.b.x1), p(self.b.x2), p(self.start), 2.0 ** -12, 2.0 ** -10,
                                                          2.0 ** -10, 2.0 ** -10, 2.0 ** -4, self.max_pivots, self.max_m, p(self.basis),
                                                          None, None, p(self.status), p(self.scratch), self.lib.current_stream()))
@@ -71,18 +83,20 @@ def random_start(b, seed, max_m=None):
     return b.repair_basis(logits=z, max_m=max_m, want=("basis",)).basis
 
 
-def measure(name, b, start, what, calls, windows, max_pivots, max_m=None, certify=True):
-    call = Call(b, start, max_pivots, max_m)
+def measure(name, b, start, what, calls, windows, max_pivots, max_m=None, certify=True, refactor=0, stall=0):
+    call = Call(b, start, max_pivots, max_m, refactor, stall)
     call()
     call()
     torch.cuda.synchronize()
-    st = call.status.cpu().numpy()
+    st, gd = call.status.cpu().numpy(), call.guard.cpu().numpy()
     dev = [device_window(call, calls) for _ in range(windows)]
     med = float(np.median(dev))
     piv = (st[:, 1] + st[:, 2]).astype(np.int64)
     done = st[:, 0] == 0
     out = {"batch": name, "start": what, "instances": b.n_inst, "max_m": call.max_m, "max_pivots": max_pivots,
-           "scratch_bytes": call.scratch_bytes, "codes": {str(c): int((st[:, 0] == c).sum()) for c in range(7)},
+           "refactor_every": call.refactor, "stall_pivots": call.stall,
+           "scratch_bytes": call.scratch_bytes, "codes": {str(c): int((st[:, 0] == c).sum()) for c in range(8)},
+           "refactorizations_per_call": int(gd[:, 0].sum()), "bland_pivots_per_call": int(gd[:, 1].sum()),
            "pivots": {"total": int(piv.sum()), "stage_D": int(st[:, 1].sum()), "stage_P": int(st[:, 2].sum()), "largest": int(piv.max(initial=0)),
                       "mean_of_the_optimal": round(float(piv[done].mean()), 2) if done.any() else None},
            "calls_per_window": calls, "windows": windows,
@@ -106,6 +120,8 @@ def main():
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--swap", type=int, default=10)
     ap.add_argument("--max-pivots", type=int, default=2000)
+    ap.add_argument("--refactor", type=int, default=0, help="refactor_every of mllp_basis_simplex_guarded (0: never)")
+    ap.add_argument("--stall", type=int, default=0, help="stall_pivots of mllp_basis_simplex_guarded (0: no Bland mode)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_simplex needs the GPU: there is no CPU path"
     from mllp_amd.data import load_packed
@@ -115,6 +131,7 @@ def main():
     internal = open(os.path.join(os.path.dirname(HEADER_PATH), "..", "mllp_amd", "csrc", "internal.h")).read()
     lds_max = int(internal.split("SIMPLEX_LDS_MAX_M =")[1].split(";")[0])
     res = []
+    guards = dict(refactor=args.refactor, stall=args.stall)
     batches = []
     for n_inst in (64, 1024):
         b, _, _ = planted_batch(n_inst, 50, 120, 6.0, 1)
@@ -124,12 +141,12 @@ def main():
     batches.append(("planted 32 x (160 x 400) + 32 x (256 x 600)", LPBatch.from_instances(batch_to_instances(lo) + batch_to_instances(hi))))
     for name, b in batches:
         res.append(measure(name, b, swapped_start(b, args.swap, 11), f"warm: {args.swap} columns swapped, repaired", args.calls,
-                           args.windows, args.max_pivots))
-        res.append(measure(name, b, random_start(b, 5), "cold: the repair of a random ranking", 2, 3, args.max_pivots))
+                           args.windows, args.max_pivots, **guards))
+        res.append(measure(name, b, random_start(b, 5), "cold: the repair of a random ranking", 2, 3, args.max_pivots, **guards))
     net = LPBatch.from_instances(load_packed())
     res.append(measure(f"Netlib {net.n_inst} instances, max_m {lds_max}", net, random_start(net, 5, lds_max),
-                       "cold: the repair of a random ranking", 1, 3, args.max_pivots, max_m=lds_max))
-    print(json.dumps({"lds_max_m": lds_max, "results": res}))
+                       "cold: the repair of a random ranking", 1, 3, args.max_pivots, max_m=lds_max, **guards))
+    print(json.dumps({"lds_max_m": lds_max, "refactor_every": args.refactor, "stall_pivots": args.stall, "results": res}))
 
 
 if __name__ == "__main__":
