@@ -135,7 +135,7 @@ int mllp_graph_invalidate_inputs(mllp_graph_t* g);
  * them outside a capture).  Every other call is a launch function: one device-to-device copy + one launch per array on
  * `stream` alone, no allocation, no synchronisation, hipGraph-capturable.  A map is freed with its copy (drop / rebuild)
  * and with the graph.  mllp_graph_set_values_bytes: bytes of the maps of the copies attached now, built or not yet.
- * The workspace record is cleared as by a path switch: mllp_gnn_backward* needs a new mllp_gnn_forward (MLLP_EINVAL
+ * The workspace record (RECORDS, below) is cleared: mllp_gnn_backward* needs a new mllp_gnn_forward (MLLP_EINVAL
  * otherwise; a captured call clears it when it is captured, not when it is replayed).  The folded weights are kept.
  * MLLP_EINVAL, before anything is written: null g or d_val; a caller-owned LDS-tiled copy is attached
  * (mllp_graph_attach_tiled) -- drop it or build it with mllp_graph_build_tiled.
@@ -513,16 +513,40 @@ int mllp_tconv_bwd(const mllp_graph_t* g, int dst_is_var, int cin, const float* 
  *      the buffers may be uninitialised, NaN included, and the same bits come out.  The only state carried between calls is
  *      what this header names: mllp_gnn_forward -> mllp_gnn_backward / _backward_inputs / _input_grads on the same workspace
  *      (mllp_gnn_loss_step_weighted leaves its forward's state likewise), mllp_gnn_train_step flags bit 0, and
- *      mllp_tconv_fwd -> mllp_tconv_bwd on the same d_ws.
+ *      mllp_tconv_fwd -> mllp_tconv_bwd on the same d_ws.  The library keeps a record of each of the first two per graph
+ *      (RECORDS below) and a call that would read carried state the record does not vouch for is refused, or (flags bit 0)
+ *      makes the state again: a call either returns the bits it returns from a fresh workspace, or MLLP_EINVAL.
  *   2. A call writes nothing outside the documented extent of the buffers it is given -- for d_ws exactly
  *      mllp_gnn_workspace_bytes() (mllp_tconv_workspace_floats() floats) from the pointer -- and never writes an input:
  *      d_params (except in the train steps), d_x1, d_x2, d_labels, d_dlogits where it is an input, d_inst_weight,
  *      d_pos_weight, d_conv_params, d_x_src, d_x_dst, d_h_out in the backward, d_H.
  *   3. A call's outputs do not depend on any byte outside those extents (a kernel may read past the end of an array
  *      inside the caller's allocation only where what it reads cannot reach a result).
- *   4. Between whole calls that carry nothing the caller may do anything to the workspace: after mllp_gnn_loss_step,
- *      _loss_step_weighted (unless mllp_gnn_input_grads follows), _loss_step_inputs, _train_step_small, and after
- *      mllp_gnn_train_step when the next call passes flags 0.
+ *   4. Between whole calls that carry nothing the caller may do anything to the workspace: after mllp_gnn_loss_step and
+ *      _loss_step_inputs (unless a backward call follows that the workspace record still allows: RECORDS),
+ *      _loss_step_weighted (unless a backward call follows), _train_step_small, and after mllp_gnn_train_step when the next
+ *      call passes flags 0.  The library cannot see such a write: a caller that clobbers a workspace whose forward it still
+ *      means to use gets that garbage's gradients.
+ *   RECORDS the library keeps per graph (tests/call_model.py states them as a model; tests/test_call_sequences.py walks
+ *      every triple of whole-model calls against it).  They hold pointer VALUES and see only calls made on
+ *      this graph: writing d_params or d_ws by other means between a forward and its backward is the caller's to avoid.
+ *      Workspace record = {d_ws, path, d_params} of the mllp_gnn_forward whose activations d_ws holds.
+ *        set by      mllp_gnn_forward (and so by mllp_gnn_loss_step_weighted, which calls it);
+ *        required by mllp_gnn_backward, _backward_inputs and _input_grads: all three must be those of the call, else
+ *                    MLLP_EINVAL with a message before any HIP call, nothing written.  The calls leave it as it is, so
+ *                    several backward calls may follow one forward, each with the bits of the first;
+ *        kept by     mllp_graph_set_path (a switch there and back changes nothing; a backward on the other path is refused)
+ *                    and by mllp_gnn_loss_step / _loss_step_inputs given the record's workspace, path and parameters: the
+ *                    step's forward writes the bits that are there (on the fused path it leaves layer 3's to that forward);
+ *        cleared by  mllp_gnn_loss_step / _loss_step_inputs in every other case (another workspace, path or parameter
+ *                    pointer: the step has rewritten the workspace with a forward that is not the recorded one),
+ *                    mllp_gnn_train_step on both paths (it rewrites the workspace, then the parameters),
+ *                    mllp_gnn_train_step_small, mllp_graph_set_values and the calls that end in it (_scale_values,
+ *                    _normalize unless compute only, _plant_basis).
+ *      Folded-weights record = {d_ws, d_params} of the fused mllp_gnn_train_step that left the NEXT step's folded weights.
+ *        set by      mllp_gnn_train_step on the fused path;   honoured by the next one with flags bit 0, when both match;
+ *        cleared by  every other whole-model call on the graph, the generic mllp_gnn_train_step and mllp_graph_set_path;
+ *        kept by     mllp_graph_set_values and the calls built on it (the folded weights depend on the parameters alone).
  *   ALIGNMENT: d_ws, d_params, d_x1 and d_x2 of the mllp_gnn_* calls must be 16-byte aligned -- the workspace's fields,
  *      fc.weight and (on the lane-per-row copy of the layer-1 sweeps) four neighbouring source values are accessed in 16-byte
  *      pieces --, as must every pointer of mllp_tconv_fwd / _bwd except d_param_grads (rows of 16 floats; d_ws, d_conv_params)
@@ -535,7 +559,11 @@ int mllp_tconv_bwd(const mllp_graph_t* g, int dst_is_var, int cin, const float* 
  * mllp_gnn_loss_step: forward + BCEWithLogitsLoss + backward in one call, loss =
  *   inv_batch * sum_k mean_i BCE(logit_i, label_i) over the instances k of this graph
  *   (linear_program_experiment.py:41,139-141 with batch size 1 and inv_batch = 1).
- *   d_labels [N] float 0/1; d_loss: 1 float.
+ *   d_labels [N] float 0/1; d_loss: 1 float.  The step rewrites d_ws with its own forward: the workspace record
+ *   (RECORDS above) survives it only when it names this d_ws, the path in use and this d_params -- then a backward call
+ *   may still follow the earlier mllp_gnn_forward, with the bits it has straight after it -- and is cleared otherwise.
+ * mllp_gnn_backward: after mllp_gnn_forward on this d_ws, on the path in use, with this d_params pointer, and nothing since
+ *   that clears the record (RECORDS); MLLP_EINVAL with a message otherwise, before any HIP call, nothing written.
  * ---------------------------------------------------------------------------------------------- */
 int mllp_gnn_workspace_bytes(const mllp_graph_t* g, int64_t* bytes);
 int mllp_gnn_forward(const mllp_graph_t* g, const float* d_params, const float* d_x1, const float* d_x2,
@@ -567,14 +595,17 @@ int mllp_gnn_backward_inputs(const mllp_graph_t* g, const float* d_params, const
 
 /* Input gradients on EITHER path (symbols added without an ABI bump: callers check for them, as for mllp_graph_set_values).
  * mllp_gnn_input_grads: call after mllp_gnn_forward on this workspace, on whichever path that forward used, with the
- *   graph still selecting that path; MLLP_EINVAL with a message, before anything is written, when no forward ran on d_ws
- *   (or mllp_graph_set_values has run since) or the path was switched in between.  Generic path: the call IS
+ *   graph still selecting that path and the d_params pointer of that forward; MLLP_EINVAL with a message, before anything
+ *   is written, when the workspace record (RECORDS above) does not name d_ws, the path in use and d_params: no forward ran on
+ *   d_ws, it ran on the other path or with another d_params, or a call that clears the record has run since
+ *   (mllp_graph_set_values, a train step, a loss step with another path or other parameters).  Generic path: the call IS
  *   mllp_gnn_backward_inputs (same code, same bits).  Fused latency-regime path (the default below 32 M nonzeros): the
  *   fused backward, then a post-pass of four launches for the renumbered workspace (mllp_amd/csrc/fused_input_grads.hip).
  *   Arguments as mllp_gnn_backward_inputs; d_grads is bit for bit what mllp_gnn_backward writes on that path, and with
  *   d_grads == NULL the parameter gradients go to d_scratch (both NULL: MLLP_EINVAL).
  * mllp_gnn_loss_step_inputs: mllp_gnn_loss_step followed by the post-pass of the path in use.  d_logits, d_loss and
- *   d_grads are bit for bit those of mllp_gnn_loss_step on the same inputs and path; arguments as there.
+ *   d_grads are bit for bit those of mllp_gnn_loss_step on the same inputs and path; arguments as there.  It keeps or
+ *   clears the workspace record exactly as mllp_gnn_loss_step does.
  * Both: d_dx1 [N], d_dx2 [M], d_dvalues [nnz] are in the caller's (original) node order, d_dvalues in the CSR order of A
  *   (mllp_graph_export 2); overwritten, not accumulated; each may be NULL, then it is not computed and its kernels are not
  *   launched (all three NULL: exactly mllp_gnn_backward / mllp_gnn_loss_step).  Bitwise reproducible: fixed launch
@@ -649,7 +680,10 @@ int mllp_adam_step(float* d_params, const float* d_grads, float* d_exp_avg, floa
  * reduction of the statistics, the gradients of the five convs, Adam, and the folded weights of the NEXT step, which
  * are left in the workspace.  flags bit 0: "the folded weights in d_ws are current" -- set it when the previous call on
  * this d_ws was mllp_gnn_train_step with these d_params and nothing else has written d_params since; the forward then
- * skips its weight-folding launch.  With several ranks the gradient all-reduce sits between the two halves, so a
+ * skips its weight-folding launch.  The library checks the claim against its folded-weights record (RECORDS above) and
+ * folds the weights itself when the record does not match, so passing bit 0 always is safe.  The step clears the workspace
+ * record on both paths: it rewrites d_ws and then d_params, so no backward call may follow an earlier forward across it.
+ * With several ranks the gradient all-reduce sits between the two halves, so a
  * data-parallel caller keeps calling mllp_gnn_loss_step and mllp_adam_step.                                      */
 int mllp_gnn_train_step(const mllp_graph_t* g, float* d_params, const float* d_x1, const float* d_x2,
                         const float* d_labels, float inv_batch, void* d_ws, float* d_logits, float* d_loss,

@@ -234,6 +234,15 @@ static bool use_fused(const mllp_graph* g) {
     return g->nnz < ((int64_t)32 << 20);     // the throughput regime keeps the generic / LDS-tiled sweeps
 }
 
+// the workspace record names this workspace, the path in use and these parameters: d_ws holds what a backward call with
+// these arguments reads (internal.h; include/mllp_hip.h, RECORDS)
+static bool forward_recorded(const mllp_graph* g, const void* d_ws, const void* d_params) {
+    return g->ws_ptr == d_ws && g->ws_path == (use_fused(g) ? 1 : 0) && g->ws_params == d_params;
+}
+#define REQUIRE_FORWARD_PARAMS(g, d_params)                                                                                  \
+    REQUIRE((g)->ws_params == (d_params), "the mllp_gnn_forward on this workspace ran with other parameters (another d_params " \
+                                          "pointer): its activations are not those of this model")
+
 }  // namespace mllp
 
 using namespace mllp;
@@ -399,6 +408,7 @@ extern "C" int mllp_gnn_forward(const mllp_graph_t* g, const float* d_params, co
     mllp_graph* gm = const_cast<mllp_graph*>(g);          // (bookkeeping only: which path wrote which workspace)
     gm->ws_ptr = d_ws;
     gm->ws_path = use_fused(g) ? 1 : 0;
+    gm->ws_params = d_params;
     gm->folded_ws = gm->folded_params = nullptr;
     if (use_fused(g))
         return fused_forward(gm, FusedModel{d_params, w, d_x1, d_x2, nullptr, 0.0f, d_logits}, 1, s);
@@ -417,7 +427,9 @@ extern "C" int mllp_gnn_backward(const mllp_graph_t* g, const float* d_params, c
     // the two paths lay the workspace out differently (the fused one in renumbered node order): backward must follow
     // a forward of the same path on the same workspace
     REQUIRE(g->ws_ptr == d_ws && g->ws_path == (use_fused(g) ? 1 : 0),
-            "no mllp_gnn_forward on this workspace with the current path (mllp_graph_set_path between forward and backward?)");
+            "no mllp_gnn_forward on this workspace with the current path (mllp_graph_set_path between forward and backward? "
+            "A train step, mllp_graph_set_values, or a loss step with other parameters since the forward?)");
+    REQUIRE_FORWARD_PARAMS(g, d_params);
     if (use_fused(g)) {      // (the node tensors of the fused path are in renumbered order: it has its own head kernel)
         const FusedModel m{d_params, w, d_x1, d_x2, nullptr, 0.0f, nullptr};
         if ((rc = fused_bind(const_cast<mllp_graph*>(g), d_x1, d_x2, nullptr, s))) return rc;
@@ -461,7 +473,12 @@ extern "C" int mllp_gnn_loss_step(const mllp_graph_t* g, const float* d_params, 
     hipStream_t s = (hipStream_t)stream;
     ModelWs w = model_ws(g, (float*)d_ws);
     int rc;
-    const_cast<mllp_graph*>(g)->folded_ws = const_cast<mllp_graph*>(g)->folded_params = nullptr;
+    mllp_graph* gm = const_cast<mllp_graph*>(g);
+    gm->folded_ws = gm->folded_params = nullptr;
+    // the step rewrites the workspace with ITS forward (on the fused path all of it but layer 3's saved state, which a
+    // recorded forward left).  After a recorded forward on this workspace, this path and these parameters those are the
+    // bits that are there already and the record stays; after any other the workspace belongs to no forward
+    if (!forward_recorded(g, d_ws, d_params)) forget_forward(gm);
     if (use_fused(g)) {
         const FusedModel m{d_params, w, d_x1, d_x2, d_labels, inv_batch, d_logits};
         if ((rc = fused_forward(const_cast<mllp_graph*>(g), m, 2, s))) return rc;
@@ -490,6 +507,7 @@ extern "C" int mllp_gnn_backward_inputs(const mllp_graph_t* g, const float* d_pa
     REQUIRE(g->ws_path == 0, "the forward on this workspace ran on the fused path: input gradients need the generic "
                              "sweeps (mllp_graph_set_path(g, 1) before mllp_gnn_forward)");
     REQUIRE(!use_fused(g), "the graph's path selects the fused kernels: set path 1 between the forward and this call");
+    REQUIRE_FORWARD_PARAMS(g, d_params);
     REQUIRE(d_grads || d_scratch, "d_grads and d_scratch are both null (mllp_gnn_input_grads_scratch_bytes)");
     hipStream_t s = (hipStream_t)stream;
     mllp_graph* gm = const_cast<mllp_graph*>(g);
@@ -511,6 +529,7 @@ extern "C" int mllp_gnn_input_grads(const mllp_graph_t* g, const float* d_params
     REQUIRE(g->ws_ptr == d_ws, "no mllp_gnn_forward on this workspace");
     REQUIRE(g->ws_path == (use_fused(g) ? 1 : 0),
             "the path was switched between the forward on this workspace and this call (mllp_graph_set_path)");
+    REQUIRE_FORWARD_PARAMS(g, d_params);
     if (!use_fused(g))
         return mllp_gnn_backward_inputs(g, d_params, d_x1, d_x2, d_ws, d_dlogits, d_grads, d_dx1, d_dx2, d_dvalues, d_scratch,
                                         stream);
@@ -553,6 +572,7 @@ extern "C" int mllp_gnn_train_step(const mllp_graph_t* g, float* d_params, const
     hipStream_t s = (hipStream_t)stream;
     int rc;
     mllp_graph* gm = const_cast<mllp_graph*>(g);
+    forget_forward(gm);      // the step rewrites the workspace and then the parameters: no backward call may follow it
     if (use_fused(g)) {
         ModelWs w = model_ws(g, (float*)d_ws);
         const FusedModel m{d_params, w, d_x1, d_x2, d_labels, inv_batch, d_logits};
@@ -610,8 +630,7 @@ extern "C" int mllp_gnn_train_step_small(const mllp_graph_t* g, float* d_params,
     // the kernel lays the workspace out as the generic path does but saves less: nothing the library remembers about
     // this graph's workspace or folded weights holds afterwards
     mllp_graph* gm = const_cast<mllp_graph*>(g);
-    gm->ws_ptr = nullptr;
-    gm->ws_path = -1;
+    forget_forward(gm);
     gm->folded_ws = gm->folded_params = nullptr;
     return launch_small_step(g, d_params, d_x1, d_x2, d_labels, inv_batch, model_ws(g, (float*)d_ws), d_logits, d_loss,
                              d_grads, d_exp_avg, d_exp_avg_sq, d_state, eps, (hipStream_t)stream);

@@ -188,8 +188,12 @@ struct mllp_graph {
     const void* bound_x2 = nullptr;
     const void* bound_labels = nullptr;
     bool bind_captured = false;  // a hipGraph captured on this graph re-makes the copies at every replay: the cache is never trusted again
-    int ws_path = -1;            // which whole-model path wrote the workspace last: 0 generic / tiled, 1 fused (backward checks it)
+    // the workspace record: the mllp_gnn_forward whose activations a workspace holds -- which buffer, on which whole-model
+    // path (0 generic / tiled, 1 fused: the two lay the workspace out differently) and with which parameters.  The backward
+    // calls run only when all three are those of the call (include/mllp_hip.h, RECORDS); forget_forward() clears it
+    int ws_path = -1;
     const void* ws_ptr = nullptr;
+    const void* ws_params = nullptr;
     // which {workspace, parameters} hold the folded weights that fused_tail_kernel left behind for the NEXT step
     // (mllp_gnn_train_step flags bit 0 is honoured only when both match; every other whole-model call, a path switch
     // and the generic branch of train_step clear the record)
@@ -212,6 +216,12 @@ struct mllp_graph {
 };
 
 namespace mllp {
+
+// the workspace no longer holds the activations of a forward that a backward call may use
+inline void forget_forward(mllp_graph* g) {
+    g->ws_ptr = g->ws_params = nullptr;
+    g->ws_path = -1;
+}
 
 // a device array that a graph makes on the first call that needs it and frees with itself (in `allocs`): a no-op once `slot`
 // is set.  Allocates: the first such call is not for a capture

@@ -240,8 +240,7 @@ extern "C" int mllp_graph_set_values(mllp_graph_t* g, const float* d_val, void* 
     REQUIRE(g && d_val, "null argument");
     REQUIRE(!borrowed_tiled(g), MLLP_BORROWED_TILED_MSG);
     hipStream_t s = (hipStream_t)stream;
-    g->ws_path = -1;            // the workspace holds activations of the old values: backward needs a new forward
-    g->ws_ptr = nullptr;
+    forget_forward(g);          // the workspace holds activations of the old values: backward needs a new forward
     const int64_t nnz = g->nnz;
     if (nnz == 0) return MLLP_OK;
     int rc;
