@@ -664,6 +664,81 @@ int mllp_gnn_loss_step_weighted(const mllp_graph_t* g, const float* d_params, co
                                 float* d_dlogits, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Soft top-m loss head (symbols added without an ABI bump: callers check for them, as for mllp_weighted_loss).
+ * The model predicts a basis: exactly m_k of instance k's n_k columns, m_k = the instance's row count in the graph.  This
+ * head trains on probabilities that sum to m_k, where mllp_weighted_loss judges every column against logit 0.  Reference:
+ * the (commented-out) gumbel_sinkhorn_topk(latent_vars, len(constrs), max_iter=cfg.sinkhorn_iter, tau=cfg.sinkhorn_tau,
+ * sample_num, noise_fact, return_prob=True) of linear_program_experiment.py:126-137, whose module the reference does not
+ * ship, and the lml projection it imports.  That call iterates Sinkhorn on a 2 x n transport problem (row masses n - m and
+ * m, column masses 1, costs = the distances of a score to the anchors min and max, temperature sinkhorn_tau); its fixed point
+ * is closed-form, p_i = sigmoid(2 z_i / sinkhorn_tau + nu) with the scalar nu fixed by sum_i p_i = m, and this head computes
+ * that fixed point: tau here = sinkhorn_tau / 2.  (mllp_amd/csrc/topm_loss.hip)
+ * Per instance k; pw_k, w_k as in mllp_weighted_loss (NULL = ones); tau > 0, sigma >= 0, S = n_samples.  ONE EVALUATION e
+ * of the head with a perturbation eps_i (0 without noise), for 0 < m_k < n_k:
+ *     a_i  = (z_i + sigma eps_i) / tau                       fp32: one product, one sum, one quotient (no noise: z_i / tau)
+ *     nu_e : the root of F(nu) = sum_i sigmoid(a_i + nu) - m_k   (unique: F is increasing)
+ *     u_i  = a_i + nu_e,  p_i = sigmoid(u_i),  q_i = p_i (1 - p_i),  Q = sum_i q_i
+ *     l_i  = (1 - y_i) u_i + (1 + (pw_k - 1) y_i) softplus(-u_i)        mllp_weighted_loss's l_i at u instead of z
+ *     L_e  = (1 / n_k) sum_i l_i
+ *     g_i  = (1 / n_k) ((1 - y_i) - (1 + (pw_k - 1) y_i) (1 - p_i)),  G = sum_i g_i
+ *     dz_i = (w_k / tau) (g_i - q_i G / Q)                   the implicit-function gradient of w_k L_e: nothing unrolled,
+ *                                                            nothing saved.  (Computed as (w_k / tau / n_k) (n_k g_i -
+ *                                                            q_i (n_k G) / Q); the quotient G / Q is taken as 0 when Q = 0.)
+ *   n_samples == 0 ('soft-topk'): one evaluation with eps = 0; L_k = L_e, dz = dz_e.
+ *   n_samples = S >= 1 ('gs-topk'): S evaluations with Gumbel noise; L_k = (sum_e L_e) / S and dz = (sum_e dz_e) / S, both
+ *     added in sample order e = 0, 1, ... from the first term.
+ *   m_k <= 0 or m_k >= n_k (no root; n_k = 0 included): L_k = 0, dz = 0, p = 0 (m_k <= 0) or 1, info = {0, 0, sum p - m_k, -1}.
+ *   loss = sum_k w_k L_k, added as mllp_weighted_loss adds it (instance order from 0, one rounded product per term).
+ * THE NOISE is a pure function of (seed, instance id, local column i, sample e), so an instance gives the same bits alone
+ * and inside any batch.  id_k = d_inst_id ? d_inst_id[k] : k.  All arithmetic uint32:
+ *     mix(x) = { x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16; }
+ *     h      = mix( mix( mix(seed ^ (id_k * 0x9E3779B9)) + i ) + e * 0x85EBCA6B )
+ *     t      = ((h >> 9) + 0.5) * 2^-23                      exact in fp32, in (0, 1)
+ *     eps_i  = -log(-log t)                                   logf twice
+ * THE ROOT (part of the bits).  c0 = logf(m / (n - m)); bracket lo = c0 - max_i a_i, hi = c0 - min_i a_i; start
+ * nu = c0 - (sum_i a_i) / n clamped to [lo, hi].  Iteration t = 1, 2, ..., at most 64: F and Q at nu; stop if F == 0;
+ * F < 0 moves lo to nu, otherwise hi; stop if hi is at most 2 ulp above lo; the Newton iterate nu - F / Q is taken when
+ * Q > 0 and it lies strictly inside (lo, hi), the midpoint lo / 2 + hi / 2 otherwise; a Newton iterate that moves nu by
+ * at most 2^-12 is taken and ends the iteration (|F''| <= Q, so what that last step leaves is below 2^-25, under the
+ * rounding of F itself; a tighter test gains nothing and can chase that rounding for all 64 iterations).  nu, lo, hi and the count come
+ * from the ordered sums below, so they are uniform in the instance's workgroup.
+ * mllp_topm_loss: d_logits, d_labels [N] in the caller's node order; d_inst_weight, d_pos_weight, d_inst_id [n_inst] or
+ *   NULL.  Outputs, each may be NULL (not computed) but not all five (MLLP_EINVAL): d_dlogits [N] (must not overlap
+ *   d_logits), d_inst_loss [n_inst] = L_k, d_loss [1], d_prob [N] = p of the NOISE-FREE evaluation (the soft basis; sums to
+ *   m_k), d_info [n_inst, 4] = {nu, Q, sum p - m_k of the noise-free evaluation, the largest iteration count over this
+ *   call's evaluations of the instance}.  With S >= 1, d_prob or d_info cost one more (noise-free) evaluation; with S = 0
+ *   nothing.  Also MLLP_EINVAL, with a message, before any HIP call, nothing written: tau not finite or <= 0, sigma not
+ *   finite or < 0, n_samples < 0 (or above 2^20).  One launch of one workgroup of 1024 threads per instance, plus one of
+ *   one workgroup for d_loss; with d_loss but no d_inst_loss ONE workgroup takes the instances in turn (same bits, slower).
+ * mllp_topm_loss_limits: limits[0] = the column count up to which an instance's a_i stay in LDS between the passes (longer
+ *   instances form them again from the logits in every pass: same bits, more time), limits[1] = threads of the workgroup.
+ *   Needs no GPU.
+ * mllp_topm_loss_math: d_y[i] = expf (which 0), log1pf (1) or logf (2) of d_x[i], i < n, as the head's translation unit
+ *   compiles them: the one ingredient of the head's error bound that its code does not state (tests/test_topm_loss.py).
+ * mllp_gnn_loss_step_topm: mllp_gnn_forward, mllp_topm_loss (no d_prob, no d_info), mllp_gnn_backward on whichever path
+ *   the graph selects.  d_logits [N] and d_grads [MLLP_NUM_PARAMS] are bit for bit what those calls write; d_dlogits [N] is
+ *   required scratch and holds dz afterwards; d_loss, d_inst_loss, d_inst_weight, d_pos_weight, d_inst_id may be NULL.  A
+ *   bad tau, sigma or n_samples is refused before the forward.  The workspace record is left as mllp_gnn_forward /
+ *   mllp_gnn_backward leave it, so mllp_gnn_input_grads may follow.
+ * All: every sum (sum p, Q, sum l, G, sum a) is ordered_sum.h's over the 1024 threads as lanes -- thread t adds terms t,
+ * t + 1024, ... from 0, then the butterfly, then the fixed tree over the wavefronts -- so it depends on n_k alone; no float
+ * atomics, one writer per word.  An instance gives the same bits alone (with its d_inst_id) and inside any batch, whichever
+ * outputs are asked for, run after run.  A null graph, logits or labels (step: as mllp_gnn_loss_step_weighted) is rejected
+ * with a message before any HIP call.  Nothing is allocated; all work is queued on `stream` (capturable).
+ * ---------------------------------------------------------------------------------------------- */
+int mllp_topm_loss(const mllp_graph_t* g, const float* d_logits, const float* d_labels,
+                   const float* d_inst_weight, const float* d_pos_weight, const int32_t* d_inst_id,
+                   float tau, float sigma, int64_t n_samples, uint32_t seed,
+                   float* d_dlogits, float* d_inst_loss, float* d_loss, float* d_prob, float* d_info, void* stream);
+int mllp_topm_loss_limits(int64_t limits[2]);
+int mllp_topm_loss_math(int which, int64_t n, const float* d_x, float* d_y, void* stream);
+int mllp_gnn_loss_step_topm(const mllp_graph_t* g, const float* d_params, const float* d_x1, const float* d_x2,
+                            const float* d_labels, const float* d_inst_weight, const float* d_pos_weight,
+                            const int32_t* d_inst_id, float tau, float sigma, int64_t n_samples, uint32_t seed,
+                            void* d_ws, float* d_logits, float* d_loss, float* d_inst_loss, float* d_grads,
+                            float* d_dlogits, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * torch.optim.Adam(lr, betas=(0.9, 0.999), eps=1e-8), no weight decay
  * (linear_program_experiment.py:119,143-144) on flat buffers.
  *   d_state: 4 floats on the device {step (as float, incremented by the kernel), lr, beta1, beta2};

@@ -6,7 +6,7 @@ symbol table (`lib()`), and every launch fails loudly without a HIP device.
 import ctypes
 import os
 import subprocess
-from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint32, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libmllp_hip.so")
@@ -126,6 +126,13 @@ _PROTOTYPES = {
     "mllp_balanced_pos_weight": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "mllp_gnn_loss_step_weighted": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mllp_topm_loss": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_int64, c_uint32,
+                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mllp_topm_loss_limits": (c_int, [POINTER(c_int64)]),
+    "mllp_topm_loss_math": (c_int, [c_int, c_int64, c_void_p, c_void_p, c_void_p]),
+    "mllp_gnn_loss_step_topm": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
+                                        c_float, c_int64, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p]),
     "mllp_adam_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_int64,
                                c_void_p]),
     "mllp_metrics_scratch_bytes": (c_int, [c_void_p, POINTER(c_int64)]),

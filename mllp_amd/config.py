@@ -30,6 +30,10 @@ HOT_PATH_DEFAULTS = {
                              # step implements; 'bf16' exists for the plain SpMM only (LPBatch.spmm_bf16 / mllp_spmm_csr_bf16)
     "pos_weight": None,      # weight of the positive labels in the loss: a float | 'balanced' (negatives / positives of each
                              # instance); None == the reference's unweighted BCEWithLogitsLoss (experiment.py:41)
+    "loss_head": "bce",      # 'bce': the per-column BCEWithLogitsLoss above.  'topm': the soft top-m head (LPBatch.loss_step_topm):
+                             # probabilities that sum to the instance's m.  Method 'soft-topk' then runs it without noise,
+                             # 'gs-topk' with train_gumbel_sample_num Gumbel samples of scale gumbel_sigma per step
+    "topm_tau": 1.0,         # temperature of the 'topm' head: p = sigmoid(z / topm_tau + nu) (= sinkhorn_tau / 2 of the reference)
     "holdout": None,         # instances evaluated every logging epoch and never trained on: a list of instance names, or a
                              # fraction f in (0, 1) (mllp_amd.experiment.holdout_by_fraction); None == train on everything
     "planted": None,         # with train_data_type: 'planted', the block {instances, m, n, row_nnz, seed} of the planted-basis

@@ -439,6 +439,16 @@ __host__ __device__ constexpr int64_t simplex_words(int64_t m, int64_t n) {     
     return (m > SIMPLEX_LDS_MAX_M ? m * m : 0) + n;
 }
 
+// ---- soft top-m loss head (topm_loss.hip): one workgroup of TOPM_LOSS_T threads per instance, many passes per evaluation ---
+// Where an instance's scaled (and perturbed) logits a_i live between the passes, by its column count n alone: up to
+// TOPM_LOSS_LDS_MAX columns in LDS (64 KB; word t + 1024 j belongs to thread t alone); longer instances form a_i again
+// from the logits in every pass.  Sixteen registers per thread hold as much, but the sixteen unrolled exp / log1p chains
+// spill at the 128 VGPRs of a 1024-thread workgroup (146 VGPRs spilled when tried).  The sums take the columns in the
+// same order in both tiers, so the threshold changes the time and never a bit.  mllp_topm_loss_limits reports it.
+constexpr int TOPM_LOSS_T = 1024;
+constexpr int TOPM_LOSS_LDS_MAX = 16 * TOPM_LOSS_T;
+constexpr int TOPM_LOSS_MAX_ITER = 64;
+
 // ---- fused latency-regime path of the whole model (fused_kernels.hip) ---------------------------------
 // one whole-model call: the flat parameters, the carved workspace, the call's inputs (labels, logits: null where unused)
 struct FusedModel {

@@ -263,7 +263,7 @@ def train_method(cfg, method_name, train_dataset, train_dict, out=print):
     trainer = LPTrainer(model.flat_parameters().detach(), lr=cfg.train_lr,
                         use_hip_graph=cfg.get_default("use_hip_graph"), with_metrics=True,
                         tiled_copies=cfg.get_default("tiled_copies"),
-                        **({} if pos_weight is None else dict(pos_weight=pos_weight)))
+                        **({} if pos_weight is None else dict(pos_weight=pos_weight)), **topm_head(cfg, method_name))
     start_epoch = 0
     if cfg.get_default("resume") and os.path.exists(ckpt_path):
         start_epoch = load_checkpoint(ckpt_path, trainer, train_dict, device)
@@ -284,16 +284,38 @@ def train_method(cfg, method_name, train_dataset, train_dict, out=print):
     return model_path
 
 
+def topm_head(cfg, method_name):
+    """LPTrainer's arguments for the yaml key `loss_head`: {} for 'bce' (or no key: the trainer of a build without it); for
+    'topm' the soft top-m head at `topm_tau` -- without noise under the method 'soft-topk', with `train_gumbel_sample_num`
+    Gumbel samples of scale `gumbel_sigma` under 'gs-topk' (the reference's yaml keys, linear_program_netlib.yaml)."""
+    head = cfg.get_default("loss_head")
+    if head in (None, "bce"):
+        return {}
+    if head != "topm":
+        raise ValueError(f"loss_head: 'bce' or 'topm', got {head!r}")
+    out = dict(loss_head="topm", topm_tau=float(cfg.get_default("topm_tau")))
+    if method_name == "gs-topk":
+        for key in ("train_gumbel_sample_num", "gumbel_sigma"):
+            if key not in cfg:
+                raise ValueError(f"loss_head 'topm' with method 'gs-topk' reads the yaml key {key}")
+        out.update(topm_samples=int(cfg["train_gumbel_sample_num"]), topm_sigma=float(cfg["gumbel_sigma"]))
+    return out
+
+
 def save_checkpoint(path, trainer, train_dict, epoch):
-    """Everything a restart needs: weights, Adam moments + step counter, the epoch, the log so far."""
+    """Everything a restart needs: weights, Adam moments + step counter, the epoch, the log so far (and, under the top-m
+    head, the step count that seeds the next step's noise)."""
+    extra = {"topm_step": int(trainer.topm_step)} if getattr(trainer, "loss_head", "bce") == "topm" else {}
     torch.save({"params": trainer.params, "opt": trainer.opt.state_dict(), "epoch": epoch,
-                "train_dict": json.dumps(train_dict)}, path)
+                "train_dict": json.dumps(train_dict), **extra}, path)
 
 
 def load_checkpoint(path, trainer, train_dict, device):
     ck = torch.load(path, map_location=device, weights_only=True)
     trainer.params.copy_(ck["params"])
     trainer.opt.load_state_dict(ck["opt"])
+    if "topm_step" in ck:
+        trainer.topm_step = int(ck["topm_step"])
     train_dict.update({k: list(v) for k, v in json.loads(ck["train_dict"]).items()})
     return int(ck["epoch"]) + 1
 

@@ -907,6 +907,91 @@ class LPBatch:
         inst = self.weighted_loss(logits, None, pos_weight, want="inst_loss")["inst_loss"]
         return dict(logits=logits, inst_loss=inst, metrics=self.topm_metrics(logits))
 
+    # ---- soft top-m loss head (mllp_topm_loss; csrc/topm_loss.hip) ------------------------------------------------
+    _TOPM_WANT = ("loss", "inst_loss", "dlogits", "prob", "info")
+
+    def _inst_ids(self, inst_id, what):
+        """None (instance k has id k) or an int32 cuda tensor [n_inst]: the id that seeds each instance's noise"""
+        if inst_id is None:
+            return None
+        if not (isinstance(inst_id, torch.Tensor) and inst_id.is_cuda and inst_id.dtype == torch.int32
+                and inst_id.is_contiguous() and inst_id.numel() == self.n_inst):
+            raise ValueError(f"{what}: inst_id must be a contiguous cuda int32 tensor of {self.n_inst} elements")
+        return inst_id
+
+    @staticmethod
+    def _topm_args(what, tau, sigma, n_samples, seed):
+        tau, sigma, n_samples, seed = float(tau), float(sigma), int(n_samples), int(seed)
+        if not (0.0 < tau < float("inf")) or not (0.0 <= sigma < float("inf")) or n_samples < 0:
+            raise ValueError(f"{what}: tau must be finite and > 0, sigma finite and >= 0, n_samples >= 0 "
+                             f"(got tau={tau}, sigma={sigma}, n_samples={n_samples})")
+        return tau, sigma, n_samples, seed & 0xFFFFFFFF
+
+    def topm_loss(self, logits, tau=1.0, sigma=0.0, n_samples=0, seed=0, inst_weight=None, pos_weight=None,
+                  want=("loss", "inst_loss", "dlogits"), inst_id=None):
+        """The soft top-m loss head (mllp_topm_loss): per instance the probabilities p_i = sigmoid(z_i / tau + nu) with nu
+        fixed by sum_i p_i = m_k (m_k = the instance's constraints), and `weighted_loss`'s BCE taken at z / tau + nu
+        instead of z; dlogits carries the implicit-function term of nu.  n_samples = 0 is the noise-free head
+        ('soft-topk'); n_samples = S >= 1 averages S evaluations with Gumbel noise of scale `sigma` on the logits
+        ('gs-topk'), a pure function of (seed, instance id, column, sample).  tau = sinkhorn_tau / 2 of the reference's
+        yaml.  Weights as in `weighted_loss`.  Returns a dict of device tensors over `want`, some of 'loss' [1],
+        'inst_loss' [n_inst], 'dlogits' [N], 'prob' [N] (noise-free p, sums to m_k) and 'info' [n_inst, 4] = (nu, Q,
+        sum p - m_k, largest iteration count); those not named are None and cost nothing.  Bitwise reproducible, the same
+        bits for an instance alone (given its `inst_id`) and inside any batch; no sync."""
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if not want or [w for w in want if w not in self._TOPM_WANT]:
+            raise ValueError(f"topm_loss: want must name some of {self._TOPM_WANT} (got {want!r})")
+        if not (logits.is_cuda and logits.dtype == torch.float32 and logits.is_contiguous() and logits.numel() == self.N):
+            raise ValueError(f"topm_loss: logits must be a contiguous cuda float32 tensor of {self.N} elements")
+        tau, sigma, n_samples, seed = self._topm_args("topm_loss", tau, sigma, n_samples, seed)
+        dev = logits.device
+        iw = self._per_instance(inst_weight, "topm_loss: inst_weight")
+        pw = self._per_instance(pos_weight, "topm_loss: pos_weight", allow_balanced=True)
+        ids = self._inst_ids(inst_id, "topm_loss")
+        new = lambda n: torch.empty(max(n, 1), device=dev, dtype=torch.float32)  # noqa: E731  (never a null pointer)
+        loss = new(1) if "loss" in want else None
+        inst = new(self.n_inst) if {"inst_loss", "loss"} & set(want) else None       # (as weighted_loss: never the serial launch)
+        dz = new(self.N) if "dlogits" in want else None
+        prob = new(self.N) if "prob" in want else None
+        info = new(4 * self.n_inst) if "info" in want else None
+        z, y = (logits, self._labels) if self.N else (torch.zeros(1, device=dev),) * 2
+        _lib.check(_lib.lib().mllp_topm_loss(self._h, _lib.ptr(z), _lib.ptr(y), _lib.ptr(iw), _lib.ptr(pw), _lib.ptr(ids), tau, sigma,
+                                             n_samples, seed, _lib.ptr(dz), _lib.ptr(inst), _lib.ptr(loss), _lib.ptr(prob),
+                                             _lib.ptr(info), _lib.current_stream()))
+        return dict(loss=loss, inst_loss=inst[:self.n_inst] if "inst_loss" in want else None,
+                    dlogits=None if dz is None else dz[:self.N], prob=None if prob is None else prob[:self.N],
+                    info=None if info is None else info[:4 * self.n_inst].view(self.n_inst, 4))
+
+    def topm_prob(self, logits, tau=1.0):
+        """The soft basis: p_i = sigmoid(z_i / tau + nu_k) with sum_i p_i = m_k per instance ([N] cuda float32; 0 for an
+        instance without constraints, 1 where m_k >= n_k).  The noise-free head's probabilities, labels not needed."""
+        return self.topm_loss(logits, tau, want="prob")["prob"]
+
+    def loss_step_topm(self, params, tau=1.0, sigma=0.0, n_samples=0, seed=0, inst_weight=None, pos_weight=None, logits=None,
+                       loss=None, inst_loss=None, grads=None, inst_id=None):
+        """`forward`, `topm_loss`, `backward` in one library call on the path in use (mllp_gnn_loss_step_topm).  Arguments
+        as `topm_loss` and `loss_step_weighted`.  Returns (loss [1], logits [N], grads, inst_loss [n_inst]); logits are bit
+        for bit those of `forward`, and `input_grads` may follow with `self.last_dlogits`."""
+        tau, sigma, n_samples, seed = self._topm_args("loss_step_topm", tau, sigma, n_samples, seed)
+        dev = params.device
+        logits = torch.empty(self.N, device=dev, dtype=torch.float32) if logits is None else logits
+        loss = torch.empty(1, device=dev, dtype=torch.float32) if loss is None else loss
+        inst_loss = torch.empty(max(self.n_inst, 1), device=dev, dtype=torch.float32)[:self.n_inst] if inst_loss is None else inst_loss
+        grads = torch.empty(_lib.NUM_PARAMS, device=dev, dtype=torch.float32) if grads is None else grads
+        if getattr(self, "last_dlogits", None) is None:
+            self.last_dlogits = torch.empty(max(self.N, 1), device=dev, dtype=torch.float32)[:self.N]
+        iw = self._per_instance(inst_weight, "loss_step_topm: inst_weight")
+        pw = self._per_instance(pos_weight, "loss_step_topm: pos_weight", allow_balanced=True)
+        ids = self._inst_ids(inst_id, "loss_step_topm")
+        self._check_inputs()
+        self._folded = None          # (as forward)
+        _lib.check(_lib.lib().mllp_gnn_loss_step_topm(self._h, _lib.ptr(params), _lib.ptr(self.x1), _lib.ptr(self.x2),
+                                                      _lib.ptr(self._labels), _lib.ptr(iw), _lib.ptr(pw), _lib.ptr(ids), tau, sigma,
+                                                      n_samples, seed, _lib.ptr(self.workspace()), _lib.ptr(logits), _lib.ptr(loss),
+                                                      _lib.ptr(inst_loss), _lib.ptr(grads), _lib.ptr(self.last_dlogits),
+                                                      _lib.current_stream()))
+        return loss, logits, grads, inst_loss
+
     def predict_basis(self, logits, want=("mask", "index", "stats")):
         """The predicted basis of every instance, on the device and without labels (mllp_topm_select): the m_k largest
         logits of instance k (m_k = its constraints), ordered and tie-broken as `topm_metrics` does -- by the key of the

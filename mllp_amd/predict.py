@@ -17,6 +17,8 @@ Written to --out:
                           that is not finite (runner_up = -inf when every column is selected) is written as the string
                           float() parses ("inf", "-inf", "nan").  With --labels (a directory of `<name>_basis.npy`),
                           also `correct` and `f1`, from `mllp_topm_metrics` for the sparse methods.
+  <name>_basis_prob.npy   only with --prob (sparse methods): float32 [n], the soft basis p_i = sigmoid(z_i / topm_tau + nu)
+                          whose sum is m (`LPBatch.topm_prob`; topm_tau from the yaml, 1 when absent)
 
 Method (the yaml's first entry): 'gs-topk' / 'soft-topk' -> GNNModel; 'angleNet' -> AngleModel on the dense angle graph
 of each instance (m = the rank of its Q factor, as in training); 'invariant' is not built.  There is no CPU path.
@@ -41,6 +43,8 @@ def parse_args(argv=None):
     p.add_argument("--mps", required=True, nargs="+", help="a directory of .mps files, or .mps files")
     p.add_argument("--out", required=True, help="output directory")
     p.add_argument("--labels", default=None, help="directory of <name>_basis.npy: also report correct / f1")
+    p.add_argument("--prob", action="store_true",
+                   help="also write <name>_basis_prob.npy: the soft basis of the top-m head (sparse methods; yaml key topm_tau)")
     return p.parse_args(argv)
 
 
@@ -86,8 +90,9 @@ def _record(m, n, thr, run, extra=None):
     return rec
 
 
-def predict_sparse(model, instances, batch_size, have_labels):
-    """[(instance, 0/1 int32 [n], record)] for the bipartite GNNModel, `batch_size` instances per block-diagonal batch."""
+def predict_sparse(model, instances, batch_size, have_labels, prob_tau=None):
+    """[(instance, 0/1 int32 [n], record)] for the bipartite GNNModel, `batch_size` instances per block-diagonal batch.
+    With `prob_tau` the tuples end in a fourth element, the soft basis float32 [n] at that temperature."""
     import torch
     from .graph import LPBatch
     bs = int(batch_size) if int(batch_size) > 0 else len(instances)
@@ -101,15 +106,20 @@ def predict_sparse(model, instances, batch_size, have_labels):
         parts = [pred.mask, pred.stats.reshape(-1).view(torch.uint8)]
         if have_labels:
             parts.append(b.topm_metrics(logits).reshape(-1).view(torch.uint8))
+        if prob_tau is not None:
+            parts.append(b.topm_prob(logits, prob_tau).view(torch.uint8))
         host = torch.cat(parts).cpu().numpy()                 # the batch's one copy back
         k = len(grp)
         mask = host[:b.N].astype(np.int32)
         stats = host[b.N:b.N + 8 * k].view(np.float32).reshape(k, 2)
-        met = host[b.N + 8 * k:].view(np.float32).reshape(k, 2) if have_labels else None
+        end = b.N + 8 * k + (8 * k if have_labels else 0)
+        met = host[b.N + 8 * k:end].view(np.float32).reshape(k, 2) if have_labels else None
+        prob = host[end:].view(np.float32) if prob_tau is not None else None
         off = np.concatenate([[0], np.cumsum(b.inst_n)])
         for j, inst in enumerate(grp):
             extra = {"correct": float(met[j, 0]), "f1": float(met[j, 1])} if have_labels else None
-            out.append((inst, mask[off[j]:off[j + 1]], _record(inst.m, inst.n, stats[j, 0], stats[j, 1], extra)))
+            row = (inst, mask[off[j]:off[j + 1]], _record(inst.m, inst.n, stats[j, 0], stats[j, 1], extra))
+            out.append(row if prob is None else row + (prob[off[j]:off[j + 1]].copy(),))
     return out
 
 
@@ -150,6 +160,8 @@ def main(argv=None):
                            "there is no CPU fallback")
     if not os.path.isfile(args.model):
         raise FileNotFoundError(f"--model {args.model}: no such file")
+    if args.prob and method not in SPARSE_METHODS:
+        raise NotImplementedError(f"--prob: the soft basis is the top-m head's, for the sparse methods {SPARSE_METHODS} only")
     files = mps_files(args.mps)
     if args.labels is not None and not os.path.isdir(args.labels):
         raise FileNotFoundError(f"--labels {args.labels}: no such directory")
@@ -174,11 +186,14 @@ def main(argv=None):
         from .model import GNNModel
         model = GNNModel().to(device)
         model.load_state_dict(state)
-        results = predict_sparse(model, instances, cfg.get_default("batch_size"), args.labels is not None)
+        results = predict_sparse(model, instances, cfg.get_default("batch_size"), args.labels is not None,
+                                 float(cfg.get_default("topm_tau")) if args.prob else None)
     os.makedirs(args.out, exist_ok=True)
     table = {}
-    for inst, mask, rec in results:
+    for inst, mask, rec, *prob in results:
         np.save(os.path.join(args.out, inst.name + "_basis_pred.npy"), mask)
+        if prob:
+            np.save(os.path.join(args.out, inst.name + "_basis_prob.npy"), prob[0])
         table[inst.name] = rec
     with open(os.path.join(args.out, "predictions.json"), "w") as fh:
         json.dump(table, fh, indent=1)

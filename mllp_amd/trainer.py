@@ -114,8 +114,10 @@ class LPTrainer:
 
     def __init__(self, params_flat: torch.Tensor, lr=1e-3, use_hip_graph="auto",
                  global_instances: Optional[int] = None, with_metrics=False, tiled_copies="auto", stream_copies=True,
-                 pos_weight=None):
+                 pos_weight=None, loss_head="bce", topm_tau=1.0, topm_sigma=0.0, topm_samples=0):
         assert params_flat.is_cuda and params_flat.numel() == NUM_PARAMS
+        if loss_head not in ("bce", "topm"):
+            raise ValueError(f"loss_head: 'bce' or 'topm', got {loss_head!r}")
         self.params = params_flat.detach().clone().float().contiguous()
         self.opt = FlatAdam(self.params, lr=lr)
         self.use_graph = use_hip_graph
@@ -126,6 +128,12 @@ class LPTrainer:
         # None: the unweighted loss of mllp_gnn_train_step / mllp_gnn_loss_step.  A float, a tensor [n_inst] or 'balanced':
         # BCEWithLogitsLoss(pos_weight) through LPBatch.loss_step_weighted, per-instance losses in `inst_loss_of`
         self.pos_weight = pos_weight
+        # 'bce': the heads above.  'topm': the soft top-m head through LPBatch.loss_step_topm (probabilities that sum to
+        # m_k; topm_samples = 0 without noise, S >= 1 the mean of S evaluations with Gumbel noise of scale topm_sigma).  The
+        # noise of a step is seeded by `topm_step`, the number of steps taken so far: a checkpoint keeps it
+        self.loss_head = loss_head
+        self.topm = dict(tau=float(topm_tau), sigma=float(topm_sigma), n_samples=int(topm_samples))
+        self.topm_step = 0
         self._plans = {}
         self._gen = 0                  # bumped at every library-side write of the parameters (LPBatch.train_step)
 
@@ -135,6 +143,8 @@ class LPTrainer:
         if p is None:
             dev = self.params.device
             graph = (batch.nnz <= self.GRAPH_NNZ_LIMIT) if self.use_graph == "auto" else bool(self.use_graph)
+            if self.loss_head == "topm" and self.topm["n_samples"] > 0:
+                graph = False          # (the seed is an argument by value and changes every step: a replay would repeat the noise)
             want_tiled = (batch.nnz >= self.TILED_NNZ_MIN) if self.tiled_copies == "auto" else bool(self.tiled_copies)
             if want_tiled and self.stream_copies:
                 if not batch._streams:
@@ -144,7 +154,7 @@ class LPTrainer:
             p = dict(batch=batch, logits=torch.empty(batch.N, device=dev), loss=torch.zeros(1, device=dev),
                      grads=torch.zeros(NUM_PARAMS, device=dev), metrics=torch.zeros(batch.n_inst, 2, device=dev),
                      g_fwd=None, g_opt=None, warm=0, graph=graph)
-            if self.pos_weight is not None:
+            if self.pos_weight is not None or self.loss_head == "topm":
                 p["inst_loss"] = torch.zeros(max(batch.n_inst, 1), device=dev)[:batch.n_inst]
             self._plans[key] = p
         return p
@@ -156,6 +166,10 @@ class LPTrainer:
     def evaluate(self, batch: LPBatch):
         """`LPBatch.evaluate` under this trainer's parameters and pos_weight: dict(logits, inst_loss, metrics).  No
         gradient, no optimizer step, no sync; parameters and Adam state are not touched."""
+        if self.loss_head == "topm":       # the noise-free head, whatever the training samples
+            logits = batch.forward(self.params)
+            inst = batch.topm_loss(logits, self.topm["tau"], pos_weight=self.pos_weight, want="inst_loss")["inst_loss"]
+            return dict(logits=logits, inst_loss=inst, metrics=batch.topm_metrics(logits))
         return batch.evaluate(self.params, self.pos_weight)
 
     def metrics_of(self, batch: LPBatch) -> torch.Tensor:
@@ -187,7 +201,11 @@ class LPTrainer:
     def _fwd_bwd(self, p):
         b = p["batch"]
         inv = 1.0 / float(self.global_instances or b.n_inst)
-        if self.pos_weight is not None:
+        if self.loss_head == "topm":
+            b.loss_step_topm(self.params, self.topm["tau"], self.topm["sigma"], self.topm["n_samples"], self.topm_step, inv,
+                             self.pos_weight, p["logits"], p["loss"], p["inst_loss"], p["grads"])
+            self.topm_step += 1
+        elif self.pos_weight is not None:
             b.loss_step_weighted(self.params, inv, self.pos_weight, p["logits"], p["loss"], p["inst_loss"], p["grads"])
         else:
             b.loss_step(self.params, inv, p["logits"], p["loss"], p["grads"])
@@ -213,7 +231,7 @@ class LPTrainer:
         multi = dist.is_available() and dist.is_initialized() and (
             dist.get_world_size() > 1 or os.environ.get("MLLP_BENCH_FORCE_DIST") == "1")
         if not p["graph"] or p["warm"] < 1:
-            if multi or self.pos_weight is not None:      # (one rank: the all-reduce is a no-op)
+            if multi or self.pos_weight is not None or self.loss_head == "topm":      # (one rank: the all-reduce is a no-op)
                 self._fwd_bwd(p)
                 allreduce_sum_(p["grads"])
                 self._opt(p)
