@@ -108,6 +108,19 @@ int mllp_graph_export(const mllp_graph_t* g, int which, void* host_dst, int64_t 
  * Both paths compute the same quantities (tests compare them with each other and with the oracle).        */
 int mllp_graph_set_path(mllp_graph_t* g, int path);
 
+/* Grid of the fused sweeps (symbols added without an ABI bump: callers check for them, as for mllp_graph_set_values).
+ * Process-wide cap on the workgroups of the fused sweeps, for graphs created AFTER the call:
+ *   G = max(min(device CUs, STAT_BLOCKS_MAX = 256, limit) / 8, 1) * 8.
+ * 0 means no limit.  It can only lower the grid: a limit above the device's CU count changes nothing, so every
+ * workgroup stays resident as today.  Needs no GPU.  Negative: MLLP_EINVAL.  *previous (may be NULL) receives the
+ * old value.  A graph keeps the limit it was created under, also when its fused arrays are built later by
+ * mllp_graph_set_path(g, 2).  What it is for, and what it does not reproduce of a partitioned device: DESIGN.md. */
+int mllp_set_fused_grid_limit(int64_t workgroups, int64_t* previous);
+
+/* info = {G of this graph's fused sweeps, partitions (8), device CUs, the limit in force when it was created}.
+ * A null argument is refused.  G is reported as the rule gives it even while the fused arrays are not built. */
+int mllp_graph_fused_grid(const mllp_graph_t* g, int64_t info[4]);
+
 /* INPUT CONTRACT of the whole-model entry points on the fused path: the graph keeps renumbered copies of d_x1, d_x2
  * and d_labels (and the layer-1 source features gathered beside the nonzeros), keyed on the POINTER VALUES -- the
  * model's inputs are data (linear_program_methods.py:90-91), constant for the life of a batch.  A caller that changes

@@ -57,6 +57,8 @@ _PROTOTYPES = {
     "mllp_graph_dims": (c_int, [c_void_p, POINTER(c_int64)]),
     "mllp_graph_export": (c_int, [c_void_p, c_int, c_void_p, c_int64]),
     "mllp_graph_set_path": (c_int, [c_void_p, c_int]),
+    "mllp_set_fused_grid_limit": (c_int, [c_int64, POINTER(c_int64)]),
+    "mllp_graph_fused_grid": (c_int, [c_void_p, POINTER(c_int64)]),
     "mllp_graph_invalidate_inputs": (c_int, [c_void_p]),
     "mllp_graph_set_values": (c_int, [c_void_p, c_void_p, c_void_p]),
     "mllp_graph_set_values_bytes": (c_int, [c_void_p, POINTER(c_int64)]),

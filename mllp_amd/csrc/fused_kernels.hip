@@ -2076,7 +2076,7 @@ int fused_graph_build(mllp_graph* g, const int* h_csr_ptr, const int* h_csc_ptr)
         set_tiers(At.t16[q], hv.t16[q]); set_tiers(At.t1[q], hv.t1[q]);
     }
     for (int q = 0; q <= NP; ++q) { A.row0[q] = hc.row0[q]; At.row0[q] = hv.row0[q]; }
-    {   // items of every wavefront at the grids the sweeps are launched with (fused_grid: fixed per device)
+    {   // items of every wavefront at the grids the sweeps are launched with (fused_grid: fixed per graph)
         const int gp = fused_grid(g) / NP;
         const HostFusedOrient* ho[2] = {&hc, &hv};
         FusedOrient* dv[2] = {&A, &At};
@@ -2164,7 +2164,8 @@ int fused_bind(mllp_graph* g, const float* x1, const float* x2, const float* lab
 // ====================================================================================================
 // the whole model on the fused path
 // ====================================================================================================
-// one workgroup per CU, a multiple of the partition count (workgroup b works on partition b % NP)
+// one workgroup per CU (g->n_cu: the device's count under the grid limit the graph was created with,
+// mllp_set_fused_grid_limit), a multiple of the partition count (workgroup b works on partition b % NP)
 int fused_grid(const mllp_graph* g) { return std::max(std::min(g->n_cu, STAT_BLOCKS_MAX) / NP, 1) * NP; }
 
 static FwdJob16 fwd_job16(const FusedOrient& o, const FusedModel& m, int c, const float* x_src, const float* x_dst, float* h) {

@@ -4,6 +4,7 @@
 // (BipartiteData.__inc__ batching offsets): done ONCE per batch, on the host, in parallel over
 // instances (they are independent blocks of the block-diagonal matrix), then uploaded.
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstring>
 
@@ -23,6 +24,9 @@ int hip_fail(hipError_t e, const char* what) {
     return e == hipErrorOutOfMemory ? MLLP_ENOMEM : MLLP_EHIP;
 }
 const char* last_error_cstr() { return g_err.c_str(); }
+
+// mllp_set_fused_grid_limit: read once per graph, in finish_common (0: no limit)
+static std::atomic<int64_t> g_fused_grid_limit{0};
 
 template <class T>
 static int upload(mllp_graph* g, const T* host, size_t count, T** dev) {
@@ -86,7 +90,9 @@ static int finish_common(mllp_graph* g) {
         int dev = 0, cus = 0;
         MLLP_HIP_TRY(hipGetDevice(&dev));
         MLLP_HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-        g->n_cu = cus > 0 ? cus : 256;
+        g->n_cu_dev = cus > 0 ? cus : 256;
+        g->grid_limit = g_fused_grid_limit.load(std::memory_order_relaxed);
+        g->n_cu = g->grid_limit > 0 ? (int)std::min<int64_t>(g->n_cu_dev, g->grid_limit) : g->n_cu_dev;
     }
     MLLP_HIP_TRY(hipStreamCreateWithFlags(&g->aux, hipStreamNonBlocking));
     for (auto& e : g->ev) MLLP_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -239,6 +245,19 @@ extern "C" int mllp_graph_dims(const mllp_graph_t* g, int64_t dims[12]) {
     dims[4] = g->A.n_group; dims[5] = g->A.n_wave; dims[6] = g->A.n_chunk;
     dims[7] = g->At.n_group; dims[8] = g->At.n_wave; dims[9] = g->At.n_chunk;
     dims[10] = g->A.n_split; dims[11] = g->At.n_split;
+    return MLLP_OK;
+}
+
+extern "C" int mllp_set_fused_grid_limit(int64_t workgroups, int64_t* previous) {
+    if (workgroups < 0) return fail(MLLP_EINVAL, "mllp_set_fused_grid_limit: the limit must be 0 (none) or a positive number of workgroups");
+    const int64_t old = g_fused_grid_limit.exchange(workgroups, std::memory_order_relaxed);
+    if (previous) *previous = old;
+    return MLLP_OK;
+}
+
+extern "C" int mllp_graph_fused_grid(const mllp_graph_t* g, int64_t info[4]) {
+    if (!g || !info) return fail(MLLP_EINVAL, "mllp_graph_fused_grid: null argument");
+    info[0] = fused_grid(g); info[1] = FUSED_PARTS; info[2] = g->n_cu_dev; info[3] = g->grid_limit;
     return MLLP_OK;
 }
 

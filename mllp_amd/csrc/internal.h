@@ -168,7 +168,10 @@ struct mllp_graph {
     std::vector<int> h_csr_ptr, h_csc_ptr;     // host copies of the row pointers (the fused path is built from them)
     int tier_wave = 0, tier_block = 0, chunk_nnz = 0;
     int max_inst_n = 0;
-    int n_cu = 256;              // compute units of the device: grid size of the persistent fused kernels
+    int n_cu = 256;              // grid size of the persistent fused kernels: the device's compute units, lowered by the
+                                 // limit in force at creation (mllp_set_fused_grid_limit)
+    int n_cu_dev = 256;          // compute units of the device
+    int64_t grid_limit = 0;      // that limit (0: none), kept because the fused arrays may be built later (set_path(2))
     int path = 0;                // whole-model path: 0 = by size (fused below 32 M nonzeros), 1 = generic / tiled, 2 = fused
     // fused path: renumbered copies of both orientations, permutations, renumbered copies of the bound inputs
     bool fused_built = false;

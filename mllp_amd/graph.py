@@ -5,6 +5,7 @@
 `BipartiteData.__inc__` batching rule (methods.py:60-72): the batch is built once, lives in HBM as
 CSR(A) + CSR(A^T) behind an opaque `mllp_graph_t*`, and every model call takes it by handle.
 """
+import contextlib
 import ctypes
 import itertools
 import time
@@ -24,6 +25,25 @@ from .data import LPInstance
 _B128_GROUPS = [[0, 1, 2, 3, 12, 13, 14, 15, 20, 21, 22, 23, 24, 25, 26, 27],
                 [4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19, 28, 29, 30, 31]]
 LANE_GROUPS = [[l + h for l in grp if (l & 3) == r] for h in (0, 32) for grp in _B128_GROUPS for r in range(4)]
+
+
+def set_fused_grid_limit(n):
+    """mllp_set_fused_grid_limit: cap the workgroups of the fused sweeps of batches created from now on (0: no limit);
+    returns the previous value.  Needs no GPU."""
+    prev = c_int64()
+    _lib.check(_lib.lib().mllp_set_fused_grid_limit(int(n), ctypes.byref(prev)))
+    return int(prev.value)
+
+
+@contextlib.contextmanager
+def fused_grid_limit(n):
+    """Batches created inside run their fused sweeps on at most `n` workgroups (rounded down to a multiple of 8, at least
+    8); the previous limit is restored on exit.  A batch keeps the grid it was created with."""
+    prev = set_fused_grid_limit(n)
+    try:
+        yield
+    finally:
+        set_fused_grid_limit(prev)
 
 
 def build_tiled_arrays(ptr, idx, val, n_dst, R, CB, variant=0, entry_order="joint"):
@@ -595,6 +615,12 @@ class LPBatch:
         keys = ["M", "N", "nnz", "n_inst", "A_group", "A_wave", "A_block", "At_group", "At_wave", "At_block",
                 "A_split", "At_split"]
         return dict(zip(keys, [int(v) for v in d]))
+
+    def fused_grid_info(self):
+        """(workgroups G of this batch's fused sweeps, partitions, the device's CUs, the grid limit it was created under)"""
+        d = (c_int64 * 4)()
+        _lib.check(_lib.lib().mllp_graph_fused_grid(self._h, d))
+        return tuple(int(v) for v in d)
 
     def export(self, which):
         sizes = {0: (self.M + 1, np.int32), 1: (self.nnz, np.int32), 2: (self.nnz, np.float32),

@@ -77,6 +77,40 @@ def grid_per_partition(cus, c=None):
     return max(min(int(cus), c["STAT_BLOCKS_MAX"]) // c["PARTS"], 1)        # fused_grid() / NP
 
 
+def reduce_loops(csrc=None):
+    """The loops of fused_reduce_body over the per-workgroup partials, PARSED from fused_kernels.hip:
+    (slices, [(lookahead, stride), ...]) for `b = slice; for (; b + lookahead < nblk; b += stride)` in source order, where
+    `slices` is the number of distinct starting values of b (RT >> the shift of `slice = tid >> ..`)."""
+    k = _src("fused_kernels.hip", csrc)
+    m = re.search(r"void\s+fused_reduce_body\s*\(.*?\n\}\n", k, re.S)
+    assert m, "cannot find fused_reduce_body"
+    body = m.group(0)
+    body = body[body.index("float* sh4"):]                  # behind the fc partials' own branch
+    rt = _ints(k, r"constexpr\s+int\s+RT\s*=\s*(\d+)", "RT")[0]
+    shift = _ints(body, r"slice\s*=\s*tid\s*>>\s*(\d+)", "slice = tid >> ..")[0]
+    assert re.search(r"int\s+b\s*=\s*slice\s*;", body), "cannot find b = slice"
+    loops = [(int(la or 0), int(st)) for la, st in
+             re.findall(r"for\s*\(\s*;\s*b(?:\s*\+\s*(\d+))?\s*<\s*A\.nblk\s*;\s*b\s*\+=\s*(\d+)\s*\)", body)]
+    assert len(loops) == 3, f"fused_reduce_body: expected three loops over the partials, found {loops}"
+    return rt >> shift, loops
+
+
+def reduce_trips(nblk, slices, loops):
+    """Trips of every loop of reduce_loops() for nblk partials, per thread: [{trips of the threads} per loop], and the
+    partials each starting value visits (they must tile 0 .. nblk - 1)."""
+    trips = [set() for _ in loops]
+    seen = []
+    for b in range(slices):
+        for i, (la, st) in enumerate(loops):
+            n = 0
+            while b + la < nblk:
+                seen += list(range(b, b + st, slices))
+                b += st
+                n += 1
+            trips[i].add(n)
+    return trips, sorted(seen)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # 2. census
 # ---------------------------------------------------------------------------------------------------------------------
@@ -246,6 +280,15 @@ def chunk_base(seed=3):
     rng = np.random.default_rng(seed)
     B = block_of(list(range(65, 101)), 192, rng)
     return two_sided(B, B, rng, "chunkbase")
+
+
+def chunk_base_small(seed=3):
+    """A base LP of three items per side (wave rows of 65 and 66 nonzeros, a group row of 17) over 70 columns of about two:
+    replicas of it move the list lengths of a SMALL grid in steps fine enough to land on 63 / 64 and 65 / 66 items, which
+    chunk_base()'s 72 wave rows per replica step over at 8 workgroups (12 wavefronts)."""
+    rng = np.random.default_rng(seed)
+    B = block_of([65, 66, 17], 70, rng)
+    return two_sided(B, B, rng, "chunksmall")
 
 
 def block_laps_instance(cus=256, seed=4, c=None):

@@ -4,7 +4,8 @@ partial item of every tier, empty tiers and empty partitions, wavefront lists of
 chunks, a second and third lap of the block-tier loop, a sharpened softmax in every merged tier, batches without
 nonzeros.  Every GPU test forces set_path(2) on a fresh batch and starts by asserting, through the census of
 tests/fused_cases.py, that its input reaches what it claims; the CPU tests make the same assertions for 256 CUs and check
-the identities that let one cheap oracle run stand for a 4.7 M-nonzero instance.
+the identities that let one cheap oracle run stand for a 4.7 M-nonzero instance.  tests/test_fused_grids.py makes them for
+grids of 8, 32, 40, 64, 128 and 168 workgroups and runs the same cases there, through the helpers of this file.
 
 Tolerances are those of tests/test_hip_parity.py: 1e-5 for logits and losses, 5e-5 for gradients, lin_key.bias masked.
 Yardstick: the same decomposition in fp32 on the CPU against fp64 (fused_cases.model_dt), as max|diff| / max|ref|; the
@@ -59,7 +60,8 @@ def _show(name, cen):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# what every case claims to reach (asserted on the CPU for 256 CUs, and again by the GPU tests for the device's CUs)
+# what every case claims to reach (asserted on the CPU for 256 CUs, and again by the GPU tests for the device's CUs; for
+# the other grids in tests/test_fused_grids.py)
 # ---------------------------------------------------------------------------------------------------------------------
 def assert_grid_reach(variant, cus):
     c = fc.constants()
@@ -89,8 +91,8 @@ def assert_grid_reach(variant, cus):
     return inst, cen
 
 
-def assert_chunk_reach(R, cus, exact=()):
-    inst = fc.replicate(fc.chunk_base(), R, basis_seed=R)
+def assert_chunk_reach(R, cus, exact=(), base=None):
+    inst = fc.replicate(base or fc.chunk_base(), R, basis_seed=R)
     cen = fc.census(inst, cus, exact=bool(exact))
     _show(inst.name, cen)
     for orient in ("A", "At"):
@@ -253,23 +255,40 @@ def _params(sd):
     return torch.tensor(flat, dtype=torch.float32, device="cuda")
 
 
-def _check_step(LPBatch, insts, sd, r, what, max_exempt=None):
+def _nan(n):
+    return torch.full((n,), float("nan"), device="cuda")
+
+
+def _poison(b, *names):
+    """The workspace and the named outputs of the next whole-model call filled with NaN (memory contract, rule 1: the bits
+    may not depend on what they held).  Returns the outputs as keyword arguments of the call."""
+    b.workspace().fill_(float("nan"))
+    n = dict(logits=b.N, loss=1, grads=4721)
+    return {k: _nan(n[k]) for k in names}
+
+
+def _check_step(LPBatch, insts, sd, r, what, max_exempt=None, make=None, poison=False, yard=None):
     """logits (max norm and element-wise), loss, gradients (max_exempt given: every tensor on its own scale too, at most
-    that many exempted by the fp32 yardstick: tests/grad_scales.py), a bitwise-equal second run, forward-only logits"""
+    that many exempted by the fp32 yardstick: tests/grad_scales.py), a bitwise-equal second run, forward-only logits.
+    make: how the batches are created (tests/test_fused_grids.py: under a grid limit); poison: NaN in the workspace and
+    in every output before every call; yard: the yardstick of this input, where the caller has it already."""
+    make = make or _fused
     p = _params(sd)
-    b = _fused(LPBatch, insts)
-    loss, logits, grads = [t.clone() for t in b.loss_step(p)]
+    b = make(LPBatch, insts)
+    out = lambda bb, *names: _poison(bb, *names) if poison else {}
+    loss, logits, grads = [t.clone() for t in b.loss_step(p, **out(b, "logits", "loss", "grads"))]
     keep = grad_mask()
     close(logits.cpu().numpy(), r["logits"], RTOL_ACT, f"{what}: logits")
     close_elementwise(logits.cpu().numpy(), r["logits"], RTOL_ACT, f"{what}: logits, element-wise")
     close(loss.cpu().numpy(), [r["loss"]], RTOL_ACT, f"{what}: loss")
     close(grads.cpu().numpy()[keep], r["grads"][keep], RTOL_GRAD, f"{what}: gradients")
     if max_exempt is not None:
-        gs.close_per_tensor(grads.cpu().numpy(), r["grads"], gs.yardstick(sd, o2.BatchCSR(insts)), f"{what}: gradients",
-                            max_exempt=max_exempt)
-    l2, z2, g2 = b.loss_step(p)
+        gs.close_per_tensor(grads.cpu().numpy(), r["grads"], yard or gs.yardstick(sd, o2.BatchCSR(insts)),
+                            f"{what}: gradients", max_exempt=max_exempt)
+    l2, z2, g2 = b.loss_step(p, **out(b, "logits", "loss", "grads"))
     assert torch.equal(l2, loss) and torch.equal(z2, logits) and torch.equal(g2, grads), f"{what}: not run-to-run exact"
-    fwd = _fused(LPBatch, insts).forward(p).cpu().numpy()
+    b2 = make(LPBatch, insts)
+    fwd = b2.forward(p, **out(b2, "logits")).cpu().numpy()
     close(fwd, r["logits"], RTOL_ACT, f"{what}: forward-only logits")
     close_elementwise(fwd, r["logits"], RTOL_ACT, f"{what}: forward-only logits, element-wise")
     return b, p
@@ -322,24 +341,27 @@ def test_spotlight_backward(dev, golden, orient, tier):
     close(g[keep], r["grads"][keep], RTOL_GRAD, f"spotlight {orient} {geo} {tier}: gradients")
 
 
-def _check_replicas(LPBatch, golden, inst, R, what, direct):
+def _check_replicas(LPBatch, golden, inst, R, what, direct, base=None, make=None, poison=False):
+    make = make or _fused
+    out = lambda bb, *names: _poison(bb, *names) if poison else {}
     sd = _sd(golden)
-    base = fc.chunk_base()
+    base = base or fc.chunk_base()
     rb = _oracle(sd, [base], f"{what}: base LP", want_grads=False)
     p = _params(sd)
-    b = _fused(LPBatch, [inst])
-    z = b.forward(p).cpu().numpy().astype(np.float64).reshape(R, base.n)
+    b = make(LPBatch, [inst])
+    z = b.forward(p, **out(b, "logits")).cpu().numpy().astype(np.float64).reshape(R, base.n)
     want = np.broadcast_to(rb["logits"], z.shape)
     close(z, want, RTOL_ACT, f"{what}: logits of the {R} replicas")
     close_elementwise(z, want, RTOL_ACT, f"{what}: logits of the {R} replicas, element-wise")
     # a dlogits that differs from replica to replica == the base LP's backward from the sum of the slices
     dz = (np.random.default_rng(R).standard_normal(inst.n) / np.sqrt(inst.n)).astype(np.float32)
-    g = b.backward(p, torch.tensor(dz, device="cuda")).cpu().numpy()
+    g = b.backward(p, torch.tensor(dz, device="cuda"), **({"grads": _nan(4721)} if poison else {})).cpu().numpy()
     rg = _oracle(sd, [base], f"{what}: base LP, summed dlogits", dlogits=dz.astype(np.float64).reshape(R, base.n).sum(0))
     keep = grad_mask()
     close(g[keep], rg["grads"][keep], RTOL_GRAD, f"{what}: gradients of a per-replica dlogits")
     # the loss step: labels differ per replica; its gradient is the backward from (sigmoid(z) - y) / N
-    loss, logits, grads = _fused(LPBatch, [inst]).loss_step(p)
+    b = make(LPBatch, [inst])
+    loss, logits, grads = b.loss_step(p, **out(b, "logits", "loss", "grads"))
     zr = np.tile(rb["logits"], R)
     y = inst.basis.astype(np.float64)
     want_loss = float((np.maximum(zr, 0) - zr * y + np.log1p(np.exp(-np.abs(zr)))).mean())
@@ -368,18 +390,25 @@ def test_list_chunks_against_oracle(dev, golden, R, exact):
 def test_block_laps_against_oracle(dev, golden):
     """I. more than 2 * gp block rows in one partition, in both geometries and both orientations."""
     LPBatch, cus = dev
+    _check_block_laps(LPBatch, golden, cus)
+
+
+def _check_block_laps(LPBatch, golden, cus, make=None, poison=False):
+    """the laps instance of a grid of `cus` workgroups: the whole step, then a spotlight on a row of the third lap"""
     inst, _ = assert_laps_reach(cus)
     sd = _sd(golden)
     r = _oracle(sd, [inst], "blocklaps")
-    b, p = _check_step(LPBatch, [inst], sd, r, "blocklaps")
+    b, p = _check_step(LPBatch, [inst], sd, r, "blocklaps", make=make, poison=poison)
     dz = np.zeros(inst.n)
     last = int(np.argsort(-fc.degrees(inst)[0], kind="stable")[2 * fc.grid_per_partition(cus)])     # a row of the third lap
     hot = fc.one_hop(inst, "A", last)
     dz[hot] = 1.0
     rs = _oracle(sd, [inst], "blocklaps, spotlight on a row of the third lap", dlogits=dz)
-    b.forward(p)
-    g = b.backward(p, torch.tensor(dz, dtype=torch.float32, device="cuda")).cpu().numpy()
+    b.forward(p, **(_poison(b, "logits") if poison else {}))
+    g = b.backward(p, torch.tensor(dz, dtype=torch.float32, device="cuda"), **({"grads": _nan(4721)} if poison else {}))
+    g = g.cpu().numpy()
     close(g[grad_mask()], rs["grads"][grad_mask()], RTOL_GRAD, "blocklaps: spotlight gradients")
+    return b
 
 
 @gpu
