@@ -521,7 +521,7 @@ int mllp_tconv_bwd(const mllp_graph_t* g, int dst_is_var, int cin, const float* 
  *   d_ws     : mllp_gnn_workspace_bytes() bytes, kept between forward and backward
  *   d_logits [N] : per-variable logits (methods.py:250-251)
  * MEMORY CONTRACT of every mllp_gnn_*, mllp_tconv_*, mllp_spmm_*, mllp_weighted_loss, mllp_balanced_pos_weight, mllp_topm_*,
- * mllp_graph_normalize, mllp_graph_plant_basis, mllp_lp_certificate, mllp_basis_repair and mllp_basis_simplex call, for every buffer the caller owns (tests/test_memory_contract.py):
+ * mllp_graph_normalize, mllp_graph_plant_basis, mllp_lp_certificate, mllp_basis_repair, mllp_basis_simplex and mllp_optim_step call, for every buffer the caller owns (tests/test_memory_contract.py):
  *   1. A call's outputs do not depend on any byte that d_ws, or any other scratch or output buffer, held before the call:
  *      the buffers may be uninitialised, NaN included, and the same bits come out.  The only state carried between calls is
  *      what this header names: mllp_gnn_forward -> mllp_gnn_backward / _backward_inputs / _input_grads on the same workspace
@@ -761,6 +761,59 @@ int mllp_gnn_loss_step_topm(const mllp_graph_t* g, const float* d_params, const 
  * ---------------------------------------------------------------------------------------------- */
 int mllp_adam_step(float* d_params, const float* d_grads, float* d_exp_avg, float* d_exp_avg_sq,
                    float* d_state, float eps, float grad_scale, int64_t n, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * AdamW, global-norm gradient clipping and a learning-rate schedule on the flat buffers, all decided on the device
+ * (mllp_amd/csrc/optim.hip): torch.optim.AdamW + torch.nn.utils.clip_grad_norm_ + a warm-up / cosine
+ * LambdaLR, without a host round trip, so that a captured step replays with the schedule advancing.  A new entry point
+ * beside mllp_adam_step, which is unchanged (symbols added without an ABI bump: callers check for them, as for
+ * mllp_graph_set_values).
+ *   d_state [8] = {step, lr_base, beta1, beta2, warmup W, total T, min_ratio r, 0}.  The first four words are
+ *            mllp_adam_step's: a state of that call is continued by padding {0, 0, 0, 0}.  Only state[0] is ever written.
+ *   d_scratch : mllp_optim_scratch_floats(n) floats (0 for n <= 16384: the pointer may then be NULL).
+ *   d_info [4] or NULL = {||g||, c, lr_t, skipped}.
+ * THE RULE.  All arithmetic is fp32; t = step + 1 is the step being taken.
+ *   gradient  g_i = grad_scale * d_grads[i].
+ *   norm      computed only when max_norm > 0 or d_info is given: ||g|| = sqrtf(sum_i g_i^2), every operation an explicit
+ *             __fmaf_rn / __fadd_rn in a FIXED ORDER THAT DEPENDS ON n ALONE -- the order is the contract:
+ *               slices of 4096 elements, slice s = [4096 s, min(n, 4096 (s + 1)));
+ *               the partial P_s of a slice by one workgroup of 1024 threads: thread t adds its terms t, t + 1024, t + 2048,
+ *               t + 3072 of the slice in that order, from 0 (acc = fmaf(g, g, acc)); the 64 lanes of a wavefront by the xor
+ *               butterfly (1, 2, half-mirror, mirror inside 16 lanes, then 16 and 32), the 16 wavefronts by the fixed binary
+ *               tree ((0 + 1) + (2 + 3)) + ... (ordered_sum.h);
+ *               the total by the same pattern over the partials: thread t adds P_t, P_(t + 1024), ... in that order, from
+ *               0, then butterfly and tree.
+ *             No float atomics, one writer per word: the same bits on every run.
+ *   clip      c = min(1, max_norm / (||g|| + 1e-6)) when max_norm > 0, else 1 (torch.nn.utils.clip_grad_norm_).
+ *   skip      where a norm was computed and it is not finite (a NaN or Inf anywhere in the gradient, or an overflow of the
+ *             sum), THE STEP IS SKIPPED: d_params, both moments and all of d_state keep their bits, d_info = {||g||, 0,
+ *             lr_t, 1}.  This is deliberately NOT torch's behaviour, which scales by NaN and writes NaN into every weight.
+ *             With max_norm == 0 and d_info == NULL nothing is inspected, as in mllp_adam_step.
+ *   rate      lr_t = lr_base * t / W                                                       for W > 0 and t <= W;
+ *             lr_t = lr_base * (r + (1 - r) * 0.5 * (1 + cosf(pi * min(1, (t - W) / (T - W)))))   otherwise, for T > W;
+ *             lr_t = lr_base                                                               otherwise.
+ *             W = T = 0 is mllp_adam_step's constant rate.  lr_t is never stored into state[1].
+ *   decay     decoupled (torch.optim.AdamW): p_i <- p_i - (lr_t * weight_decay) * p_i (one fmaf), then Adam's update of
+ *             mllp_adam_step with c * g_i and lr_t.  An element with g_i == 0 and both moments 0 is NOT TOUCHED AT ALL, and
+ *             is not decayed either: the flat buffer cannot tell "grad is None" from 0 (gconv3_s2w), and this is what AdamW
+ *             does to a parameter without a gradient.
+ *   equivalence  with weight_decay = 0, max_norm = 0, W = T = 0 and d_info == NULL, d_params, both moments and state[0]
+ *             get the bits mllp_adam_step gives them, at every n.
+ * SHAPE.  n <= 16384: one launch of one workgroup (norm, barrier, update, tick).  Larger n: at most three launches -- the
+ *   slice partials into d_scratch (not run when no norm is needed), the sliced update in which every workgroup adds the
+ *   partials itself in the order above, a one-thread tick of the step counter.  Stream order between the launches is the
+ *   only synchronisation.  A launch function: it works on `stream` only, allocates nothing, never synchronises and can be
+ *   captured into a hipGraph.  Under the MEMORY CONTRACT above: d_scratch and d_info may hold anything, NaN included.
+ * REFUSALS, MLLP_EINVAL with a message before any HIP call, nothing written: null d_params, d_grads, moments or d_state;
+ *   n < 0 (or n >= 2^30); eps, grad_scale, weight_decay or max_norm not finite; weight_decay < 0; max_norm < 0; a null
+ *   d_scratch when mllp_optim_scratch_floats(n) > 0.  W, T and r live on the device and CANNOT be checked by a launch
+ *   function: the caller validates W >= 0, T >= 0, 0 <= r <= 1 where it fills the state (mllp_amd.trainer.FlatAdamW does).
+ * mllp_optim_scratch_floats needs no GPU.
+ * ---------------------------------------------------------------------------------------------- */
+int mllp_optim_scratch_floats(int64_t n, int64_t* out);
+int mllp_optim_step(float* d_params, const float* d_grads, float* d_exp_avg, float* d_exp_avg_sq, float* d_state,
+                    float eps, float grad_scale, float weight_decay, float max_norm, float* d_scratch, float* d_info,
+                    int64_t n, void* stream);
 
 /* One whole training step of a single rank: mllp_gnn_loss_step followed by mllp_adam_step (grad_scale 1) on the
  * MLLP_NUM_PARAMS parameters -- the body of the reference's loop, linear_program_experiment.py:139-144 -- with the same

@@ -137,6 +137,9 @@ _PROTOTYPES = {
                                         c_void_p]),
     "mllp_adam_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_int64,
                                c_void_p]),
+    "mllp_optim_scratch_floats": (c_int, [c_int64, POINTER(c_int64)]),
+    "mllp_optim_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float,
+                                c_void_p, c_void_p, c_int64, c_void_p]),
     "mllp_metrics_scratch_bytes": (c_int, [c_void_p, POINTER(c_int64)]),
     "mllp_topm_metrics": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mllp_topm_select": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -176,11 +176,12 @@ class AngleStepper:
     (trainer.FlatAdam = torch.optim.Adam's arithmetic).  Same numbers as the module + torch.optim loop (tests), about a
     dozen small torch kernels fewer per step."""
 
-    def __init__(self, model: "AngleModel", lr=1e-3):
-        from .trainer import FlatAdam
+    def __init__(self, model: "AngleModel", lr=1e-3, weight_decay=0.0, clip_norm=0.0, lr_schedule=None):
+        from .trainer import make_optimizer
         self.feat_dim = model.feat_dim
         self.params = model.flat_parameters().detach().clone().float().contiguous()
-        self.opt = FlatAdam(self.params, lr=lr)
+        # FlatAdam with nothing set; with a weight decay, a clip norm or a schedule a FlatAdamW (mllp_optim_step)
+        self.opt = make_optimizer(self.params, lr, weight_decay, clip_norm, lr_schedule)
         self.grads = torch.empty_like(self.params)
 
     def step(self, g: "AngleGraph", y: torch.Tensor):

@@ -46,6 +46,12 @@ HOT_PATH_DEFAULTS = {
                              # the optimum with at most K simplex pivots per instance (LPBatch.simplex), and their total;
                              # `refactor: R` / `stall: S` beside it are that call's refactor_every / stall_pivots (a fresh
                              # factorization every R pivots, Bland's rule after S degenerate pivots); absent == the plain call
+    "weight_decay": 0.0,     # decoupled weight decay of the optimizer (torch.optim.AdamW); 0 == the reference's Adam
+    "clip_norm": 0.0,        # cap on the global gradient norm of a step (torch.nn.utils.clip_grad_norm_); 0 == no clipping
+    "lr_schedule": None,     # the block {warmup: W, total: T, min_ratio: r}: the rate rises linearly over the first W steps, then
+                             # falls along half a cosine to r * train_lr at step T and stays there; None == constant train_lr.
+                             # With any of the three keys set the step runs mllp_optim_step (everything decided on the device),
+                             # a step with a non-finite gradient norm is skipped, and train_log.json gains grad_norm and lr
 }
 
 

@@ -115,17 +115,21 @@ def run_epochs(cfg, instances, train_dict, trainer, batches, rank, world, device
     log_every = max(int(cfg.get_default("log_every")), 1)
     report = cfg.get_default("report_solved")
     save_every = int(cfg.get_default("save_every"))
+    optim_log = OptimLog(trainer)
     for epoch in range(start_epoch, cfg.train_iter):                                # reference :120
         obj_sum = torch.zeros(1, device=device)
+        optim_log.reset()
         logging = epoch % log_every == 0
         table = torch.zeros(len(instances), 2, device=device) if logging else None
         train_solved = torch.zeros(len(report_keys(report)), device=device) if logging and report is not None and not n_holdout else None
         for mine, b, gcount in batches:
             if b is None:      # a rank without instances in this batch still joins the all-reduce
                 trainer.step_empty()
+                optim_log.add()
                 continue
             trainer.global_instances = gcount
             loss, step_logits = trainer.step(b)                                     # reference :124-144
+            optim_log.add()
             if train_solved is not None:            # (the logits of the step's forward, valid until the next step)
                 train_solved += report_counts(b, step_logits, report).to(device)
             obj_sum += loss.to(device) * gcount     # loss is the batch mean over gcount instances (this rank's share)
@@ -165,6 +169,8 @@ def run_epochs(cfg, instances, train_dict, trainer, batches, rank, world, device
             for key, v in zip(report_keys(report), solved.cpu().tolist()):
                 train_dict.setdefault(key, []).append(int(v))
         train_dict["obj"].append(obj)                  # plain float: the reference's numpy.float32 breaks json.dump
+        if logging:
+            optim_log.log(train_dict)
         val_obj = None
         if val_sum is not None:
             val_obj = float(val_sum[0]) / n_holdout
@@ -263,7 +269,8 @@ def train_method(cfg, method_name, train_dataset, train_dict, out=print):
     trainer = LPTrainer(model.flat_parameters().detach(), lr=cfg.train_lr,
                         use_hip_graph=cfg.get_default("use_hip_graph"), with_metrics=True,
                         tiled_copies=cfg.get_default("tiled_copies"),
-                        **({} if pos_weight is None else dict(pos_weight=pos_weight)), **topm_head(cfg, method_name))
+                        **({} if pos_weight is None else dict(pos_weight=pos_weight)), **topm_head(cfg, method_name),
+                        **optimizer_options(cfg))
     start_epoch = 0
     if cfg.get_default("resume") and os.path.exists(ckpt_path):
         start_epoch = load_checkpoint(ckpt_path, trainer, train_dict, device)
@@ -302,9 +309,47 @@ def topm_head(cfg, method_name):
     return out
 
 
+def optimizer_options(cfg):
+    """LPTrainer's / AngleStepper's arguments for the yaml keys `weight_decay`, `clip_norm` and `lr_schedule` {warmup, total,
+    min_ratio}: {} with none of them set (the trainer of a build without the keys); ValueError for a bad value."""
+    from .trainer import check_optim_options, lr_schedule_args
+    wd, clip, sched = cfg.get_default("weight_decay"), cfg.get_default("clip_norm"), cfg.get_default("lr_schedule")
+    wd, clip = 0.0 if wd is None else wd, 0.0 if clip is None else clip
+    check_optim_options(wd, clip, *lr_schedule_args(sched))
+    if not wd and not clip and sched is None:
+        return {}
+    return dict(weight_decay=float(wd), clip_norm=float(clip), lr_schedule=None if sched is None else dict(sched))
+
+
+class OptimLog:
+    """`grad_norm` and `lr` of train_log.json for an optimizer with `info` (FlatAdamW): the mean of info[0] over the steps
+    an epoch took (skipped steps apart) and the last info[2], accumulated on the device -- `add` never synchronises."""
+
+    def __init__(self, trainer):
+        self.info = getattr(getattr(trainer, "opt", None), "info", None)
+        self.reset()
+
+    def reset(self):
+        if self.info is not None:
+            self.acc = torch.zeros(2, device=self.info.device)      # {sum of norms, steps taken}
+
+    def add(self):
+        if self.info is not None:
+            taken = 1.0 - self.info[3]
+            self.acc += torch.stack([torch.where(taken > 0, self.info[0], torch.zeros_like(taken)), taken])
+
+    def log(self, train_dict):
+        if self.info is not None:
+            total, steps = self.acc.tolist()
+            train_dict.setdefault("grad_norm", []).append(total / max(steps, 1.0))
+            train_dict.setdefault("lr", []).append(float(self.info[2]))
+
+
 def save_checkpoint(path, trainer, train_dict, epoch):
     """Everything a restart needs: weights, Adam moments + step counter, the epoch, the log so far (and, under the top-m
-    head, the step count that seeds the next step's noise)."""
+    head, the step count that seeds the next step's noise).  Under weight_decay / clip_norm / lr_schedule the optimizer's
+    state has 8 words (FlatAdamW: the schedule travels with it and a resume continues it); a checkpoint from before those
+    keys holds 4, which FlatAdamW.load_state_dict continues under the schedule of the yaml file."""
     extra = {"topm_step": int(trainer.topm_step)} if getattr(trainer, "loss_head", "bce") == "topm" else {}
     torch.save({"params": trainer.params, "opt": trainer.opt.state_dict(), "epoch": epoch,
                 "train_dict": json.dumps(train_dict), **extra}, path)
@@ -338,13 +383,16 @@ def train_angle(cfg, method_name, train_dataset, train_dict, out=print):
     # reference :41, :87-96: BCEWithLogitsLoss + torch.optim.Adam around autograd -- here the same arithmetic on flat
     # parameters without autograd (AngleStepper: C ABI forward / backward, the library's Adam kernel; tests/test_angle.py
     # checks it step for step against the nn.Module + torch.optim loop), 2-3 x faster per step on small instances
-    stepper = AngleStepper(model, lr=cfg.train_lr)
+    stepper = AngleStepper(model, lr=cfg.train_lr, **optimizer_options(cfg))
+    optim_log = OptimLog(stepper)
     for epoch in range(cfg.train_iter):
         obj_sum = 0.0
+        optim_log.reset()
         for graph in train_loader:
             name, basis_num, var_num = graph.name, graph.basis_num, graph.var_num
             basis_opt = torch.tensor(np.asarray(graph.basis_opt), dtype=torch.float, device=device)
             obj, latent_vars = stepper.step(graph, basis_opt)
+            optim_log.add()
             obj_sum += float(obj.detach())
             pred_indices = torch.topk(latent_vars, k=basis_num)[-1].cpu().detach().numpy()
             pred = np.zeros(var_num)
@@ -356,6 +404,7 @@ def train_angle(cfg, method_name, train_dataset, train_dict, out=print):
             out("%8d, %8d, %8d, %5f" % (correct_num, basis_num, var_num, f1))
             train_dict[name].append(correct_num)
         train_dict["obj"].append(obj_sum / len(train_dataset))
+        optim_log.log(train_dict)
         with open("train_log.json", "w") as json_file:
             json.dump(train_dict, json_file)
         out(f"epoch {epoch}, obj={obj_sum / len(train_dataset)}")

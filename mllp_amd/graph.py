@@ -1286,6 +1286,25 @@ def adam_step(params, grads, exp_avg, exp_avg_sq, state, eps=1e-8, grad_scale=1.
                                          _lib.ptr(state), eps, grad_scale, params.numel(), _lib.current_stream()))
 
 
+def optim_scratch_floats(n):
+    """floats of scratch `optim_step` needs for n parameters (mllp_optim_scratch_floats; 0 for small n); needs no GPU."""
+    out = c_int64()
+    _lib.check(_lib.lib().mllp_optim_scratch_floats(int(n), ctypes.byref(out)))
+    return int(out.value)
+
+
+def optim_step(params, grads, exp_avg, exp_avg_sq, state, eps=1e-8, grad_scale=1.0, weight_decay=0.0, max_norm=0.0,
+               scratch=None, info=None):
+    """AdamW + global-norm clipping + warm-up / cosine schedule in one call, decided on the device (mllp_optim_step).
+    state: cuda float tensor [step, lr_base, beta1, beta2, warmup W, total T, min_ratio r, 0]; step is incremented on the
+    device unless the step is skipped (a non-finite gradient norm).  scratch: `optim_scratch_floats(n)` floats (None when
+    that is 0); info: None or a float tensor [4] that receives {grad norm, clip coefficient, lr of the step, skipped}."""
+    assert state.numel() >= 8, "optim_step: an 8-word state (pad mllp_adam_step's with four zeros)"
+    _lib.check(_lib.lib().mllp_optim_step(_lib.ptr(params), _lib.ptr(grads), _lib.ptr(exp_avg), _lib.ptr(exp_avg_sq),
+                                          _lib.ptr(state), eps, grad_scale, weight_decay, max_norm, _lib.ptr(scratch),
+                                          _lib.ptr(info), params.numel(), _lib.current_stream()))
+
+
 # ----------------------------------------------------------------------------------------------
 # synthetic batches generated on the device (BASELINE.json configs[3]/[4]; SURVEY.md section 8d)
 # ----------------------------------------------------------------------------------------------

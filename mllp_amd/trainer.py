@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .graph import LPBatch, adam_step
+from .graph import LPBatch, adam_step, optim_scratch_floats, optim_step
 
 NUM_PARAMS = _lib.NUM_PARAMS
 
@@ -71,6 +71,131 @@ class FlatAdam:
         self.state.copy_(sd["state"])
 
 
+def lr_schedule_args(lr_schedule):
+    """(warmup W, total T, min_ratio r) of the yaml block / keyword `lr_schedule`: None (the constant rate) or a mapping
+    with any of the keys warmup, total, min_ratio.  ValueError for anything else or an unknown key (the values are checked by
+    `check_optim_options`)."""
+    if lr_schedule is None:
+        return 0, 0, 0.0
+    if not hasattr(lr_schedule, "items"):
+        raise ValueError(f"lr_schedule: a mapping {{warmup, total, min_ratio}} or None, got {lr_schedule!r}")
+    unknown = sorted(set(lr_schedule) - {"warmup", "total", "min_ratio"})
+    if unknown:
+        raise ValueError(f"lr_schedule: unknown key(s) {unknown} (known: warmup, total, min_ratio)")
+    return lr_schedule.get("warmup", 0), lr_schedule.get("total", 0), lr_schedule.get("min_ratio", 0.0)
+
+
+def _number(name, v, integral=False):
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+        raise ValueError(f"{name}: a finite number, got {v!r}")
+    if integral and float(v) != int(v):
+        raise ValueError(f"{name}: a whole number of steps, got {v!r}")
+    return float(v)
+
+
+def check_optim_options(weight_decay=0.0, clip_norm=0.0, warmup_steps=0, total_steps=0, lr_min_ratio=0.0):
+    """The five numbers as floats, or ValueError: weight_decay >= 0, clip_norm >= 0, whole W >= 0 and T >= 0, 0 <= r <= 1.
+    (W, T and r live in the device state, which mllp_optim_step cannot check: this is where they are checked.)"""
+    wd, clip = _number("weight_decay", weight_decay), _number("clip_norm", clip_norm)
+    W, T = _number("warmup_steps", warmup_steps, True), _number("total_steps", total_steps, True)
+    r = _number("lr_min_ratio", lr_min_ratio)
+    if wd < 0 or clip < 0:
+        raise ValueError(f"weight_decay and clip_norm must not be negative, got {weight_decay!r}, {clip_norm!r}")
+    if W < 0 or T < 0:
+        raise ValueError(f"warmup_steps and total_steps must not be negative, got {warmup_steps!r}, {total_steps!r}")
+    if W >= 1 << 24 or T >= 1 << 24:
+        raise ValueError("warmup_steps and total_steps: the step counter is a float, whole numbers end at 2^24")
+    if not 0.0 <= r <= 1.0:
+        raise ValueError(f"lr_min_ratio must lie in [0, 1], got {lr_min_ratio!r}")
+    return wd, clip, W, T, r
+
+
+class FlatAdamW:
+    """torch.optim.AdamW + clip_grad_norm_(clip_norm) + a warm-up / cosine LambdaLR on flat buffers, every decision on the
+    device (mllp_optim_step; include/mllp_hip.h states the rule): the rate of step t is lr * t / W up to step W, then
+    lr * (r + (1 - r) (1 + cos(pi (t - W) / (T - W))) / 2) down to r * lr at step T and constant after it; W = T = 0 is the
+    constant rate.  A step whose gradient norm is not finite is skipped (nothing moves, info[3] = 1).  Elements whose
+    gradient is 0 with zero moments are not touched, and not decayed either (a parameter without a gradient).
+
+    `backend='hip'` uses mllp_optim_step, `backend='torch'` is the same arithmetic in torch ops (the CPU tests and the gloo
+    driver).  `info` = float tensor [4] {gradient norm, clip coefficient, rate, skipped} of the last step, on the
+    parameters' device.  With everything at its default the parameters get FlatAdam's bits."""
+
+    def __init__(self, params: torch.Tensor, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip_norm=0.0,
+                 warmup_steps=0, total_steps=0, lr_min_ratio=0.0, backend="hip"):
+        wd, clip, W, T, r = check_optim_options(weight_decay, clip_norm, warmup_steps, total_steps, lr_min_ratio)
+        self.params = params
+        self.m = torch.zeros_like(params)
+        self.v = torch.zeros_like(params)
+        self.eps = eps
+        self.weight_decay, self.clip_norm = wd, clip
+        self.backend = backend
+        self.state = torch.tensor([0.0, lr, betas[0], betas[1], W, T, r, 0.0], dtype=torch.float32, device=params.device)
+        self.info = torch.zeros(4, dtype=torch.float32, device=params.device)
+        self.scratch = None
+        if backend == "hip":
+            n_scratch = optim_scratch_floats(params.numel())
+            if n_scratch:
+                self.scratch = torch.empty(n_scratch, dtype=torch.float32, device=params.device)
+
+    def step(self, grads, grad_scale=1.0):
+        if self.backend == "hip":
+            optim_step(self.params, grads, self.m, self.v, self.state, self.eps, grad_scale, self.weight_decay,
+                       self.clip_norm, self.scratch, self.info)
+            return
+        f = np.float32
+        step, lr0, b1, b2, W, T, r, _ = (f(x) for x in self.state.tolist())
+        t = step + f(1)
+        if W > 0 and t <= W:
+            lr = lr0 * t / W
+        elif T > W:
+            x = min(f(1), (t - W) / (T - W))
+            lr = lr0 * (r + (f(1) - r) * (f(0.5) * (f(1) + np.cos(f(np.pi) * x, dtype=f))))
+        else:
+            lr = lr0
+        g = grads * float(f(grad_scale))
+        norm = f(float(g.square().sum().sqrt()))
+        if not np.isfinite(norm):
+            self.info.copy_(torch.tensor([float(norm), 0.0, float(lr), 1.0]))
+            return
+        c = min(f(1), f(self.clip_norm) / (norm + f(1e-6))) if self.clip_norm > 0 else f(1)
+        live = (g != 0) | (self.m != 0) | (self.v != 0)
+        g = g * float(c)
+        p = self.params - float(lr * f(self.weight_decay)) * self.params
+        m = self.m * float(b1) + g * float(f(1) - b1)
+        v = self.v * float(b2) + g * g * float(f(1) - b2)
+        bc1, bc2 = f(1) - np.power(b1, t, dtype=f), f(1) - np.power(b2, t, dtype=f)
+        denom = v.sqrt() * float(f(1) / np.sqrt(bc2)) + float(f(self.eps))
+        p = p - float(lr / bc1) * (m / denom)
+        self.params.copy_(torch.where(live, p, self.params))
+        self.m.copy_(torch.where(live, m, self.m))
+        self.v.copy_(torch.where(live, v, self.v))
+        self.state[0] = float(t)
+        self.info.copy_(torch.tensor([float(norm), float(c), float(lr), 0.0]))
+
+    def state_dict(self):
+        return dict(m=self.m.clone(), v=self.v.clone(), state=self.state.clone())
+
+    def load_state_dict(self, sd):
+        """An 8-word state continues its own schedule; the 4-word state of a FlatAdam checkpoint continues its step count,
+        rate and betas under the schedule this optimizer was built with."""
+        st = sd["state"]
+        if st.numel() not in (4, 8):
+            raise ValueError(f"optimizer state: 4 or 8 words, got {st.numel()}")
+        self.m.copy_(sd["m"])
+        self.v.copy_(sd["v"])
+        self.state[:st.numel()].copy_(st)
+
+
+def make_optimizer(params, lr, weight_decay=0.0, clip_norm=0.0, lr_schedule=None, backend="hip"):
+    """FlatAdam with nothing set (every call is the one it was), else a FlatAdamW"""
+    if not weight_decay and not clip_norm and lr_schedule is None:
+        return FlatAdam(params, lr=lr, backend=backend)
+    W, T, r = lr_schedule_args(lr_schedule)
+    return FlatAdamW(params, lr=lr, weight_decay=weight_decay, clip_norm=clip_norm, warmup_steps=W, total_steps=T,
+                     lr_min_ratio=r, backend=backend)
+
+
 def allreduce_sum_(t: torch.Tensor):
     import torch.distributed as dist
     if dist.is_available() and dist.is_initialized() and (
@@ -114,12 +239,17 @@ class LPTrainer:
 
     def __init__(self, params_flat: torch.Tensor, lr=1e-3, use_hip_graph="auto",
                  global_instances: Optional[int] = None, with_metrics=False, tiled_copies="auto", stream_copies=True,
-                 pos_weight=None, loss_head="bce", topm_tau=1.0, topm_sigma=0.0, topm_samples=0):
+                 pos_weight=None, loss_head="bce", topm_tau=1.0, topm_sigma=0.0, topm_samples=0,
+                 weight_decay=0.0, clip_norm=0.0, lr_schedule=None):
         assert params_flat.is_cuda and params_flat.numel() == NUM_PARAMS
         if loss_head not in ("bce", "topm"):
             raise ValueError(f"loss_head: 'bce' or 'topm', got {loss_head!r}")
         self.params = params_flat.detach().clone().float().contiguous()
-        self.opt = FlatAdam(self.params, lr=lr)
+        # weight_decay, clip_norm, lr_schedule {warmup, total, min_ratio}: with any of them set the optimizer is a FlatAdamW
+        # (mllp_optim_step) and `step` takes the loss step -> all-reduce -> optimizer route, never the whole step, whose fused
+        # tail contains plain Adam.  With none of them every call is the one it was
+        self.opt = make_optimizer(self.params, lr, weight_decay, clip_norm, lr_schedule)
+        self.split_opt = isinstance(self.opt, FlatAdamW)
         self.use_graph = use_hip_graph
         self.global_instances = global_instances
         self.with_metrics = with_metrics
@@ -231,7 +361,7 @@ class LPTrainer:
         multi = dist.is_available() and dist.is_initialized() and (
             dist.get_world_size() > 1 or os.environ.get("MLLP_BENCH_FORCE_DIST") == "1")
         if not p["graph"] or p["warm"] < 1:
-            if multi or self.pos_weight is not None or self.loss_head == "topm":      # (one rank: the all-reduce is a no-op)
+            if multi or self.pos_weight is not None or self.loss_head == "topm" or self.split_opt:      # (one rank: the all-reduce is a no-op)
                 self._fwd_bwd(p)
                 allreduce_sum_(p["grads"])
                 self._opt(p)
