@@ -389,6 +389,66 @@ int mllp_basis_simplex_guarded(const mllp_graph_t* g, const float* d_x1 /*c [N]*
                                int32_t* d_trace /*[n_inst, max_pivots, 2] or NULL*/, int32_t* d_status /*[n_inst, 4], required*/,
                                int32_t* d_guard /*[n_inst, 2] or NULL*/, void* d_scratch, void* stream);
 
+/* Solve every instance by restarted PDHG (mllp_amd/csrc/pdhg.hip): a first-order method -- two sparse
+ * matrix-vector products per iteration over the two resident orientations, no factorization, memory O(n + m) per instance,
+ * no row limit.  Added after ABI 6 without a bump, as mllp_basis_simplex was.
+ * THE RULE.  The LP of instance k is the one mllp_lp_certificate judges: min c'x, A_k x = b, x >= 0, c = d_x1, b = d_x2, A_k
+ * as the batch stores it now.  All arithmetic is fp32; every operation is one of fadd, fsub, fmul, fma, fdiv, fsqrt, each
+ * rounded to nearest, in the expressions written here; clip(t) = t > 0 ? t : 0 (a NaN gives 0).
+ *   Step.  eta = step / sqrt(|A_k|_1 |A_k|_inf): the largest column sum and the largest row sum of |a_ij|, each a fadd
+ *     chain in the order below; eta = fdiv(step, fsqrt(fmul(.,.))).  eta = step when that product is not > 0 (A_k has no
+ *     nonzero entry).  Computed by the call itself, per instance.
+ *   Start.  x = clip(x0), y = y0; a NULL d_x0 (d_y0) means zeros.
+ *   Iteration.  s_j = sum_i a_ij y_i (fma chain);  g_j = fsub(c_j, s_j);  x+_j = clip(fsub(x_j, fmul(eta, g_j)));
+ *     xbar_j = fsub(fadd(x+_j, x+_j), x_j);  t_i = sum_j a_ij xbar_j (fma chain);  y+_i = fadd(y_i, fmul(eta, fsub(b_i, t_i))).
+ *     With check_every > 0 the sums xs += x+, ys += y+ (fadd) of the iterates since the last restart and their count cnt
+ *     are kept.
+ *   Check, after every check_every iterations.  (xa, ya) = (fdiv(xs_j, (float)cnt), fdiv(ys_i, (float)cnt)).  For a point
+ *     z = (x, y):  primal(z) = max_i |fsub(sum_j a_ij x_j, b_i)| / (1 + |b|_inf);  dual(z) = max_j max(fsub(sum_i a_ij y_i,
+ *     c_j), 0) / (1 + |c|_inf);  gap(z) = |fsub(c'x, b'y)| / fadd(fadd(1, |c'x|), |b'y|);  err(z) = the largest of the three.
+ *     Every max keeps a NaN (it is an integer max over the patterns of non-negative floats).  The candidate is the average
+ *     if err(avg) < err(cur), else the current iterate; e is its error.  e not finite: code 8, the output is the current
+ *     iterate.  e <= eps: code 0, the output is the candidate.  Otherwise, if e <= fmul(beta, e_last) or
+ *     25 cnt >= 9 (iterations so far): restart -- (x, y) <- candidate, e_last = e, sums and cnt cleared.  e_last is +inf at
+ *     the start, so the first check restarts.
+ *   Limit.  After max_iters iterations without code 0 or 8: code 6, the output is the current iterate (the candidate, when
+ *     the check that falls on max_iters restarted) and its three errors are evaluated for d_kkt.  check_every == 0: no
+ *     checks, no sums, no restarts -- plain PDHG for max_iters iterations, code 6.
+ *   Order.  A row's (column's) terms are added in mllp_graph_normalize's three tiers, picked by the row's length alone
+ *     (ordered_sum.h: up to 64 terms by 16 lanes, up to 1024 by a wavefront, longer by the workgroup of 1024 threads; lane
+ *     l adds terms l, l + G, ... from 0, then the butterfly, then the binary tree over the wavefronts).  c'x and b'y: thread
+ *     t adds j = t, t + 1024, ... (fma), then that butterfly and tree.  The average and the current iterate share every walk.
+ * WHAT THE RULE DOES NOT CLAIM.  No diagonal preconditioning or equilibration; no adaptive step or primal weight; no
+ * infeasibility detection (an infeasible or unbounded LP ends with code 6, or 8 once an iterate overflows); fp32 residuals
+ * bottom out around 1e-6.  It is a BASELINE first-order solve: LPBatch.normalize's row scaling is the only conditioning it
+ * gets, and on Netlib it needs tens of thousands of iterations where it converges at all.
+ *   d_x1 [N] = c, d_x2 [M] = b : inputs.   d_x0 [N], d_y0 [M] : inputs or NULL; must not overlap an output.
+ *   max_iters >= 0, check_every >= 0;  eps finite, >= 0;  step finite, in (0, 1];  beta finite, in (0, 1).
+ *   max_lds_words : an instance keeps its five vectors (x, xbar, xs, y, ys: 3 n + 2 m words) in LDS when that is at most
+ *             min(max_lds_words, limits[0]), in d_scratch otherwise, with the same bits either way; 0: every instance in
+ *             scratch.  mllp_lp_pdhg_limits: {LDS words the kernel can give to vectors (36 864), threads per workgroup
+ *             (1024)}; needs no GPU.
+ *   d_x [N], d_y [M] : outputs, required.   d_status [n_inst, 4] int32, required : {code, iterations, restarts, 1 if the
+ *             average was returned}; code 0: err <= eps;  6: max_iters reached;  8: the error was not finite.
+ *   d_kkt [n_inst, 4] or NULL : {primal, dual, gap of the output -- the three terms of err --, eta}.
+ *   d_scratch : mllp_lp_pdhg_scratch_bytes(g, max_lds_words) bytes: 3 n + 2 m words for every instance that does not fit
+ *             LDS; may be NULL when that is 0.
+ * Every requested output is fully written for every instance; n = 0 or m = 0 is legal.  A launch function: `stream` only,
+ * no allocation, no synchronisation, hipGraph-capturable; one workgroup per instance, persistent over the iterations; two
+ * workgroup barriers per iteration (two more per row of the workgroup tier), and the loop is bounded by max_iters and
+ * nothing else.  It reads the graph's plain CSR(A) and CSR(A^T) only.  No float atomics, one writer per word: bitwise
+ * reproducible, and the same bits for an instance alone and inside any batch.  Under the MEMORY CONTRACT below.
+ * MLLP_EINVAL before any launch, nothing written: null g, d_x1, d_x2, d_x, d_y or d_status (before any HIP call);
+ * max_iters < 0; check_every < 0; max_lds_words < 0; eps not finite or < 0; step not finite or outside (0, 1]; beta not
+ * finite or outside (0, 1); null d_scratch with a non-zero scratch size; d_x0 or d_y0 overlapping an output.            */
+int mllp_lp_pdhg_limits(int64_t limits[2]);
+int mllp_lp_pdhg_scratch_bytes(const mllp_graph_t* g, int64_t max_lds_words, int64_t* bytes);
+int mllp_lp_pdhg(const mllp_graph_t* g, const float* d_x1 /*c [N]*/, const float* d_x2 /*b [M]*/,
+                 const float* d_x0 /*[N] or NULL*/, const float* d_y0 /*[M] or NULL*/, int64_t max_iters,
+                 int64_t check_every, float eps, float step, float beta, int64_t max_lds_words, float* d_x /*[N]*/,
+                 float* d_y /*[M]*/, int32_t* d_status /*[n_inst,4]*/, float* d_kkt /*[n_inst,4] or NULL*/,
+                 void* d_scratch, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Plain CSR SpMM (the roofline kernel named in BASELINE.json's metric):
  *   transpose == 0:  Y[M,16] = A   * H[N,16]       transpose == 1:  Y[N,16] = A^T * H[M,16]
@@ -521,7 +581,7 @@ int mllp_tconv_bwd(const mllp_graph_t* g, int dst_is_var, int cin, const float* 
  *   d_ws     : mllp_gnn_workspace_bytes() bytes, kept between forward and backward
  *   d_logits [N] : per-variable logits (methods.py:250-251)
  * MEMORY CONTRACT of every mllp_gnn_*, mllp_tconv_*, mllp_spmm_*, mllp_weighted_loss, mllp_balanced_pos_weight, mllp_topm_*,
- * mllp_graph_normalize, mllp_graph_plant_basis, mllp_lp_certificate, mllp_basis_repair, mllp_basis_simplex and mllp_optim_step call, for every buffer the caller owns (tests/test_memory_contract.py):
+ * mllp_graph_normalize, mllp_graph_plant_basis, mllp_lp_certificate, mllp_basis_repair, mllp_basis_simplex, mllp_lp_pdhg and mllp_optim_step call, for every buffer the caller owns (tests/test_memory_contract.py):
  *   1. A call's outputs do not depend on any byte that d_ws, or any other scratch or output buffer, held before the call:
  *      the buffers may be uninitialised, NaN included, and the same bits come out.  The only state carried between calls is
  *      what this header names: mllp_gnn_forward -> mllp_gnn_backward / _backward_inputs / _input_grads on the same workspace
@@ -565,7 +625,7 @@ int mllp_tconv_bwd(const mllp_graph_t* g, int dst_is_var, int cin, const float* 
  *      pieces --, as must every pointer of mllp_tconv_fwd / _bwd except d_param_grads (rows of 16 floats; d_ws, d_conv_params)
  *      and d_H, d_Y of mllp_spmm_csr_f32.  A misaligned one is refused with MLLP_EINVAL and a message before any HIP call,
  *      nothing written.  d_logits, d_labels, d_loss, d_grads, d_dlogits, d_dx1, d_dx2, d_dvalues, d_scratch, the optimizer
- *      buffers, the per-instance arrays and the buffers of the loss-head, top-m, normalize, basis-repair and basis-simplex calls need only the natural
+ *      buffers, the per-instance arrays and the buffers of the loss-head, top-m, normalize, basis-repair, basis-simplex and PDHG calls need only the natural
  *      alignment of their element type.
  * mllp_gnn_backward: d_dlogits [N] -> d_grads [MLLP_NUM_PARAMS] (overwritten; the never-called
  *   gconv3_s2w block, methods.py:248, is written as zeros).

@@ -46,6 +46,10 @@ HOT_PATH_DEFAULTS = {
                              # the optimum with at most K simplex pivots per instance (LPBatch.simplex), and their total;
                              # `refactor: R` / `stall: S` beside it are that call's refactor_every / stall_pivots (a fresh
                              # factorization every R pivots, Bland's rule after S degenerate pivots); absent == the plain call
+                             # `pdhg: {iters: K, eps: E}` in the block (optional `check`, default 64, and `warm`, default true)
+                             # adds pdhg_converged / pdhg_iterations / optimal_after_pdhg: every instance solved by restarted
+                             # PDHG (LPBatch.pdhg) from the repaired prediction's basic solution (warm) or from zeros, and the
+                             # vertex its iterate points at certified (LPBatch.pdhg_basis + solved)
     "weight_decay": 0.0,     # decoupled weight decay of the optimizer (torch.optim.AdamW); 0 == the reference's Adam
     "clip_norm": 0.0,        # cap on the global gradient norm of a step (torch.nn.utils.clip_grad_norm_); 0 == no clipping
     "lr_schedule": None,     # the block {warmup: W, total: T, min_ratio: r}: the rate rises linearly over the first W steps, then

@@ -442,6 +442,15 @@ __host__ __device__ constexpr int64_t simplex_words(int64_t m, int64_t n) {     
     return (m > SIMPLEX_LDS_MAX_M ? m * m : 0) + n;
 }
 
+// ---- restarted PDHG (pdhg.hip): one workgroup per instance, five vectors of 3 n + 2 m words in all --------------------------
+// The vectors live in LDS up to PDHG_LDS_WORDS words: 144 KB, beside under 1 KB of static LDS, within the 160 KB of a
+// workgroup (92 of the 97 Netlib instances fit); longer instances keep them in the caller's scratch, the same bits either
+// way.  1024 threads: a workgroup is alone on its CU at that LDS size, and the sweeps read A from L2 / HBM in every
+// iteration, so the sixteen wavefronts are what hides that latency.  mllp_lp_pdhg_limits reports both.
+constexpr int64_t PDHG_LDS_WORDS = 36864;
+constexpr int PDHG_THREADS = 1024;
+__host__ __device__ constexpr int64_t pdhg_words(int64_t m, int64_t n) { return 3 * n + 2 * m; }   // x, 2x+ - x, xs, y, ys
+
 // ---- soft top-m loss head (topm_loss.hip): one workgroup of TOPM_LOSS_T threads per instance, many passes per evaluation ---
 // Where an instance's scaled (and perturbed) logits a_i live between the passes, by its column count n alone: up to
 // TOPM_LOSS_LDS_MAX columns in LDS (64 KB; word t + 1024 j belongs to thread t alone); longer instances form a_i again

@@ -217,14 +217,40 @@ def pivot_counts(batch, logits, report):
     return torch.stack([done.sum(), (got["pivots"] * done).sum()]).float()
 
 
+PDHG_KEYS = ("pdhg_converged", "pdhg_iterations", "optimal_after_pdhg")
+
+
+def pdhg_counts(batch, logits, report):
+    """[3] device counts over a batch's instances, by PDHG_KEYS, under `report_solved` {..., pdhg: {iters: K, eps: E}}
+    (optional: `check`, default 64, and `warm`, default true): every instance solved by restarted PDHG on the device
+    (LPBatch.pdhg, at most K iterations, relative KKT error E) -- the instances that converged, the iterations all of them
+    took, and the instances whose iterate points at a vertex that is certified optimal (LPBatch.pdhg_basis + solved, under
+    the block's tolerances and max_m).  With `warm` the start is the repaired prediction's basic solution where it is
+    usable and cold (zeros, which is what repair_basis leaves) otherwise.  PDHG itself has no row limit.  No sync."""
+    opt = report["pdhg"]
+    for key in ("iters", "eps"):
+        if key not in opt:
+            raise ValueError(f"report_solved: pdhg: {key} is required")
+    max_m = report.get("max_m")
+    start = batch.repair_basis(logits, max_m=max_m, want=("basis", "x", "y")) if opt.get("warm", True) else None
+    res = batch.pdhg(int(opt["iters"]), eps=float(opt["eps"]), check_every=int(opt.get("check", 64)), start=start)
+    got = batch.solved(batch.pdhg_basis(res, max_m=max_m), report["feas_tol"], report["opt_tol"])
+    return torch.stack([(res.status[:, 0] == 0).sum(), res.status[:, 1].sum(), got["optimal"].sum()]).float()
+
+
 def report_keys(report):
-    """the keys `report_solved` adds to the log: SOLVED_KEYS, and PIVOT_KEYS when the block has `pivots`"""
-    return SOLVED_KEYS + (PIVOT_KEYS if report.get("pivots") is not None else ())
+    """the keys `report_solved` adds to the log: SOLVED_KEYS, PIVOT_KEYS when the block has `pivots`, PDHG_KEYS when it
+    has `pdhg`"""
+    return SOLVED_KEYS + (PIVOT_KEYS if report.get("pivots") is not None else ()) + (PDHG_KEYS if report.get("pdhg") is not None else ())
 
 
 def report_counts(batch, logits, report):
-    counts = solved_counts(batch, logits, report)
-    return counts if report.get("pivots") is None else torch.cat([counts, pivot_counts(batch, logits, report)])
+    counts = [solved_counts(batch, logits, report)]
+    if report.get("pivots") is not None:
+        counts.append(pivot_counts(batch, logits, report))
+    if report.get("pdhg") is not None:
+        counts.append(pdhg_counts(batch, logits, report))
+    return counts[0] if len(counts) == 1 else torch.cat(counts)
 
 
 def train_method(cfg, method_name, train_dataset, train_dict, out=print):

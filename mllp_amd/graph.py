@@ -1196,6 +1196,56 @@ class LPBatch:
         got["pivots"] = res.status[:, 1] + res.status[:, 2]
         return got
 
+    # ---- restarted PDHG on every instance (mllp_lp_pdhg; csrc/pdhg.hip) ----------------------------------------------
+    def pdhg(self, max_iters, eps=2.0 ** -10, check_every=64, step=0.9, beta=0.5, x0=None, y0=None, start=None,
+             max_lds_words=None):
+        """A first-order solve of every instance on the device: PDHG with averaging and restarts (mllp_lp_pdhg; the rule
+        is stated in include/mllp_hip.h).  No factorization and no row limit: memory O(n + m) per instance.  `max_iters`:
+        the limit per instance (code 6 at it).  `eps`: the relative KKT error (primal, dual, gap) at which an instance stops
+        with code 0.  `check_every`: iterations between two checks; 0: plain PDHG, no averaging, no restarts.  `step`: the
+        fraction of 1 / sqrt(|A|_1 |A|_inf) both steps take, in (0, 1].  `beta`: a check restarts when the error fell below
+        beta times the last restart's.  `x0` [N], `y0` [M]: the start (zeros when None), or `start`: a `BasisRepair` whose
+        `x`, `y` are the warm start.  `max_lds_words`: test hook -- instances whose 3 n + 2 m words exceed it keep their
+        vectors in scratch (None: the kernel's limit).  Returns an `LPPdhg` of device tensors.  The scratch is asked for
+        once per max_lds_words and kept on the batch.  A BASELINE: no preconditioning, no adaptive step.  No sync."""
+        if start is not None:
+            if x0 is not None or y0 is not None:
+                raise ValueError("pdhg: give start or x0 / y0, not both")
+            if not isinstance(start, BasisRepair) or start.x is None or start.y is None:
+                raise ValueError("pdhg: start must be a BasisRepair with x and y")
+            x0, y0 = start.x, start.y
+        for t, n, what in ((x0, self.N, "x0"), (y0, self.M, "y0")):
+            if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n):
+                raise ValueError(f"pdhg: {what} must be a contiguous cuda float32 tensor of {n} elements")
+        max_iters, check_every = int(max_iters), int(check_every)
+        if max_iters < 0 or check_every < 0:
+            raise ValueError("pdhg: max_iters and check_every must not be negative")
+        dev = self.x1.device
+        max_lds_words = pdhg_limits()[0] if max_lds_words is None else int(max_lds_words)
+        kept = getattr(self, "_pdhg_scratch", None)
+        if kept is None or kept[0] != max_lds_words:
+            n = c_int64()
+            _lib.check(_lib.lib().mllp_lp_pdhg_scratch_bytes(self._h, max_lds_words, ctypes.byref(n)))
+            kept = self._pdhg_scratch = (max_lds_words, torch.empty(n.value // 4, device=dev, dtype=torch.float32) if n.value else None)
+        # (at least one element each: an empty torch tensor has a null pointer, which the library refuses)
+        new = lambda n, dt: torch.empty(max(n, 1), dtype=dt, device=dev)      # noqa: E731
+        x, y = new(self.N, torch.float32), new(self.M, torch.float32)
+        status, kkt = new(self.n_inst * 4, torch.int32), new(self.n_inst * 4, torch.float32)
+        pad = lambda t: t if t.numel() else torch.zeros(1, dtype=torch.float32, device=dev)   # noqa: E731
+        opt = lambda t: None if t is None or not t.numel() else t                             # noqa: E731
+        _lib.check(_lib.lib().mllp_lp_pdhg(self._h, _lib.ptr(pad(self.x1)), _lib.ptr(pad(self.x2)), _lib.ptr(opt(x0)), _lib.ptr(opt(y0)),
+                                           max_iters, check_every, float(eps), float(step), float(beta), max_lds_words, _lib.ptr(x),
+                                           _lib.ptr(y), _lib.ptr(status), _lib.ptr(kkt), _lib.ptr(kept[1]), _lib.current_stream()))
+        return LPPdhg(x[:self.N], y[:self.M], status[:self.n_inst * 4].view(self.n_inst, 4), kkt[:self.n_inst * 4].view(self.n_inst, 4))
+
+    def pdhg_basis(self, res, tol=2.0 ** -12, max_m=None):
+        """The vertex a PDHG iterate points at: `repair_basis` on the ranking of `res.x` (its m largest entries first), so the
+        `BasisRepair` of the best-ranked nonsingular basis and its basic solution, which `solved` certifies -- for the
+        instances the dense call can hold (`max_m`; the others are skipped, code 2).  No sync."""
+        if not isinstance(res, LPPdhg):
+            raise ValueError("pdhg_basis: res must be the LPPdhg of LPBatch.pdhg")
+        return self.repair_basis(order=self.ranking(res.x.contiguous()), tol=tol, max_m=max_m, want=("basis", "col_of_row", "x", "y", "quality"))
+
 
 def _select_outputs(want, n, m, n_seg, dev):
     """(mask, index, stats) buffers of the select entry points, None where not wanted.  At least one element each: an
@@ -1253,6 +1303,23 @@ class BasisSimplex:
 
     def __init__(self, basis, col_of_row, trace, status, guard=None):
         self.basis, self.col_of_row, self.trace, self.status, self.guard = basis, col_of_row, trace, status, guard
+
+
+class LPPdhg:
+    """What `LPBatch.pdhg` returns, all device tensors, nothing copied back: `.x` [N], `.y` [M] (the output point: the
+    candidate of the check that stopped, or the current iterate), `.status` (int32 [n_inst, 4] = code, iterations, restarts,
+    1 if the average was returned; code 0 converged, 6 max_iters reached, 8 the error was not finite) and `.kkt` (float32
+    [n_inst, 4] = relative primal residual, dual residual and gap of the output, and the step eta)."""
+
+    def __init__(self, x, y, status, kkt):
+        self.x, self.y, self.status, self.kkt = x, y, status, kkt
+
+
+def pdhg_limits():
+    """(LDS words the PDHG kernel can give to an instance's vectors, threads per workgroup) (mllp_lp_pdhg_limits; no GPU)"""
+    lim = (c_int64 * 2)()
+    _lib.check(_lib.lib().mllp_lp_pdhg_limits(lim))
+    return int(lim[0]), int(lim[1])
 
 
 def topm_select_dense(logits, m, want=("mask", "index", "stats")):

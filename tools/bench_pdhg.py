@@ -1,0 +1,126 @@
+"""Cost and reach of restarted PDHG on the resident batch (mllp_lp_pdhg).  Prints one JSON line (profiles/pdhg_bench.json).
+
+    python tools/bench_pdhg.py [--calls 2] [--windows 5] [--plain-iters 256] [--netlib-iters 60000] [--synthetic 4]
+
+  per_iteration   plain PDHG (check_every = 0) for --plain-iters iterations on the Netlib batch, on planted batches (256 and
+                  1024 x (50 x 120), all in LDS; 64 x (500 x 1200); the same 64 with max_lds_words = 0, all in scratch) and on
+                  --synthetic instances of the synthetic batch's size (10 000 x 20 000, about 2 M nonzeros each).  DEVICE
+                  figures in the protocol of tools/bench_basis_repair.py: device events around `calls` back-to-back launches
+                  into outputs allocated once, after a warm-up; the median, min and max over `windows` windows, per call and
+                  per iteration.  One workgroup works on one instance, so a call lasts as long as its slowest instance.
+  netlib          per instance at eps 1e-3 and 1e-4 under --netlib-iters: code, iterations, restarts and the three errors.
+  cold_warm       planted 256 x (50 x 120): iterations from zeros against iterations from repair_basis(labels)'s x and y.
+  oracle_deviation  the figure behind the bars of tests/test_pdhg.py: the fp32 numpy oracle against the fp64 one (CPU code
+                  both) after 64 and 512 plain iterations, in units of 2^-24 max|.|, on that test's shapes.
+No number here is a gate.
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from bench_basis_repair import device_window  # noqa: E402
+
+
+def timed(b, iters, calls, windows, max_lds_words=None, **kw):
+    run = lambda: b.pdhg(iters, max_lds_words=max_lds_words, **kw)      # noqa: E731
+    run()
+    run()
+    torch.cuda.synchronize()
+    dev = [device_window(run, calls) for _ in range(windows)]
+    med = float(np.median(dev))
+    return {"iterations": iters, "calls_per_window": calls, "windows": windows,
+            "device_ms_per_call": {"median": round(med * 1e3, 3), "min": round(min(dev) * 1e3, 3), "max": round(max(dev) * 1e3, 3)},
+            "us_per_iteration": {"median": round(med * 1e6 / iters, 3), "min": round(min(dev) * 1e6 / iters, 3),
+                                 "max": round(max(dev) * 1e6 / iters, 3)}}
+
+
+def shape_of(b):
+    from mllp_amd.graph import pdhg_limits
+    words = [3 * n + 2 * m for m, n in zip(b.inst_m, b.inst_n)]
+    return {"instances": b.n_inst, "nnz": b.dims()["nnz"], "largest_m": max(b.inst_m), "largest_n": max(b.inst_n),
+            "instances_in_lds": int(sum(w <= pdhg_limits()[0] for w in words))}
+
+
+def oracle_deviation():
+    import pdhg_oracle as pg
+    import planted_oracle as po
+    import test_basis_repair as tb
+    out = {}
+    insts = pg.cpu_planted(tb.planted_shapes([(1, 1), (3, 3), (5, 12), (40, 100)], 20)) + pg.cpu_planted(po.ragged_case(which=[4]))
+    for K in (64, 512):
+        worst = 0.0
+        for i in insts:
+            a = pg.solve(i["A"], i["b"], i["c"], K, check_every=0)
+            f = pg.solve(i["A"], i["b"], i["c"], K, check_every=0, dtype=np.float32)
+            for v in ("x", "y"):
+                worst = max(worst, float(np.abs(a[v] - f[v]).max() / (2.0 ** -24 * np.abs(a[v]).max())))
+        out[str(K)] = round(worst, 2)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--calls", type=int, default=2)
+    ap.add_argument("--windows", type=int, default=5)
+    ap.add_argument("--plain-iters", type=int, default=256)
+    ap.add_argument("--netlib-iters", type=int, default=60000)
+    ap.add_argument("--synthetic", type=int, default=4)
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "bench_pdhg needs the GPU: there is no CPU path"
+    from mllp_amd.data import load_packed
+    from mllp_amd.graph import LPBatch, pdhg_limits, synthetic_batch
+    from mllp_amd.planted import planted_batch
+    out = {"limits": {"lds_words": pdhg_limits()[0], "threads": pdhg_limits()[1]}, "oracle_deviation_units": oracle_deviation()}
+    net = LPBatch.from_instances(load_packed())
+    per_it = []
+    small, _, _ = planted_batch(256, 50, 120, 6.0, 1)
+    many, _, _ = planted_batch(1024, 50, 120, 6.0, 1)
+    mid, _, _ = planted_batch(64, 500, 1200, 6.0, 2)
+    for name, b, lds in ((f"Netlib {net.n_inst} instances", net, None), ("planted 256 x (50 x 120)", small, None),
+                         ("planted 1024 x (50 x 120)", many, None), ("planted 64 x (500 x 1200)", mid, None),
+                         ("planted 64 x (500 x 1200), vectors in scratch", mid, 0)):
+        per_it.append({"batch": name, **shape_of(b), **timed(b, args.plain_iters, args.calls, args.windows, lds, check_every=0)})
+    if args.synthetic > 0:
+        syn = synthetic_batch(n_inst=args.synthetic)
+        per_it.append({"batch": f"synthetic {args.synthetic} x (10000 x 20000)", **shape_of(syn), **timed(syn, 16, 1, 3, None, check_every=0)})
+        del syn
+    out["per_iteration"] = per_it
+    # Netlib: where the baseline gets within --netlib-iters
+    table = {}
+    for eps in (1e-3, 1e-4):
+        res = net.pdhg(args.netlib_iters, eps=eps)
+        torch.cuda.synchronize()
+        st, kkt = res.status.cpu().numpy(), res.kkt.cpu().numpy()
+        for k, name in enumerate(net.names):
+            table.setdefault(name, {"m": net.inst_m[k], "n": net.inst_n[k]})[f"eps_{eps:g}"] = {
+                "code": int(st[k, 0]), "iterations": int(st[k, 1]), "restarts": int(st[k, 2]),
+                "primal": float(f"{kkt[k, 0]:.3g}"), "dual": float(f"{kkt[k, 1]:.3g}"), "gap": float(f"{kkt[k, 2]:.3g}")}
+        out.setdefault("netlib_converged", {})[f"eps_{eps:g}"] = int((st[:, 0] == 0).sum())
+    out["netlib_max_iters"] = args.netlib_iters
+    out["netlib"] = table
+    # cold against warm on a planted batch
+    cold = small.pdhg(8192)
+    warm = small.pdhg(8192, start=small.solve_basis(small.labels))
+    far = small.pdhg(8192, start=small.repair_basis(torch.randn(small.N, device="cuda", generator=torch.Generator(device="cuda").manual_seed(5))))
+    torch.cuda.synchronize()
+    rows = {}
+    for name, r in (("cold", cold), ("warm_from_repair_basis_of_the_labels", warm), ("warm_from_repair_basis_of_a_random_ranking", far)):
+        st = r.status.cpu().numpy()
+        rows[name] = {"converged": int((st[:, 0] == 0).sum()), "iterations_mean": round(float(st[:, 1].mean()), 1),
+                      "iterations_max": int(st[:, 1].max())}
+    got = small.solved(small.pdhg_basis(cold), 1e-3, 1e-3)
+    rows["cold"]["optimal_after_pdhg"] = int(got["optimal"].sum())
+    out["cold_warm"] = {"batch": "planted 256 x (50 x 120)", "eps": 2.0 ** -10, "max_iters": 8192, **rows}
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
