@@ -22,12 +22,16 @@
 // iteration, coalesced.  Whether a column is basic is read from d_basis, which the kernel keeps current.
 // No float atomics; every sum has an order that depends on the instance alone: the same bits alone and inside any batch.
 //
-// mllp_basis_simplex_guarded has a kernel of its own, basis_simplex_guarded_kernel.  In Bland mode -- after
-// stall_pivots degenerate pivots of a stage, the same in every thread -- the reductions of S1, S3 and S4 take other keys
-// ({basic column, row}, {column}, clipped ratios), and S4 of stage P a second reduction (the lowest basic column among the
-// bit-equal smallest ratios: a seventh barrier, in that iteration only); after every refactor_every pivots the factorization
-// of the start runs again on d_basis, in place.  mllp_basis_simplex's kernel and host code are untouched.
+// mllp_basis_simplex_guarded is the same kernel source, instantiated on its own argument struct, and the
+// same host path.  In Bland mode -- after stall_pivots degenerate pivots of a stage, the same in every thread -- the
+// reductions of S1, S3 and S4 take other keys ({basic column, row}, {column}, clipped ratios), and S4 of stage P a second
+// reduction (the lowest basic column among the bit-equal smallest ratios: a seventh barrier, in that iteration only); after
+// every refactor_every pivots the factorization of the start runs again on d_basis, in place.  All of that is compiled out of
+// mllp_basis_simplex's instantiations.  One deliberate duplicate is left: those instantiations factorize the start by inline
+// text, not through sx_factorize, because any function form of it changes their instruction streams.
 #include <cmath>
+#include <string>
+#include <type_traits>
 
 #include "device_utils.h"
 #include "internal.h"
@@ -175,313 +179,19 @@ struct SimplexArgs {
     float* scratch;
 };
 
-template <bool IN_LDS, int NT>
-__global__ __launch_bounds__(NT) void basis_simplex_kernel(const SimplexArgs A) {
-    constexpr int NW = NT / 64;
-    extern __shared__ float sx_lds[];
-    __shared__ unsigned long long s_fkey[2][NW];    // the factorization's pivot search
-    __shared__ unsigned long long s_key[3][NW];     // leaving row (D), pricing, ratio test (P)
-    __shared__ long long s_off[NW];
-    __shared__ int s_cnt[NW];
-    const int k = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int row0 = A.ptr_m[k], m = A.ptr_m[k + 1] - row0;
-    const int col0 = A.ptr_n[k], n = A.ptr_n[k + 1] - col0;
-    if ((m <= SIMPLEX_LDS_MAX_M) != IN_LDS) return;     // the other launch's instance
-    int* st = A.status + 4 * (size_t)k;
-    // defaults of the outputs; a running instance writes them again behind at least one barrier
-    for (int j = tid; j < n; j += NT) A.basis[col0 + j] = 0.0f;
-    if (A.trace) {
-        int* tr = A.trace + 2 * (size_t)k * (size_t)A.max_pivots;
-        for (long long q = tid; q < 2 * A.max_pivots; q += NT) tr[q] = -1;
-    }
-    int count = 0;
-    if ((long long)m <= A.max_m) {
-        for (int j = tid; j < n; j += NT) count += A.start[col0 + j] != 0.0f;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) count += __shfl_xor(count, o, 64);
-        if (lane == 0) s_cnt[wave] = count;
-        __syncthreads();
-        count = 0;
-#pragma unroll
-        for (int v = 0; v < NW; ++v) count += s_cnt[v];
-    }
-    if ((long long)m > A.max_m || count != m) {
-        for (int i = tid; i < m; i += NT)
-            if (A.col_of_row) A.col_of_row[row0 + i] = -1;
-        if (tid == 0) { st[0] = (long long)m > A.max_m ? SX_SKIPPED : SX_BAD_MASK; st[1] = 0; st[2] = 0; st[3] = 0; }
-        return;
-    }
-    // this instance's piece of the scratch: behind those of the earlier instances that may run (integer sum: exact)
-    long long off = 0;
-    for (int j = tid; j < k; j += NT) {
-        const long long mj = A.ptr_m[j + 1] - A.ptr_m[j], nj = A.ptr_n[j + 1] - A.ptr_n[j];
-        if (mj <= A.max_m) off += simplex_words(mj, nj);
-    }
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) off += __shfl_xor(off, o, 64);
-    if (lane == 0) s_off[wave] = off;
-    __syncthreads();
-    off = 0;
-#pragma unroll
-    for (int v = 0; v < NW; ++v) off += s_off[v];
-    float* T;                                       // [m][m] column-major
-    float* w;                                       // [m] T a_j
-    float* sh;                                      // [n] the shifts of stage D
-    if constexpr (IN_LDS) {
-        T = sx_lds;
-        w = sx_lds + (size_t)m * m;
-        sh = A.scratch + off;
-    } else {
-        T = A.scratch + off;
-        w = sx_lds;
-        sh = A.scratch + off + (size_t)m * m;
-    }
-    float* prow = w + m;                            // [m] the staged pivot row; rho (row p of T) before it in stage D
-    int* crow = reinterpret_cast<int*>(prow + m);   // [m] local column whose row this is, or -1
-    float* xB = reinterpret_cast<float*>(crow + m); // [m] T b
-    int* piv = reinterpret_cast<int*>(xB);          //     (the factorization's pivoted rows in order, before there is an x_B)
-    float* yv = xB + m;                             // [m] T' g_B
-    float* gB = yv + m;                             // [m] the stage's costs of the basic columns
-    for (int i = tid; i < m; i += NT) crow[i] = -1;
-    __syncthreads();
-
-    // ---- the start: the rule of mllp_basis_repair on the mask's columns in ascending order (basis.hip) ------------------
-    int rank = 0, par = 0;
-    for (int j = 0; j < n && rank < m; ++j) {
-        if (A.start[col0 + j] == 0.0f) continue;
-        const int beg = A.at_ptr[col0 + j], end = A.at_ptr[col0 + j + 1];
-        float amax = 0.0f;
-        for (int e = beg; e < end; ++e) amax = fmaxf(amax, fabsf(A.at_val[e]));
-        unsigned long long best = 0ull;             // (every row that is not pivoted has a key above 0)
-        for (int i = tid; i < m; i += NT) {
-            float acc = 0.0f;
-            for (int e = beg; e < end; ++e) {
-                const int r = A.at_idx[e] - row0;
-                const float a = A.at_val[e];
-                if (crow[r] >= 0) acc = __fmaf_rn(a, T[(size_t)r * m + i], acc);
-                else if (r == i) acc = __fadd_rn(acc, a);
-            }
-            w[i] = acc;
-            if (crow[i] < 0) {
-                const unsigned long long key = ((unsigned long long)__float_as_uint(fabsf(acc)) << 32) | (unsigned)(0x7fffffff - i);
-                best = key > best ? key : best;
-            }
-        }
-        best = sx_wave_max(best);
-        if (lane == 0) s_fkey[par][wave] = best;
-        __syncthreads();        // (also: every w_i is written)
-        best = 0ull;
-#pragma unroll
-        for (int v = 0; v < NW; ++v) best = s_fkey[par][v] > best ? s_fkey[par][v] : best;
-        par ^= 1;               // (this buffer is written again two candidates on: a barrier lies between)
-        const float r = __uint_as_float((unsigned)(best >> 32));
-        const int p = 0x7fffffff - (int)(unsigned)(best & 0xffffffffull);
-        if (!(amax > 0.0f && r > __fmul_rn(A.tol, amax))) continue;     // (no barrier: nobody reads another thread's w_i)
-        const float wp = w[p];
-        for (int q = tid; q <= rank; q += NT)
-            prow[q] = q < rank ? __fdiv_rn(T[(size_t)piv[q] * m + p], wp) : __fdiv_rn(1.0f, wp);
-        __syncthreads();
-        for (int q = wave; q <= rank; q += NW) {    // a column per wavefront, the rows over its lanes
-            const float pc = prow[q];
-            const bool fresh = q == rank;           // column p was e_p until now
-            if (!fresh && pc == 0.0f) continue;
-            float* col = T + (size_t)(fresh ? p : piv[q]) * m;
-            for (int i0 = lane; i0 < m; i0 += 64 * SX_UNROLL) {
-                float tv[SX_UNROLL], wv[SX_UNROLL];
-#pragma unroll
-                for (int u = 0; u < SX_UNROLL; ++u) {
-                    const int i = i0 + 64 * u;
-                    wv[u] = i < m ? w[i] : 0.0f;
-                    tv[u] = (i < m && !fresh) ? col[i] : 0.0f;
-                }
-#pragma unroll
-                for (int u = 0; u < SX_UNROLL; ++u) {
-                    const int i = i0 + 64 * u;
-                    if (i >= m) continue;
-                    if (i == p) col[i] = pc;
-                    else if (fresh || wv[u] != 0.0f) col[i] = __fmaf_rn(-wv[u], pc, tv[u]);
-                }
-            }
-        }
-        if (tid == 0) {
-            piv[rank] = p;
-            crow[p] = j;
-        }
-        ++rank;
-        __syncthreads();
-    }
-    if (rank < m) {
-        for (int i = tid; i < m; i += NT)
-            if (A.col_of_row) A.col_of_row[row0 + i] = -1;
-        if (tid == 0) { st[0] = SX_SINGULAR; st[1] = 0; st[2] = 0; st[3] = rank; }
-        return;
-    }
-    for (int i = tid; i < m; i += NT) A.basis[col0 + crow[i]] = 1.0f;
-
-    // y = T' g_B: a wavefront per column of T
-    auto dual = [&]() {
-        for (int cc = wave; cc < m; cc += NW) {
-            const float* col = T + (size_t)cc * m;
-            float acc = 0.0f;
-            for (int p = lane; p < m; p += 64) acc = __fmaf_rn(col[p], gB[p], acc);
-            acc = group_sum<64>(acc);
-            if (lane == 0) yv[cc] = acc;
-        }
-    };
-
-    // ---- the shifts: s_j = max(0, dshift - d0_j) off the basis, 0 on it, d0 the reduced costs of c ------------------------
-    for (int i = tid; i < m; i += NT) gB[i] = A.c[col0 + crow[i]];
-    __syncthreads();            // (also: d_basis holds the start)
-    dual();
-    __syncthreads();
-    for (int j = tid; j < n; j += NT) {
-        float s = 0.0f;
-        if (A.basis[col0 + j] == 0.0f) {
-            float ay = 0.0f;
-            for (int e = A.at_ptr[col0 + j]; e < A.at_ptr[col0 + j + 1]; ++e) ay = __fmaf_rn(A.at_val[e], yv[A.at_idx[e] - row0], ay);
-            const float t = __fsub_rn(A.dshift, __fsub_rn(A.c[col0 + j], ay));
-            s = t > 0.0f ? t : 0.0f;
-        }
-        sh[j] = s;
-    }
-    __syncthreads();
-
-    // ---- the pivots ---------------------------------------------------------------------------------------------------------
-    int stage = 0, code = SX_LIMIT;
-    long long nD = 0, nP = 0;
-    int* tr = A.trace ? A.trace + 2 * (size_t)k * (size_t)A.max_pivots : nullptr;
-    while (true) {
-        // S1
-        for (int i = tid; i < m; i += NT) {
-            const int j = crow[i];
-            const float g = A.c[col0 + j];
-            gB[i] = stage == 0 ? __fadd_rn(g, sh[j]) : g;
-        }
-        unsigned long long best = SX_NONE;
-        for (int p = tid; p < m; p += NT) {
-            float acc = 0.0f;
-#pragma unroll 8
-            for (int cc = 0; cc < m; ++cc) acc = __fmaf_rn(T[(size_t)cc * m + p], A.b[row0 + cc], acc);
-            xB[p] = acc;
-            const unsigned long long key = ((unsigned long long)sx_order_key(acc) << 32) | (unsigned)p;
-            best = key < best ? key : best;
-        }
-        int p = -1;
-        if (stage == 0) {
-            best = sx_block_min<NW>(best, s_key[0]);
-            if (best == SX_NONE || !(sx_key_value((unsigned)(best >> 32)) < -A.ftol)) {
-                stage = 1;          // primal feasible: stage D is over for good; S1 once more with the true costs
-                continue;           // (nothing S1 writes is read before its barrier, and s_key[0] is not written again)
-            }
-            p = (int)(unsigned)(best & 0xffffffffull);
-        } else {
-            __syncthreads();
-        }
-        // S2
-        dual();
-        if (stage == 0)
-            for (int cc = tid; cc < m; cc += NT) prow[cc] = T[(size_t)cc * m + p];
-        __syncthreads();
-        // S3
-        best = SX_NONE;
-        for (int j = tid; j < n; j += NT) {
-            if (A.basis[col0 + j] != 0.0f) continue;
-            const int beg = A.at_ptr[col0 + j], end = A.at_ptr[col0 + j + 1];
-            float ay = 0.0f, ar = 0.0f;
-            for (int e = beg; e < end; ++e) {
-                const int r = A.at_idx[e] - row0;
-                const float a = A.at_val[e];
-                ay = __fmaf_rn(a, yv[r], ay);
-                if (stage == 0) ar = __fmaf_rn(a, prow[r], ar);
-            }
-            float g = A.c[col0 + j];
-            if (stage == 0) g = __fadd_rn(g, sh[j]);
-            const float d = __fsub_rn(g, ay);
-            unsigned long long key = SX_NONE;
-            if (stage == 0) {
-                if (ar < -A.ptol) key = ((unsigned long long)__float_as_uint(__fdiv_rn(d > 0.0f ? d : 0.0f, -ar)) << 32) | (unsigned)j;
-            } else {
-                key = ((unsigned long long)sx_order_key(d) << 32) | (unsigned)j;
-            }
-            best = key < best ? key : best;
-        }
-        best = sx_block_min<NW>(best, s_key[1]);
-        if (stage == 0 && best == SX_NONE) { code = SX_INFEASIBLE; break; }
-        if (stage == 1 && (best == SX_NONE || !(sx_key_value((unsigned)(best >> 32)) < -A.dtol))) { code = SX_OPTIMAL; break; }
-        const int j = (int)(unsigned)(best & 0xffffffffull);
-        // S4
-        const int beg = A.at_ptr[col0 + j], end = A.at_ptr[col0 + j + 1];
-        best = SX_NONE;
-        for (int i = tid; i < m; i += NT) {
-            float acc = 0.0f;
-            for (int e = beg; e < end; ++e) acc = __fmaf_rn(A.at_val[e], T[(size_t)(A.at_idx[e] - row0) * m + i], acc);
-            w[i] = acc;
-            if (stage == 1 && acc > A.ptol) {
-                const float x = xB[i];
-                const unsigned long long key = ((unsigned long long)__float_as_uint(__fdiv_rn(x > 0.0f ? x : 0.0f, acc)) << 32) | (unsigned)i;
-                best = key < best ? key : best;
-            }
-        }
-        if (stage == 1) {
-            best = sx_block_min<NW>(best, s_key[2]);
-            if (best == SX_NONE) { code = SX_UNBOUNDED; break; }
-            p = (int)(unsigned)(best & 0xffffffffull);
-        } else {
-            __syncthreads();
-        }
-        if (nD + nP >= A.max_pivots) { code = SX_LIMIT; break; }
-        // S5
-        const float wp = w[p];
-        for (int cc = tid; cc < m; cc += NT) prow[cc] = __fdiv_rn(stage == 0 ? prow[cc] : T[(size_t)cc * m + p], wp);
-        __syncthreads();
-        // S6
-        for (int cc = wave; cc < m; cc += NW) {     // a column per wavefront, the rows over its lanes
-            const float pc = prow[cc];
-            if (pc == 0.0f) continue;               // (row p holds a zero here already; every other row keeps its bits)
-            float* col = T + (size_t)cc * m;
-            for (int i0 = lane; i0 < m; i0 += 64 * SX_UNROLL) {
-                float tv[SX_UNROLL], wv[SX_UNROLL];
-#pragma unroll
-                for (int u = 0; u < SX_UNROLL; ++u) {
-                    const int i = i0 + 64 * u;
-                    wv[u] = i < m ? w[i] : 0.0f;
-                    tv[u] = i < m ? col[i] : 0.0f;
-                }
-#pragma unroll
-                for (int u = 0; u < SX_UNROLL; ++u) {
-                    const int i = i0 + 64 * u;
-                    if (i >= m) continue;
-                    if (i == p) col[i] = pc;
-                    else if (wv[u] != 0.0f) col[i] = __fmaf_rn(-wv[u], pc, tv[u]);
-                }
-            }
-        }
-        if (tid == 0) {
-            A.basis[col0 + crow[p]] = 0.0f;
-            A.basis[col0 + j] = 1.0f;
-            crow[p] = j;
-            if (tr) { tr[2 * (nD + nP)] = j; tr[2 * (nD + nP) + 1] = p; }
-        }
-        if (stage == 0) ++nD;
-        else ++nP;
-        __syncthreads();
-    }
-    for (int i = tid; i < m; i += NT)
-        if (A.col_of_row) A.col_of_row[row0 + i] = crow[i];
-    if (tid == 0) { st[0] = code; st[1] = (int)nD; st[2] = (int)nP; st[3] = m; }
-}
-
 // mllp_basis_simplex_guarded: the same, and the two guards
 struct SimplexGuardedArgs : SimplexArgs {
     long long refactor_every, stall_pivots;
     int* guard;
 };
 
-// The kernel above once more, with Bland's rule after stall_pivots degenerate pivots of a stage and a fresh factorization
-// every refactor_every pivots (mllp_basis_simplex_guarded).  A copy, not a flag of the kernel above: as a
-// third template flag the plain instantiations measured 2.4 % and 3.4 % slower than the kernel above.
-template <bool IN_LDS, int NT>
-__global__ __launch_bounds__(NT) void basis_simplex_guarded_kernel(const SimplexGuardedArgs A) {
+// The one kernel of both entry points.  Args = SimplexGuardedArgs adds Bland's rule after stall_pivots degenerate pivots of a
+// stage and a fresh factorization every refactor_every pivots; with Args = SimplexArgs every guard is
+// discarded at compile time, and what is left is mllp_basis_simplex's rule.  A change meant for one entry point is held to
+// leaving the other's instantiations instruction for instruction what they were (tools/kernel_streams.py).
+template <bool IN_LDS, int NT, class Args>
+__global__ __launch_bounds__(NT) void basis_simplex_kernel(const Args A) {
+    constexpr bool G = std::is_same<Args, SimplexGuardedArgs>::value;
     constexpr int NW = NT / 64;
     extern __shared__ float sx_lds[];
     __shared__ unsigned long long s_fkey[2][NW];    // the factorization's pivot search
@@ -494,7 +204,8 @@ __global__ __launch_bounds__(NT) void basis_simplex_guarded_kernel(const Simplex
     if ((m <= SIMPLEX_LDS_MAX_M) != IN_LDS) return;     // the other launch's instance
     int* st = A.status + 4 * (size_t)k;
     auto write_guard = [&](long long refactorizations, long long bland) {      // (one thread)
-        if (A.guard) { A.guard[2 * (size_t)k] = (int)refactorizations; A.guard[2 * (size_t)k + 1] = (int)bland; }
+        if constexpr (G)
+            if (A.guard) { A.guard[2 * (size_t)k] = (int)refactorizations; A.guard[2 * (size_t)k + 1] = (int)bland; }
     };
     // defaults of the outputs; a running instance writes them again behind at least one barrier
     for (int j = tid; j < n; j += NT) A.basis[col0 + j] = 0.0f;
@@ -550,7 +261,82 @@ __global__ __launch_bounds__(NT) void basis_simplex_guarded_kernel(const Simplex
     int* piv = reinterpret_cast<int*>(xB);          //     (the factorization's pivoted rows in order, before there is an x_B)
     float* yv = xB + m;                             // [m] T' g_B
     float* gB = yv + m;                             // [m] the stage's costs of the basic columns
-    const int rank = sx_factorize<NT>(A.start, A.at_ptr, A.at_idx, A.at_val, A.tol, row0, col0, m, n, T, w, prow, crow, piv, s_fkey);
+    // ---- the start: the rule of mllp_basis_repair on the mask's columns in ascending order (basis.hip) ----------------------
+    int rank;
+    if constexpr (G) {
+        rank = sx_factorize<NT>(A.start, A.at_ptr, A.at_idx, A.at_val, A.tol, row0, col0, m, n, T, w, prow, crow, piv, s_fkey);
+    } else {
+        // sx_factorize's text once more, on purpose: with the start factorized through any function the plain instantiations
+        // are scheduled and allocated differently from here on, and measured 2.4 % and 3.4 % slower.  The
+        // one duplicate left in this file; a change to either copy goes into both.
+        for (int i = tid; i < m; i += NT) crow[i] = -1;
+        __syncthreads();
+        rank = 0;
+        int par = 0;
+        for (int j = 0; j < n && rank < m; ++j) {
+            if (A.start[col0 + j] == 0.0f) continue;
+            const int beg = A.at_ptr[col0 + j], end = A.at_ptr[col0 + j + 1];
+            float amax = 0.0f;
+            for (int e = beg; e < end; ++e) amax = fmaxf(amax, fabsf(A.at_val[e]));
+            unsigned long long best = 0ull;             // (every row that is not pivoted has a key above 0)
+            for (int i = tid; i < m; i += NT) {
+                float acc = 0.0f;
+                for (int e = beg; e < end; ++e) {
+                    const int r = A.at_idx[e] - row0;
+                    const float a = A.at_val[e];
+                    if (crow[r] >= 0) acc = __fmaf_rn(a, T[(size_t)r * m + i], acc);
+                    else if (r == i) acc = __fadd_rn(acc, a);
+                }
+                w[i] = acc;
+                if (crow[i] < 0) {
+                    const unsigned long long key = ((unsigned long long)__float_as_uint(fabsf(acc)) << 32) | (unsigned)(0x7fffffff - i);
+                    best = key > best ? key : best;
+                }
+            }
+            best = sx_wave_max(best);
+            if (lane == 0) s_fkey[par][wave] = best;
+            __syncthreads();        // (also: every w_i is written)
+            best = 0ull;
+#pragma unroll
+            for (int v = 0; v < NW; ++v) best = s_fkey[par][v] > best ? s_fkey[par][v] : best;
+            par ^= 1;               // (this buffer is written again two candidates on: a barrier lies between)
+            const float r = __uint_as_float((unsigned)(best >> 32));
+            const int p = 0x7fffffff - (int)(unsigned)(best & 0xffffffffull);
+            if (!(amax > 0.0f && r > __fmul_rn(A.tol, amax))) continue;     // (no barrier: nobody reads another thread's w_i)
+            const float wp = w[p];
+            for (int q = tid; q <= rank; q += NT)
+                prow[q] = q < rank ? __fdiv_rn(T[(size_t)piv[q] * m + p], wp) : __fdiv_rn(1.0f, wp);
+            __syncthreads();
+            for (int q = wave; q <= rank; q += NW) {    // a column per wavefront, the rows over its lanes
+                const float pc = prow[q];
+                const bool fresh = q == rank;           // column p was e_p until now
+                if (!fresh && pc == 0.0f) continue;
+                float* col = T + (size_t)(fresh ? p : piv[q]) * m;
+                for (int i0 = lane; i0 < m; i0 += 64 * SX_UNROLL) {
+                    float tv[SX_UNROLL], wv[SX_UNROLL];
+#pragma unroll
+                    for (int u = 0; u < SX_UNROLL; ++u) {
+                        const int i = i0 + 64 * u;
+                        wv[u] = i < m ? w[i] : 0.0f;
+                        tv[u] = (i < m && !fresh) ? col[i] : 0.0f;
+                    }
+#pragma unroll
+                    for (int u = 0; u < SX_UNROLL; ++u) {
+                        const int i = i0 + 64 * u;
+                        if (i >= m) continue;
+                        if (i == p) col[i] = pc;
+                        else if (fresh || wv[u] != 0.0f) col[i] = __fmaf_rn(-wv[u], pc, tv[u]);
+                    }
+                }
+            }
+            if (tid == 0) {
+                piv[rank] = p;
+                crow[p] = j;
+            }
+            ++rank;
+            __syncthreads();
+        }
+    }
     if (rank < m) {
         for (int i = tid; i < m; i += NT)
             if (A.col_of_row) A.col_of_row[row0 + i] = -1;
@@ -592,9 +378,11 @@ __global__ __launch_bounds__(NT) void basis_simplex_guarded_kernel(const Simplex
     long long nD = 0, nP = 0;
     int* tr = A.trace ? A.trace + 2 * (size_t)k * (size_t)A.max_pivots : nullptr;
     // the consecutive degenerate pivots of the stage, the pivots until the next refactorization, the two counts
-    long long stall = 0, until = A.refactor_every, nRef = 0, nBl = 0;
+    long long stall = 0, until = 0, nRef = 0, nBl = 0;
+    if constexpr (G) until = A.refactor_every;
     while (true) {
-        const bool bland = A.stall_pivots > 0 && stall >= A.stall_pivots;    // the same in every thread: a property of the instance
+        bool bland = false;         // the same in every thread: a property of the instance; never, without the guards
+        if constexpr (G) bland = A.stall_pivots > 0 && stall >= A.stall_pivots;
         // S1
         for (int i = tid; i < m; i += NT) {
             const int j = crow[i];
@@ -696,15 +484,16 @@ __global__ __launch_bounds__(NT) void basis_simplex_guarded_kernel(const Simplex
         }
         if (nD + nP >= A.max_pivots) { code = SX_LIMIT; break; }
         bool degenerate = false;
-        if (A.stall_pivots > 0) {
-            if (stage == 1) {
-                degenerate = xB[p] <= A.ftol;
-            } else {                // dtilde_j again, in pricing's order: the same bits
-                float ay = 0.0f;
-                for (int e = beg; e < end; ++e) ay = __fmaf_rn(A.at_val[e], yv[A.at_idx[e] - row0], ay);
-                degenerate = __fsub_rn(__fadd_rn(A.c[col0 + j], sh[j]), ay) <= A.dtol;
+        if constexpr (G)
+            if (A.stall_pivots > 0) {
+                if (stage == 1) {
+                    degenerate = xB[p] <= A.ftol;
+                } else {            // dtilde_j again, in pricing's order: the same bits
+                    float ay = 0.0f;
+                    for (int e = beg; e < end; ++e) ay = __fmaf_rn(A.at_val[e], yv[A.at_idx[e] - row0], ay);
+                    degenerate = __fsub_rn(__fadd_rn(A.c[col0 + j], sh[j]), ay) <= A.dtol;
+                }
             }
-        }
         // S5
         const float wp = w[p];
         for (int cc = tid; cc < m; cc += NT) prow[cc] = __fdiv_rn(stage == 0 ? prow[cc] : T[(size_t)cc * m + p], wp);
@@ -740,17 +529,19 @@ __global__ __launch_bounds__(NT) void basis_simplex_guarded_kernel(const Simplex
         if (stage == 0) ++nD;
         else ++nP;
         __syncthreads();
-        stall = degenerate ? stall + 1 : 0;
-        nBl += bland;
-        if (A.refactor_every > 0 && --until == 0) {
-            // discard T: the current basis, factorized as the start was (x_B, w and the staged row are dead here)
-            until = A.refactor_every;
-            if (sx_factorize<NT>(A.basis, A.at_ptr, A.at_idx, A.at_val, A.tol, row0, col0, m, n, T, w, prow, crow, piv, s_fkey) < m) { code = SX_REFACTOR; break; }
-            ++nRef;
+        if constexpr (G) {
+            stall = degenerate ? stall + 1 : 0;
+            nBl += bland;
+            if (A.refactor_every > 0 && --until == 0) {
+                // discard T: the current basis, factorized as the start was (x_B, w and the staged row are dead here)
+                until = A.refactor_every;
+                if (sx_factorize<NT>(A.basis, A.at_ptr, A.at_idx, A.at_val, A.tol, row0, col0, m, n, T, w, prow, crow, piv, s_fkey) < m) { code = SX_REFACTOR; break; }
+                ++nRef;
+            }
         }
     }
     for (int i = tid; i < m; i += NT)
-        if (A.col_of_row) A.col_of_row[row0 + i] = code == SX_REFACTOR ? -1 : crow[i];
+        if (A.col_of_row) A.col_of_row[row0 + i] = (G && code == SX_REFACTOR) ? -1 : crow[i];
     if (tid == 0) { st[0] = code; st[1] = (int)nD; st[2] = (int)nP; st[3] = m; write_guard(nRef, nBl); }
 }
 
@@ -775,6 +566,60 @@ SimplexPlan simplex_plan(const mllp_graph_t* g, int64_t max_m) {
     return p;
 }
 
+// REQUIRE on behalf of the entry point `fn`: the message names that function
+#define REQUIRE_FOR(fn, cond, msg) \
+    if (!(cond)) return ::mllp::fail(MLLP_EINVAL, std::string(fn) + ": " + (msg))
+
+// The checks that both entry points make first, and the arguments that both kernels take.
+int simplex_args(const char* fn, const mllp_graph_t* g, const float* d_x1, const float* d_x2, const float* d_start, float tol, float ftol,
+                 float dtol, float ptol, float dshift, int64_t max_pivots, int64_t max_m, float* d_basis, int32_t* d_col_of_row,
+                 int32_t* d_trace, int32_t* d_status, void* d_scratch, SimplexArgs* args) {
+    REQUIRE_FOR(fn, g && d_x1 && d_x2 && d_start && d_basis && d_status,
+                "null argument (g, d_x1, d_x2, d_start, d_basis and d_status are required)");
+    REQUIRE_FOR(fn, std::isfinite(tol) && tol >= 0.0f, "tol must be finite and not negative");
+    REQUIRE_FOR(fn, std::isfinite(ftol) && ftol > 0.0f && std::isfinite(dtol) && dtol > 0.0f && std::isfinite(ptol) && ptol > 0.0f &&
+                        std::isfinite(dshift) && dshift > 0.0f,
+                "ftol, dtol, ptol and dshift must be finite and positive");
+    REQUIRE_FOR(fn, max_pivots >= 0, "max_pivots must not be negative");
+    REQUIRE_FOR(fn, max_m >= 0, "max_m must not be negative");
+    *args = {g->inst_ptr_m, g->inst_ptr_n, g->At.ptr, g->At.idx, g->At.val, d_x1, d_x2, d_start, tol, ftol, dtol, ptol, dshift,
+             (long long)max_pivots, (long long)std::min<int64_t>(max_m, SIMPLEX_MAX_M), d_basis, d_col_of_row, d_trace, d_status,
+             static_cast<float*>(d_scratch)};
+    return MLLP_OK;
+}
+
+// One instantiation's launch.  Once per process and instantiation: the kernel may take more dynamic LDS than the default
+// limit (no stream operation).
+template <bool IN_LDS, int NT, class Args>
+int simplex_launch_one(const std::string& name, const char* where, const mllp_graph_t* g, const SimplexPlan& plan, const Args& args,
+                       hipStream_t s) {
+    constexpr int64_t limit =
+        IN_LDS ? SIMPLEX_LDS_MAX_M * SIMPLEX_LDS_MAX_M + simplex_vec_words(SIMPLEX_LDS_MAX_M) : simplex_vec_words(SIMPLEX_MAX_M);
+    static const hipError_t attr =
+        hipFuncSetAttribute(reinterpret_cast<const void*>(basis_simplex_kernel<IN_LDS, NT, Args>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)(limit * sizeof(float)));
+    if (attr != hipSuccess) return hip_fail(attr, (name + ": hipFuncSetAttribute").c_str());
+    const int64_t words = IN_LDS ? plan.lds_m * plan.lds_m + simplex_vec_words(plan.lds_m) : simplex_vec_words(plan.glb_m);
+    const size_t lds = (size_t)std::max<int64_t>(words, 1) * sizeof(float);
+    hipLaunchKernelGGL((basis_simplex_kernel<IN_LDS, NT, Args>), dim3((unsigned)g->n_inst), dim3(NT), lds, s, args);
+    return check_launch((name + where).c_str());
+}
+
+// The rest of a call, after the entry point's own checks: the plan, the scratch check, and a launch per address space of T
+// that has an instance.  Errors of HIP carry the entry point's name without its prefix.
+template <class Args>
+int simplex_launch(const char* fn, const mllp_graph_t* g, const Args& args, void* stream) {
+    const SimplexPlan plan = simplex_plan(g, args.max_m);
+    REQUIRE_FOR(fn, plan.words == 0 || args.scratch, "null d_scratch (mllp_basis_simplex_scratch_bytes is not 0)");
+    if (g->n_inst <= 0) return MLLP_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const std::string name = fn + sizeof("mllp_") - 1;
+    int rc;
+    if (plan.any_lds && (rc = simplex_launch_one<true, SX_T_LDS>(name, " (LDS)", g, plan, args, s))) return rc;
+    if (plan.any_glb && (rc = simplex_launch_one<false, SX_T_GLB>(name, " (scratch)", g, plan, args, s))) return rc;
+    return MLLP_OK;
+}
+
 }  // namespace
 
 }  // namespace mllp
@@ -792,44 +637,11 @@ extern "C" int mllp_basis_simplex(const mllp_graph_t* g, const float* d_x1, cons
                                   float ftol, float dtol, float ptol, float dshift, int64_t max_pivots, int64_t max_m,
                                   float* d_basis, int32_t* d_col_of_row, int32_t* d_trace, int32_t* d_status, void* d_scratch,
                                   void* stream) {
-    REQUIRE(g && d_x1 && d_x2 && d_start && d_basis && d_status,
-            "null argument (g, d_x1, d_x2, d_start, d_basis and d_status are required)");
-    REQUIRE(std::isfinite(tol) && tol >= 0.0f, "tol must be finite and not negative");
-    REQUIRE(std::isfinite(ftol) && ftol > 0.0f && std::isfinite(dtol) && dtol > 0.0f && std::isfinite(ptol) && ptol > 0.0f &&
-                std::isfinite(dshift) && dshift > 0.0f,
-            "ftol, dtol, ptol and dshift must be finite and positive");
-    REQUIRE(max_pivots >= 0, "max_pivots must not be negative");
-    REQUIRE(max_m >= 0, "max_m must not be negative");
-    const SimplexPlan plan = simplex_plan(g, max_m);
-    REQUIRE(plan.words == 0 || d_scratch, "null d_scratch (mllp_basis_simplex_scratch_bytes is not 0)");
-    if (g->n_inst <= 0) return MLLP_OK;
-    hipStream_t s = (hipStream_t)stream;
-    max_m = std::min<int64_t>(max_m, SIMPLEX_MAX_M);
-    const SimplexArgs args = {g->inst_ptr_m, g->inst_ptr_n, g->At.ptr, g->At.idx, g->At.val, d_x1, d_x2, d_start, tol, ftol, dtol, ptol,
-                              dshift, (long long)max_pivots, (long long)max_m, d_basis, d_col_of_row, d_trace, d_status,
-                              static_cast<float*>(d_scratch)};
-    int rc;
-    if (plan.any_lds) {
-        // once per process: the kernel may take more dynamic LDS than the default limit (no stream operation)
-        static const hipError_t attr =
-            hipFuncSetAttribute(reinterpret_cast<const void*>(basis_simplex_kernel<true, SX_T_LDS>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)((SIMPLEX_LDS_MAX_M * SIMPLEX_LDS_MAX_M + simplex_vec_words(SIMPLEX_LDS_MAX_M)) * sizeof(float)));
-        if (attr != hipSuccess) return hip_fail(attr, "basis_simplex: hipFuncSetAttribute");
-        const size_t lds = (size_t)std::max<int64_t>(plan.lds_m * plan.lds_m + simplex_vec_words(plan.lds_m), 1) * sizeof(float);
-        hipLaunchKernelGGL((basis_simplex_kernel<true, SX_T_LDS>), dim3((unsigned)g->n_inst), dim3(SX_T_LDS), lds, s, args);
-        if ((rc = check_launch("basis_simplex (LDS)"))) return rc;
-    }
-    if (plan.any_glb) {
-        static const hipError_t attr =
-            hipFuncSetAttribute(reinterpret_cast<const void*>(basis_simplex_kernel<false, SX_T_GLB>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)(simplex_vec_words(SIMPLEX_MAX_M) * sizeof(float)));
-        if (attr != hipSuccess) return hip_fail(attr, "basis_simplex: hipFuncSetAttribute");
-        const size_t lds = (size_t)std::max<int64_t>(simplex_vec_words(plan.glb_m), 1) * sizeof(float);
-        hipLaunchKernelGGL((basis_simplex_kernel<false, SX_T_GLB>), dim3((unsigned)g->n_inst), dim3(SX_T_GLB), lds, s, args);
-        if ((rc = check_launch("basis_simplex (scratch)"))) return rc;
-    }
-    return MLLP_OK;
+    SimplexArgs args;
+    if (int rc = simplex_args(__func__, g, d_x1, d_x2, d_start, tol, ftol, dtol, ptol, dshift, max_pivots, max_m, d_basis, d_col_of_row,
+                              d_trace, d_status, d_scratch, &args))
+        return rc;
+    return simplex_launch(__func__, g, args, stream);
 }
 
 extern "C" int mllp_basis_simplex_guarded(const mllp_graph_t* g, const float* d_x1, const float* d_x2, const float* d_start,
@@ -837,43 +649,13 @@ extern "C" int mllp_basis_simplex_guarded(const mllp_graph_t* g, const float* d_
                                           int64_t max_m, int64_t refactor_every, int64_t stall_pivots, float* d_basis,
                                           int32_t* d_col_of_row, int32_t* d_trace, int32_t* d_status, int32_t* d_guard,
                                           void* d_scratch, void* stream) {
-    REQUIRE(g && d_x1 && d_x2 && d_start && d_basis && d_status,
-            "null argument (g, d_x1, d_x2, d_start, d_basis and d_status are required)");
-    REQUIRE(std::isfinite(tol) && tol >= 0.0f, "tol must be finite and not negative");
-    REQUIRE(std::isfinite(ftol) && ftol > 0.0f && std::isfinite(dtol) && dtol > 0.0f && std::isfinite(ptol) && ptol > 0.0f &&
-                std::isfinite(dshift) && dshift > 0.0f,
-            "ftol, dtol, ptol and dshift must be finite and positive");
-    REQUIRE(max_pivots >= 0, "max_pivots must not be negative");
-    REQUIRE(max_m >= 0, "max_m must not be negative");
+    SimplexGuardedArgs args;
+    if (int rc = simplex_args(__func__, g, d_x1, d_x2, d_start, tol, ftol, dtol, ptol, dshift, max_pivots, max_m, d_basis, d_col_of_row,
+                              d_trace, d_status, d_scratch, &args))
+        return rc;
     REQUIRE(refactor_every >= 0 && stall_pivots >= 0, "refactor_every and stall_pivots must not be negative");
-    const SimplexPlan plan = simplex_plan(g, max_m);
-    REQUIRE(plan.words == 0 || d_scratch, "null d_scratch (mllp_basis_simplex_scratch_bytes is not 0)");
-    if (g->n_inst <= 0) return MLLP_OK;
-    hipStream_t s = (hipStream_t)stream;
-    max_m = std::min<int64_t>(max_m, SIMPLEX_MAX_M);
-    const SimplexGuardedArgs args = {{g->inst_ptr_m, g->inst_ptr_n, g->At.ptr, g->At.idx, g->At.val, d_x1, d_x2, d_start, tol, ftol, dtol,
-                                      ptol, dshift, (long long)max_pivots, (long long)max_m, d_basis, d_col_of_row, d_trace, d_status,
-                                      static_cast<float*>(d_scratch)},
-                                     (long long)refactor_every, (long long)stall_pivots, d_guard};
-    int rc;
-    if (plan.any_lds) {     // (the LDS sizes and the launches of mllp_basis_simplex, on the guarded kernel)
-        static const hipError_t attr =
-            hipFuncSetAttribute(reinterpret_cast<const void*>(basis_simplex_guarded_kernel<true, SX_T_LDS>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)((SIMPLEX_LDS_MAX_M * SIMPLEX_LDS_MAX_M + simplex_vec_words(SIMPLEX_LDS_MAX_M)) * sizeof(float)));
-        if (attr != hipSuccess) return hip_fail(attr, "basis_simplex_guarded: hipFuncSetAttribute");
-        const size_t lds = (size_t)std::max<int64_t>(plan.lds_m * plan.lds_m + simplex_vec_words(plan.lds_m), 1) * sizeof(float);
-        hipLaunchKernelGGL((basis_simplex_guarded_kernel<true, SX_T_LDS>), dim3((unsigned)g->n_inst), dim3(SX_T_LDS), lds, s, args);
-        if ((rc = check_launch("basis_simplex_guarded (LDS)"))) return rc;
-    }
-    if (plan.any_glb) {
-        static const hipError_t attr =
-            hipFuncSetAttribute(reinterpret_cast<const void*>(basis_simplex_guarded_kernel<false, SX_T_GLB>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)(simplex_vec_words(SIMPLEX_MAX_M) * sizeof(float)));
-        if (attr != hipSuccess) return hip_fail(attr, "basis_simplex_guarded: hipFuncSetAttribute");
-        const size_t lds = (size_t)std::max<int64_t>(simplex_vec_words(plan.glb_m), 1) * sizeof(float);
-        hipLaunchKernelGGL((basis_simplex_guarded_kernel<false, SX_T_GLB>), dim3((unsigned)g->n_inst), dim3(SX_T_GLB), lds, s, args);
-        if ((rc = check_launch("basis_simplex_guarded (scratch)"))) return rc;
-    }
-    return MLLP_OK;
+    args.refactor_every = (long long)refactor_every;
+    args.stall_pivots = (long long)stall_pivots;
+    args.guard = d_guard;
+    return simplex_launch(__func__, g, args, stream);
 }
