@@ -449,6 +449,66 @@ int mllp_lp_pdhg(const mllp_graph_t* g, const float* d_x1 /*c [N]*/, const float
                  float* d_y /*[M]*/, int32_t* d_status /*[n_inst,4]*/, float* d_kkt /*[n_inst,4] or NULL*/,
                  void* d_scratch, void* stream);
 
+/* Solve every instance by PRECONDITIONED restarted PDHG (mllp_amd/csrc/pdhg_scaled.hip): mllp_lp_pdhg's
+ * iteration with diagonal scaling (Ruiz passes, an optional Pock-Chambolle pass) and a clamped primal weight, all computed
+ * by the call itself.  Added after ABI 6 without a bump.  mllp_lp_pdhg is unchanged.
+ * THE RULE.  The LP, the number format and clip are mllp_lp_pdhg's: fp32; fadd, fsub, fmul, fma, fdiv, fsqrt only, each
+ * rounded to nearest, in the expressions written here.
+ *   Scaling.  dr = 1 [m], dc = 1 [n];  s_ij = fmul(fmul(|a_ij|, dr_i), dc_j) -- this one expression from both orientations.
+ *     A Ruiz pass (ruiz_passes of them): R_i = max_j s_ij, C_j = max_i s_ij, both from the same dr and dc, each an integer max
+ *     over the bit patterns (exact in any order);  dr_i = fdiv(dr_i, fsqrt(R_i)) where R_i > 0, unchanged otherwise (an empty
+ *     row, a NaN);  dc likewise from C.  The Pock-Chambolle pass (pock_chambolle != 0; alpha = 1) is the same update with
+ *     R_i = sum_j s_ij, C_j = sum_i s_ij, fadd chains in the order below.  Finally tr_i = fmul(dr_i, dr_i), tc_j =
+ *     fmul(dc_j, dc_j).
+ *   Step.  eta = fdiv(step, fsqrt(fmul(|S|_1, |S|_inf))): the largest column sum and the largest row sum of the final s_ij,
+ *     fadd chains;  eta = step when the product is not > 0.  This square root alone is taken by mllp_lp_pdhg's own
+ *     instruction (the hardware's, within 1 ulp of the rounded one), which is what makes the neutral settings hold; every
+ *     other fsqrt of this rule is correctly rounded, as every fdiv is.
+ *   Weight. w0 = fdiv(|dc o c|_2, |dr o b|_2) when primal_weight != 0 and both norms are finite and > 0, else w0 = 1;
+ *     each norm is fsqrt of the fma chain  q = fma(v, v, q), v = fmul(dc_j, c_j)  (fmul(dr_i, b_i)), in the order of c'x.
+ *     w = w0;  tau = fdiv(eta, w), sigma = fmul(eta, w), formed again whenever w changes.
+ *   Start, (xr, yr).  x = clip(x0), y = y0 as in mllp_lp_pdhg;  (xr, yr) = (x, y).
+ *   Iteration.  s_j, g_j, xbar_j, t_i as in mllp_lp_pdhg;  x+_j = clip(fsub(x_j, fmul(fmul(tau, tc_j), g_j)));
+ *     y+_i = fadd(y_i, fmul(fmul(sigma, tr_i), fsub(b_i, t_i))).  This is PDHG on the scaled LP written in the unscaled
+ *     variables: no scaled matrix is stored.
+ *   Check, stop, restart, limit.  mllp_lp_pdhg's, word for word: the errors are those of the ORIGINAL LP, so codes and
+ *     d_kkt[0..2] mean the same in both calls.
+ *   Weight update.  With primal_weight != 0, at a restart, after the candidate has become the iterate:
+ *     dx = fsqrt(sum_j fma(d_j, fdiv(d_j, tc_j), .)), d_j = fsub(x_j, xr_j);  dy likewise with y, yr, tr;  the sums in the
+ *     order of c'x.  If dx and dy are both finite and > 0:  w = min(max(fsqrt(fmul(w, fdiv(dy, dx))), fdiv(w0, weight_span)),
+ *     fmul(w0, weight_span)).  Then (xr, yr) = (x, y), whether w moved or not.  A stop (code 0) does not update.
+ *   Order.  mllp_lp_pdhg's: a row's (column's) terms in the three tiers picked by its length alone; sums over columns or rows
+ *     by thread t adding j = t, t + 1024, ..., then the butterfly and the tree.
+ *   Neutral settings.  ruiz_passes = 0, pock_chambolle = 0, primal_weight = 0 give tc = tr = 1, tau = sigma = eta and
+ *     therefore the bits of mllp_lp_pdhg in d_x, d_y, d_status and d_kkt[0..3] (fmul by 1 and fdiv by 1 are exact).
+ * WHAT THIS RULE STILL DOES NOT DO.  No adaptive step size (eta is fixed by the norms of S); no infeasibility detection (an
+ * infeasible or unbounded LP ends with code 6 or 8); no feasibility polishing; fp32 residuals bottom out around 1e-6, and
+ * the factors themselves can underflow or overflow on a badly scaled matrix (the iterate then turns not finite: code 8).
+ *   d_x1, d_x2, d_x0, d_y0, max_iters, check_every, eps, step, beta, max_lds_words, d_x, d_y, d_status : as mllp_lp_pdhg.
+ *   ruiz_passes in 0 .. 64;  pock_chambolle, primal_weight : 0 or not 0;  weight_span finite, >= 1 (1 keeps w = w0).
+ *   d_dr [M], d_dc [N] or NULL : the factors dr and dc (before squaring).
+ *   d_kkt [n_inst, 6] or NULL : {primal, dual, gap of the output, eta, w0, the final w}.
+ *   d_scratch : mllp_lp_pdhg_scaled_scratch_bytes(g, max_lds_words) bytes: 2 n + 2 m words for EVERY instance (tc, xr, tr,
+ *             yr: read once per finished row, as c and b are, never gathered) and 3 n + 2 m more for every instance whose
+ *             five vectors do not fit LDS; may be NULL when that is 0 (a batch without rows and columns).
+ *             mllp_lp_pdhg_scaled_limits: {LDS words (36 864), threads per workgroup (1024), largest ruiz_passes (64)}.
+ * Every requested output is fully written for every instance; n = 0 or m = 0 is legal.  A launch function: `stream` only,
+ * no allocation, no synchronisation, hipGraph-capturable; one workgroup per instance, persistent; the set-up takes
+ * 2 (ruiz_passes + pock_chambolle + 1) sweeps, then two workgroup barriers per iteration as mllp_lp_pdhg.  No float atomics,
+ * one writer per word: bitwise reproducible, the same bits in LDS and in scratch, alone and inside any batch.
+ * mllp_lp_pdhg_scaled is under the MEMORY CONTRACT below as mllp_lp_pdhg is.
+ * MLLP_EINVAL before any launch, nothing written: every refusal of mllp_lp_pdhg; ruiz_passes outside 0 .. 64; weight_span
+ * not finite or < 1; d_x0 or d_y0 overlapping d_dr or d_dc.                                                               */
+int mllp_lp_pdhg_scaled_limits(int64_t limits[3]);
+int mllp_lp_pdhg_scaled_scratch_bytes(const mllp_graph_t* g, int64_t max_lds_words, int64_t* bytes);
+int mllp_lp_pdhg_scaled(const mllp_graph_t* g, const float* d_x1 /*c [N]*/, const float* d_x2 /*b [M]*/,
+                        const float* d_x0 /*[N] or NULL*/, const float* d_y0 /*[M] or NULL*/, int64_t max_iters,
+                        int64_t check_every, float eps, float step, float beta, int64_t ruiz_passes,
+                        int32_t pock_chambolle, int32_t primal_weight, float weight_span, int64_t max_lds_words,
+                        float* d_x /*[N]*/, float* d_y /*[M]*/, float* d_dr /*[M] or NULL*/, float* d_dc /*[N] or NULL*/,
+                        int32_t* d_status /*[n_inst,4]*/, float* d_kkt /*[n_inst,6] or NULL*/, void* d_scratch,
+                        void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Plain CSR SpMM (the roofline kernel named in BASELINE.json's metric):
  *   transpose == 0:  Y[M,16] = A   * H[N,16]       transpose == 1:  Y[N,16] = A^T * H[M,16]

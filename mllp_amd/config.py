@@ -49,7 +49,10 @@ HOT_PATH_DEFAULTS = {
                              # `pdhg: {iters: K, eps: E}` in the block (optional `check`, default 64, and `warm`, default true)
                              # adds pdhg_converged / pdhg_iterations / optimal_after_pdhg: every instance solved by restarted
                              # PDHG (LPBatch.pdhg) from the repaired prediction's basic solution (warm) or from zeros, and the
-                             # vertex its iterate points at certified (LPBatch.pdhg_basis + solved)
+                             # vertex its iterate points at certified (LPBatch.pdhg_basis + solved);  `scaled: true` inside
+                             # `pdhg` solves by the preconditioned call instead (LPBatch.pdhg_scaled: Ruiz and Pock-Chambolle
+                             # scaling, a clamped primal weight) under the same three keys, or `scaled: {ruiz: 10,
+                             # pock_chambolle: true, weight: true, span: 16}` with any of its options; absent == LPBatch.pdhg
     "weight_decay": 0.0,     # decoupled weight decay of the optimizer (torch.optim.AdamW); 0 == the reference's Adam
     "clip_norm": 0.0,        # cap on the global gradient norm of a step (torch.nn.utils.clip_grad_norm_); 0 == no clipping
     "lr_schedule": None,     # the block {warmup: W, total: T, min_ratio: r}: the rate rises linearly over the first W steps, then

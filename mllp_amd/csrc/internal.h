@@ -451,6 +451,17 @@ constexpr int64_t PDHG_LDS_WORDS = 36864;
 constexpr int PDHG_THREADS = 1024;
 __host__ __device__ constexpr int64_t pdhg_words(int64_t m, int64_t n) { return 3 * n + 2 * m; }   // x, 2x+ - x, xs, y, ys
 
+// ---- preconditioned PDHG (pdhg_scaled.hip): the same five vectors, and four more that no sweep gathers --------------------
+// x, xbar, xs, y, ys (pdhg_words) live in LDS up to PDHG_SCALED_LDS_WORDS, the threshold of pdhg.hip, so the same 92 of the
+// 97 Netlib instances fit.  tc, xr, tr, yr (pdhg_scaled_side_words) are read once per finished row, as c and b are, and live
+// in the caller's scratch for EVERY instance: in LDS they would raise an instance's image to 5 n + 4 m words and move 8 more
+// Netlib instances out of LDS (84 fit) to save one cached, coalesced load per row.  mllp_lp_pdhg_scaled_limits reports the
+// three constants.
+constexpr int64_t PDHG_SCALED_LDS_WORDS = 36864;
+constexpr int PDHG_SCALED_THREADS = 1024;
+constexpr int PDHG_SCALED_MAX_RUIZ = 64;
+__host__ __device__ constexpr int64_t pdhg_scaled_side_words(int64_t m, int64_t n) { return 2 * n + 2 * m; }   // tc, xr, tr, yr
+
 // ---- soft top-m loss head (topm_loss.hip): one workgroup of TOPM_LOSS_T threads per instance, many passes per evaluation ---
 // Where an instance's scaled (and perturbed) logits a_i live between the passes, by its column count n alone: up to
 // TOPM_LOSS_LDS_MAX columns in LDS (64 KB; word t + 1024 j belongs to thread t alone); longer instances form a_i again

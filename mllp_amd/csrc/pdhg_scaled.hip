@@ -1,0 +1,628 @@
+// pdhg_scaled.hip -- diagonally preconditioned, restarted PDHG with a clamped primal weight on every instance of the resident
+// batch (mllp_lp_pdhg_scaled; the rule is stated in include/mllp_hip.h, the design in DESIGN.md 4.21).  The structure is
+// pdhg.hip's: one workgroup per instance, persistent over the iterations, two sweeps and two barriers per iteration, every
+// row sum in ordered_sum.h's order, every decision taken from bits that all threads hold alike.  What is new:
+//   set-up     dr [m], dc [n] by ruiz_passes passes on the maxima and an optional one on the sums of
+//              s_ij = fmul(fmul(|a_ij|, dr_i), dc_j) -- ONE expression, walked from both orientations, so CSR(A) and
+//              CSR(A^T) see the same bits; then tr = dr^2, tc = dc^2, eta from the sums of the final s_ij, w0 from two norms
+//   iteration  x+_j = clip(x_j - (tau tc_j)(c_j - s_j)),  y+_i = y_i + (sigma tr_i)(b_i - t_i):  preconditioned PDHG written in
+//              the unscaled variables -- no scaled matrix is stored; one more load and one more multiply per finished row
+//   restart    the weight w moves to sqrt(w dy / dx), clamped to [w0 / span, w0 span]; tau = eta / w, sigma = eta w
+// The checks evaluate the ORIGINAL LP, in pdhg.hip's expressions and order.
+//
+// WHERE THE VECTORS LIVE.  x, xbar, xs, y, ys (3 n + 2 m words) are gathered through idx in every sweep and live in LDS when
+// they fit min(max_lds_words, PDHG_SCALED_LDS_WORDS), as in pdhg.hip.  tc, xr, tr, yr (2 n + 2 m words) are read once per
+// finished row by the lane that finishes it -- the access pattern of c and b -- and ALWAYS live in the caller's scratch:
+// sharing the LDS image would take 5 n + 4 m words and move instances out of LDS to save one cached load per row.  During
+// the set-up the same words hold dc, C, dr, R.
+//
+// The sweep helpers below are copies of pdhg.hip's (anonymous namespace there): that file and its instruction streams stay
+// untouched, as simplex.hip's did when the guarded entry point was added.
+#include <cmath>
+#include <type_traits>
+
+#include "ordered_sum.h"
+
+namespace mllp {
+
+namespace {
+
+constexpr int PS_CODE_OPTIMAL = 0, PS_CODE_LIMIT = 6, PS_CODE_NOT_FINITE = 8;
+
+__device__ __forceinline__ unsigned abs_bits(float v) { return __float_as_uint(v) & 0x7fffffffu; }
+// the key of max(v, 0) that keeps a NaN
+__device__ __forceinline__ unsigned pos_bits(float v) { return (v > 0.0f || v != v) ? abs_bits(v) : 0u; }
+__device__ __forceinline__ float clip0(float t) { return t > 0.0f ? t : 0.0f; }
+// max of two non-negative floats (or NaN) by their patterns
+__device__ __forceinline__ float nn_max(float a, float b) {
+    const unsigned ka = abs_bits(a), kb = abs_bits(b);
+    return __uint_as_float(ka > kb ? ka : kb);
+}
+__device__ __forceinline__ bool finite_bits(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
+// the correctly rounded square root (__fsqrt_rn is the hardware's approximation, within 1 ulp: numpy's differs from it)
+__device__ __forceinline__ float sqrt_rn(float v) { return __builtin_sqrtf(v); }
+__device__ __forceinline__ bool finite_pos(float v) { return finite_bits(v) && v > 0.0f; }
+
+// the maxima of K integers over the workgroup, in every thread (two barriers; `s` [NW * K] is reusable afterwards)
+template <int NW, int K>
+__device__ __forceinline__ void block_max_u32(unsigned (&v)[K], unsigned* s) {
+#pragma unroll
+    for (int q = 0; q < K; ++q) {
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const unsigned u = (unsigned)__shfl_xor((int)v[q], o, 64);
+            v[q] = u > v[q] ? u : v[q];
+        }
+    }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int q = 0; q < K; ++q) s[(threadIdx.x >> 6) * K + q] = v[q];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < K; ++q) {
+        unsigned best = 0u;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) best = s[w * K + q] > best ? s[w * K + q] : best;
+        v[q] = best;
+    }
+    __syncthreads();
+}
+
+// How a sweep combines the lanes of a row: the ordered sum (pdhg.hip's only one) ...
+struct BySum {
+    template <int G, class T>
+    static __device__ __forceinline__ T group(T v) { return group_sum<G>(v); }
+    template <int NW, class T>
+    static __device__ __forceinline__ T block(T v, T* part) { return block_tree_sum<NW>(v, part); }
+};
+// ... or the max of non-negative floats by their patterns: exact in any order, keeps a NaN
+struct ByMax {
+    template <int G>
+    static __device__ __forceinline__ float group(float v) {
+        unsigned k = __float_as_uint(v);
+#pragma unroll
+        for (int o = 1; o < G; o <<= 1) {
+            const unsigned u = (unsigned)__shfl_xor((int)k, o, 64);
+            k = u > k ? u : k;
+        }
+        return __uint_as_float(k);
+    }
+    template <int NW>
+    static __device__ __forceinline__ float block(float v, float* part) {
+        v = group<64>(v);
+        if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+        __syncthreads();
+        float best = 0.0f;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) best = nn_max(best, part[w]);
+        __syncthreads();
+        return best;
+    }
+};
+
+// pdhg.hip's wg_sweep: one sweep of a workgroup over the n_rows rows of ITS instance in the three tiers of ordered_sum.h.
+// ptr: the row pointers of the instance's first row; [lo2, hi2): a range that holds every row of the block tier (uniform in
+// the workgroup: the block tier has barriers).  Op::By combines the lanes.  No barrier at the end
+template <int NT, class Op>
+__device__ __forceinline__ void wg_sweep(const int* __restrict__ ptr, int n_rows, int lo2, int hi2, const Op& op,
+                                         typename Op::Acc* part) {
+    using Acc = typename Op::Acc;
+    using By = typename Op::By;
+    const int tid = threadIdx.x, lane = tid & 63;
+    for (int r0 = 0; r0 < n_rows; r0 += NT / 16) {           // (r0 is uniform in the workgroup)
+        const int r = r0 + (tid >> 4);
+        const bool in = r < n_rows;
+        const int beg = in ? ptr[r] : 0, len = in ? ptr[r + 1] - beg : 0;
+        {   // group tier: every lane reaches the butterfly; a row of another tier runs it over no terms
+            const bool mine = in && row_tier(len) == 0;
+            const typename Op::Row rc = op.row(mine ? r : 0);
+            const Acc q = By::template group<16>(strided_terms<16>(op, rc, beg, mine ? len : 0, tid & 15));
+            if (mine && (tid & 15) == 0) op.finish(r, rc, q);
+        }
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {                        // wave tier: the wavefront's four rows in turn
+            const int b4 = __shfl(beg, 16 * g, 64), l4 = __shfl(len, 16 * g, 64);
+            if (row_tier(l4) != 1) continue;                 // (uniform in the wavefront)
+            const int r4 = r0 + (tid >> 6) * 4 + g;
+            const typename Op::Row rc = op.row(r4);
+            const Acc q = By::template group<64>(strided_terms<64>(op, rc, b4, l4, lane));
+            if (lane == 0) op.finish(r4, rc, q);
+        }
+    }
+    for (int r = lo2; r < hi2; ++r) {                        // block tier
+        const int beg = ptr[r], len = ptr[r + 1] - beg;
+        if (row_tier(len) != 2) continue;
+        const typename Op::Row rc = op.row(r);
+        const Acc q = By::template block<NT / 64>(strided_terms<NT>(op, rc, beg, len, tid), part);
+        if (tid == 0) op.finish(r, rc, q);
+    }
+}
+
+struct NoRow {};
+struct OwnFactor {
+    float d;
+};
+
+// a set-up walk of one orientation over s_e = fmul(fmul(|a_e|, dr_i), dc_j): a row's max (MAX) or its fadd chain.  `own`:
+// the factors of this orientation's rows, `other`: those the walk gathers; ROWS says which of the two is dr, so that both
+// orientations form the product in the same order.  The result goes to out[r] (unless null) and into the largest so far
+template <bool ROWS, bool MAX>
+struct ScaledAbs {
+    using Acc = float;
+    using Row = OwnFactor;
+    using By = std::conditional_t<MAX, ByMax, BySum>;
+    const int* __restrict__ idx;
+    const float* __restrict__ val;
+    int off;
+    const float *own, *other;
+    float* out;
+    unsigned* best;
+    __device__ __forceinline__ Row row(int r) const { return {own[r]}; }
+    __device__ __forceinline__ void term(const Row& rc, int e, float& q) const {
+        const float o = other[idx[e] - off], a = fabsf(val[e]);
+        const float s = ROWS ? __fmul_rn(__fmul_rn(a, rc.d), o) : __fmul_rn(__fmul_rn(a, o), rc.d);
+        q = MAX ? nn_max(q, s) : __fadd_rn(q, s);
+    }
+    __device__ __forceinline__ void finish(int r, const Row&, float q) const {
+        if (out) out[r] = q;
+        const unsigned k = abs_bits(q);
+        *best = k > *best ? k : *best;
+    }
+};
+
+// the column sweep of an iteration
+struct ColStep {
+    using Acc = float;
+    using Row = NoRow;
+    using By = BySum;
+    const int* __restrict__ idx;
+    const float* __restrict__ val;
+    const float* __restrict__ c;       // of the instance's first column
+    const float* tc;
+    int row0;
+    float tau;
+    bool sums;
+    float *x, *xb, *xs;
+    const float* y;
+    __device__ __forceinline__ Row row(int) const { return {}; }
+    __device__ __forceinline__ void term(const Row&, int e, float& q) const { q = __fmaf_rn(val[e], y[idx[e] - row0], q); }
+    __device__ __forceinline__ void finish(int j, const Row&, float s) const {
+        const float g = __fsub_rn(c[j], s), xo = x[j];
+        const float xn = clip0(__fsub_rn(xo, __fmul_rn(__fmul_rn(tau, tc[j]), g)));
+        x[j] = xn;
+        xb[j] = __fsub_rn(__fadd_rn(xn, xn), xo);
+        if (sums) xs[j] = __fadd_rn(xs[j], xn);
+    }
+};
+
+// the row sweep of an iteration
+struct RowStep {
+    using Acc = float;
+    using Row = NoRow;
+    using By = BySum;
+    const int* __restrict__ idx;
+    const float* __restrict__ val;
+    const float* __restrict__ b;       // of the instance's first row
+    const float* tr;
+    int col0;
+    float sigma;
+    bool sums;
+    float *y, *ys;
+    const float* xb;
+    __device__ __forceinline__ Row row(int) const { return {}; }
+    __device__ __forceinline__ void term(const Row&, int e, float& q) const { q = __fmaf_rn(val[e], xb[idx[e] - col0], q); }
+    __device__ __forceinline__ void finish(int i, const Row&, float t) const {
+        const float yn = __fadd_rn(y[i], __fmul_rn(__fmul_rn(sigma, tr[i]), __fsub_rn(b[i], t)));
+        y[i] = yn;
+        if (sums) ys[i] = __fadd_rn(ys[i], yn);
+    }
+};
+
+// a check's walk of one orientation (pdhg.hip's): the product with the average (a) and with the current iterate (b) of the
+// OTHER side's vector, then the residual against `rhs`: |.| for rows (primal), max(., 0) for columns (dual)
+template <bool ROWS>
+struct EvalSweep {
+    using Acc = Sum2;
+    using Row = NoRow;
+    using By = BySum;
+    const int* __restrict__ idx;
+    const float* __restrict__ val;
+    const float* __restrict__ rhs;
+    int off;
+    bool with_avg;
+    float cntf;
+    const float *v, *vs;               // the current vector and the sum of its iterates
+    unsigned *best_a, *best_b;
+    __device__ __forceinline__ Row row(int) const { return {}; }
+    __device__ __forceinline__ void term(const Row&, int e, Sum2& q) const {
+        const int i = idx[e] - off;
+        const float a = val[e], cur = v[i], avg = with_avg ? __fdiv_rn(vs[i], cntf) : cur;
+        q.a = __fmaf_rn(a, avg, q.a);
+        q.b = __fmaf_rn(a, cur, q.b);
+    }
+    __device__ __forceinline__ void finish(int r, const Row&, Sum2 q) const {
+        const float t = rhs[r], da = __fsub_rn(q.a, t), db = __fsub_rn(q.b, t);
+        const unsigned ka = ROWS ? abs_bits(da) : pos_bits(da), kb = ROWS ? abs_bits(db) : pos_bits(db);
+        *best_a = ka > *best_a ? ka : *best_a;
+        *best_b = kb > *best_b ? kb : *best_b;
+    }
+};
+
+struct ScaledArgs {
+    const int* __restrict__ ptr_m;
+    const int* __restrict__ ptr_n;
+    const int* __restrict__ a_ptr;      // CSR(A)
+    const int* __restrict__ a_idx;
+    const float* __restrict__ a_val;
+    const int* __restrict__ at_ptr;     // CSR(A^T)
+    const int* __restrict__ at_idx;
+    const float* __restrict__ at_val;
+    const float* __restrict__ c;
+    const float* __restrict__ b;
+    const float* x0;
+    const float* y0;
+    long long max_iters, check_every, lim;
+    float eps, step, beta, span;
+    int ruiz_passes, pock_chambolle, primal_weight;
+    float* x;
+    float* y;
+    float* dr;
+    float* dc;
+    int* status;
+    float* kkt;
+    float* scratch;
+};
+
+struct PdhgErr {
+    float p, d, g;      // primal, dual, gap
+    __device__ __forceinline__ float worst() const { return nn_max(nn_max(p, d), g); }
+};
+
+template <bool IN_LDS, int NT>
+__global__ __launch_bounds__(NT) void pdhg_scaled_kernel(const ScaledArgs A) {
+    constexpr int NW = NT / 64;
+    extern __shared__ float ps_lds[];
+    __shared__ Sum2 s_part2[NW];
+    __shared__ float s_part[NW];
+    __shared__ unsigned s_key[NW * 4];
+    __shared__ long long s_off[NW];
+    const int k = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int row0 = A.ptr_m[k], m = A.ptr_m[k + 1] - row0;
+    const int col0 = A.ptr_n[k], n = A.ptr_n[k + 1] - col0;
+    if ((pdhg_words(m, n) <= A.lim) != IN_LDS) return;      // the other launch's instance
+    const float inf = __builtin_huge_valf();
+    // this instance's piece of the scratch: behind those of the earlier instances (integer sum: exact).  Every instance
+    // takes its 2 n + 2 m side words there, and its five vectors too when they do not fit LDS
+    float* side;
+    {
+        long long off = 0;
+        for (int j = tid; j < k; j += NT) {
+            const long long mj = A.ptr_m[j + 1] - A.ptr_m[j], nj = A.ptr_n[j + 1] - A.ptr_n[j];
+            off += pdhg_scaled_side_words(mj, nj) + (pdhg_words(mj, nj) > A.lim ? pdhg_words(mj, nj) : 0);
+        }
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) off += __shfl_xor(off, o, 64);
+        if (lane == 0) s_off[wave] = off;
+        __syncthreads();
+        off = 0;
+#pragma unroll
+        for (int v = 0; v < NW; ++v) off += s_off[v];
+        side = A.scratch + off;
+    }
+    float* tc = side;               // [n] dc, then dc^2
+    float* xr = tc + n;             // [n] the set-up's C, then x at the last restart
+    float* tr = xr + n;             // [m] dr, then dr^2
+    float* yr = tr + m;             // [m] the set-up's R, then y at the last restart
+    float* base = IN_LDS ? ps_lds : yr + m;
+    float* x = base;                // [n] the iterate
+    float* xb = x + n;              // [n] 2 x+ - x
+    float* xs = xb + n;             // [n] the sum of the iterates since the last restart
+    float* y = xs + n;              // [m]
+    float* ys = y + m;              // [m]
+    const int* a_ptr = A.a_ptr + row0;
+    const int* at_ptr = A.at_ptr + col0;
+    const float* c = A.c + col0;
+    const float* b = A.b + row0;
+    const bool sums = A.check_every > 0;
+    const bool weigh = A.primal_weight != 0;
+
+    // ---- start: the clipped start, the norms of b and c, where the block tier's rows are ----
+    unsigned kn[2] = {0u, 0u};      // ||b||inf, ||c||inf
+    unsigned kr[4] = {0u, 0u, 0u, 0u};      // block tier: {~first, last + 1} of the columns, of the rows
+    for (int j = tid; j < n; j += NT) {
+        kn[1] = max(kn[1], abs_bits(c[j]));
+        x[j] = A.x0 ? clip0(A.x0[col0 + j]) : 0.0f;
+        if (sums) xs[j] = 0.0f;
+        tc[j] = 1.0f;
+        if (row_tier(at_ptr[j + 1] - at_ptr[j]) == 2) {
+            kr[0] = max(kr[0], (unsigned)(0x7fffffff - j));
+            kr[1] = max(kr[1], (unsigned)(j + 1));
+        }
+    }
+    for (int i = tid; i < m; i += NT) {
+        kn[0] = max(kn[0], abs_bits(b[i]));
+        y[i] = A.y0 ? A.y0[row0 + i] : 0.0f;
+        if (sums) ys[i] = 0.0f;
+        tr[i] = 1.0f;
+        if (row_tier(a_ptr[i + 1] - a_ptr[i]) == 2) {
+            kr[2] = max(kr[2], (unsigned)(0x7fffffff - i));
+            kr[3] = max(kr[3], (unsigned)(i + 1));
+        }
+    }
+    block_max_u32<NW, 4>(kr, s_key);
+    block_max_u32<NW, 2>(kn, s_key);        // (also: every x_j, y_i, dc_j and dr_i is written)
+    const int c_lo = kr[1] ? 0x7fffffff - (int)kr[0] : 0, c_hi = (int)kr[1];
+    const int r_lo = kr[3] ? 0x7fffffff - (int)kr[2] : 0, r_hi = (int)kr[3];
+    const float den_p = __fadd_rn(1.0f, __uint_as_float(kn[0])), den_d = __fadd_rn(1.0f, __uint_as_float(kn[1]));
+
+    // ---- the scaling: C and R from the SAME dr, dc, then both updated (tc holds dc, tr holds dr until they are squared) ----
+    unsigned ka[2] = {0u, 0u};      // the largest column result, the largest row result of the last walk
+    auto walk = [&](auto is_max, float* out_c, float* out_r) {
+        constexpr bool MAX = decltype(is_max)::value;
+        ka[0] = ka[1] = 0u;
+        wg_sweep<NT>(at_ptr, n, c_lo, c_hi, ScaledAbs<false, MAX>{A.at_idx, A.at_val, row0, tc, tr, out_c, &ka[0]}, s_part);
+        wg_sweep<NT>(a_ptr, m, r_lo, r_hi, ScaledAbs<true, MAX>{A.a_idx, A.a_val, col0, tr, tc, out_r, &ka[1]}, s_part);
+    };
+    const int passes = A.ruiz_passes + (A.pock_chambolle ? 1 : 0);
+    for (int p = 0; p < passes; ++p) {      // (uniform in the workgroup)
+        if (p < A.ruiz_passes) walk(std::true_type{}, xr, yr);
+        else walk(std::false_type{}, xr, yr);
+        __syncthreads();
+        for (int j = tid; j < n; j += NT) {
+            const float v = xr[j];
+            if (v > 0.0f) tc[j] = __fdiv_rn(tc[j], sqrt_rn(v));
+        }
+        for (int i = tid; i < m; i += NT) {
+            const float v = yr[i];
+            if (v > 0.0f) tr[i] = __fdiv_rn(tr[i], sqrt_rn(v));
+        }
+        __syncthreads();
+    }
+    float eta;
+    {   // ||S||1 (largest column sum), ||S||inf (largest row sum) of the final s_ij
+        walk(std::false_type{}, nullptr, nullptr);
+        block_max_u32<NW, 2>(ka, s_key);
+        const float prod = __fmul_rn(__uint_as_float(ka[0]), __uint_as_float(ka[1]));
+        eta = prod > 0.0f ? __fdiv_rn(A.step, __fsqrt_rn(prod)) : A.step;      // (pdhg.hip's own square root: the neutral settings' bits)
+    }
+    // ---- the weight's start, the factors' squares, the restart point (thread t owns words t, t + NT, ... of all of them) ----
+    float w0 = 1.0f;
+    {
+        Sum2 nn = {0.0f, 0.0f};     // |dc o c|^2, |dr o b|^2
+        for (int j = tid; j < n; j += NT) {
+            const float d = tc[j], v = __fmul_rn(d, c[j]);
+            nn.a = __fmaf_rn(v, v, nn.a);
+            if (A.dc) A.dc[col0 + j] = d;
+            tc[j] = __fmul_rn(d, d);
+            xr[j] = x[j];
+        }
+        for (int i = tid; i < m; i += NT) {
+            const float d = tr[i], v = __fmul_rn(d, b[i]);
+            nn.b = __fmaf_rn(v, v, nn.b);
+            if (A.dr) A.dr[row0 + i] = d;
+            tr[i] = __fmul_rn(d, d);
+            yr[i] = y[i];
+        }
+        nn = block_tree_sum<NW>(nn, s_part2);       // (its barriers: tc, tr are written before a sweep's lane reads them)
+        const float nc = sqrt_rn(nn.a), nb = sqrt_rn(nn.b);
+        if (weigh && finite_pos(nc) && finite_pos(nb)) w0 = __fdiv_rn(nc, nb);
+    }
+    const float w_lo = __fdiv_rn(w0, A.span), w_hi = __fmul_rn(w0, A.span);
+    float w = w0, tau = __fdiv_rn(eta, w), sigma = __fmul_rn(eta, w);
+
+    long long cnt = 0;
+    // both points of a check (with_avg) or the current iterate alone, in every thread (barriers inside)
+    auto evaluate = [&](bool with_avg, PdhgErr& avg, PdhgErr& cur) {
+        const float cntf = (float)cnt;
+        unsigned key[4] = {0u, 0u, 0u, 0u};     // primal avg, primal cur, dual avg, dual cur
+        wg_sweep<NT>(a_ptr, m, r_lo, r_hi, EvalSweep<true>{A.a_idx, A.a_val, b, col0, with_avg, cntf, x, xs, &key[0], &key[1]}, s_part2);
+        wg_sweep<NT>(at_ptr, n, c_lo, c_hi, EvalSweep<false>{A.at_idx, A.at_val, c, row0, with_avg, cntf, y, ys, &key[2], &key[3]}, s_part2);
+        Sum2 cx = {0.0f, 0.0f}, by = {0.0f, 0.0f};
+        for (int j = tid; j < n; j += NT) {
+            const float v = x[j], a = with_avg ? __fdiv_rn(xs[j], cntf) : v;
+            cx.a = __fmaf_rn(c[j], a, cx.a);
+            cx.b = __fmaf_rn(c[j], v, cx.b);
+        }
+        for (int i = tid; i < m; i += NT) {
+            const float v = y[i], a = with_avg ? __fdiv_rn(ys[i], cntf) : v;
+            by.a = __fmaf_rn(b[i], a, by.a);
+            by.b = __fmaf_rn(b[i], v, by.b);
+        }
+        cx = block_tree_sum<NW>(cx, s_part2);
+        by = block_tree_sum<NW>(by, s_part2);
+        block_max_u32<NW, 4>(key, s_key);
+        auto gap = [](float p, float d) {
+            return __fdiv_rn(fabsf(__fsub_rn(p, d)), __fadd_rn(__fadd_rn(1.0f, fabsf(p)), fabsf(d)));
+        };
+        avg = {__fdiv_rn(__uint_as_float(key[0]), den_p), __fdiv_rn(__uint_as_float(key[2]), den_d), gap(cx.a, by.a)};
+        cur = {__fdiv_rn(__uint_as_float(key[1]), den_p), __fdiv_rn(__uint_as_float(key[3]), den_d), gap(cx.b, by.b)};
+    };
+
+    // ---- the iterations: bounded by max_iters and nothing else ----
+    int code = -1, restarts = 0, avg_out = 0;
+    long long it = 0, since = 0;
+    float e_last = inf;
+    PdhgErr out = {0.0f, 0.0f, 0.0f};
+    while (it < A.max_iters) {
+        wg_sweep<NT>(at_ptr, n, c_lo, c_hi, ColStep{A.at_idx, A.at_val, c, tc, row0, tau, sums, x, xb, xs, y}, s_part);
+        __syncthreads();
+        wg_sweep<NT>(a_ptr, m, r_lo, r_hi, RowStep{A.a_idx, A.a_val, b, tr, col0, sigma, sums, y, ys, xb}, s_part);
+        __syncthreads();
+        ++it;
+        if (!sums) continue;
+        ++cnt;
+        if (++since < A.check_every) continue;
+        since = 0;
+        PdhgErr avg, cur;
+        evaluate(true, avg, cur);
+        const float ea = avg.worst(), ec = cur.worst();
+        const bool use_avg = ea < ec;
+        const float e = use_avg ? ea : ec;
+        if (!finite_bits(e)) {
+            code = PS_CODE_NOT_FINITE;
+            out = cur;
+            break;
+        }
+        const bool stop = e <= A.eps;
+        if (!stop && !(e <= __fmul_rn(A.beta, e_last) || 25 * cnt >= 9 * it)) continue;
+        // the candidate becomes the iterate: the output of code 0, the start of the next period otherwise
+        const float cntf = (float)cnt;
+        for (int j = tid; j < n; j += NT) {
+            if (use_avg) x[j] = __fdiv_rn(xs[j], cntf);
+            xs[j] = 0.0f;
+        }
+        for (int i = tid; i < m; i += NT) {
+            if (use_avg) y[i] = __fdiv_rn(ys[i], cntf);
+            ys[i] = 0.0f;
+        }
+        __syncthreads();
+        if (stop) {
+            code = PS_CODE_OPTIMAL;
+            avg_out = use_avg ? 1 : 0;
+            out = use_avg ? avg : cur;
+            break;
+        }
+        ++restarts;
+        e_last = e;
+        cnt = 0;
+        if (!weigh) continue;
+        // the weight: how far the restart moved in each space, in the metric of the scaled variables.  Every thread gets the
+        // tree's bits, so every thread holds the same w, tau and sigma
+        Sum2 dd = {0.0f, 0.0f};
+        for (int j = tid; j < n; j += NT) {
+            const float v = x[j], d = __fsub_rn(v, xr[j]);
+            dd.a = __fmaf_rn(d, __fdiv_rn(d, tc[j]), dd.a);
+            xr[j] = v;
+        }
+        for (int i = tid; i < m; i += NT) {
+            const float v = y[i], d = __fsub_rn(v, yr[i]);
+            dd.b = __fmaf_rn(d, __fdiv_rn(d, tr[i]), dd.b);
+            yr[i] = v;
+        }
+        dd = block_tree_sum<NW>(dd, s_part2);
+        const float dx = sqrt_rn(dd.a), dy = sqrt_rn(dd.b);
+        if (finite_pos(dx) && finite_pos(dy)) {
+            const float raw = sqrt_rn(__fmul_rn(w, __fdiv_rn(dy, dx)));
+            const float up = raw > w_lo ? raw : w_lo;
+            w = up < w_hi ? up : w_hi;
+            tau = __fdiv_rn(eta, w);
+            sigma = __fmul_rn(eta, w);
+        }
+    }
+    if (code < 0) {
+        code = PS_CODE_LIMIT;
+        PdhgErr unused;
+        evaluate(false, unused, out);
+    }
+    for (int j = tid; j < n; j += NT) A.x[col0 + j] = x[j];
+    for (int i = tid; i < m; i += NT) A.y[row0 + i] = y[i];
+    if (tid == 0) {
+        int* st = A.status + 4 * (size_t)k;
+        st[0] = code;
+        st[1] = (int)min(it, (long long)0x7fffffff);
+        st[2] = restarts;
+        st[3] = avg_out;
+        if (A.kkt) {
+            float* q = A.kkt + 6 * (size_t)k;
+            q[0] = out.p; q[1] = out.d; q[2] = out.g; q[3] = eta; q[4] = w0; q[5] = w;
+        }
+    }
+}
+
+// what a call needs, from the host copy of the instance offsets
+struct ScaledPlan {
+    int64_t lim = 0;            // the largest 3 n + 2 m that runs with its five vectors in LDS
+    int64_t words = 0;          // scratch, in 4-byte words
+    int64_t lds_words = 0;      // the most LDS words an instance takes
+    bool any_lds = false, any_glb = false;
+};
+ScaledPlan scaled_plan(const mllp_graph_t* g, int64_t max_lds_words) {
+    ScaledPlan p;
+    p.lim = std::min<int64_t>(max_lds_words, PDHG_SCALED_LDS_WORDS);
+    for (int64_t k = 0; k < g->n_inst && k + 1 < (int64_t)g->h_inst_ptr_m.size() && k + 1 < (int64_t)g->h_inst_ptr_n.size(); ++k) {
+        const int64_t m = g->h_inst_ptr_m[k + 1] - g->h_inst_ptr_m[k], n = g->h_inst_ptr_n[k + 1] - g->h_inst_ptr_n[k];
+        const int64_t w = pdhg_words(m, n);
+        p.words += pdhg_scaled_side_words(m, n);
+        if (w <= p.lim) {
+            p.any_lds = true;
+            p.lds_words = std::max(p.lds_words, w);
+        } else {
+            p.any_glb = true;
+            p.words += w;
+        }
+    }
+    return p;
+}
+
+bool overlaps(const void* a, int64_t a_bytes, const void* b, int64_t b_bytes) {
+    if (!a || !b || a_bytes <= 0 || b_bytes <= 0) return false;
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + (uintptr_t)b_bytes && b0 < a0 + (uintptr_t)a_bytes;
+}
+
+}  // namespace
+
+}  // namespace mllp
+
+using namespace mllp;
+
+extern "C" int mllp_lp_pdhg_scaled_limits(int64_t* limits) {
+    REQUIRE(limits, "null argument");
+    limits[0] = PDHG_SCALED_LDS_WORDS;
+    limits[1] = PDHG_SCALED_THREADS;
+    limits[2] = PDHG_SCALED_MAX_RUIZ;
+    return MLLP_OK;
+}
+
+extern "C" int mllp_lp_pdhg_scaled_scratch_bytes(const mllp_graph_t* g, int64_t max_lds_words, int64_t* bytes) {
+    REQUIRE(g && bytes, "null argument");
+    REQUIRE(max_lds_words >= 0, "max_lds_words must not be negative");
+    *bytes = scaled_plan(g, max_lds_words).words * (int64_t)sizeof(float);
+    return MLLP_OK;
+}
+
+extern "C" int mllp_lp_pdhg_scaled(const mllp_graph_t* g, const float* d_x1, const float* d_x2, const float* d_x0, const float* d_y0,
+                                   int64_t max_iters, int64_t check_every, float eps, float step, float beta, int64_t ruiz_passes,
+                                   int32_t pock_chambolle, int32_t primal_weight, float weight_span, int64_t max_lds_words,
+                                   float* d_x, float* d_y, float* d_dr, float* d_dc, int32_t* d_status, float* d_kkt,
+                                   void* d_scratch, void* stream) {
+    REQUIRE(g && d_x1 && d_x2 && d_x && d_y && d_status, "null argument (g, d_x1, d_x2, d_x, d_y and d_status are required)");
+    REQUIRE(max_iters >= 0, "max_iters must not be negative");
+    REQUIRE(check_every >= 0, "check_every must not be negative");
+    REQUIRE(max_lds_words >= 0, "max_lds_words must not be negative");
+    REQUIRE(std::isfinite(eps) && eps >= 0.0f, "eps must be finite and not negative");
+    REQUIRE(std::isfinite(step) && step > 0.0f && step <= 1.0f, "step must be in (0, 1]");
+    REQUIRE(std::isfinite(beta) && beta > 0.0f && beta < 1.0f, "beta must be in (0, 1)");
+    REQUIRE(ruiz_passes >= 0 && ruiz_passes <= PDHG_SCALED_MAX_RUIZ, "ruiz_passes must be in 0 .. 64");
+    REQUIRE(std::isfinite(weight_span) && weight_span >= 1.0f, "weight_span must be finite and at least 1");
+    const ScaledPlan plan = scaled_plan(g, max_lds_words);
+    REQUIRE(plan.words == 0 || d_scratch, "null d_scratch (mllp_lp_pdhg_scaled_scratch_bytes is not 0)");
+    const struct {
+        const void* p;
+        int64_t bytes;
+    } outs[] = {{d_x, g->N * 4}, {d_y, g->M * 4}, {d_dr, g->M * 4}, {d_dc, g->N * 4}, {d_status, g->n_inst * 16}, {d_kkt, g->n_inst * 24}};
+    for (const auto& o : outs)
+        REQUIRE(!overlaps(d_x0, g->N * 4, o.p, o.bytes) && !overlaps(d_y0, g->M * 4, o.p, o.bytes), "d_x0 or d_y0 overlaps an output");
+    if (g->n_inst <= 0) return MLLP_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const ScaledArgs args = {g->inst_ptr_m, g->inst_ptr_n, g->A.ptr, g->A.idx, g->A.val, g->At.ptr, g->At.idx, g->At.val, d_x1, d_x2,
+                             d_x0, d_y0, (long long)max_iters, (long long)check_every, (long long)plan.lim, eps, step, beta, weight_span,
+                             (int)ruiz_passes, pock_chambolle != 0, primal_weight != 0,
+                             d_x, d_y, d_dr, d_dc, d_status, d_kkt, static_cast<float*>(d_scratch)};
+    int rc;
+    if (plan.any_lds) {
+        // once per process: the kernel may take more dynamic LDS than the default limit (no stream operation)
+        static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(pdhg_scaled_kernel<true, PDHG_SCALED_THREADS>),
+                                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)(PDHG_SCALED_LDS_WORDS * sizeof(float)));
+        if (attr != hipSuccess) return hip_fail(attr, "lp_pdhg_scaled: hipFuncSetAttribute");
+        const size_t lds = (size_t)std::max<int64_t>(plan.lds_words, 1) * sizeof(float);
+        hipLaunchKernelGGL((pdhg_scaled_kernel<true, PDHG_SCALED_THREADS>), dim3((unsigned)g->n_inst), dim3(PDHG_SCALED_THREADS), lds, s, args);
+        if ((rc = check_launch("lp_pdhg_scaled (LDS)"))) return rc;
+    }
+    if (plan.any_glb) {
+        hipLaunchKernelGGL((pdhg_scaled_kernel<false, PDHG_SCALED_THREADS>), dim3((unsigned)g->n_inst), dim3(PDHG_SCALED_THREADS), 0, s, args);
+        if ((rc = check_launch("lp_pdhg_scaled (scratch)"))) return rc;
+    }
+    return MLLP_OK;
+}

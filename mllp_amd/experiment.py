@@ -226,14 +226,26 @@ def pdhg_counts(batch, logits, report):
     (LPBatch.pdhg, at most K iterations, relative KKT error E) -- the instances that converged, the iterations all of them
     took, and the instances whose iterate points at a vertex that is certified optimal (LPBatch.pdhg_basis + solved, under
     the block's tolerances and max_m).  With `warm` the start is the repaired prediction's basic solution where it is
-    usable and cold (zeros, which is what repair_basis leaves) otherwise.  PDHG itself has no row limit.  No sync."""
+    usable and cold (zeros, which is what repair_basis leaves) otherwise.  PDHG itself has no row limit.  `scaled: true`
+    selects the preconditioned call (LPBatch.pdhg_scaled) with its defaults; a mapping {ruiz, pock_chambolle, weight, span}
+    sets its options.  Without the key (or `scaled: false`) the call is LPBatch.pdhg.  No sync."""
     opt = report["pdhg"]
     for key in ("iters", "eps"):
         if key not in opt:
             raise ValueError(f"report_solved: pdhg: {key} is required")
     max_m = report.get("max_m")
     start = batch.repair_basis(logits, max_m=max_m, want=("basis", "x", "y")) if opt.get("warm", True) else None
-    res = batch.pdhg(int(opt["iters"]), eps=float(opt["eps"]), check_every=int(opt.get("check", 64)), start=start)
+    scaled = opt.get("scaled")
+    if scaled is None or scaled is False:
+        res = batch.pdhg(int(opt["iters"]), eps=float(opt["eps"]), check_every=int(opt.get("check", 64)), start=start)
+    else:
+        more = {} if scaled is True else dict(scaled)
+        unknown = set(more) - {"ruiz", "pock_chambolle", "weight", "span"}
+        if unknown:
+            raise ValueError(f"report_solved: pdhg: scaled: unknown keys {sorted(unknown)}")
+        res = batch.pdhg_scaled(int(opt["iters"]), eps=float(opt["eps"]), check_every=int(opt.get("check", 64)), start=start,
+                                ruiz=int(more.get("ruiz", 10)), pock_chambolle=bool(more.get("pock_chambolle", True)),
+                                primal_weight=bool(more.get("weight", True)), weight_span=float(more.get("span", 16.0)))
     got = batch.solved(batch.pdhg_basis(res, max_m=max_m), report["feas_tol"], report["opt_tol"])
     return torch.stack([(res.status[:, 0] == 0).sum(), res.status[:, 1].sum(), got["optimal"].sum()]).float()
 

@@ -1238,6 +1238,49 @@ class LPBatch:
                                            _lib.ptr(y), _lib.ptr(status), _lib.ptr(kkt), _lib.ptr(kept[1]), _lib.current_stream()))
         return LPPdhg(x[:self.N], y[:self.M], status[:self.n_inst * 4].view(self.n_inst, 4), kkt[:self.n_inst * 4].view(self.n_inst, 4))
 
+    # ---- preconditioned PDHG on every instance (mllp_lp_pdhg_scaled; csrc/pdhg_scaled.hip) ------------------------------
+    def pdhg_scaled(self, max_iters, eps=2.0 ** -10, check_every=64, step=0.9, beta=0.5, ruiz=10, pock_chambolle=True,
+                    primal_weight=True, weight_span=16.0, x0=None, y0=None, start=None, max_lds_words=None):
+        """`pdhg` with diagonal preconditioning and a primal weight, both computed on the device by the call itself
+        (mllp_lp_pdhg_scaled; the rule is stated in include/mllp_hip.h).  `ruiz`: passes of Ruiz equilibration (0 .. 64);
+        `pock_chambolle`: one more pass on the row and column sums; `primal_weight`: start the weight at |dc c| / |dr b| and
+        move it at every restart, inside [w0 / weight_span, w0 * weight_span].  The other arguments, the checks and the codes
+        are `pdhg`'s (the errors are those of the original LP); with ruiz=0, pock_chambolle=False, primal_weight=False the
+        result has `pdhg`'s bits.  Returns an `LPPdhgScaled`.  The scratch is asked for once per max_lds_words and kept on
+        the batch.  No adaptive step, no infeasibility detection.  No sync."""
+        if start is not None:
+            if x0 is not None or y0 is not None:
+                raise ValueError("pdhg_scaled: give start or x0 / y0, not both")
+            if not isinstance(start, BasisRepair) or start.x is None or start.y is None:
+                raise ValueError("pdhg_scaled: start must be a BasisRepair with x and y")
+            x0, y0 = start.x, start.y
+        for t, n, what in ((x0, self.N, "x0"), (y0, self.M, "y0")):
+            if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n):
+                raise ValueError(f"pdhg_scaled: {what} must be a contiguous cuda float32 tensor of {n} elements")
+        max_iters, check_every, ruiz = int(max_iters), int(check_every), int(ruiz)
+        if max_iters < 0 or check_every < 0:
+            raise ValueError("pdhg_scaled: max_iters and check_every must not be negative")
+        dev = self.x1.device
+        max_lds_words = pdhg_scaled_limits()[0] if max_lds_words is None else int(max_lds_words)
+        kept = getattr(self, "_pdhg_scaled_scratch", None)
+        if kept is None or kept[0] != max_lds_words:
+            n = c_int64()
+            _lib.check(_lib.lib().mllp_lp_pdhg_scaled_scratch_bytes(self._h, max_lds_words, ctypes.byref(n)))
+            kept = self._pdhg_scaled_scratch = (max_lds_words, torch.empty(n.value // 4, device=dev, dtype=torch.float32) if n.value else None)
+        # (at least one element each: an empty torch tensor has a null pointer, which the library refuses)
+        new = lambda n, dt: torch.empty(max(n, 1), dtype=dt, device=dev)      # noqa: E731
+        x, y, dr, dc = new(self.N, torch.float32), new(self.M, torch.float32), new(self.M, torch.float32), new(self.N, torch.float32)
+        status, kkt = new(self.n_inst * 4, torch.int32), new(self.n_inst * 6, torch.float32)
+        pad = lambda t: t if t.numel() else torch.zeros(1, dtype=torch.float32, device=dev)   # noqa: E731
+        opt = lambda t: None if t is None or not t.numel() else t                             # noqa: E731
+        _lib.check(_lib.lib().mllp_lp_pdhg_scaled(self._h, _lib.ptr(pad(self.x1)), _lib.ptr(pad(self.x2)), _lib.ptr(opt(x0)), _lib.ptr(opt(y0)),
+                                                  max_iters, check_every, float(eps), float(step), float(beta), ruiz, int(bool(pock_chambolle)),
+                                                  int(bool(primal_weight)), float(weight_span), max_lds_words, _lib.ptr(x), _lib.ptr(y),
+                                                  _lib.ptr(dr), _lib.ptr(dc), _lib.ptr(status), _lib.ptr(kkt), _lib.ptr(kept[1]),
+                                                  _lib.current_stream()))
+        return LPPdhgScaled(x[:self.N], y[:self.M], status[:self.n_inst * 4].view(self.n_inst, 4), kkt[:self.n_inst * 6].view(self.n_inst, 6),
+                            dr[:self.M], dc[:self.N])
+
     def pdhg_basis(self, res, tol=2.0 ** -12, max_m=None):
         """The vertex a PDHG iterate points at: `repair_basis` on the ranking of `res.x` (its m largest entries first), so the
         `BasisRepair` of the best-ranked nonsingular basis and its basic solution, which `solved` certifies -- for the
@@ -1313,6 +1356,24 @@ class LPPdhg:
 
     def __init__(self, x, y, status, kkt):
         self.x, self.y, self.status, self.kkt = x, y, status, kkt
+
+
+class LPPdhgScaled(LPPdhg):
+    """What `LPBatch.pdhg_scaled` returns: an `LPPdhg` (so `pdhg_basis` and everything behind it take it) whose `.kkt` is
+    float32 [n_inst, 6] = primal residual, dual residual, gap, the step eta, the starting weight w0 and the final weight,
+    with `.dr` [M] and `.dc` [N], the row and column scaling factors the call computed."""
+
+    def __init__(self, x, y, status, kkt, dr, dc):
+        super().__init__(x, y, status, kkt)
+        self.dr, self.dc = dr, dc
+
+
+def pdhg_scaled_limits():
+    """(LDS words the preconditioned PDHG kernel can give to an instance's vectors, threads per workgroup, the most Ruiz
+    passes) (mllp_lp_pdhg_scaled_limits; no GPU)"""
+    lim = (c_int64 * 3)()
+    _lib.check(_lib.lib().mllp_lp_pdhg_scaled_limits(lim))
+    return int(lim[0]), int(lim[1]), int(lim[2])
 
 
 def pdhg_limits():

@@ -1,6 +1,11 @@
-"""Cost and reach of restarted PDHG on the resident batch (mllp_lp_pdhg).  Prints one JSON line (profiles/pdhg_bench.json).
+"""Cost and reach of restarted PDHG on the resident batch (mllp_lp_pdhg; with --scaled: mllp_lp_pdhg_scaled).  Prints one
+JSON line (profiles/pdhg_bench.json; profiles/pdhg_scaled_bench.json holds the --scaled runs).
 
     python tools/bench_pdhg.py [--calls 2] [--windows 5] [--plain-iters 256] [--netlib-iters 60000] [--synthetic 4]
+                               [--scaled [--ruiz 10] [--no-pock-chambolle] [--no-weight] [--span 16]] [--only PART,...]
+
+  --scaled        the same batches and the same Netlib table through LPBatch.pdhg_scaled with the options given; the output
+                  gains "call" and "options".  --only per_iteration,netlib,cold_warm,oracle runs the named parts alone.
 
   per_iteration   plain PDHG (check_every = 0) for --plain-iters iterations on the Netlib batch, on planted batches (256 and
                   1024 x (50 x 120), all in LDS; 64 x (500 x 1200); the same 64 with max_lds_words = 0, all in scratch) and on
@@ -29,8 +34,15 @@ import torch  # noqa: E402
 from bench_basis_repair import device_window  # noqa: E402
 
 
+SOLVE = {"scaled": False, "options": {}}       # set by main: which call `solve` makes
+
+
+def solve(b, iters, **kw):
+    return b.pdhg_scaled(iters, **SOLVE["options"], **kw) if SOLVE["scaled"] else b.pdhg(iters, **kw)
+
+
 def timed(b, iters, calls, windows, max_lds_words=None, **kw):
-    run = lambda: b.pdhg(iters, max_lds_words=max_lds_words, **kw)      # noqa: E731
+    run = lambda: solve(b, iters, max_lds_words=max_lds_words, **kw)      # noqa: E731
     run()
     run()
     torch.cuda.synchronize()
@@ -73,30 +85,43 @@ def main():
     ap.add_argument("--plain-iters", type=int, default=256)
     ap.add_argument("--netlib-iters", type=int, default=60000)
     ap.add_argument("--synthetic", type=int, default=4)
+    ap.add_argument("--scaled", action="store_true")
+    ap.add_argument("--ruiz", type=int, default=10)
+    ap.add_argument("--no-pock-chambolle", action="store_true")
+    ap.add_argument("--no-weight", action="store_true")
+    ap.add_argument("--span", type=float, default=16.0)
+    ap.add_argument("--only", default="per_iteration,netlib,cold_warm,oracle")
     args = ap.parse_args()
+    parts = set(args.only.split(","))
+    if args.scaled:
+        SOLVE.update(scaled=True, options={"ruiz": args.ruiz, "pock_chambolle": not args.no_pock_chambolle,
+                                           "primal_weight": not args.no_weight, "weight_span": args.span})
     assert torch.cuda.is_available(), "bench_pdhg needs the GPU: there is no CPU path"
     from mllp_amd.data import load_packed
     from mllp_amd.graph import LPBatch, pdhg_limits, synthetic_batch
     from mllp_amd.planted import planted_batch
-    out = {"limits": {"lds_words": pdhg_limits()[0], "threads": pdhg_limits()[1]}, "oracle_deviation_units": oracle_deviation()}
+    out = {"call": "mllp_lp_pdhg_scaled" if args.scaled else "mllp_lp_pdhg", "options": SOLVE["options"],
+           "limits": {"lds_words": pdhg_limits()[0], "threads": pdhg_limits()[1]}}
+    if "oracle" in parts:
+        out["oracle_deviation_units"] = oracle_deviation()
     net = LPBatch.from_instances(load_packed())
     per_it = []
     small, _, _ = planted_batch(256, 50, 120, 6.0, 1)
     many, _, _ = planted_batch(1024, 50, 120, 6.0, 1)
     mid, _, _ = planted_batch(64, 500, 1200, 6.0, 2)
-    for name, b, lds in ((f"Netlib {net.n_inst} instances", net, None), ("planted 256 x (50 x 120)", small, None),
+    for name, b, lds in () if "per_iteration" not in parts else ((f"Netlib {net.n_inst} instances", net, None), ("planted 256 x (50 x 120)", small, None),
                          ("planted 1024 x (50 x 120)", many, None), ("planted 64 x (500 x 1200)", mid, None),
                          ("planted 64 x (500 x 1200), vectors in scratch", mid, 0)):
         per_it.append({"batch": name, **shape_of(b), **timed(b, args.plain_iters, args.calls, args.windows, lds, check_every=0)})
-    if args.synthetic > 0:
+    if args.synthetic > 0 and "per_iteration" in parts:
         syn = synthetic_batch(n_inst=args.synthetic)
         per_it.append({"batch": f"synthetic {args.synthetic} x (10000 x 20000)", **shape_of(syn), **timed(syn, 16, 1, 3, None, check_every=0)})
         del syn
     out["per_iteration"] = per_it
     # Netlib: where the baseline gets within --netlib-iters
     table = {}
-    for eps in (1e-3, 1e-4):
-        res = net.pdhg(args.netlib_iters, eps=eps)
+    for eps in (1e-3, 1e-4) if "netlib" in parts else ():
+        res = solve(net, args.netlib_iters, eps=eps)
         torch.cuda.synchronize()
         st, kkt = res.status.cpu().numpy(), res.kkt.cpu().numpy()
         for k, name in enumerate(net.names):
@@ -106,10 +131,13 @@ def main():
         out.setdefault("netlib_converged", {})[f"eps_{eps:g}"] = int((st[:, 0] == 0).sum())
     out["netlib_max_iters"] = args.netlib_iters
     out["netlib"] = table
+    if "cold_warm" not in parts:
+        print(json.dumps(out))
+        return
     # cold against warm on a planted batch
-    cold = small.pdhg(8192)
-    warm = small.pdhg(8192, start=small.solve_basis(small.labels))
-    far = small.pdhg(8192, start=small.repair_basis(torch.randn(small.N, device="cuda", generator=torch.Generator(device="cuda").manual_seed(5))))
+    cold = solve(small, 8192)
+    warm = solve(small, 8192, start=small.solve_basis(small.labels))
+    far = solve(small, 8192, start=small.repair_basis(torch.randn(small.N, device="cuda", generator=torch.Generator(device="cuda").manual_seed(5))))
     torch.cuda.synchronize()
     rows = {}
     for name, r in (("cold", cold), ("warm_from_repair_basis_of_the_labels", warm), ("warm_from_repair_basis_of_a_random_ranking", far)):
