@@ -449,7 +449,7 @@ int mllp_lp_pdhg(const mllp_graph_t* g, const float* d_x1 /*c [N]*/, const float
                  float* d_y /*[M]*/, int32_t* d_status /*[n_inst,4]*/, float* d_kkt /*[n_inst,4] or NULL*/,
                  void* d_scratch, void* stream);
 
-/* Solve every instance by PRECONDITIONED restarted PDHG (mllp_amd/csrc/pdhg_scaled.hip): mllp_lp_pdhg's
+/* Solve every instance by PRECONDITIONED restarted PDHG (mllp_amd/csrc/pdhg.hip): mllp_lp_pdhg's
  * iteration with diagonal scaling (Ruiz passes, an optional Pock-Chambolle pass) and a clamped primal weight, all computed
  * by the call itself.  Added after ABI 6 without a bump.  mllp_lp_pdhg is unchanged.
  * THE RULE.  The LP, the number format and clip are mllp_lp_pdhg's: fp32; fadd, fsub, fmul, fma, fdiv, fsqrt only, each

@@ -31,6 +31,9 @@ int hip_fail(hipError_t e, const char* what);
 // argument check of an extern "C" entry point: the message names the function
 #define REQUIRE(cond, msg) \
     if (!(cond)) return ::mllp::fail(MLLP_EINVAL, std::string(__func__) + ": " + (msg))
+// REQUIRE on behalf of the entry point `fn`, in a function that several entry points share: the message names that function
+#define REQUIRE_FOR(fn, cond, msg) \
+    if (!(cond)) return ::mllp::fail(MLLP_EINVAL, std::string(fn) + ": " + (msg))
 
 // after a kernel launch: the launch error, if any, under the kernel's name
 inline int check_launch(const char* what) {
@@ -442,24 +445,22 @@ __host__ __device__ constexpr int64_t simplex_words(int64_t m, int64_t n) {     
     return (m > SIMPLEX_LDS_MAX_M ? m * m : 0) + n;
 }
 
-// ---- restarted PDHG (pdhg.hip): one workgroup per instance, five vectors of 3 n + 2 m words in all --------------------------
-// The vectors live in LDS up to PDHG_LDS_WORDS words: 144 KB, beside under 1 KB of static LDS, within the 160 KB of a
-// workgroup (92 of the 97 Netlib instances fit); longer instances keep them in the caller's scratch, the same bits either
-// way.  1024 threads: a workgroup is alone on its CU at that LDS size, and the sweeps read A from L2 / HBM in every
+// ---- restarted PDHG, plain and preconditioned (pdhg.hip): one workgroup per instance, five vectors of 3 n + 2 m words ------
+// x, xbar, xs, y, ys (pdhg_words) live in LDS up to PDHG_LDS_WORDS words: 144 KB, beside under 1 KB of static LDS, within the
+// 160 KB of a workgroup (92 of the 97 Netlib instances fit); longer instances keep them in the caller's scratch, the same bits
+// either way.  1024 threads: a workgroup is alone on its CU at that LDS size, and the sweeps read A from L2 / HBM in every
 // iteration, so the sixteen wavefronts are what hides that latency.  mllp_lp_pdhg_limits reports both.
+// The preconditioned entry point runs the same kernel source, so its threshold and threads ARE these, and the same 92
+// instances fit.  Its four more vectors tc, xr, tr, yr (pdhg_scaled_side_words) are gathered by no sweep: they are read once per
+// finished row, as c and b are, and live in the caller's scratch for EVERY instance: in LDS they would raise an instance's
+// image to 5 n + 4 m words and move 8 more Netlib instances out of LDS (84 fit) to save one cached, coalesced load per row.
+// mllp_lp_pdhg_scaled_limits reports its three constants.
 constexpr int64_t PDHG_LDS_WORDS = 36864;
 constexpr int PDHG_THREADS = 1024;
-__host__ __device__ constexpr int64_t pdhg_words(int64_t m, int64_t n) { return 3 * n + 2 * m; }   // x, 2x+ - x, xs, y, ys
-
-// ---- preconditioned PDHG (pdhg_scaled.hip): the same five vectors, and four more that no sweep gathers --------------------
-// x, xbar, xs, y, ys (pdhg_words) live in LDS up to PDHG_SCALED_LDS_WORDS, the threshold of pdhg.hip, so the same 92 of the
-// 97 Netlib instances fit.  tc, xr, tr, yr (pdhg_scaled_side_words) are read once per finished row, as c and b are, and live
-// in the caller's scratch for EVERY instance: in LDS they would raise an instance's image to 5 n + 4 m words and move 8 more
-// Netlib instances out of LDS (84 fit) to save one cached, coalesced load per row.  mllp_lp_pdhg_scaled_limits reports the
-// three constants.
-constexpr int64_t PDHG_SCALED_LDS_WORDS = 36864;
-constexpr int PDHG_SCALED_THREADS = 1024;
+constexpr int64_t PDHG_SCALED_LDS_WORDS = PDHG_LDS_WORDS;
+constexpr int PDHG_SCALED_THREADS = PDHG_THREADS;
 constexpr int PDHG_SCALED_MAX_RUIZ = 64;
+__host__ __device__ constexpr int64_t pdhg_words(int64_t m, int64_t n) { return 3 * n + 2 * m; }   // x, 2x+ - x, xs, y, ys
 __host__ __device__ constexpr int64_t pdhg_scaled_side_words(int64_t m, int64_t n) { return 2 * n + 2 * m; }   // tc, xr, tr, yr
 
 // ---- soft top-m loss head (topm_loss.hip): one workgroup of TOPM_LOSS_T threads per instance, many passes per evaluation ---

@@ -1,6 +1,8 @@
-// pdhg.hip -- restarted PDHG on every instance of the resident batch (mllp_lp_pdhg; the rule is stated in
-// include/mllp_hip.h, the design in DESIGN.md 4.20).  A first-order solve of  min c'x, A_k x = b, x >= 0  that needs two
-// sparse matrix-vector products per iteration and no factorization: memory O(n + m) per instance, no row limit.
+// pdhg.hip -- restarted PDHG on every instance of the resident batch: mllp_lp_pdhg and its diagonally
+// preconditioned form with a clamped primal weight, mllp_lp_pdhg_scaled.  The rules are stated in
+// include/mllp_hip.h.  ONE kernel source, instantiated on the entry point's argument struct (S = Args::scaled), and one host
+// path.  A first-order solve of  min c'x, A_k x = b, x >= 0  that needs two sparse matrix-vector products per
+// iteration and no factorization: memory O(n + m) per instance, no row limit.
 //
 // One workgroup per instance, persistent over the iterations (the structure of basis.hip and simplex.hip, for the same
 // reason: no cross-workgroup synchronisation, no atomics, the same bits alone and inside any batch).  Per iteration
@@ -18,9 +20,29 @@
 // holds the same bits of both errors, so stop / restart / which candidate are taken alike by all wavefronts: a decision
 // that differed between two of them would leave a barrier unmatched.
 //
-// IN_LDS: the five vectors x, xbar, xs, y, ys (3 n + 2 m words) live in LDS when they fit min(max_lds_words,
-// PDHG_LDS_WORDS), in the caller's scratch otherwise -- the same code instantiated twice, the same bits either way.
+// What S adds; all of it is compiled out of mllp_lp_pdhg's instantiations:
+//   set-up     dr [m], dc [n] by ruiz_passes passes on the maxima and an optional one on the sums of
+//              s_ij = fmul(fmul(|a_ij|, dr_i), dc_j) -- ONE expression, walked from both orientations, so CSR(A) and
+//              CSR(A^T) see the same bits; then tr = dr^2, tc = dc^2, eta from the sums of the final s_ij, w0 from two norms
+//   iteration  x+_j = clip(x_j - (tau tc_j)(c_j - s_j)),  y+_i = y_i + (sigma tr_i)(b_i - t_i):  preconditioned PDHG written in
+//              the unscaled variables -- no scaled matrix is stored; one more load and one more multiply per finished row
+//   restart    the weight w moves to sqrt(w dy / dx), clamped to [w0 / span, w0 span]; tau = eta / w, sigma = eta w
+// The checks evaluate the ORIGINAL LP either way, in the same expressions and order.
+//
+// WHERE THE VECTORS LIVE.  x, xbar, xs, y, ys (3 n + 2 m words) are gathered through idx in every sweep and live in LDS
+// (IN_LDS) when they fit min(max_lds_words, PDHG_LDS_WORDS), in the caller's scratch otherwise -- the same code instantiated
+// twice, the same bits either way.  S's tc, xr, tr, yr (2 n + 2 m words) are read once per finished row by the lane that
+// finishes it -- the access pattern of c and b -- and ALWAYS live in the caller's scratch: sharing the LDS image would take
+// 5 n + 4 m words and move instances out of LDS to save one cached load per row.  During the set-up the same words hold dc,
+// C, dr, R.
+//
+// All four instantiations are instruction for instruction what the two files they came from compiled to.
+// That holds the kernel's text to two habits: a value that S changes is DEFINED once, through a ternary on S or an accessor of
+// Args, never set and then overwritten under `if constexpr`; and one deliberate duplicate stays, AbsSum beside ScaledAbs (a
+// ScaledAbs with unit factors folded at compile time moves all four streams).
 #include <cmath>
+#include <string>
+#include <type_traits>
 
 #include "ordered_sum.h"
 
@@ -40,6 +62,9 @@ __device__ __forceinline__ float nn_max(float a, float b) {
     return __uint_as_float(ka > kb ? ka : kb);
 }
 __device__ __forceinline__ bool finite_bits(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
+// the correctly rounded square root (__fsqrt_rn is the hardware's approximation, within 1 ulp: numpy's differs from it)
+__device__ __forceinline__ float sqrt_rn(float v) { return __builtin_sqrtf(v); }
+__device__ __forceinline__ bool finite_pos(float v) { return finite_bits(v) && v > 0.0f; }
 
 // the maxima of K integers over the workgroup, in every thread (two barriers; `s` [NW * K] is reusable afterwards)
 template <int NW, int K>
@@ -67,13 +92,46 @@ __device__ __forceinline__ void block_max_u32(unsigned (&v)[K], unsigned* s) {
     __syncthreads();
 }
 
+// How a sweep combines the lanes of a row: the ordered sum (every sweep of an iteration and of a check) ...
+struct BySum {
+    template <int G, class T>
+    static __device__ __forceinline__ T group(T v) { return group_sum<G>(v); }
+    template <int NW, class T>
+    static __device__ __forceinline__ T block(T v, T* part) { return block_tree_sum<NW>(v, part); }
+};
+// ... or the max of non-negative floats by their patterns: exact in any order, keeps a NaN
+struct ByMax {
+    template <int G>
+    static __device__ __forceinline__ float group(float v) {
+        unsigned k = __float_as_uint(v);
+#pragma unroll
+        for (int o = 1; o < G; o <<= 1) {
+            const unsigned u = (unsigned)__shfl_xor((int)k, o, 64);
+            k = u > k ? u : k;
+        }
+        return __uint_as_float(k);
+    }
+    template <int NW>
+    static __device__ __forceinline__ float block(float v, float* part) {
+        v = group<64>(v);
+        if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+        __syncthreads();
+        float best = 0.0f;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) best = nn_max(best, part[w]);
+        __syncthreads();
+        return best;
+    }
+};
+
 // One sweep of a workgroup over the n_rows rows of ITS instance in the three tiers of ordered_sum.h.  ptr: the row
 // pointers of the instance's first row; [lo2, hi2): a range that holds every row of the block tier (uniform in the
-// workgroup: the block tier has barriers).  Op as in tier_sweep_kernel; no barrier at the end
+// workgroup: the block tier has barriers).  Op as in tier_sweep_kernel, and Op::By combines the lanes.  No barrier at the end
 template <int NT, class Op>
 __device__ __forceinline__ void wg_sweep(const int* __restrict__ ptr, int n_rows, int lo2, int hi2, const Op& op,
                                          typename Op::Acc* part) {
     using Acc = typename Op::Acc;
+    using By = typename Op::By;
     const int tid = threadIdx.x, lane = tid & 63;
     for (int r0 = 0; r0 < n_rows; r0 += NT / 16) {           // (r0 is uniform in the workgroup)
         const int r = r0 + (tid >> 4);
@@ -82,7 +140,7 @@ __device__ __forceinline__ void wg_sweep(const int* __restrict__ ptr, int n_rows
         {   // group tier: every lane reaches the butterfly; a row of another tier runs it over no terms
             const bool mine = in && row_tier(len) == 0;
             const typename Op::Row rc = op.row(mine ? r : 0);
-            const Acc q = group_sum<16>(strided_terms<16>(op, rc, beg, mine ? len : 0, tid & 15));
+            const Acc q = By::template group<16>(strided_terms<16>(op, rc, beg, mine ? len : 0, tid & 15));
             if (mine && (tid & 15) == 0) op.finish(r, rc, q);
         }
 #pragma unroll
@@ -91,7 +149,7 @@ __device__ __forceinline__ void wg_sweep(const int* __restrict__ ptr, int n_rows
             if (row_tier(l4) != 1) continue;                 // (uniform in the wavefront)
             const int r4 = r0 + (tid >> 6) * 4 + g;
             const typename Op::Row rc = op.row(r4);
-            const Acc q = group_sum<64>(strided_terms<64>(op, rc, b4, l4, lane));
+            const Acc q = By::template group<64>(strided_terms<64>(op, rc, b4, l4, lane));
             if (lane == 0) op.finish(r4, rc, q);
         }
     }
@@ -99,17 +157,22 @@ __device__ __forceinline__ void wg_sweep(const int* __restrict__ ptr, int n_rows
         const int beg = ptr[r], len = ptr[r + 1] - beg;
         if (row_tier(len) != 2) continue;
         const typename Op::Row rc = op.row(r);
-        const Acc q = block_tree_sum<NT / 64>(strided_terms<NT>(op, rc, beg, len, tid), part);
+        const Acc q = By::template block<NT / 64>(strided_terms<NT>(op, rc, beg, len, tid), part);
         if (tid == 0) op.finish(r, rc, q);
     }
 }
 
 struct NoRow {};
+struct OwnFactor {
+    float d;
+};
 
-// sum_e |a_e| of a row; the largest over the rows this lane finished
+// sum_e |a_e| of a row; the largest over the rows this lane finished (mllp_lp_pdhg's set-up: the deliberate duplicate of
+// ScaledAbs with unit factors, see the head of the file)
 struct AbsSum {
     using Acc = float;
     using Row = NoRow;
+    using By = BySum;
     const float* __restrict__ val;
     unsigned* best;
     __device__ __forceinline__ Row row(int) const { return {}; }
@@ -120,15 +183,45 @@ struct AbsSum {
     }
 };
 
-// the column sweep of an iteration
+// a set-up walk of one orientation over s_e = fmul(fmul(|a_e|, dr_i), dc_j): a row's max (MAX) or its fadd chain.  `own`:
+// the factors of this orientation's rows, `other`: those the walk gathers; ROWS says which of the two is dr, so that both
+// orientations form the product in the same order.  The result goes to out[r] (unless null) and into the largest so far
+template <bool ROWS, bool MAX>
+struct ScaledAbs {
+    using Acc = float;
+    using Row = OwnFactor;
+    using By = std::conditional_t<MAX, ByMax, BySum>;
+    const int* __restrict__ idx;
+    const float* __restrict__ val;
+    int off;
+    const float *own, *other;
+    float* out;
+    unsigned* best;
+    __device__ __forceinline__ Row row(int r) const { return {own[r]}; }
+    __device__ __forceinline__ void term(const Row& rc, int e, float& q) const {
+        const float o = other[idx[e] - off], a = fabsf(val[e]);
+        const float s = ROWS ? __fmul_rn(__fmul_rn(a, rc.d), o) : __fmul_rn(__fmul_rn(a, o), rc.d);
+        q = MAX ? nn_max(q, s) : __fadd_rn(q, s);
+    }
+    __device__ __forceinline__ void finish(int r, const Row&, float q) const {
+        if (out) out[r] = q;
+        const unsigned k = abs_bits(q);
+        *best = k > *best ? k : *best;
+    }
+};
+
+// the column sweep of an iteration; S: the step of column j is tau tc_j (tc is null otherwise)
+template <bool S>
 struct ColStep {
     using Acc = float;
     using Row = NoRow;
+    using By = BySum;
     const int* __restrict__ idx;
     const float* __restrict__ val;
     const float* __restrict__ c;       // of the instance's first column
+    const float* tc;
     int row0;
-    float eta;
+    float tau;
     bool sums;
     float *x, *xb, *xs;
     const float* y;
@@ -136,29 +229,32 @@ struct ColStep {
     __device__ __forceinline__ void term(const Row&, int e, float& q) const { q = __fmaf_rn(val[e], y[idx[e] - row0], q); }
     __device__ __forceinline__ void finish(int j, const Row&, float s) const {
         const float g = __fsub_rn(c[j], s), xo = x[j];
-        const float xn = clip0(__fsub_rn(xo, __fmul_rn(eta, g)));
+        const float xn = clip0(__fsub_rn(xo, __fmul_rn(S ? __fmul_rn(tau, tc[j]) : tau, g)));
         x[j] = xn;
         xb[j] = __fsub_rn(__fadd_rn(xn, xn), xo);
         if (sums) xs[j] = __fadd_rn(xs[j], xn);
     }
 };
 
-// the row sweep of an iteration
+// the row sweep of an iteration; S: the step of row i is sigma tr_i (tr is null otherwise)
+template <bool S>
 struct RowStep {
     using Acc = float;
     using Row = NoRow;
+    using By = BySum;
     const int* __restrict__ idx;
     const float* __restrict__ val;
     const float* __restrict__ b;       // of the instance's first row
+    const float* tr;
     int col0;
-    float eta;
+    float sigma;
     bool sums;
     float *y, *ys;
     const float* xb;
     __device__ __forceinline__ Row row(int) const { return {}; }
     __device__ __forceinline__ void term(const Row&, int e, float& q) const { q = __fmaf_rn(val[e], xb[idx[e] - col0], q); }
     __device__ __forceinline__ void finish(int i, const Row&, float t) const {
-        const float yn = __fadd_rn(y[i], __fmul_rn(eta, __fsub_rn(b[i], t)));
+        const float yn = __fadd_rn(y[i], __fmul_rn(S ? __fmul_rn(sigma, tr[i]) : sigma, __fsub_rn(b[i], t)));
         y[i] = yn;
         if (sums) ys[i] = __fadd_rn(ys[i], yn);
     }
@@ -170,6 +266,7 @@ template <bool ROWS>
 struct EvalSweep {
     using Acc = Sum2;
     using Row = NoRow;
+    using By = BySum;
     const int* __restrict__ idx;
     const float* __restrict__ val;
     const float* __restrict__ rhs;
@@ -193,7 +290,12 @@ struct EvalSweep {
     }
 };
 
+// The kernel's arguments, one struct per entry point.  The fields of PdhgArgs are fields of ScaledArgs under the same
+// names (pdhg_args fills them by name); `scaled` is the kernel's S, kkt_words a row of d_kkt, and the two accessors are what
+// the shared text reads of ScaledArgs' own fields outside `if constexpr (S)`.
 struct PdhgArgs {
+    static constexpr bool scaled = false;
+    static constexpr int kkt_words = 4;
     const int* __restrict__ ptr_m;
     const int* __restrict__ ptr_n;
     const int* __restrict__ a_ptr;      // CSR(A)
@@ -213,6 +315,37 @@ struct PdhgArgs {
     int* status;
     float* kkt;
     float* scratch;
+    __device__ bool weigh() const { return false; }
+    __device__ float weight_span() const { return 1.0f; }
+};
+
+struct ScaledArgs {
+    static constexpr bool scaled = true;
+    static constexpr int kkt_words = 6;
+    const int* __restrict__ ptr_m;
+    const int* __restrict__ ptr_n;
+    const int* __restrict__ a_ptr;      // CSR(A)
+    const int* __restrict__ a_idx;
+    const float* __restrict__ a_val;
+    const int* __restrict__ at_ptr;     // CSR(A^T)
+    const int* __restrict__ at_idx;
+    const float* __restrict__ at_val;
+    const float* __restrict__ c;
+    const float* __restrict__ b;
+    const float* x0;
+    const float* y0;
+    long long max_iters, check_every, lim;
+    float eps, step, beta, span;
+    int ruiz_passes, pock_chambolle, primal_weight;
+    float* x;
+    float* y;
+    float* dr;
+    float* dc;
+    int* status;
+    float* kkt;
+    float* scratch;
+    __device__ bool weigh() const { return primal_weight != 0; }
+    __device__ float weight_span() const { return span; }
 };
 
 struct PdhgErr {
@@ -220,8 +353,9 @@ struct PdhgErr {
     __device__ __forceinline__ float worst() const { return nn_max(nn_max(p, d), g); }
 };
 
-template <bool IN_LDS, int NT>
-__global__ __launch_bounds__(NT) void pdhg_kernel(const PdhgArgs A) {
+template <bool IN_LDS, int NT, class Args>
+__global__ __launch_bounds__(NT) void pdhg_kernel(const Args A) {
+    constexpr bool S = Args::scaled;
     constexpr int NW = NT / 64;
     extern __shared__ float pd_lds[];
     __shared__ Sum2 s_part2[NW];
@@ -233,15 +367,19 @@ __global__ __launch_bounds__(NT) void pdhg_kernel(const PdhgArgs A) {
     const int col0 = A.ptr_n[k], n = A.ptr_n[k + 1] - col0;
     if ((pdhg_words(m, n) <= A.lim) != IN_LDS) return;      // the other launch's instance
     const float inf = __builtin_huge_valf();
-    float* base;
-    if constexpr (IN_LDS) {
-        base = pd_lds;
-    } else {
-        // this instance's piece of the scratch: behind those of the earlier instances that take one (integer sum: exact)
-        long long off = 0;
+    // This instance's piece of the scratch: behind those of the earlier instances (integer sum: exact).  S: every instance
+    // takes its 2 n + 2 m side words there, and its five vectors too when they do not fit LDS; otherwise only the instances
+    // whose vectors do not fit take one
+    long long off = 0;
+    if constexpr (S || !IN_LDS) {
         for (int j = tid; j < k; j += NT) {
-            const long long w = pdhg_words(A.ptr_m[j + 1] - A.ptr_m[j], A.ptr_n[j + 1] - A.ptr_n[j]);
-            if (w > A.lim) off += w;
+            const long long mj = A.ptr_m[j + 1] - A.ptr_m[j], nj = A.ptr_n[j + 1] - A.ptr_n[j];
+            if constexpr (S) {
+                off += pdhg_scaled_side_words(mj, nj) + (pdhg_words(mj, nj) > A.lim ? pdhg_words(mj, nj) : 0);
+            } else {
+                const long long w = pdhg_words(mj, nj);
+                if (w > A.lim) off += w;
+            }
         }
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) off += __shfl_xor(off, o, 64);
@@ -250,8 +388,13 @@ __global__ __launch_bounds__(NT) void pdhg_kernel(const PdhgArgs A) {
         off = 0;
 #pragma unroll
         for (int v = 0; v < NW; ++v) off += s_off[v];
-        base = A.scratch + off;
     }
+    float* side = A.scratch + off;
+    float* tc = S ? side : nullptr;         // [n] dc, then dc^2                              (these four: S only)
+    float* xr = S ? tc + n : nullptr;       // [n] the set-up's C, then x at the last restart
+    float* tr = S ? xr + n : nullptr;       // [m] dr, then dr^2
+    float* yr = S ? tr + m : nullptr;       // [m] the set-up's R, then y at the last restart
+    float* base = IN_LDS ? pd_lds : S ? yr + m : side;
     float* x = base;                // [n] the iterate
     float* xb = x + n;              // [n] 2 x+ - x
     float* xs = xb + n;             // [n] the sum of the iterates since the last restart
@@ -262,14 +405,16 @@ __global__ __launch_bounds__(NT) void pdhg_kernel(const PdhgArgs A) {
     const float* c = A.c + col0;
     const float* b = A.b + row0;
     const bool sums = A.check_every > 0;
+    const bool weigh = A.weigh();
 
-    // ---- start: the clipped start, the norms of b and c, where the block tier's rows are, eta ----
+    // ---- start: the clipped start, the norms of b and c, where the block tier's rows are ----
     unsigned kn[2] = {0u, 0u};      // ||b||inf, ||c||inf
     unsigned kr[4] = {0u, 0u, 0u, 0u};      // block tier: {~first, last + 1} of the columns, of the rows
     for (int j = tid; j < n; j += NT) {
         kn[1] = max(kn[1], abs_bits(c[j]));
         x[j] = A.x0 ? clip0(A.x0[col0 + j]) : 0.0f;
         if (sums) xs[j] = 0.0f;
+        if constexpr (S) tc[j] = 1.0f;
         if (row_tier(at_ptr[j + 1] - at_ptr[j]) == 2) {
             kr[0] = max(kr[0], (unsigned)(0x7fffffff - j));
             kr[1] = max(kr[1], (unsigned)(j + 1));
@@ -279,25 +424,80 @@ __global__ __launch_bounds__(NT) void pdhg_kernel(const PdhgArgs A) {
         kn[0] = max(kn[0], abs_bits(b[i]));
         y[i] = A.y0 ? A.y0[row0 + i] : 0.0f;
         if (sums) ys[i] = 0.0f;
+        if constexpr (S) tr[i] = 1.0f;
         if (row_tier(a_ptr[i + 1] - a_ptr[i]) == 2) {
             kr[2] = max(kr[2], (unsigned)(0x7fffffff - i));
             kr[3] = max(kr[3], (unsigned)(i + 1));
         }
     }
     block_max_u32<NW, 4>(kr, s_key);
-    block_max_u32<NW, 2>(kn, s_key);        // (also: every x_j and y_i is written)
+    block_max_u32<NW, 2>(kn, s_key);        // (also: every x_j and y_i, S: dc_j and dr_i, is written)
     const int c_lo = kr[1] ? 0x7fffffff - (int)kr[0] : 0, c_hi = (int)kr[1];
     const int r_lo = kr[3] ? 0x7fffffff - (int)kr[2] : 0, r_hi = (int)kr[3];
     const float den_p = __fadd_rn(1.0f, __uint_as_float(kn[0])), den_d = __fadd_rn(1.0f, __uint_as_float(kn[1]));
-    float eta;
-    {
-        unsigned ka[2] = {0u, 0u};  // ||A||1 (largest column sum), ||A||inf (largest row sum)
+
+    // ---- the step eta; S: first the scaling, then the weight's start ----
+    unsigned ka[2] = {0u, 0u};      // the largest column result, the largest row result of the last walk
+    if constexpr (S) {
+        // C and R from the SAME dr, dc, then both updated (tc holds dc, tr holds dr until they are squared)
+        auto walk = [&](auto is_max, float* out_c, float* out_r) {
+            constexpr bool MAX = decltype(is_max)::value;
+            ka[0] = ka[1] = 0u;
+            wg_sweep<NT>(at_ptr, n, c_lo, c_hi, ScaledAbs<false, MAX>{A.at_idx, A.at_val, row0, tc, tr, out_c, &ka[0]}, s_part);
+            wg_sweep<NT>(a_ptr, m, r_lo, r_hi, ScaledAbs<true, MAX>{A.a_idx, A.a_val, col0, tr, tc, out_r, &ka[1]}, s_part);
+        };
+        const int passes = A.ruiz_passes + (A.pock_chambolle ? 1 : 0);
+        for (int p = 0; p < passes; ++p) {      // (uniform in the workgroup)
+            if (p < A.ruiz_passes) walk(std::true_type{}, xr, yr);
+            else walk(std::false_type{}, xr, yr);
+            __syncthreads();
+            for (int j = tid; j < n; j += NT) {
+                const float v = xr[j];
+                if (v > 0.0f) tc[j] = __fdiv_rn(tc[j], sqrt_rn(v));
+            }
+            for (int i = tid; i < m; i += NT) {
+                const float v = yr[i];
+                if (v > 0.0f) tr[i] = __fdiv_rn(tr[i], sqrt_rn(v));
+            }
+            __syncthreads();
+        }
+        walk(std::false_type{}, nullptr, nullptr);      // ||S||1 (largest column sum), ||S||inf (largest row sum) of the final s_ij
+    } else {
+        // ||A||1 (largest column sum), ||A||inf (largest row sum)
         wg_sweep<NT>(at_ptr, n, c_lo, c_hi, AbsSum{A.at_val, &ka[0]}, s_part);
         wg_sweep<NT>(a_ptr, m, r_lo, r_hi, AbsSum{A.a_val, &ka[1]}, s_part);
+    }
+    float eta;
+    {
         block_max_u32<NW, 2>(ka, s_key);
         const float prod = __fmul_rn(__uint_as_float(ka[0]), __uint_as_float(ka[1]));
-        eta = prod > 0.0f ? __fdiv_rn(A.step, __fsqrt_rn(prod)) : A.step;
+        eta = prod > 0.0f ? __fdiv_rn(A.step, __fsqrt_rn(prod)) : A.step;      // (the hardware's root for both: the neutral settings' bits)
     }
+    float w0 = 1.0f;
+    if constexpr (S) {
+        // the weight's start, the factors' squares, the restart point (thread t owns words t, t + NT, ... of all of them)
+        Sum2 nn = {0.0f, 0.0f};     // |dc o c|^2, |dr o b|^2
+        for (int j = tid; j < n; j += NT) {
+            const float d = tc[j], v = __fmul_rn(d, c[j]);
+            nn.a = __fmaf_rn(v, v, nn.a);
+            if (A.dc) A.dc[col0 + j] = d;
+            tc[j] = __fmul_rn(d, d);
+            xr[j] = x[j];
+        }
+        for (int i = tid; i < m; i += NT) {
+            const float d = tr[i], v = __fmul_rn(d, b[i]);
+            nn.b = __fmaf_rn(v, v, nn.b);
+            if (A.dr) A.dr[row0 + i] = d;
+            tr[i] = __fmul_rn(d, d);
+            yr[i] = y[i];
+        }
+        nn = block_tree_sum<NW>(nn, s_part2);       // (its barriers: tc, tr are written before a sweep's lane reads them)
+        const float nc = sqrt_rn(nn.a), nb = sqrt_rn(nn.b);
+        if (weigh && finite_pos(nc) && finite_pos(nb)) w0 = __fdiv_rn(nc, nb);
+    }
+    // the weight w and its clamp, the two steps: both are eta without S, and w never moves
+    const float w_lo = __fdiv_rn(w0, A.weight_span()), w_hi = __fmul_rn(w0, A.weight_span());
+    float w = w0, tau = S ? __fdiv_rn(eta, w) : eta, sigma = S ? __fmul_rn(eta, w) : eta;
 
     long long cnt = 0;
     // both points of a check (with_avg) or the current iterate alone, in every thread (barriers inside)
@@ -333,9 +533,9 @@ __global__ __launch_bounds__(NT) void pdhg_kernel(const PdhgArgs A) {
     float e_last = inf;
     PdhgErr out = {0.0f, 0.0f, 0.0f};
     while (it < A.max_iters) {
-        wg_sweep<NT>(at_ptr, n, c_lo, c_hi, ColStep{A.at_idx, A.at_val, c, row0, eta, sums, x, xb, xs, y}, s_part);
+        wg_sweep<NT>(at_ptr, n, c_lo, c_hi, ColStep<S>{A.at_idx, A.at_val, c, tc, row0, tau, sums, x, xb, xs, y}, s_part);
         __syncthreads();
-        wg_sweep<NT>(a_ptr, m, r_lo, r_hi, RowStep{A.a_idx, A.a_val, b, col0, eta, sums, y, ys, xb}, s_part);
+        wg_sweep<NT>(a_ptr, m, r_lo, r_hi, RowStep<S>{A.a_idx, A.a_val, b, tr, col0, sigma, sums, y, ys, xb}, s_part);
         __syncthreads();
         ++it;
         if (!sums) continue;
@@ -374,6 +574,31 @@ __global__ __launch_bounds__(NT) void pdhg_kernel(const PdhgArgs A) {
         ++restarts;
         e_last = e;
         cnt = 0;
+        if constexpr (S) {
+            if (!weigh) continue;
+            // the weight: how far the restart moved in each space, in the metric of the scaled variables.  Every thread gets
+            // the tree's bits, so every thread holds the same w, tau and sigma
+            Sum2 dd = {0.0f, 0.0f};
+            for (int j = tid; j < n; j += NT) {
+                const float v = x[j], d = __fsub_rn(v, xr[j]);
+                dd.a = __fmaf_rn(d, __fdiv_rn(d, tc[j]), dd.a);
+                xr[j] = v;
+            }
+            for (int i = tid; i < m; i += NT) {
+                const float v = y[i], d = __fsub_rn(v, yr[i]);
+                dd.b = __fmaf_rn(d, __fdiv_rn(d, tr[i]), dd.b);
+                yr[i] = v;
+            }
+            dd = block_tree_sum<NW>(dd, s_part2);
+            const float dx = sqrt_rn(dd.a), dy = sqrt_rn(dd.b);
+            if (finite_pos(dx) && finite_pos(dy)) {
+                const float raw = sqrt_rn(__fmul_rn(w, __fdiv_rn(dy, dx)));
+                const float up = raw > w_lo ? raw : w_lo;
+                w = up < w_hi ? up : w_hi;
+                tau = __fdiv_rn(eta, w);
+                sigma = __fmul_rn(eta, w);
+            }
+        }
     }
     if (code < 0) {
         code = PD_CODE_LIMIT;
@@ -389,24 +614,27 @@ __global__ __launch_bounds__(NT) void pdhg_kernel(const PdhgArgs A) {
         st[2] = restarts;
         st[3] = avg_out;
         if (A.kkt) {
-            float* q = A.kkt + 4 * (size_t)k;
+            float* q = A.kkt + Args::kkt_words * (size_t)k;
             q[0] = out.p; q[1] = out.d; q[2] = out.g; q[3] = eta;
+            if constexpr (S) { q[4] = w0; q[5] = w; }
         }
     }
 }
 
-// what a call needs, from the host copy of the instance offsets
+// what a call needs, from the host copy of the instance offsets.  side: every instance takes its side words in the scratch
 struct PdhgPlan {
-    int64_t lim = 0;            // the largest 3 n + 2 m that runs with its vectors in LDS
+    int64_t lim = 0;            // the largest 3 n + 2 m that runs with its five vectors in LDS
     int64_t words = 0;          // scratch, in 4-byte words
     int64_t lds_words = 0;      // the most LDS words an instance takes
     bool any_lds = false, any_glb = false;
 };
-PdhgPlan pdhg_plan(const mllp_graph_t* g, int64_t max_lds_words) {
+PdhgPlan pdhg_plan(const mllp_graph_t* g, int64_t max_lds_words, bool side) {
     PdhgPlan p;
     p.lim = std::min<int64_t>(max_lds_words, PDHG_LDS_WORDS);
     for (int64_t k = 0; k < g->n_inst && k + 1 < (int64_t)g->h_inst_ptr_m.size() && k + 1 < (int64_t)g->h_inst_ptr_n.size(); ++k) {
-        const int64_t w = pdhg_words(g->h_inst_ptr_m[k + 1] - g->h_inst_ptr_m[k], g->h_inst_ptr_n[k + 1] - g->h_inst_ptr_n[k]);
+        const int64_t m = g->h_inst_ptr_m[k + 1] - g->h_inst_ptr_m[k], n = g->h_inst_ptr_n[k + 1] - g->h_inst_ptr_n[k];
+        const int64_t w = pdhg_words(m, n);
+        if (side) p.words += pdhg_scaled_side_words(m, n);
         if (w <= p.lim) {
             p.any_lds = true;
             p.lds_words = std::max(p.lds_words, w);
@@ -424,6 +652,73 @@ bool overlaps(const void* a, int64_t a_bytes, const void* b, int64_t b_bytes) {
     return a0 < b0 + (uintptr_t)b_bytes && b0 < a0 + (uintptr_t)a_bytes;
 }
 
+// The checks that both entry points make first, and the arguments that both kernels take.
+template <class Args>
+int pdhg_args(const char* fn, const mllp_graph_t* g, const float* d_x1, const float* d_x2, const float* d_x0, const float* d_y0,
+              int64_t max_iters, int64_t check_every, float eps, float step, float beta, int64_t max_lds_words, float* d_x,
+              float* d_y, int32_t* d_status, float* d_kkt, void* d_scratch, Args* args) {
+    REQUIRE_FOR(fn, g && d_x1 && d_x2 && d_x && d_y && d_status, "null argument (g, d_x1, d_x2, d_x, d_y and d_status are required)");
+    REQUIRE_FOR(fn, max_iters >= 0, "max_iters must not be negative");
+    REQUIRE_FOR(fn, check_every >= 0, "check_every must not be negative");
+    REQUIRE_FOR(fn, max_lds_words >= 0, "max_lds_words must not be negative");
+    REQUIRE_FOR(fn, std::isfinite(eps) && eps >= 0.0f, "eps must be finite and not negative");
+    REQUIRE_FOR(fn, std::isfinite(step) && step > 0.0f && step <= 1.0f, "step must be in (0, 1]");
+    REQUIRE_FOR(fn, std::isfinite(beta) && beta > 0.0f && beta < 1.0f, "beta must be in (0, 1)");
+    Args& a = *args = Args{};
+    a.ptr_m = g->inst_ptr_m; a.ptr_n = g->inst_ptr_n;
+    a.a_ptr = g->A.ptr; a.a_idx = g->A.idx; a.a_val = g->A.val;
+    a.at_ptr = g->At.ptr; a.at_idx = g->At.idx; a.at_val = g->At.val;
+    a.c = d_x1; a.b = d_x2; a.x0 = d_x0; a.y0 = d_y0;
+    a.max_iters = (long long)max_iters; a.check_every = (long long)check_every;
+    a.lim = (long long)std::min<int64_t>(max_lds_words, PDHG_LDS_WORDS);
+    a.eps = eps; a.step = step; a.beta = beta;
+    a.x = d_x; a.y = d_y; a.status = d_status; a.kkt = d_kkt; a.scratch = static_cast<float*>(d_scratch);
+    return MLLP_OK;
+}
+
+// The rest of a call, after the entry point's own checks: the plan, the scratch and overlap checks, and a launch per address
+// space of the five vectors that has an instance.  Errors of HIP carry the entry point's name without its prefix.
+template <class Args>
+int pdhg_launch(const char* fn, const mllp_graph_t* g, const Args& args, void* stream) {
+    const PdhgPlan plan = pdhg_plan(g, args.lim, Args::scaled);
+    REQUIRE_FOR(fn, plan.words == 0 || args.scratch, std::string("null d_scratch (") + fn + "_scratch_bytes is not 0)");
+    const float *dr = nullptr, *dc = nullptr;
+    if constexpr (Args::scaled) { dr = args.dr; dc = args.dc; }
+    const struct {
+        const void* p;
+        int64_t bytes;
+    } outs[] = {{args.x, g->N * 4}, {args.y, g->M * 4}, {dr, g->M * 4}, {dc, g->N * 4}, {args.status, g->n_inst * 16},
+                {args.kkt, g->n_inst * 4 * Args::kkt_words}};
+    for (const auto& o : outs)
+        REQUIRE_FOR(fn, !overlaps(args.x0, g->N * 4, o.p, o.bytes) && !overlaps(args.y0, g->M * 4, o.p, o.bytes),
+                    "d_x0 or d_y0 overlaps an output");
+    if (g->n_inst <= 0) return MLLP_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const std::string name = fn + sizeof("mllp_") - 1;
+    int rc;
+    if (plan.any_lds) {
+        // once per process and instantiation: the kernel may take more dynamic LDS than the default limit (no stream operation)
+        static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(pdhg_kernel<true, PDHG_THREADS, Args>),
+                                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)(PDHG_LDS_WORDS * sizeof(float)));
+        if (attr != hipSuccess) return hip_fail(attr, (name + ": hipFuncSetAttribute").c_str());
+        const size_t lds = (size_t)std::max<int64_t>(plan.lds_words, 1) * sizeof(float);
+        hipLaunchKernelGGL((pdhg_kernel<true, PDHG_THREADS, Args>), dim3((unsigned)g->n_inst), dim3(PDHG_THREADS), lds, s, args);
+        if ((rc = check_launch((name + " (LDS)").c_str()))) return rc;
+    }
+    if (plan.any_glb) {
+        hipLaunchKernelGGL((pdhg_kernel<false, PDHG_THREADS, Args>), dim3((unsigned)g->n_inst), dim3(PDHG_THREADS), 0, s, args);
+        if ((rc = check_launch((name + " (scratch)").c_str()))) return rc;
+    }
+    return MLLP_OK;
+}
+
+int pdhg_scratch_bytes(const char* fn, const mllp_graph_t* g, int64_t max_lds_words, bool side, int64_t* bytes) {
+    REQUIRE_FOR(fn, g && bytes, "null argument");
+    REQUIRE_FOR(fn, max_lds_words >= 0, "max_lds_words must not be negative");
+    *bytes = pdhg_plan(g, max_lds_words, side).words * (int64_t)sizeof(float);
+    return MLLP_OK;
+}
+
 }  // namespace
 
 }  // namespace mllp
@@ -437,49 +732,48 @@ extern "C" int mllp_lp_pdhg_limits(int64_t* limits) {
     return MLLP_OK;
 }
 
-extern "C" int mllp_lp_pdhg_scratch_bytes(const mllp_graph_t* g, int64_t max_lds_words, int64_t* bytes) {
-    REQUIRE(g && bytes, "null argument");
-    REQUIRE(max_lds_words >= 0, "max_lds_words must not be negative");
-    *bytes = pdhg_plan(g, max_lds_words).words * (int64_t)sizeof(float);
+extern "C" int mllp_lp_pdhg_scaled_limits(int64_t* limits) {
+    REQUIRE(limits, "null argument");
+    limits[0] = PDHG_SCALED_LDS_WORDS;
+    limits[1] = PDHG_SCALED_THREADS;
+    limits[2] = PDHG_SCALED_MAX_RUIZ;
     return MLLP_OK;
+}
+
+extern "C" int mllp_lp_pdhg_scratch_bytes(const mllp_graph_t* g, int64_t max_lds_words, int64_t* bytes) {
+    return pdhg_scratch_bytes(__func__, g, max_lds_words, false, bytes);
+}
+
+extern "C" int mllp_lp_pdhg_scaled_scratch_bytes(const mllp_graph_t* g, int64_t max_lds_words, int64_t* bytes) {
+    return pdhg_scratch_bytes(__func__, g, max_lds_words, true, bytes);
 }
 
 extern "C" int mllp_lp_pdhg(const mllp_graph_t* g, const float* d_x1, const float* d_x2, const float* d_x0, const float* d_y0,
                             int64_t max_iters, int64_t check_every, float eps, float step, float beta, int64_t max_lds_words,
                             float* d_x, float* d_y, int32_t* d_status, float* d_kkt, void* d_scratch, void* stream) {
-    REQUIRE(g && d_x1 && d_x2 && d_x && d_y && d_status, "null argument (g, d_x1, d_x2, d_x, d_y and d_status are required)");
-    REQUIRE(max_iters >= 0, "max_iters must not be negative");
-    REQUIRE(check_every >= 0, "check_every must not be negative");
-    REQUIRE(max_lds_words >= 0, "max_lds_words must not be negative");
-    REQUIRE(std::isfinite(eps) && eps >= 0.0f, "eps must be finite and not negative");
-    REQUIRE(std::isfinite(step) && step > 0.0f && step <= 1.0f, "step must be in (0, 1]");
-    REQUIRE(std::isfinite(beta) && beta > 0.0f && beta < 1.0f, "beta must be in (0, 1)");
-    const PdhgPlan plan = pdhg_plan(g, max_lds_words);
-    REQUIRE(plan.words == 0 || d_scratch, "null d_scratch (mllp_lp_pdhg_scratch_bytes is not 0)");
-    const struct {
-        const void* p;
-        int64_t bytes;
-    } outs[] = {{d_x, g->N * 4}, {d_y, g->M * 4}, {d_status, g->n_inst * 16}, {d_kkt, g->n_inst * 16}};
-    for (const auto& o : outs)
-        REQUIRE(!overlaps(d_x0, g->N * 4, o.p, o.bytes) && !overlaps(d_y0, g->M * 4, o.p, o.bytes), "d_x0 or d_y0 overlaps an output");
-    if (g->n_inst <= 0) return MLLP_OK;
-    hipStream_t s = (hipStream_t)stream;
-    const PdhgArgs args = {g->inst_ptr_m, g->inst_ptr_n, g->A.ptr, g->A.idx, g->A.val, g->At.ptr, g->At.idx, g->At.val, d_x1, d_x2,
-                           d_x0, d_y0, (long long)max_iters, (long long)check_every, (long long)plan.lim, eps, step, beta,
-                           d_x, d_y, d_status, d_kkt, static_cast<float*>(d_scratch)};
-    int rc;
-    if (plan.any_lds) {
-        // once per process: the kernel may take more dynamic LDS than the default limit (no stream operation)
-        static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(pdhg_kernel<true, PDHG_THREADS>),
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)(PDHG_LDS_WORDS * sizeof(float)));
-        if (attr != hipSuccess) return hip_fail(attr, "lp_pdhg: hipFuncSetAttribute");
-        const size_t lds = (size_t)std::max<int64_t>(plan.lds_words, 1) * sizeof(float);
-        hipLaunchKernelGGL((pdhg_kernel<true, PDHG_THREADS>), dim3((unsigned)g->n_inst), dim3(PDHG_THREADS), lds, s, args);
-        if ((rc = check_launch("lp_pdhg (LDS)"))) return rc;
-    }
-    if (plan.any_glb) {
-        hipLaunchKernelGGL((pdhg_kernel<false, PDHG_THREADS>), dim3((unsigned)g->n_inst), dim3(PDHG_THREADS), 0, s, args);
-        if ((rc = check_launch("lp_pdhg (scratch)"))) return rc;
-    }
-    return MLLP_OK;
+    PdhgArgs args;
+    if (int rc = pdhg_args(__func__, g, d_x1, d_x2, d_x0, d_y0, max_iters, check_every, eps, step, beta, max_lds_words, d_x, d_y,
+                           d_status, d_kkt, d_scratch, &args))
+        return rc;
+    return pdhg_launch(__func__, g, args, stream);
+}
+
+extern "C" int mllp_lp_pdhg_scaled(const mllp_graph_t* g, const float* d_x1, const float* d_x2, const float* d_x0, const float* d_y0,
+                                   int64_t max_iters, int64_t check_every, float eps, float step, float beta, int64_t ruiz_passes,
+                                   int32_t pock_chambolle, int32_t primal_weight, float weight_span, int64_t max_lds_words,
+                                   float* d_x, float* d_y, float* d_dr, float* d_dc, int32_t* d_status, float* d_kkt,
+                                   void* d_scratch, void* stream) {
+    ScaledArgs args;
+    if (int rc = pdhg_args(__func__, g, d_x1, d_x2, d_x0, d_y0, max_iters, check_every, eps, step, beta, max_lds_words, d_x, d_y,
+                           d_status, d_kkt, d_scratch, &args))
+        return rc;
+    REQUIRE(ruiz_passes >= 0 && ruiz_passes <= PDHG_SCALED_MAX_RUIZ, "ruiz_passes must be in 0 .. 64");
+    REQUIRE(std::isfinite(weight_span) && weight_span >= 1.0f, "weight_span must be finite and at least 1");
+    args.span = weight_span;
+    args.ruiz_passes = (int)ruiz_passes;
+    args.pock_chambolle = pock_chambolle != 0;
+    args.primal_weight = primal_weight != 0;
+    args.dr = d_dr;
+    args.dc = d_dc;
+    return pdhg_launch(__func__, g, args, stream);
 }

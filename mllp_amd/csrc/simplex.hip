@@ -566,10 +566,6 @@ SimplexPlan simplex_plan(const mllp_graph_t* g, int64_t max_m) {
     return p;
 }
 
-// REQUIRE on behalf of the entry point `fn`: the message names that function
-#define REQUIRE_FOR(fn, cond, msg) \
-    if (!(cond)) return ::mllp::fail(MLLP_EINVAL, std::string(fn) + ": " + (msg))
-
 // The checks that both entry points make first, and the arguments that both kernels take.
 int simplex_args(const char* fn, const mllp_graph_t* g, const float* d_x1, const float* d_x2, const float* d_start, float tol, float ftol,
                  float dtol, float ptol, float dshift, int64_t max_pivots, int64_t max_m, float* d_basis, int32_t* d_col_of_row,

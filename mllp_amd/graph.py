@@ -1196,7 +1196,53 @@ class LPBatch:
         got["pivots"] = res.status[:, 1] + res.status[:, 2]
         return got
 
-    # ---- restarted PDHG on every instance (mllp_lp_pdhg; csrc/pdhg.hip) ----------------------------------------------
+    # ---- restarted PDHG on every instance, plain and preconditioned (mllp_lp_pdhg, mllp_lp_pdhg_scaled; csrc/pdhg.hip) ----
+    def _pdhg(self, who, max_iters, check_every, params, x0, y0, start, max_lds_words):
+        """What `pdhg` and `pdhg_scaled` share: the start, the validation, the scratch kept on the batch, the outputs and the
+        call.  `who`: "pdhg" or "pdhg_scaled" -- the prefix of the messages, and what names the entry points (mllp_lp_pdhg,
+        mllp_lp_pdhg_scaled and their _scratch_bytes) and the attribute that keeps the scratch (`_pdhg_scratch`,
+        `_pdhg_scaled_scratch`).  `params`: the entry point's own arguments between check_every and max_lds_words -- eps,
+        step, beta, and for pdhg_scaled ruiz, pock_chambolle, primal_weight, weight_span.  Returns x, y, status, kkt (and dr,
+        dc)."""
+        scaled = who == "pdhg_scaled"
+        if start is not None:
+            if x0 is not None or y0 is not None:
+                raise ValueError(f"{who}: give start or x0 / y0, not both")
+            if not isinstance(start, BasisRepair) or start.x is None or start.y is None:
+                raise ValueError(f"{who}: start must be a BasisRepair with x and y")
+            x0, y0 = start.x, start.y
+        for t, n, what in ((x0, self.N, "x0"), (y0, self.M, "y0")):
+            if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n):
+                raise ValueError(f"{who}: {what} must be a contiguous cuda float32 tensor of {n} elements")
+        max_iters, check_every = int(max_iters), int(check_every)
+        if scaled:
+            params = params[:3] + (int(params[3]),) + params[4:]       # ruiz
+        if max_iters < 0 or check_every < 0:
+            raise ValueError(f"{who}: max_iters and check_every must not be negative")
+        dev = self.x1.device
+        max_lds_words = (pdhg_scaled_limits if scaled else pdhg_limits)()[0] if max_lds_words is None else int(max_lds_words)
+        kept = getattr(self, f"_{who}_scratch", None)
+        if kept is None or kept[0] != max_lds_words:
+            n = c_int64()
+            _lib.check(getattr(_lib.lib(), f"mllp_lp_{who}_scratch_bytes")(self._h, max_lds_words, ctypes.byref(n)))
+            kept = (max_lds_words, torch.empty(n.value // 4, device=dev, dtype=torch.float32) if n.value else None)
+            setattr(self, f"_{who}_scratch", kept)
+        # (at least one element each: an empty torch tensor has a null pointer, which the library refuses)
+        new = lambda n, dt: torch.empty(max(n, 1), dtype=dt, device=dev)      # noqa: E731
+        x, y = new(self.N, torch.float32), new(self.M, torch.float32)
+        side = (new(self.M, torch.float32), new(self.N, torch.float32)) if scaled else ()         # dr, dc
+        kkt_words = 6 if scaled else 4
+        status, kkt = new(self.n_inst * 4, torch.int32), new(self.n_inst * kkt_words, torch.float32)
+        pad = lambda t: t if t.numel() else torch.zeros(1, dtype=torch.float32, device=dev)   # noqa: E731
+        opt = lambda t: None if t is None or not t.numel() else t                             # noqa: E731
+        flag = lambda v: int(bool(v))                                                         # noqa: E731
+        _lib.check(getattr(_lib.lib(), f"mllp_lp_{who}")(
+            self._h, _lib.ptr(pad(self.x1)), _lib.ptr(pad(self.x2)), _lib.ptr(opt(x0)), _lib.ptr(opt(y0)), max_iters, check_every,
+            *[f(v) for f, v in zip((float, float, float, int, flag, flag, float), params)], max_lds_words, _lib.ptr(x), _lib.ptr(y),
+            *[_lib.ptr(t) for t in side], _lib.ptr(status), _lib.ptr(kkt), _lib.ptr(kept[1]), _lib.current_stream()))
+        return (x[:self.N], y[:self.M], status[:self.n_inst * 4].view(self.n_inst, 4),
+                kkt[:self.n_inst * kkt_words].view(self.n_inst, kkt_words), *(t[:n] for t, n in zip(side, (self.M, self.N))))
+
     def pdhg(self, max_iters, eps=2.0 ** -10, check_every=64, step=0.9, beta=0.5, x0=None, y0=None, start=None,
              max_lds_words=None):
         """A first-order solve of every instance on the device: PDHG with averaging and restarts (mllp_lp_pdhg; the rule
@@ -1208,37 +1254,8 @@ class LPBatch:
         `x`, `y` are the warm start.  `max_lds_words`: test hook -- instances whose 3 n + 2 m words exceed it keep their
         vectors in scratch (None: the kernel's limit).  Returns an `LPPdhg` of device tensors.  The scratch is asked for
         once per max_lds_words and kept on the batch.  A BASELINE: no preconditioning, no adaptive step.  No sync."""
-        if start is not None:
-            if x0 is not None or y0 is not None:
-                raise ValueError("pdhg: give start or x0 / y0, not both")
-            if not isinstance(start, BasisRepair) or start.x is None or start.y is None:
-                raise ValueError("pdhg: start must be a BasisRepair with x and y")
-            x0, y0 = start.x, start.y
-        for t, n, what in ((x0, self.N, "x0"), (y0, self.M, "y0")):
-            if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n):
-                raise ValueError(f"pdhg: {what} must be a contiguous cuda float32 tensor of {n} elements")
-        max_iters, check_every = int(max_iters), int(check_every)
-        if max_iters < 0 or check_every < 0:
-            raise ValueError("pdhg: max_iters and check_every must not be negative")
-        dev = self.x1.device
-        max_lds_words = pdhg_limits()[0] if max_lds_words is None else int(max_lds_words)
-        kept = getattr(self, "_pdhg_scratch", None)
-        if kept is None or kept[0] != max_lds_words:
-            n = c_int64()
-            _lib.check(_lib.lib().mllp_lp_pdhg_scratch_bytes(self._h, max_lds_words, ctypes.byref(n)))
-            kept = self._pdhg_scratch = (max_lds_words, torch.empty(n.value // 4, device=dev, dtype=torch.float32) if n.value else None)
-        # (at least one element each: an empty torch tensor has a null pointer, which the library refuses)
-        new = lambda n, dt: torch.empty(max(n, 1), dtype=dt, device=dev)      # noqa: E731
-        x, y = new(self.N, torch.float32), new(self.M, torch.float32)
-        status, kkt = new(self.n_inst * 4, torch.int32), new(self.n_inst * 4, torch.float32)
-        pad = lambda t: t if t.numel() else torch.zeros(1, dtype=torch.float32, device=dev)   # noqa: E731
-        opt = lambda t: None if t is None or not t.numel() else t                             # noqa: E731
-        _lib.check(_lib.lib().mllp_lp_pdhg(self._h, _lib.ptr(pad(self.x1)), _lib.ptr(pad(self.x2)), _lib.ptr(opt(x0)), _lib.ptr(opt(y0)),
-                                           max_iters, check_every, float(eps), float(step), float(beta), max_lds_words, _lib.ptr(x),
-                                           _lib.ptr(y), _lib.ptr(status), _lib.ptr(kkt), _lib.ptr(kept[1]), _lib.current_stream()))
-        return LPPdhg(x[:self.N], y[:self.M], status[:self.n_inst * 4].view(self.n_inst, 4), kkt[:self.n_inst * 4].view(self.n_inst, 4))
+        return LPPdhg(*self._pdhg("pdhg", max_iters, check_every, (eps, step, beta), x0, y0, start, max_lds_words))
 
-    # ---- preconditioned PDHG on every instance (mllp_lp_pdhg_scaled; csrc/pdhg_scaled.hip) ------------------------------
     def pdhg_scaled(self, max_iters, eps=2.0 ** -10, check_every=64, step=0.9, beta=0.5, ruiz=10, pock_chambolle=True,
                     primal_weight=True, weight_span=16.0, x0=None, y0=None, start=None, max_lds_words=None):
         """`pdhg` with diagonal preconditioning and a primal weight, both computed on the device by the call itself
@@ -1248,38 +1265,8 @@ class LPBatch:
         are `pdhg`'s (the errors are those of the original LP); with ruiz=0, pock_chambolle=False, primal_weight=False the
         result has `pdhg`'s bits.  Returns an `LPPdhgScaled`.  The scratch is asked for once per max_lds_words and kept on
         the batch.  No adaptive step, no infeasibility detection.  No sync."""
-        if start is not None:
-            if x0 is not None or y0 is not None:
-                raise ValueError("pdhg_scaled: give start or x0 / y0, not both")
-            if not isinstance(start, BasisRepair) or start.x is None or start.y is None:
-                raise ValueError("pdhg_scaled: start must be a BasisRepair with x and y")
-            x0, y0 = start.x, start.y
-        for t, n, what in ((x0, self.N, "x0"), (y0, self.M, "y0")):
-            if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n):
-                raise ValueError(f"pdhg_scaled: {what} must be a contiguous cuda float32 tensor of {n} elements")
-        max_iters, check_every, ruiz = int(max_iters), int(check_every), int(ruiz)
-        if max_iters < 0 or check_every < 0:
-            raise ValueError("pdhg_scaled: max_iters and check_every must not be negative")
-        dev = self.x1.device
-        max_lds_words = pdhg_scaled_limits()[0] if max_lds_words is None else int(max_lds_words)
-        kept = getattr(self, "_pdhg_scaled_scratch", None)
-        if kept is None or kept[0] != max_lds_words:
-            n = c_int64()
-            _lib.check(_lib.lib().mllp_lp_pdhg_scaled_scratch_bytes(self._h, max_lds_words, ctypes.byref(n)))
-            kept = self._pdhg_scaled_scratch = (max_lds_words, torch.empty(n.value // 4, device=dev, dtype=torch.float32) if n.value else None)
-        # (at least one element each: an empty torch tensor has a null pointer, which the library refuses)
-        new = lambda n, dt: torch.empty(max(n, 1), dtype=dt, device=dev)      # noqa: E731
-        x, y, dr, dc = new(self.N, torch.float32), new(self.M, torch.float32), new(self.M, torch.float32), new(self.N, torch.float32)
-        status, kkt = new(self.n_inst * 4, torch.int32), new(self.n_inst * 6, torch.float32)
-        pad = lambda t: t if t.numel() else torch.zeros(1, dtype=torch.float32, device=dev)   # noqa: E731
-        opt = lambda t: None if t is None or not t.numel() else t                             # noqa: E731
-        _lib.check(_lib.lib().mllp_lp_pdhg_scaled(self._h, _lib.ptr(pad(self.x1)), _lib.ptr(pad(self.x2)), _lib.ptr(opt(x0)), _lib.ptr(opt(y0)),
-                                                  max_iters, check_every, float(eps), float(step), float(beta), ruiz, int(bool(pock_chambolle)),
-                                                  int(bool(primal_weight)), float(weight_span), max_lds_words, _lib.ptr(x), _lib.ptr(y),
-                                                  _lib.ptr(dr), _lib.ptr(dc), _lib.ptr(status), _lib.ptr(kkt), _lib.ptr(kept[1]),
-                                                  _lib.current_stream()))
-        return LPPdhgScaled(x[:self.N], y[:self.M], status[:self.n_inst * 4].view(self.n_inst, 4), kkt[:self.n_inst * 6].view(self.n_inst, 6),
-                            dr[:self.M], dc[:self.N])
+        return LPPdhgScaled(*self._pdhg("pdhg_scaled", max_iters, check_every,
+                                        (eps, step, beta, ruiz, pock_chambolle, primal_weight, weight_span), x0, y0, start, max_lds_words))
 
     def pdhg_basis(self, res, tol=2.0 ** -12, max_m=None):
         """The vertex a PDHG iterate points at: `repair_basis` on the ranking of `res.x` (its m largest entries first), so the

@@ -1,4 +1,4 @@
-"""GPU: mllp_lp_pdhg_scaled (preconditioned restarted PDHG; csrc/pdhg_scaled.hip) against the numpy oracle of THE RULE
+"""GPU: mllp_lp_pdhg_scaled (preconditioned restarted PDHG; csrc/pdhg.hip) against the numpy oracle of THE RULE
 (tests/pdhg_scaled_oracle.py), on planted LPs (the device plants them, the oracle gets what the batch stores), in the
 pattern of tests/test_pdhg.py.
 
