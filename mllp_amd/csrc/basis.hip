@@ -25,6 +25,7 @@
 
 #include "device_utils.h"
 #include "internal.h"
+#include "lp_launch.h"
 
 namespace mllp {
 
@@ -227,30 +228,12 @@ __global__ __launch_bounds__(NT) void basis_repair_kernel(const RepairArgs A) {
     }
 }
 
-// what a call needs, from the host copy of the instance offsets
-struct RepairPlan {
-    int64_t words = 0;      // scratch, in 4-byte words
-    int64_t lds_m = 0;      // the largest m that runs with T in LDS
-    int64_t glb_m = 0;      // ... with T in scratch
-    bool any_lds = false, any_glb = false;      // which launches have an instance (a skipped one included)
-};
-RepairPlan repair_plan(const mllp_graph_t* g, int64_t max_m) {
-    RepairPlan p;
+LpPlan repair_plan(const mllp_graph_t* g, int64_t max_m) {
     max_m = std::min<int64_t>(max_m, BASIS_MAX_M);
-    for (int64_t k = 0; k < g->n_inst && k + 1 < (int64_t)g->h_inst_ptr_m.size(); ++k) {
-        const int64_t m = g->h_inst_ptr_m[k + 1] - g->h_inst_ptr_m[k];
-        if (m <= BASIS_LDS_MAX_M) {
-            p.any_lds = true;
-            if (m <= max_m) p.lds_m = std::max(p.lds_m, m);
-        } else {
-            p.any_glb = true;
-            if (m <= max_m) {
-                p.words += basis_repair_words(m);
-                p.glb_m = std::max(p.glb_m, m);
-            }
-        }
-    }
-    return p;
+    return lp_plan(g, [=](int64_t m, int64_t) {
+        const bool in_lds = m <= BASIS_LDS_MAX_M;
+        return LpInstance{in_lds, m <= max_m, in_lds ? 0 : basis_repair_words(m), m};
+    });
 }
 
 }  // namespace
@@ -274,33 +257,21 @@ extern "C" int mllp_basis_repair(const mllp_graph_t* g, const float* d_x1, const
     REQUIRE(!d_x || (d_x1 && d_x2), "null d_x1 or d_x2 with d_x and d_y asked for");
     REQUIRE(std::isfinite(tol) && tol >= 0.0f, "tol must be finite and not negative");
     REQUIRE(max_m >= 0, "max_m must not be negative");
-    const RepairPlan plan = repair_plan(g, max_m);
+    const LpPlan plan = repair_plan(g, max_m);
     REQUIRE(plan.words == 0 || d_scratch, "null d_scratch (mllp_basis_repair_scratch_bytes is not 0)");
     if (g->n_inst <= 0) return MLLP_OK;
     hipStream_t s = (hipStream_t)stream;
     max_m = std::min<int64_t>(max_m, BASIS_MAX_M);
     const RepairArgs args = {g->inst_ptr_m, g->inst_ptr_n, g->At.ptr, g->At.idx, g->At.val, d_x1, d_x2, d_order, tol, (long long)max_m,
                              d_basis, d_col_of_row, d_x, d_y, d_status, d_quality, static_cast<float*>(d_scratch)};
-    int rc;
-    if (plan.any_lds) {
-        // once per process: the kernel may take more dynamic LDS than the default limit (no stream operation)
-        static const hipError_t attr =
-            hipFuncSetAttribute(reinterpret_cast<const void*>(basis_repair_kernel<true, BR_T_LDS>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)((BASIS_LDS_MAX_M * BASIS_LDS_MAX_M + basis_repair_vec_words(BASIS_LDS_MAX_M)) * sizeof(float)));
-        if (attr != hipSuccess) return hip_fail(attr, "basis_repair: hipFuncSetAttribute");
-        const size_t lds = (size_t)std::max<int64_t>(plan.lds_m * plan.lds_m + basis_repair_vec_words(plan.lds_m), 1) * sizeof(float);
-        hipLaunchKernelGGL((basis_repair_kernel<true, BR_T_LDS>), dim3((unsigned)g->n_inst), dim3(BR_T_LDS), lds, s, args);
-        if ((rc = check_launch("basis_repair (LDS)"))) return rc;
-    }
-    if (plan.any_glb) {
-        static const hipError_t attr =
-            hipFuncSetAttribute(reinterpret_cast<const void*>(basis_repair_kernel<false, BR_T_GLB>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)(basis_repair_vec_words(BASIS_MAX_M) * sizeof(float)));
-        if (attr != hipSuccess) return hip_fail(attr, "basis_repair: hipFuncSetAttribute");
-        const size_t lds = (size_t)std::max<int64_t>(basis_repair_vec_words(plan.glb_m), 1) * sizeof(float);
-        hipLaunchKernelGGL((basis_repair_kernel<false, BR_T_GLB>), dim3((unsigned)g->n_inst), dim3(BR_T_GLB), lds, s, args);
-        if ((rc = check_launch("basis_repair (scratch)"))) return rc;
-    }
-    return MLLP_OK;
+    // a launch's dynamic LDS, its largest instance having m rows: the four vectors, and T where it lives there
+    constexpr auto lds = [](bool in_lds, int64_t m) { return lp_lds_bytes((in_lds ? m * m : 0) + basis_repair_vec_words(m)); };
+    int rc = MLLP_OK;
+    if (plan.any_lds)
+        rc = lp_launch<basis_repair_kernel<true, BR_T_LDS>, BR_T_LDS>("basis_repair", " (LDS)", g->n_inst, lds(true, BASIS_LDS_MAX_M),
+                                                                      lds(true, plan.lds_extent), s, args);
+    if (!rc && plan.any_glb)
+        rc = lp_launch<basis_repair_kernel<false, BR_T_GLB>, BR_T_GLB>("basis_repair", " (scratch)", g->n_inst, lds(false, BASIS_MAX_M),
+                                                                       lds(false, plan.glb_extent), s, args);
+    return rc;
 }

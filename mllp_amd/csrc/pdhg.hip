@@ -44,6 +44,7 @@
 #include <string>
 #include <type_traits>
 
+#include "lp_launch.h"
 #include "ordered_sum.h"
 
 namespace mllp {
@@ -621,29 +622,14 @@ __global__ __launch_bounds__(NT) void pdhg_kernel(const Args A) {
     }
 }
 
-// what a call needs, from the host copy of the instance offsets.  side: every instance takes its side words in the scratch
-struct PdhgPlan {
-    int64_t lim = 0;            // the largest 3 n + 2 m that runs with its five vectors in LDS
-    int64_t words = 0;          // scratch, in 4-byte words
-    int64_t lds_words = 0;      // the most LDS words an instance takes
-    bool any_lds = false, any_glb = false;
-};
-PdhgPlan pdhg_plan(const mllp_graph_t* g, int64_t max_lds_words, bool side) {
-    PdhgPlan p;
-    p.lim = std::min<int64_t>(max_lds_words, PDHG_LDS_WORDS);
-    for (int64_t k = 0; k < g->n_inst && k + 1 < (int64_t)g->h_inst_ptr_m.size() && k + 1 < (int64_t)g->h_inst_ptr_n.size(); ++k) {
-        const int64_t m = g->h_inst_ptr_m[k + 1] - g->h_inst_ptr_m[k], n = g->h_inst_ptr_n[k + 1] - g->h_inst_ptr_n[k];
+// side: every instance takes its side words in the scratch
+LpPlan pdhg_plan(const mllp_graph_t* g, int64_t max_lds_words, bool side) {
+    // the largest 3 n + 2 m that runs with its five vectors in LDS
+    const int64_t lim = std::min<int64_t>(max_lds_words, PDHG_LDS_WORDS);
+    return lp_plan(g, [=](int64_t m, int64_t n) {
         const int64_t w = pdhg_words(m, n);
-        if (side) p.words += pdhg_scaled_side_words(m, n);
-        if (w <= p.lim) {
-            p.any_lds = true;
-            p.lds_words = std::max(p.lds_words, w);
-        } else {
-            p.any_glb = true;
-            p.words += w;
-        }
-    }
-    return p;
+        return LpInstance{w <= lim, true, (side ? pdhg_scaled_side_words(m, n) : 0) + (w <= lim ? 0 : w), w};
+    });
 }
 
 bool overlaps(const void* a, int64_t a_bytes, const void* b, int64_t b_bytes) {
@@ -680,7 +666,7 @@ int pdhg_args(const char* fn, const mllp_graph_t* g, const float* d_x1, const fl
 // space of the five vectors that has an instance.  Errors of HIP carry the entry point's name without its prefix.
 template <class Args>
 int pdhg_launch(const char* fn, const mllp_graph_t* g, const Args& args, void* stream) {
-    const PdhgPlan plan = pdhg_plan(g, args.lim, Args::scaled);
+    const LpPlan plan = pdhg_plan(g, args.lim, Args::scaled);
     REQUIRE_FOR(fn, plan.words == 0 || args.scratch, std::string("null d_scratch (") + fn + "_scratch_bytes is not 0)");
     const float *dr = nullptr, *dc = nullptr;
     if constexpr (Args::scaled) { dr = args.dr; dc = args.dc; }
@@ -695,21 +681,13 @@ int pdhg_launch(const char* fn, const mllp_graph_t* g, const Args& args, void* s
     if (g->n_inst <= 0) return MLLP_OK;
     hipStream_t s = (hipStream_t)stream;
     const std::string name = fn + sizeof("mllp_") - 1;
-    int rc;
-    if (plan.any_lds) {
-        // once per process and instantiation: the kernel may take more dynamic LDS than the default limit (no stream operation)
-        static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(pdhg_kernel<true, PDHG_THREADS, Args>),
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)(PDHG_LDS_WORDS * sizeof(float)));
-        if (attr != hipSuccess) return hip_fail(attr, (name + ": hipFuncSetAttribute").c_str());
-        const size_t lds = (size_t)std::max<int64_t>(plan.lds_words, 1) * sizeof(float);
-        hipLaunchKernelGGL((pdhg_kernel<true, PDHG_THREADS, Args>), dim3((unsigned)g->n_inst), dim3(PDHG_THREADS), lds, s, args);
-        if ((rc = check_launch((name + " (LDS)").c_str()))) return rc;
-    }
-    if (plan.any_glb) {
-        hipLaunchKernelGGL((pdhg_kernel<false, PDHG_THREADS, Args>), dim3((unsigned)g->n_inst), dim3(PDHG_THREADS), 0, s, args);
-        if ((rc = check_launch((name + " (scratch)").c_str()))) return rc;
-    }
-    return MLLP_OK;
+    int rc = MLLP_OK;
+    if (plan.any_lds)
+        rc = lp_launch<pdhg_kernel<true, PDHG_THREADS, Args>, PDHG_THREADS>(name, " (LDS)", g->n_inst, lp_lds_bytes(PDHG_LDS_WORDS),
+                                                                            lp_lds_bytes(plan.lds_extent), s, args);
+    if (!rc && plan.any_glb)    // (no dynamic LDS: no limit to raise)
+        rc = lp_launch<pdhg_kernel<false, PDHG_THREADS, Args>, PDHG_THREADS>(name, " (scratch)", g->n_inst, 0, 0, s, args);
+    return rc;
 }
 
 int pdhg_scratch_bytes(const char* fn, const mllp_graph_t* g, int64_t max_lds_words, bool side, int64_t* bytes) {

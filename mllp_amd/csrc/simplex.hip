@@ -35,6 +35,7 @@
 
 #include "device_utils.h"
 #include "internal.h"
+#include "lp_launch.h"
 
 namespace mllp {
 
@@ -545,25 +546,9 @@ __global__ __launch_bounds__(NT) void basis_simplex_kernel(const Args A) {
     if (tid == 0) { st[0] = code; st[1] = (int)nD; st[2] = (int)nP; st[3] = m; write_guard(nRef, nBl); }
 }
 
-// what a call needs, from the host copy of the instance offsets
-struct SimplexPlan {
-    int64_t words = 0;      // scratch, in 4-byte words
-    int64_t lds_m = 0;      // the largest m that runs with T in LDS
-    int64_t glb_m = 0;      // ... with T in scratch
-    bool any_lds = false, any_glb = false;      // which launches have an instance (a skipped one included)
-};
-SimplexPlan simplex_plan(const mllp_graph_t* g, int64_t max_m) {
-    SimplexPlan p;
+LpPlan simplex_plan(const mllp_graph_t* g, int64_t max_m) {
     max_m = std::min<int64_t>(max_m, SIMPLEX_MAX_M);
-    for (int64_t k = 0; k < g->n_inst && k + 1 < (int64_t)g->h_inst_ptr_m.size() && k + 1 < (int64_t)g->h_inst_ptr_n.size(); ++k) {
-        const int64_t m = g->h_inst_ptr_m[k + 1] - g->h_inst_ptr_m[k], n = g->h_inst_ptr_n[k + 1] - g->h_inst_ptr_n[k];
-        (m <= SIMPLEX_LDS_MAX_M ? p.any_lds : p.any_glb) = true;
-        if (m > max_m) continue;
-        p.words += simplex_words(m, n);
-        if (m <= SIMPLEX_LDS_MAX_M) p.lds_m = std::max(p.lds_m, m);
-        else p.glb_m = std::max(p.glb_m, m);
-    }
-    return p;
+    return lp_plan(g, [=](int64_t m, int64_t n) { return LpInstance{m <= SIMPLEX_LDS_MAX_M, m <= max_m, simplex_words(m, n), m}; });
 }
 
 // The checks that both entry points make first, and the arguments that both kernels take.
@@ -584,36 +569,25 @@ int simplex_args(const char* fn, const mllp_graph_t* g, const float* d_x1, const
     return MLLP_OK;
 }
 
-// One instantiation's launch.  Once per process and instantiation: the kernel may take more dynamic LDS than the default
-// limit (no stream operation).
-template <bool IN_LDS, int NT, class Args>
-int simplex_launch_one(const std::string& name, const char* where, const mllp_graph_t* g, const SimplexPlan& plan, const Args& args,
-                       hipStream_t s) {
-    constexpr int64_t limit =
-        IN_LDS ? SIMPLEX_LDS_MAX_M * SIMPLEX_LDS_MAX_M + simplex_vec_words(SIMPLEX_LDS_MAX_M) : simplex_vec_words(SIMPLEX_MAX_M);
-    static const hipError_t attr =
-        hipFuncSetAttribute(reinterpret_cast<const void*>(basis_simplex_kernel<IN_LDS, NT, Args>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)(limit * sizeof(float)));
-    if (attr != hipSuccess) return hip_fail(attr, (name + ": hipFuncSetAttribute").c_str());
-    const int64_t words = IN_LDS ? plan.lds_m * plan.lds_m + simplex_vec_words(plan.lds_m) : simplex_vec_words(plan.glb_m);
-    const size_t lds = (size_t)std::max<int64_t>(words, 1) * sizeof(float);
-    hipLaunchKernelGGL((basis_simplex_kernel<IN_LDS, NT, Args>), dim3((unsigned)g->n_inst), dim3(NT), lds, s, args);
-    return check_launch((name + where).c_str());
-}
-
 // The rest of a call, after the entry point's own checks: the plan, the scratch check, and a launch per address space of T
-// that has an instance.  Errors of HIP carry the entry point's name without its prefix.
+// that has an instance.
 template <class Args>
 int simplex_launch(const char* fn, const mllp_graph_t* g, const Args& args, void* stream) {
-    const SimplexPlan plan = simplex_plan(g, args.max_m);
+    const LpPlan plan = simplex_plan(g, args.max_m);
     REQUIRE_FOR(fn, plan.words == 0 || args.scratch, "null d_scratch (mllp_basis_simplex_scratch_bytes is not 0)");
     if (g->n_inst <= 0) return MLLP_OK;
     hipStream_t s = (hipStream_t)stream;
     const std::string name = fn + sizeof("mllp_") - 1;
-    int rc;
-    if (plan.any_lds && (rc = simplex_launch_one<true, SX_T_LDS>(name, " (LDS)", g, plan, args, s))) return rc;
-    if (plan.any_glb && (rc = simplex_launch_one<false, SX_T_GLB>(name, " (scratch)", g, plan, args, s))) return rc;
-    return MLLP_OK;
+    // a launch's dynamic LDS, its largest instance having m rows: the six vectors, and T where it lives there
+    constexpr auto lds = [](bool in_lds, int64_t m) { return lp_lds_bytes((in_lds ? m * m : 0) + simplex_vec_words(m)); };
+    int rc = MLLP_OK;
+    if (plan.any_lds)
+        rc = lp_launch<basis_simplex_kernel<true, SX_T_LDS, Args>, SX_T_LDS>(name, " (LDS)", g->n_inst, lds(true, SIMPLEX_LDS_MAX_M),
+                                                                             lds(true, plan.lds_extent), s, args);
+    if (!rc && plan.any_glb)
+        rc = lp_launch<basis_simplex_kernel<false, SX_T_GLB, Args>, SX_T_GLB>(name, " (scratch)", g->n_inst, lds(false, SIMPLEX_MAX_M),
+                                                                              lds(false, plan.glb_extent), s, args);
+    return rc;
 }
 
 }  // namespace

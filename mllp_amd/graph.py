@@ -8,6 +8,7 @@ CSR(A) + CSR(A^T) behind an opaque `mllp_graph_t*`, and every model call takes i
 import contextlib
 import ctypes
 import itertools
+import math
 import time
 from ctypes import c_int32, c_int64, c_double, c_void_p
 from typing import List, Optional, Sequence
@@ -197,6 +198,41 @@ def build_tiled_arrays(ptr, idx, val, n_dst, R, CB, variant=0, entry_order="join
     return keep, info
 
 
+# ---- what the wrappers below share: arguments in, buffers out ----------------------------------------------------------------
+def _parse_want(who, want, names, saying, allow_empty=False, together=()):
+    """The `want=` of a call as a tuple (a lone name stands for itself).  ValueError "<who>: <saying> (got ...)" unless it
+    names only `names` -- at least one of them unless `allow_empty`, and all or none of `together`."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if [w for w in want if w not in names] or not (want or allow_empty) or (together and len({w in want for w in together}) > 1):
+        raise ValueError(f"{who}: {saying} (got {want!r})")
+    return want
+
+
+def _checked(who, what, t, n, dtype=torch.float32):
+    """`t`, the argument `what` of `who`: a contiguous cuda tensor of n elements of `dtype`, or ValueError"""
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous() and t.numel() == n):
+        raise ValueError(f"{who}: {what} must be a contiguous cuda {str(dtype).split('.')[1]} tensor of {n} elements")
+    return t
+
+
+def _out(n, dtype, dev, wanted=True):
+    """An output buffer of n elements, None when not wanted.  At least one element: an empty torch tensor has a null
+    pointer, which the library refuses or reads as "not wanted"."""
+    return torch.empty(max(n, 1), dtype=dtype, device=dev) if wanted else None
+
+
+def _pad(t):
+    """`t` as an input of the library: one zero where it is empty (never a null pointer)"""
+    return t if t.numel() else torch.zeros(1, dtype=t.dtype, device=t.device)
+
+
+def _cut(t, *shape):
+    """What the caller gets of the buffer `_out` made: its first elements, in `shape`; None for None"""
+    if t is None:
+        return None
+    return t[:shape[0]] if len(shape) == 1 else t[:math.prod(shape)].view(shape)
+
+
 class LPBatch:
     _tokens = itertools.count(1)
     # whole-model kernels: 0 = by size (fused latency-regime kernels below 32 M nonzeros, generic / LDS-tiled sweeps
@@ -243,8 +279,7 @@ class LPBatch:
         that holds values -- both orientations, the fused path's copies, every streamed and device-built tiled copy -- is
         refreshed on the device; a backward needs a new forward afterwards.  The first call (and the first after a copy
         was built) allocates the position maps and synchronises; later calls only launch."""
-        if not (values.is_cuda and values.dtype == torch.float32 and values.is_contiguous() and values.numel() == self.nnz):
-            raise ValueError(f"set_values: values must be a contiguous cuda float32 tensor of {self.nnz} elements")
+        _checked("set_values", "values", values, self.nnz)
         _lib.check(_lib.lib().mllp_graph_set_values(self._h, _lib.ptr(values) if self.nnz else _lib.ptr(self.x1),
                                                     _lib.current_stream()))
         self._fwd_token = getattr(self, "_fwd_token", 0) + 1      # (model.py: a pending autograd backward must not run)
@@ -262,8 +297,8 @@ class LPBatch:
         `row_scale` [M] / `col_scale` [N] are cuda float32 tensors; None = ones.  `normalize` brings the rescaled batch
         back to the normalization the weights were trained on (it cancels a positive row scaling, a column scaling stays)."""
         for t, n, what in ((row_scale, self.M, "row_scale"), (col_scale, self.N, "col_scale")):
-            if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n):
-                raise ValueError(f"rescale: {what} must be a contiguous cuda float32 tensor of {n} elements")
+            if t is not None:
+                _checked("rescale", what, t, n)
         _lib.check(_lib.lib().mllp_graph_scale_values(self._h, _lib.ptr(row_scale), _lib.ptr(col_scale),
                                                       _lib.current_stream()))
         self._fwd_token = getattr(self, "_fwd_token", 0) + 1
@@ -300,14 +335,10 @@ class LPBatch:
         (`certificate` reports).  Every value-holding array of the batch is refreshed as by `set_values`; a backward needs
         a new forward.  A setup call: validates the pivots on the device and synchronises; a bad pivot raises MllpError
         with nothing written."""
-        if not (pivot.is_cuda and pivot.dtype == torch.int32 and pivot.is_contiguous() and pivot.numel() == self.M):
-            raise ValueError(f"plant_basis: pivot must be a contiguous cuda int32 tensor of {self.M} elements")
+        _checked("plant_basis", "pivot", pivot, self.M, torch.int32)
         for t, n, what in ((xstar, self.N, "xstar"), (ystar, self.M, "ystar"), (slack, self.N, "slack")):
-            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n):
-                raise ValueError(f"plant_basis: {what} must be a contiguous cuda float32 tensor of {n} elements")
-        # (at least one element each: an empty torch tensor has a null pointer, which the library refuses)
-        pad = lambda t, dt: t if t.numel() else torch.zeros(1, dtype=dt, device=self.x1.device)   # noqa: E731
-        args = [pad(pivot, torch.int32)] + [pad(t, torch.float32) for t in (xstar, ystar, slack, self.x1, self.x2, self._labels)]
+            _checked("plant_basis", what, t, n)
+        args = [_pad(t) for t in (pivot, xstar, ystar, slack, self.x1, self.x2, self._labels)]
         _lib.check(_lib.lib().mllp_graph_plant_basis(self._h, *[_lib.ptr(a) for a in args[:4]], float(dominance), float(floor),
                                                      *[_lib.ptr(a) for a in args[4:]], _lib.current_stream()))
         self._fwd_token = getattr(self, "_fwd_token", 0) + 1      # (as set_values; the library invalidated its input copies)
@@ -322,17 +353,15 @@ class LPBatch:
         library."""
         basis = self._labels if basis is None else basis
         for t, n, what in ((x, self.N, "x"), (y, self.M, "y"), (basis, self.N, "basis")):
-            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n):
-                raise ValueError(f"certificate: {what} must be a contiguous cuda float32 tensor of {n} elements")
+            _checked("certificate", what, t, n)
         dev = self.x1.device
         if getattr(self, "_cert_scratch", None) is None:
             n = c_int64()
             _lib.check(_lib.lib().mllp_lp_certificate_scratch_bytes(self._h, ctypes.byref(n)))
             self._cert_scratch = torch.empty(n.value // 4, device=dev, dtype=torch.float32)
         if out is None:
-            out = torch.empty(max(self.n_inst, 1), 6, device=dev, dtype=torch.float32)[:self.n_inst]
-        pad = lambda t: t if t.numel() else torch.zeros(1, device=dev)      # noqa: E731
-        _lib.check(_lib.lib().mllp_lp_certificate(self._h, *[_lib.ptr(pad(t)) for t in (self.x1, self.x2, x, y, basis)],
+            out = _cut(_out(self.n_inst * 6, torch.float32, dev), self.n_inst, 6)
+        _lib.check(_lib.lib().mllp_lp_certificate(self._h, *[_lib.ptr(_pad(t)) for t in (self.x1, self.x2, x, y, basis)],
                                                   _lib.ptr(out), _lib.ptr(self._cert_scratch), _lib.current_stream()))
         return out
 
@@ -851,24 +880,21 @@ class LPBatch:
         the next call compute it again."""
         key = (self._labels.data_ptr(), self._labels._version)
         if self._balanced_pw is None or self._balanced_pw[0] != key:
-            out = torch.empty(max(self.n_inst, 1), device=self._labels.device, dtype=torch.float32)
-            y = self._labels if self.N else torch.zeros(1, device=out.device)       # (a batch without columns)
-            _lib.check(_lib.lib().mllp_balanced_pos_weight(self._h, _lib.ptr(y), _lib.ptr(out), _lib.current_stream()))
-            self._balanced_pw = (key, out[:self.n_inst])
+            out = _out(self.n_inst, torch.float32, self._labels.device)
+            _lib.check(_lib.lib().mllp_balanced_pos_weight(self._h, _lib.ptr(_pad(self._labels)), _lib.ptr(out), _lib.current_stream()))
+            self._balanced_pw = (key, _cut(out, self.n_inst))
         return self._balanced_pw[1]
 
-    def _per_instance(self, v, what, allow_balanced=False):
+    def _per_instance(self, v, who, what, allow_balanced=False):
         """None, a float (broadcast), a tensor [n_inst] or (pos_weight only) 'balanced' -> None or a cuda float32 [n_inst]"""
         if v is None:
             return None
         if isinstance(v, str):
             if allow_balanced and v == "balanced":
                 return self.balanced_pos_weight()
-            raise ValueError(f"{what}: {v!r} is not understood" + (" (a float, a tensor [n_inst] or 'balanced')" if allow_balanced else ""))
+            raise ValueError(f"{who}: {what}: {v!r} is not understood" + (" (a float, a tensor [n_inst] or 'balanced')" if allow_balanced else ""))
         if isinstance(v, torch.Tensor):
-            if not (v.is_cuda and v.dtype == torch.float32 and v.is_contiguous() and v.numel() == self.n_inst):
-                raise ValueError(f"{what} must be a contiguous cuda float32 tensor of {self.n_inst} elements")
-            return v
+            return _checked(who, what, v, self.n_inst)
         consts = self.__dict__.setdefault("_inst_consts", {})
         if float(v) not in consts:
             consts[float(v)] = torch.full((max(self.n_inst, 1),), float(v), device=self.x1.device, dtype=torch.float32)
@@ -881,25 +907,29 @@ class LPBatch:
         None (ones), a float or a tensor [n_inst]; `pos_weight`: None (ones), a float, a tensor [n_inst] or 'balanced'.
         Returns dict(loss [1], inst_loss [n_inst], dlogits [N]) of device tensors; those not named in `want` are None and
         cost nothing.  Bitwise reproducible, the same bits for an instance alone and inside any batch; no sync."""
-        want = (want,) if isinstance(want, str) else tuple(want)
-        bad = [w for w in want if w not in ("loss", "inst_loss", "dlogits")]
-        if bad or not want:
-            raise ValueError(f"weighted_loss: want must name some of 'loss', 'inst_loss', 'dlogits' (got {want!r})")
-        if not (logits.is_cuda and logits.dtype == torch.float32 and logits.is_contiguous() and logits.numel() == self.N):
-            raise ValueError(f"weighted_loss: logits must be a contiguous cuda float32 tensor of {self.N} elements")
+        want = _parse_want("weighted_loss", want, ("loss", "inst_loss", "dlogits"), "want must name some of 'loss', 'inst_loss', 'dlogits'")
+        _checked("weighted_loss", "logits", logits, self.N)
         dev = logits.device
-        iw = self._per_instance(inst_weight, "weighted_loss: inst_weight")
-        pw = self._per_instance(pos_weight, "weighted_loss: pos_weight", allow_balanced=True)
-        # (at least one element each: an empty torch tensor has a null pointer, which the library reads as "not wanted")
-        loss = torch.empty(1, device=dev, dtype=torch.float32) if "loss" in want else None
+        iw = self._per_instance(inst_weight, "weighted_loss", "inst_weight")
+        pw = self._per_instance(pos_weight, "weighted_loss", "pos_weight", allow_balanced=True)
+        loss = _out(1, torch.float32, dev, "loss" in want)
         # (loss without inst_loss: the L_k still get a buffer -- without one the library walks the instances in ONE workgroup)
-        inst = torch.empty(max(self.n_inst, 1), device=dev, dtype=torch.float32) if {"inst_loss", "loss"} & set(want) else None
-        dz = torch.empty(max(self.N, 1), device=dev, dtype=torch.float32) if "dlogits" in want else None
-        z, y = (logits, self._labels) if self.N else (torch.zeros(1, device=dev),) * 2      # (a batch without columns)
-        _lib.check(_lib.lib().mllp_weighted_loss(self._h, _lib.ptr(z), _lib.ptr(y), _lib.ptr(iw), _lib.ptr(pw), _lib.ptr(dz),
-                                                 _lib.ptr(inst), _lib.ptr(loss), _lib.current_stream()))
-        return dict(loss=loss, inst_loss=inst[:self.n_inst] if "inst_loss" in want else None,
-                    dlogits=None if dz is None else dz[:self.N])
+        inst = _out(self.n_inst, torch.float32, dev, {"inst_loss", "loss"} & set(want))
+        dz = _out(self.N, torch.float32, dev, "dlogits" in want)
+        _lib.check(_lib.lib().mllp_weighted_loss(self._h, _lib.ptr(_pad(logits)), _lib.ptr(_pad(self._labels)), _lib.ptr(iw), _lib.ptr(pw),
+                                                 _lib.ptr(dz), _lib.ptr(inst), _lib.ptr(loss), _lib.current_stream()))
+        return dict(loss=loss, inst_loss=_cut(inst, self.n_inst) if "inst_loss" in want else None, dlogits=_cut(dz, self.N))
+
+    def _loss_step_outputs(self, dev, logits, loss, inst_loss, grads):
+        """What `loss_step_weighted` and `loss_step_topm` do first: the outputs the caller did not give, and `last_dlogits`,
+        made once and kept on the batch"""
+        logits = torch.empty(self.N, device=dev, dtype=torch.float32) if logits is None else logits
+        loss = torch.empty(1, device=dev, dtype=torch.float32) if loss is None else loss
+        inst_loss = _cut(_out(self.n_inst, torch.float32, dev), self.n_inst) if inst_loss is None else inst_loss
+        grads = torch.empty(_lib.NUM_PARAMS, device=dev, dtype=torch.float32) if grads is None else grads
+        if getattr(self, "last_dlogits", None) is None:
+            self.last_dlogits = _cut(_out(self.N, torch.float32, dev), self.N)
+        return logits, loss, inst_loss, grads
 
     def loss_step_weighted(self, params, inst_weight=None, pos_weight=None, logits=None, loss=None, inst_loss=None,
                            grads=None):
@@ -907,15 +937,9 @@ class LPBatch:
         Weights as in `weighted_loss`; inst_weight None is all ONES (loss = sum_k L_k) -- pass 1 / n_inst for the batch mean
         that `loss_step` computes.  Returns (loss [1], logits [N], grads, inst_loss [n_inst]); logits are bit for bit those
         of `forward`, and `input_grads` may follow with `self.last_dlogits`."""
-        dev = params.device
-        logits = torch.empty(self.N, device=dev, dtype=torch.float32) if logits is None else logits
-        loss = torch.empty(1, device=dev, dtype=torch.float32) if loss is None else loss
-        inst_loss = torch.empty(max(self.n_inst, 1), device=dev, dtype=torch.float32)[:self.n_inst] if inst_loss is None else inst_loss
-        grads = torch.empty(_lib.NUM_PARAMS, device=dev, dtype=torch.float32) if grads is None else grads
-        if getattr(self, "last_dlogits", None) is None:
-            self.last_dlogits = torch.empty(max(self.N, 1), device=dev, dtype=torch.float32)[:self.N]
-        iw = self._per_instance(inst_weight, "loss_step_weighted: inst_weight")
-        pw = self._per_instance(pos_weight, "loss_step_weighted: pos_weight", allow_balanced=True)
+        logits, loss, inst_loss, grads = self._loss_step_outputs(params.device, logits, loss, inst_loss, grads)
+        iw = self._per_instance(inst_weight, "loss_step_weighted", "inst_weight")
+        pw = self._per_instance(pos_weight, "loss_step_weighted", "pos_weight", allow_balanced=True)
         self._check_inputs()
         self._folded = None          # (as forward)
         _lib.check(_lib.lib().mllp_gnn_loss_step_weighted(self._h, _lib.ptr(params), _lib.ptr(self.x1), _lib.ptr(self.x2),
@@ -938,12 +962,7 @@ class LPBatch:
 
     def _inst_ids(self, inst_id, what):
         """None (instance k has id k) or an int32 cuda tensor [n_inst]: the id that seeds each instance's noise"""
-        if inst_id is None:
-            return None
-        if not (isinstance(inst_id, torch.Tensor) and inst_id.is_cuda and inst_id.dtype == torch.int32
-                and inst_id.is_contiguous() and inst_id.numel() == self.n_inst):
-            raise ValueError(f"{what}: inst_id must be a contiguous cuda int32 tensor of {self.n_inst} elements")
-        return inst_id
+        return None if inst_id is None else _checked(what, "inst_id", inst_id, self.n_inst, torch.int32)
 
     @staticmethod
     def _topm_args(what, tau, sigma, n_samples, seed):
@@ -964,29 +983,21 @@ class LPBatch:
         'inst_loss' [n_inst], 'dlogits' [N], 'prob' [N] (noise-free p, sums to m_k) and 'info' [n_inst, 4] = (nu, Q,
         sum p - m_k, largest iteration count); those not named are None and cost nothing.  Bitwise reproducible, the same
         bits for an instance alone (given its `inst_id`) and inside any batch; no sync."""
-        want = (want,) if isinstance(want, str) else tuple(want)
-        if not want or [w for w in want if w not in self._TOPM_WANT]:
-            raise ValueError(f"topm_loss: want must name some of {self._TOPM_WANT} (got {want!r})")
-        if not (logits.is_cuda and logits.dtype == torch.float32 and logits.is_contiguous() and logits.numel() == self.N):
-            raise ValueError(f"topm_loss: logits must be a contiguous cuda float32 tensor of {self.N} elements")
+        want = _parse_want("topm_loss", want, self._TOPM_WANT, f"want must name some of {self._TOPM_WANT}")
+        _checked("topm_loss", "logits", logits, self.N)
         tau, sigma, n_samples, seed = self._topm_args("topm_loss", tau, sigma, n_samples, seed)
-        dev = logits.device
-        iw = self._per_instance(inst_weight, "topm_loss: inst_weight")
-        pw = self._per_instance(pos_weight, "topm_loss: pos_weight", allow_balanced=True)
+        iw = self._per_instance(inst_weight, "topm_loss", "inst_weight")
+        pw = self._per_instance(pos_weight, "topm_loss", "pos_weight", allow_balanced=True)
         ids = self._inst_ids(inst_id, "topm_loss")
-        new = lambda n: torch.empty(max(n, 1), device=dev, dtype=torch.float32)  # noqa: E731  (never a null pointer)
-        loss = new(1) if "loss" in want else None
-        inst = new(self.n_inst) if {"inst_loss", "loss"} & set(want) else None       # (as weighted_loss: never the serial launch)
-        dz = new(self.N) if "dlogits" in want else None
-        prob = new(self.N) if "prob" in want else None
-        info = new(4 * self.n_inst) if "info" in want else None
-        z, y = (logits, self._labels) if self.N else (torch.zeros(1, device=dev),) * 2
-        _lib.check(_lib.lib().mllp_topm_loss(self._h, _lib.ptr(z), _lib.ptr(y), _lib.ptr(iw), _lib.ptr(pw), _lib.ptr(ids), tau, sigma,
-                                             n_samples, seed, _lib.ptr(dz), _lib.ptr(inst), _lib.ptr(loss), _lib.ptr(prob),
-                                             _lib.ptr(info), _lib.current_stream()))
-        return dict(loss=loss, inst_loss=inst[:self.n_inst] if "inst_loss" in want else None,
-                    dlogits=None if dz is None else dz[:self.N], prob=None if prob is None else prob[:self.N],
-                    info=None if info is None else info[:4 * self.n_inst].view(self.n_inst, 4))
+        new = lambda n, wanted: _out(n, torch.float32, logits.device, wanted)  # noqa: E731
+        loss = new(1, "loss" in want)
+        inst = new(self.n_inst, {"inst_loss", "loss"} & set(want))       # (as weighted_loss: never the serial launch)
+        dz, prob, info = new(self.N, "dlogits" in want), new(self.N, "prob" in want), new(4 * self.n_inst, "info" in want)
+        _lib.check(_lib.lib().mllp_topm_loss(self._h, _lib.ptr(_pad(logits)), _lib.ptr(_pad(self._labels)), _lib.ptr(iw), _lib.ptr(pw),
+                                             _lib.ptr(ids), tau, sigma, n_samples, seed, _lib.ptr(dz), _lib.ptr(inst), _lib.ptr(loss),
+                                             _lib.ptr(prob), _lib.ptr(info), _lib.current_stream()))
+        return dict(loss=loss, inst_loss=_cut(inst, self.n_inst) if "inst_loss" in want else None, dlogits=_cut(dz, self.N),
+                    prob=_cut(prob, self.N), info=_cut(info, self.n_inst, 4))
 
     def topm_prob(self, logits, tau=1.0):
         """The soft basis: p_i = sigmoid(z_i / tau + nu_k) with sum_i p_i = m_k per instance ([N] cuda float32; 0 for an
@@ -999,15 +1010,9 @@ class LPBatch:
         as `topm_loss` and `loss_step_weighted`.  Returns (loss [1], logits [N], grads, inst_loss [n_inst]); logits are bit
         for bit those of `forward`, and `input_grads` may follow with `self.last_dlogits`."""
         tau, sigma, n_samples, seed = self._topm_args("loss_step_topm", tau, sigma, n_samples, seed)
-        dev = params.device
-        logits = torch.empty(self.N, device=dev, dtype=torch.float32) if logits is None else logits
-        loss = torch.empty(1, device=dev, dtype=torch.float32) if loss is None else loss
-        inst_loss = torch.empty(max(self.n_inst, 1), device=dev, dtype=torch.float32)[:self.n_inst] if inst_loss is None else inst_loss
-        grads = torch.empty(_lib.NUM_PARAMS, device=dev, dtype=torch.float32) if grads is None else grads
-        if getattr(self, "last_dlogits", None) is None:
-            self.last_dlogits = torch.empty(max(self.N, 1), device=dev, dtype=torch.float32)[:self.N]
-        iw = self._per_instance(inst_weight, "loss_step_topm: inst_weight")
-        pw = self._per_instance(pos_weight, "loss_step_topm: pos_weight", allow_balanced=True)
+        logits, loss, inst_loss, grads = self._loss_step_outputs(params.device, logits, loss, inst_loss, grads)
+        iw = self._per_instance(inst_weight, "loss_step_topm", "inst_weight")
+        pw = self._per_instance(pos_weight, "loss_step_topm", "pos_weight", allow_balanced=True)
         ids = self._inst_ids(inst_id, "loss_step_topm")
         self._check_inputs()
         self._folded = None          # (as forward)
@@ -1025,16 +1030,11 @@ class LPBatch:
         (uint8 [N]), `.index` (int32 [M], instance-local column ids, ascending, at the instance's constraint offset) and
         `.stats` (float32 [n_inst, 2] = threshold, runner-up) are device tensors; those not named in `want` are None and
         cost nothing."""
-        want = (want,) if isinstance(want, str) else tuple(want)
-        bad = [w for w in want if w not in ("mask", "index", "stats")]
-        if bad or not want:
-            raise ValueError(f"predict_basis: want must name some of 'mask', 'index', 'stats' (got {want!r})")
-        if not (logits.is_cuda and logits.dtype == torch.float32 and logits.is_contiguous() and logits.numel() == self.N):
-            raise ValueError(f"predict_basis: logits must be a contiguous cuda float32 tensor of {self.N} elements")
+        want = _parse_want("predict_basis", want, _SELECT_WANT, "want must name some of 'mask', 'index', 'stats'")
+        _checked("predict_basis", "logits", logits, self.N)
         bufs = _select_outputs(want, self.N, self.M, self.n_inst, logits.device)
         _lib.check(_lib.lib().mllp_topm_select(self._h, _lib.ptr(logits), *[_lib.ptr(b) for b in bufs], _lib.current_stream()))
-        mask, index, stats = _select_views(bufs, self.N, self.M)
-        return BasisPrediction(mask, index, stats, self.inst_n, self.inst_m, self.names)
+        return BasisPrediction(_cut(bufs[0], self.N), _cut(bufs[1], self.M), bufs[2], self.inst_n, self.inst_m, self.names)
 
     # ---- repair and solve a predicted basis (mllp_basis_repair; csrc/basis.hip) ---------------------------------
     def _column_segments(self):
@@ -1047,12 +1047,22 @@ class LPBatch:
             self._col_seg = (inst, first)
         return self._col_seg
 
+    def _kept_scratch(self, attr, key, scratch_bytes):
+        """The scratch of a solver call (None when it needs none): asked of the library's entry point `scratch_bytes` once
+        per `key`, the one argument its size depends on, and kept on the batch as `attr` = (key, scratch)"""
+        kept = getattr(self, attr, None)
+        if kept is None or kept[0] != key:
+            n = c_int64()
+            _lib.check(getattr(_lib.lib(), scratch_bytes)(self._h, key, ctypes.byref(n)))
+            kept = (key, torch.empty(n.value // 4, device=self.x1.device, dtype=torch.float32) if n.value else None)
+            setattr(self, attr, kept)
+        return kept[1]
+
     def ranking(self, logits):
         """int32 [N]: the candidate list `repair_basis` walks -- per instance its LOCAL column ids by descending logit, in
         the total order of `predict_basis` (the key of the bit pattern, -0.0 < +0.0), lowest index first among equal
         logits.  Plain torch on the device: the key, then two stable sorts."""
-        if not (logits.is_cuda and logits.dtype == torch.float32 and logits.is_contiguous() and logits.numel() == self.N):
-            raise ValueError(f"ranking: logits must be a contiguous cuda float32 tensor of {self.N} elements")
+        _checked("ranking", "logits", logits, self.N)
         inst, first = self._column_segments()
         v = logits.reshape(-1).view(torch.int32)
         key = torch.where(v >= 0, v, v ^ 0x7FFFFFFF)        # signed and monotone in the select kernels' unsigned key
@@ -1070,38 +1080,25 @@ class LPBatch:
         instances with more rows are skipped (status code 2); None = the batch's largest m.  Returns a `BasisRepair` of
         device tensors; those not named in `want` are None and cost nothing (`x` and `y` come together, `status` always).
         The scratch is asked for once per max_m and kept on the batch.  No sync."""
-        want = (want,) if isinstance(want, str) else tuple(want)
         names = ("basis", "col_of_row", "x", "y", "quality")
-        if [w for w in want if w not in names] or ("x" in want) != ("y" in want):
-            raise ValueError(f"repair_basis: want names some of {names}, 'x' and 'y' together (got {want!r})")
+        want = _parse_want("repair_basis", want, names, f"want names some of {names}, 'x' and 'y' together", allow_empty=True,
+                           together=("x", "y"))
         if (logits is None) == (order is None):
             raise ValueError("repair_basis: give logits or order, one of them")
         if order is None:
             order = self.ranking(logits)
-        if not (order.is_cuda and order.dtype == torch.int32 and order.is_contiguous() and order.numel() == self.N):
-            raise ValueError(f"repair_basis: order must be a contiguous cuda int32 tensor of {self.N} elements")
-        dev = self.x1.device
+        _checked("repair_basis", "order", order, self.N, torch.int32)
+        dev, f32, i32 = self.x1.device, torch.float32, torch.int32
         max_m = max(self.inst_m, default=0) if max_m is None else int(max_m)
-        kept = getattr(self, "_repair_scratch", None)
-        if kept is None or kept[0] != max_m:
-            n = c_int64()
-            _lib.check(_lib.lib().mllp_basis_repair_scratch_bytes(self._h, max_m, ctypes.byref(n)))
-            kept = self._repair_scratch = (max_m, torch.empty(n.value // 4, device=dev, dtype=torch.float32) if n.value else None)
-        # (at least one element each: an empty torch tensor has a null pointer, which the library reads as "not wanted")
-        new = lambda n, dt: torch.empty(max(n, 1), dtype=dt, device=dev)      # noqa: E731
-        out = dict(basis=new(self.N, torch.float32) if "basis" in want else None,
-                   col_of_row=new(self.M, torch.int32) if "col_of_row" in want else None,
-                   x=new(self.N, torch.float32) if "x" in want else None, y=new(self.M, torch.float32) if "y" in want else None,
-                   status=new(self.n_inst * 4, torch.int32), quality=new(self.n_inst * 2, torch.float32) if "quality" in want else None)
-        pad = lambda t, dt=torch.float32: t if t.numel() else torch.zeros(1, dtype=dt, device=dev)   # noqa: E731
-        _lib.check(_lib.lib().mllp_basis_repair(self._h, _lib.ptr(pad(self.x1)), _lib.ptr(pad(self.x2)), _lib.ptr(pad(order, torch.int32)),
-                                                float(tol), max_m, *[_lib.ptr(out[k]) for k in ("basis", "col_of_row", "x", "y", "status",
-                                                                                               "quality")],
-                                                _lib.ptr(kept[1]), _lib.current_stream()))
-        cut = lambda t, n: None if t is None else t[:n]      # noqa: E731
-        return BasisRepair(cut(out["basis"], self.N), cut(out["col_of_row"], self.M), cut(out["x"], self.N), cut(out["y"], self.M),
-                           out["status"][:self.n_inst * 4].view(self.n_inst, 4),
-                           None if out["quality"] is None else out["quality"][:self.n_inst * 2].view(self.n_inst, 2))
+        scratch = self._kept_scratch("_repair_scratch", max_m, "mllp_basis_repair_scratch_bytes")
+        basis, col_of_row = _out(self.N, f32, dev, "basis" in want), _out(self.M, i32, dev, "col_of_row" in want)
+        x, y = _out(self.N, f32, dev, "x" in want), _out(self.M, f32, dev, "y" in want)
+        status, quality = _out(self.n_inst * 4, i32, dev), _out(self.n_inst * 2, f32, dev, "quality" in want)
+        _lib.check(_lib.lib().mllp_basis_repair(self._h, _lib.ptr(_pad(self.x1)), _lib.ptr(_pad(self.x2)), _lib.ptr(_pad(order)), float(tol),
+                                                max_m, *[_lib.ptr(t) for t in (basis, col_of_row, x, y, status, quality)],
+                                                _lib.ptr(scratch), _lib.current_stream()))
+        return BasisRepair(_cut(basis, self.N), _cut(col_of_row, self.M), _cut(x, self.N), _cut(y, self.M),
+                           _cut(status, self.n_inst, 4), _cut(quality, self.n_inst, 2))
 
     def solve_basis(self, basis, tol=2.0 ** -12, max_m=None, want=("basis", "col_of_row", "x", "y", "quality")):
         """The basic solution of a GIVEN basis (labels, a solver's output; [N], nonzero = basic): `repair_basis` on the list
@@ -1143,10 +1140,8 @@ class LPBatch:
         `refactor_every` = R > 0: the basis is factorized afresh after every R pivots; `stall_pivots` = S > 0: Bland's rule
         after S consecutive degenerate pivots of a stage.  With both 0 this is mllp_basis_simplex as ever; otherwise
         mllp_basis_simplex_guarded (code 7: a basis could not be refactorized), and the result has `.guard`."""
-        want = (want,) if isinstance(want, str) else tuple(want)
         names = ("basis", "col_of_row", "trace")
-        if [w for w in want if w not in names]:
-            raise ValueError(f"simplex: want names some of {names} (got {want!r})")
+        want = _parse_want("simplex", want, names, f"want names some of {names}", allow_empty=True)
         if isinstance(start, BasisRepair):
             start = start.basis
         if start is None or not (start.is_cuda and start.numel() == self.N):
@@ -1158,35 +1153,24 @@ class LPBatch:
         refactor_every, stall_pivots = int(refactor_every), int(stall_pivots)
         if refactor_every < 0 or stall_pivots < 0:
             raise ValueError("simplex: refactor_every and stall_pivots must not be negative")
-        dev = self.x1.device
+        dev, i32 = self.x1.device, torch.int32
         max_m = max(self.inst_m, default=0) if max_m is None else int(max_m)
-        kept = getattr(self, "_simplex_scratch", None)
-        if kept is None or kept[0] != max_m:
-            n = c_int64()
-            _lib.check(_lib.lib().mllp_basis_simplex_scratch_bytes(self._h, max_m, ctypes.byref(n)))
-            kept = self._simplex_scratch = (max_m, torch.empty(n.value // 4, device=dev, dtype=torch.float32) if n.value else None)
-        # (at least one element each: an empty torch tensor has a null pointer, which the library reads as "not wanted")
-        new = lambda n, dt: torch.empty(max(n, 1), dtype=dt, device=dev)      # noqa: E731
-        basis, status = new(self.N, torch.float32), new(self.n_inst * 4, torch.int32)
-        col_of_row = new(self.M, torch.int32) if "col_of_row" in want else None
-        trace = new(self.n_inst * max_pivots * 2, torch.int32) if "trace" in want else None
-        pad = lambda t: t if t.numel() else torch.zeros(1, dtype=torch.float32, device=dev)   # noqa: E731
-        guard = None
-        if refactor_every == 0 and stall_pivots == 0:
-            _lib.check(_lib.lib().mllp_basis_simplex(self._h, _lib.ptr(pad(self.x1)), _lib.ptr(pad(self.x2)), _lib.ptr(pad(start)),
-                                                     float(tol), float(ftol), float(dtol), float(ptol), float(dshift), max_pivots, max_m,
-                                                     _lib.ptr(basis), _lib.ptr(col_of_row), _lib.ptr(trace), _lib.ptr(status),
-                                                     _lib.ptr(kept[1]), _lib.current_stream()))
+        scratch = self._kept_scratch("_simplex_scratch", max_m, "mllp_basis_simplex_scratch_bytes")
+        basis, status = _out(self.N, torch.float32, dev), _out(self.n_inst * 4, i32, dev)
+        col_of_row = _out(self.M, i32, dev, "col_of_row" in want)
+        trace = _out(self.n_inst * max_pivots * 2, i32, dev, "trace" in want)
+        guarded = refactor_every != 0 or stall_pivots != 0
+        guard = _out(self.n_inst * 2, i32, dev, guarded)
+        head = (self._h, _lib.ptr(_pad(self.x1)), _lib.ptr(_pad(self.x2)), _lib.ptr(_pad(start)), float(tol), float(ftol), float(dtol),
+                float(ptol), float(dshift), max_pivots, max_m)
+        outs = (_lib.ptr(basis), _lib.ptr(col_of_row), _lib.ptr(trace), _lib.ptr(status))
+        if guarded:
+            _lib.check(_lib.lib().mllp_basis_simplex_guarded(*head, refactor_every, stall_pivots, *outs, _lib.ptr(guard),
+                                                             _lib.ptr(scratch), _lib.current_stream()))
         else:
-            guard = new(self.n_inst * 2, torch.int32)
-            _lib.check(_lib.lib().mllp_basis_simplex_guarded(
-                self._h, _lib.ptr(pad(self.x1)), _lib.ptr(pad(self.x2)), _lib.ptr(pad(start)), float(tol), float(ftol), float(dtol),
-                float(ptol), float(dshift), max_pivots, max_m, refactor_every, stall_pivots, _lib.ptr(basis), _lib.ptr(col_of_row),
-                _lib.ptr(trace), _lib.ptr(status), _lib.ptr(guard), _lib.ptr(kept[1]), _lib.current_stream()))
-            guard = guard[:self.n_inst * 2].view(self.n_inst, 2)
-        return BasisSimplex(basis[:self.N], None if col_of_row is None else col_of_row[:self.M],
-                            None if trace is None else trace[:self.n_inst * max_pivots * 2].view(self.n_inst, max_pivots, 2),
-                            status[:self.n_inst * 4].view(self.n_inst, 4), guard)
+            _lib.check(_lib.lib().mllp_basis_simplex(*head, *outs, _lib.ptr(scratch), _lib.current_stream()))
+        return BasisSimplex(_cut(basis, self.N), _cut(col_of_row, self.M), _cut(trace, self.n_inst, max_pivots, 2),
+                            _cut(status, self.n_inst, 4), _cut(guard, self.n_inst, 2))
 
     def simplex_solved(self, res, feas_tol, opt_tol, tol=2.0 ** -12, max_m=None):
         """What a `BasisSimplex` is worth: `solve_basis(res.basis)` -- a FRESH factorization of the final basis, which the
@@ -1212,36 +1196,28 @@ class LPBatch:
                 raise ValueError(f"{who}: start must be a BasisRepair with x and y")
             x0, y0 = start.x, start.y
         for t, n, what in ((x0, self.N, "x0"), (y0, self.M, "y0")):
-            if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n):
-                raise ValueError(f"{who}: {what} must be a contiguous cuda float32 tensor of {n} elements")
+            if t is not None:
+                _checked(who, what, t, n)
         max_iters, check_every = int(max_iters), int(check_every)
         if scaled:
             params = params[:3] + (int(params[3]),) + params[4:]       # ruiz
         if max_iters < 0 or check_every < 0:
             raise ValueError(f"{who}: max_iters and check_every must not be negative")
-        dev = self.x1.device
+        dev, f32 = self.x1.device, torch.float32
         max_lds_words = (pdhg_scaled_limits if scaled else pdhg_limits)()[0] if max_lds_words is None else int(max_lds_words)
-        kept = getattr(self, f"_{who}_scratch", None)
-        if kept is None or kept[0] != max_lds_words:
-            n = c_int64()
-            _lib.check(getattr(_lib.lib(), f"mllp_lp_{who}_scratch_bytes")(self._h, max_lds_words, ctypes.byref(n)))
-            kept = (max_lds_words, torch.empty(n.value // 4, device=dev, dtype=torch.float32) if n.value else None)
-            setattr(self, f"_{who}_scratch", kept)
-        # (at least one element each: an empty torch tensor has a null pointer, which the library refuses)
-        new = lambda n, dt: torch.empty(max(n, 1), dtype=dt, device=dev)      # noqa: E731
-        x, y = new(self.N, torch.float32), new(self.M, torch.float32)
-        side = (new(self.M, torch.float32), new(self.N, torch.float32)) if scaled else ()         # dr, dc
+        scratch = self._kept_scratch(f"_{who}_scratch", max_lds_words, f"mllp_lp_{who}_scratch_bytes")
+        x, y = _out(self.N, f32, dev), _out(self.M, f32, dev)
+        side = (_out(self.M, f32, dev), _out(self.N, f32, dev)) if scaled else ()         # dr, dc
         kkt_words = 6 if scaled else 4
-        status, kkt = new(self.n_inst * 4, torch.int32), new(self.n_inst * kkt_words, torch.float32)
-        pad = lambda t: t if t.numel() else torch.zeros(1, dtype=torch.float32, device=dev)   # noqa: E731
+        status, kkt = _out(self.n_inst * 4, torch.int32, dev), _out(self.n_inst * kkt_words, f32, dev)
         opt = lambda t: None if t is None or not t.numel() else t                             # noqa: E731
         flag = lambda v: int(bool(v))                                                         # noqa: E731
         _lib.check(getattr(_lib.lib(), f"mllp_lp_{who}")(
-            self._h, _lib.ptr(pad(self.x1)), _lib.ptr(pad(self.x2)), _lib.ptr(opt(x0)), _lib.ptr(opt(y0)), max_iters, check_every,
+            self._h, _lib.ptr(_pad(self.x1)), _lib.ptr(_pad(self.x2)), _lib.ptr(opt(x0)), _lib.ptr(opt(y0)), max_iters, check_every,
             *[f(v) for f, v in zip((float, float, float, int, flag, flag, float), params)], max_lds_words, _lib.ptr(x), _lib.ptr(y),
-            *[_lib.ptr(t) for t in side], _lib.ptr(status), _lib.ptr(kkt), _lib.ptr(kept[1]), _lib.current_stream()))
-        return (x[:self.N], y[:self.M], status[:self.n_inst * 4].view(self.n_inst, 4),
-                kkt[:self.n_inst * kkt_words].view(self.n_inst, kkt_words), *(t[:n] for t, n in zip(side, (self.M, self.N))))
+            *[_lib.ptr(t) for t in side], _lib.ptr(status), _lib.ptr(kkt), _lib.ptr(scratch), _lib.current_stream()))
+        return (_cut(x, self.N), _cut(y, self.M), _cut(status, self.n_inst, 4), _cut(kkt, self.n_inst, kkt_words),
+                *(_cut(t, n) for t, n in zip(side, (self.M, self.N))))
 
     def pdhg(self, max_iters, eps=2.0 ** -10, check_every=64, step=0.9, beta=0.5, x0=None, y0=None, start=None,
              max_lds_words=None):
@@ -1277,17 +1253,13 @@ class LPBatch:
         return self.repair_basis(order=self.ranking(res.x.contiguous()), tol=tol, max_m=max_m, want=("basis", "col_of_row", "x", "y", "quality"))
 
 
+_SELECT_WANT = ("mask", "index", "stats")
+
+
 def _select_outputs(want, n, m, n_seg, dev):
-    """(mask, index, stats) buffers of the select entry points, None where not wanted.  At least one element each: an
-    empty torch tensor has a null pointer, which the library reads as "not wanted"."""
-    return (torch.empty(max(n, 1), dtype=torch.uint8, device=dev) if "mask" in want else None,
-            torch.empty(max(m, 1), dtype=torch.int32, device=dev) if "index" in want else None,
+    """(mask, index, stats) buffers of the select entry points, None where not wanted"""
+    return (_out(n, torch.uint8, dev, "mask" in want), _out(m, torch.int32, dev, "index" in want),
             torch.empty(max(n_seg, 1), 2, dtype=torch.float32, device=dev) if "stats" in want else None)
-
-
-def _select_views(bufs, n, m):
-    mask, index, stats = bufs
-    return (None if mask is None else mask[:n], None if index is None else index[:m], stats)
 
 
 class BasisPrediction:
@@ -1373,10 +1345,7 @@ def pdhg_limits():
 def topm_select_dense(logits, m, want=("mask", "index", "stats")):
     """`LPBatch.predict_basis` for ONE segment without a graph (mllp_topm_select_dense): the m largest of a contiguous
     cuda float32 vector, same order and tie rule.  `.index` has m entries (-1 past the vector's length)."""
-    want = (want,) if isinstance(want, str) else tuple(want)
-    bad = [w for w in want if w not in ("mask", "index", "stats")]
-    if bad or not want:
-        raise ValueError(f"topm_select_dense: want must name some of 'mask', 'index', 'stats' (got {want!r})")
+    want = _parse_want("topm_select_dense", want, _SELECT_WANT, "want must name some of 'mask', 'index', 'stats'")
     if not (logits.is_cuda and logits.dtype == torch.float32 and logits.is_contiguous() and logits.dim() == 1):
         raise ValueError("topm_select_dense: logits must be a contiguous 1-d cuda float32 tensor")
     n, m, dev = int(logits.numel()), int(m), logits.device
@@ -1384,8 +1353,7 @@ def topm_select_dense(logits, m, want=("mask", "index", "stats")):
         raise ValueError("topm_select_dense: m must not be negative")
     bufs = _select_outputs(want, n, m, 1, dev)
     _lib.check(_lib.lib().mllp_topm_select_dense(n, m, _lib.ptr(logits), *[_lib.ptr(b) for b in bufs], _lib.current_stream()))
-    mask, index, stats = _select_views(bufs, n, m)
-    return BasisPrediction(mask, index, stats, [n], [m])
+    return BasisPrediction(_cut(bufs[0], n), _cut(bufs[1], m), bufs[2], [n], [m])
 
 
 def small_step_limits():

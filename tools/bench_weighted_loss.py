@@ -54,7 +54,7 @@ def main():
         return lambda: (b.forward(params, logits), b.backward(params, dl, grads))
 
     from mllp_amd import _lib
-    wt, pw, lo = b2._per_instance(w, "w"), b2.balanced_pos_weight(), torch.zeros(1, device="cuda")
+    wt, pw, lo = b2._per_instance(w, "bench", "w"), b2.balanced_pos_weight(), torch.zeros(1, device="cuda")
 
     def serial():
         _lib.check(_lib.lib().mllp_weighted_loss(b2._h, _lib.ptr(z), _lib.ptr(b2.labels), _lib.ptr(wt), _lib.ptr(pw), None, None,
