@@ -509,6 +509,63 @@ int mllp_lp_pdhg_scaled(const mllp_graph_t* g, const float* d_x1 /*c [N]*/, cons
                         int32_t* d_status /*[n_inst,4]*/, float* d_kkt /*[n_inst,6] or NULL*/, void* d_scratch,
                         void* stream);
 
+/* Solve every instance by preconditioned, restarted HALPERN PDHG with reflection (mllp_amd/csrc/pdhg.hip):
+ * mllp_lp_pdhg_scaled's scaling, step and weight, with the running average replaced by an anchored step,
+ * z <- (k+1)/(k+2) (2 T(z) - z) + 1/(k+2) z_anchor, T one PDHG step, the anchor the last restart point (Lu and Yang's rHPDHG).
+ * Added after ABI 6 without a bump.  mllp_lp_pdhg and mllp_lp_pdhg_scaled are unchanged.
+ * THE RULE.  The LP, the number format and clip are mllp_lp_pdhg's: fp32; fadd, fsub, fmul, fma, fdiv, fsqrt only, each
+ * rounded to nearest, in the expressions written here.
+ *   Scaling, step, weight, start.  mllp_lp_pdhg_scaled's, word for word: dr, dc, tr, tc, eta, w0, w = w0, tau, sigma;
+ *     x = clip(x0), y = y0.  In addition the anchor (xa, ya) = (x, y), the step's output (xh, yh) = (x, y), and k = 0.
+ *   Iteration.  w1 = fdiv((float)(k + 1), (float)(k + 2)), w2 = fdiv(1, (float)(k + 2)), k the number of iterations since the
+ *     last restart before this one; the conversions round to nearest (without restarts k may pass 2^24).
+ *     s_j, g_j as in mllp_lp_pdhg;  xh_j = clip(fsub(x_j, fmul(fmul(tau, tc_j), g_j)));  xbar_j = fsub(fadd(xh_j, xh_j), x_j);
+ *     p_j = reflect ? xbar_j : xh_j;  x_j <- fma(w1, p_j, fmul(w2, xa_j)).
+ *     t_i = sum_j a_ij xbar_j;  yh_i = fadd(y_i, fmul(fmul(sigma, tr_i), fsub(b_i, t_i)));
+ *     q_i = reflect ? fsub(fadd(yh_i, yh_i), y_i) : yh_i;  y_i <- fma(w1, q_i, fmul(w2, ya_i)).  Then k <- k + 1.
+ *     Under reflection the iterate's x may be negative; the iterate is never an output.
+ *   Check, after every check_every iterations.  ONE point, (xh, yh), with mllp_lp_pdhg's three errors of the ORIGINAL LP and
+ *     its NaN-keeping maxima; e is the largest of the three.  e not finite: code 8.  e <= eps: code 0.  Otherwise, if
+ *     e <= fmul(beta, e_last) or 25 k >= 9 (iterations so far): restart.  e_last is +inf at the start.
+ *   Restart, in this order.  (x, y) <- (xh, yh).  With primal_weight != 0, mllp_lp_pdhg_scaled's weight update with
+ *     d_j = fsub(x_j, xa_j) (y likewise, with ya).  (xa, ya) <- (x, y), whether the weight is on or not, moved or not.
+ *     k <- 0, e_last = e, restarts + 1.
+ *   Output.  Always (xh, yh): at code 0 and code 8 the point that was checked; at code 6 the last iteration's point (the
+ *     start when max_iters == 0), with its errors evaluated.  check_every == 0: no checks and no restarts, code 6.
+ *   Order.  mllp_lp_pdhg's.
+ *   Identity with mllp_lp_pdhg_scaled.  At max_iters = 1, d_x and d_y are that call's at max_iters = 1, check_every = 0, bit
+ *     for bit, for either reflect (the first step's output does not depend on w1, w2).  d_dr, d_dc, eta and w0 are that call's
+ *     bits at any max_iters.
+ * WHAT THIS RULE STILL DOES NOT DO.  No adaptive step size; no infeasibility detection (an infeasible or unbounded LP ends
+ * with code 6 or 8); no feasibility polishing; fp32 residuals bottom out around 1e-6.  It changes how fast an instance
+ * converges -- usually fewer iterations than mllp_lp_pdhg_scaled, on some instances more -- and it is no superset: on Netlib
+ * at 1e-3 it solves four instances that call does not and misses four that it does; most instances that
+ * stall there stall here.  An iteration costs 1 to 15 % more than that call's.  reflect = 0 is the unreflected Halpern
+ * iteration, which is slower than mllp_lp_pdhg_scaled; it exists to pin the reflection in tests.
+ *   d_x1 .. beta, ruiz_passes, pock_chambolle, primal_weight, weight_span, max_lds_words, d_x, d_y, d_dr, d_dc : as
+ *             mllp_lp_pdhg_scaled.   reflect : 0 or not 0.
+ *   d_status [n_inst, 4] int32, required : {code, iterations, restarts, 0}.
+ *   d_kkt [n_inst, 6] or NULL : {primal, dual, gap of the output, eta, w0, the final w}.
+ *   d_scratch : mllp_lp_pdhg_halpern_scratch_bytes(g, max_lds_words) bytes, which is mllp_lp_pdhg_scaled_scratch_bytes' closed
+ *             form: the LDS image stays 3 n + 2 m words (x, xbar, xh, y, yh) and the anchor is that call's (xr, yr) in the
+ *             2 n + 2 m side words.  mllp_lp_pdhg_halpern_limits: mllp_lp_pdhg_scaled_limits' three values.
+ * Every requested output is fully written for every instance; n = 0 or m = 0 is legal.  A launch function: `stream` only,
+ * no allocation, no synchronisation, hipGraph-capturable; one workgroup per instance, persistent; mllp_lp_pdhg_scaled's
+ * set-up, then two workgroup barriers per iteration.  No float atomics, one writer per word: bitwise reproducible, the same
+ * bits in LDS and in scratch, alone and inside any batch.
+ * mllp_lp_pdhg_halpern is under the MEMORY CONTRACT below as mllp_lp_pdhg is.
+ * MLLP_EINVAL before any launch, nothing written: every refusal of mllp_lp_pdhg_scaled, in its order and words, under this
+ * call's name.                                                                                                            */
+int mllp_lp_pdhg_halpern_limits(int64_t limits[3]);
+int mllp_lp_pdhg_halpern_scratch_bytes(const mllp_graph_t* g, int64_t max_lds_words, int64_t* bytes);
+int mllp_lp_pdhg_halpern(const mllp_graph_t* g, const float* d_x1 /*c [N]*/, const float* d_x2 /*b [M]*/,
+                         const float* d_x0 /*[N] or NULL*/, const float* d_y0 /*[M] or NULL*/, int64_t max_iters,
+                         int64_t check_every, float eps, float step, float beta, int64_t ruiz_passes,
+                         int32_t pock_chambolle, int32_t primal_weight, float weight_span, int32_t reflect,
+                         int64_t max_lds_words, float* d_x /*[N]*/, float* d_y /*[M]*/, float* d_dr /*[M] or NULL*/,
+                         float* d_dc /*[N] or NULL*/, int32_t* d_status /*[n_inst,4]*/, float* d_kkt /*[n_inst,6] or NULL*/,
+                         void* d_scratch, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Plain CSR SpMM (the roofline kernel named in BASELINE.json's metric):
  *   transpose == 0:  Y[M,16] = A   * H[N,16]       transpose == 1:  Y[N,16] = A^T * H[M,16]

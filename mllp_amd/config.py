@@ -52,7 +52,9 @@ HOT_PATH_DEFAULTS = {
                              # vertex its iterate points at certified (LPBatch.pdhg_basis + solved);  `scaled: true` inside
                              # `pdhg` solves by the preconditioned call instead (LPBatch.pdhg_scaled: Ruiz and Pock-Chambolle
                              # scaling, a clamped primal weight) under the same three keys, or `scaled: {ruiz: 10,
-                             # pock_chambolle: true, weight: true, span: 16}` with any of its options; absent == LPBatch.pdhg
+                             # pock_chambolle: true, weight: true, span: 16}` with any of its options; absent == LPBatch.pdhg;
+                             # `halpern: true` (or `halpern: {reflect: false}`) inside `pdhg` solves by the preconditioned call
+                             # with Halpern's iteration (LPBatch.pdhg_halpern), with the `scaled:` options if they are given
     "weight_decay": 0.0,     # decoupled weight decay of the optimizer (torch.optim.AdamW); 0 == the reference's Adam
     "clip_norm": 0.0,        # cap on the global gradient norm of a step (torch.nn.utils.clip_grad_norm_); 0 == no clipping
     "lr_schedule": None,     # the block {warmup: W, total: T, min_ratio: r}: the rate rises linearly over the first W steps, then

@@ -1,7 +1,8 @@
-// pdhg.hip -- restarted PDHG on every instance of the resident batch: mllp_lp_pdhg and its diagonally
-// preconditioned form with a clamped primal weight, mllp_lp_pdhg_scaled.  The rules are stated in
-// include/mllp_hip.h.  ONE kernel source, instantiated on the entry point's argument struct (S = Args::scaled), and one host
-// path.  A first-order solve of  min c'x, A_k x = b, x >= 0  that needs two sparse matrix-vector products per
+// pdhg.hip -- restarted PDHG on every instance of the resident batch: mllp_lp_pdhg, its diagonally
+// preconditioned form with a clamped primal weight, mllp_lp_pdhg_scaled, and the preconditioned form whose
+// iteration is Halpern's anchored step with reflection, mllp_lp_pdhg_halpern.  The rules are stated in
+// include/mllp_hip.h.  ONE kernel source, instantiated on the entry point's argument struct (S = Args::scaled,
+// H = Args::halpern), and one host path.  A first-order solve of  min c'x, A_k x = b, x >= 0  that needs two sparse matrix-vector products per
 // iteration and no factorization: memory O(n + m) per instance, no row limit.
 //
 // One workgroup per instance, persistent over the iterations (the structure of basis.hip and simplex.hip, for the same
@@ -29,6 +30,14 @@
 //   restart    the weight w moves to sqrt(w dy / dx), clamped to [w0 / span, w0 span]; tau = eta / w, sigma = eta w
 // The checks evaluate the ORIGINAL LP either way, in the same expressions and order.
 //
+// What H changes (H implies S); all of it is compiled out of the other four instantiations:
+//   iteration  the step's output goes to xh_j (yh_i), which take the words of xs (ys), and the iterate moves to
+//              w1 p + w2 anchor, p the reflected point 2 xh - x (or xh), w1 = (k + 1) / (k + 2), w2 = 1 / (k + 2), k the
+//              iterations since the last restart; the anchor is S's (xr, yr): one more cached load per finished row
+//   check      ONE point, (xh, yh), which is also the output; no average, no choice between two candidates
+//   restart    (x, y) <- (xh, yh), S's weight update from the anchor, and the anchor moves whether the weight is on or not.
+//              xr, yr are then read by the lane that finishes a row, not by the thread that wrote them: a barrier ends it
+//
 // WHERE THE VECTORS LIVE.  x, xbar, xs, y, ys (3 n + 2 m words) are gathered through idx in every sweep and live in LDS
 // (IN_LDS) when they fit min(max_lds_words, PDHG_LDS_WORDS), in the caller's scratch otherwise -- the same code instantiated
 // twice, the same bits either way.  S's tc, xr, tr, yr (2 n + 2 m words) are read once per finished row by the lane that
@@ -36,7 +45,7 @@
 // 5 n + 4 m words and move instances out of LDS to save one cached load per row.  During the set-up the same words hold dc,
 // C, dr, R.
 //
-// All four instantiations are instruction for instruction what the two files they came from compiled to.
+// The four instantiations of mllp_lp_pdhg and mllp_lp_pdhg_scaled are instruction for instruction what the two files they came from compiled to.
 // That holds the kernel's text to two habits: a value that S changes is DEFINED once, through a ternary on S or an accessor of
 // Args, never set and then overwritten under `if constexpr`; and one deliberate duplicate stays, AbsSum beside ScaledAbs (a
 // ScaledAbs with unit factors folded at compile time moves all four streams).
@@ -261,6 +270,57 @@ struct RowStep {
     }
 };
 
+// the column sweep of a Halpern iteration: the step's output to xh, its reflection to xb (what the row sweep gathers), and
+// the iterate to w1 p + w2 anchor.  One writer per word: x_j, xb_j, xh_j of its own j
+struct HalpernCol {
+    using Acc = float;
+    using Row = NoRow;
+    using By = BySum;
+    const int* __restrict__ idx;
+    const float* __restrict__ val;
+    const float* __restrict__ c;       // of the instance's first column
+    const float *tc, *xa;              // the column's step factor, the anchor
+    int row0;
+    float tau, w1, w2;
+    bool reflect;
+    float *x, *xb, *xh;
+    const float* y;
+    __device__ __forceinline__ Row row(int) const { return {}; }
+    __device__ __forceinline__ void term(const Row&, int e, float& q) const { q = __fmaf_rn(val[e], y[idx[e] - row0], q); }
+    __device__ __forceinline__ void finish(int j, const Row&, float s) const {
+        const float g = __fsub_rn(c[j], s), xo = x[j];
+        const float xn = clip0(__fsub_rn(xo, __fmul_rn(__fmul_rn(tau, tc[j]), g)));
+        const float xf = __fsub_rn(__fadd_rn(xn, xn), xo);
+        xh[j] = xn;
+        xb[j] = xf;
+        x[j] = __fmaf_rn(w1, reflect ? xf : xn, __fmul_rn(w2, xa[j]));
+    }
+};
+
+// the row sweep of a Halpern iteration: y_i, yh_i of its own i
+struct HalpernRow {
+    using Acc = float;
+    using Row = NoRow;
+    using By = BySum;
+    const int* __restrict__ idx;
+    const float* __restrict__ val;
+    const float* __restrict__ b;       // of the instance's first row
+    const float *tr, *ya;              // the row's step factor, the anchor
+    int col0;
+    float sigma, w1, w2;
+    bool reflect;
+    float *y, *yh;
+    const float* xb;
+    __device__ __forceinline__ Row row(int) const { return {}; }
+    __device__ __forceinline__ void term(const Row&, int e, float& q) const { q = __fmaf_rn(val[e], xb[idx[e] - col0], q); }
+    __device__ __forceinline__ void finish(int i, const Row&, float t) const {
+        const float yo = y[i];
+        const float yn = __fadd_rn(yo, __fmul_rn(__fmul_rn(sigma, tr[i]), __fsub_rn(b[i], t)));
+        yh[i] = yn;
+        y[i] = __fmaf_rn(w1, reflect ? __fsub_rn(__fadd_rn(yn, yn), yo) : yn, __fmul_rn(w2, ya[i]));
+    }
+};
+
 // a check's walk of one orientation: the product with the average (a) and with the current iterate (b) of the OTHER
 // side's vector, then the residual against `rhs`: |.| for rows (primal), max(., 0) for columns (dual)
 template <bool ROWS>
@@ -292,10 +352,12 @@ struct EvalSweep {
 };
 
 // The kernel's arguments, one struct per entry point.  The fields of PdhgArgs are fields of ScaledArgs under the same
-// names (pdhg_args fills them by name); `scaled` is the kernel's S, kkt_words a row of d_kkt, and the two accessors are what
-// the shared text reads of ScaledArgs' own fields outside `if constexpr (S)`.
+// names (pdhg_args fills them by name), and HalpernArgs is ScaledArgs with `reflect` (scaled_options fills both); `scaled` is
+// the kernel's S, `halpern` its H, kkt_words a row of d_kkt, and the two accessors are what the shared text reads of ScaledArgs'
+// own fields outside `if constexpr (S)`.
 struct PdhgArgs {
     static constexpr bool scaled = false;
+    static constexpr bool halpern = false;
     static constexpr int kkt_words = 4;
     const int* __restrict__ ptr_m;
     const int* __restrict__ ptr_n;
@@ -322,6 +384,7 @@ struct PdhgArgs {
 
 struct ScaledArgs {
     static constexpr bool scaled = true;
+    static constexpr bool halpern = false;
     static constexpr int kkt_words = 6;
     const int* __restrict__ ptr_m;
     const int* __restrict__ ptr_n;
@@ -349,6 +412,36 @@ struct ScaledArgs {
     __device__ float weight_span() const { return span; }
 };
 
+struct HalpernArgs {
+    static constexpr bool scaled = true;
+    static constexpr bool halpern = true;
+    static constexpr int kkt_words = 6;
+    const int* __restrict__ ptr_m;
+    const int* __restrict__ ptr_n;
+    const int* __restrict__ a_ptr;      // CSR(A)
+    const int* __restrict__ a_idx;
+    const float* __restrict__ a_val;
+    const int* __restrict__ at_ptr;     // CSR(A^T)
+    const int* __restrict__ at_idx;
+    const float* __restrict__ at_val;
+    const float* __restrict__ c;
+    const float* __restrict__ b;
+    const float* x0;
+    const float* y0;
+    long long max_iters, check_every, lim;
+    float eps, step, beta, span;
+    int ruiz_passes, pock_chambolle, primal_weight, reflect;
+    float* x;
+    float* y;
+    float* dr;
+    float* dc;
+    int* status;
+    float* kkt;
+    float* scratch;
+    __device__ bool weigh() const { return primal_weight != 0; }
+    __device__ float weight_span() const { return span; }
+};
+
 struct PdhgErr {
     float p, d, g;      // primal, dual, gap
     __device__ __forceinline__ float worst() const { return nn_max(nn_max(p, d), g); }
@@ -356,7 +449,8 @@ struct PdhgErr {
 
 template <bool IN_LDS, int NT, class Args>
 __global__ __launch_bounds__(NT) void pdhg_kernel(const Args A) {
-    constexpr bool S = Args::scaled;
+    constexpr bool S = Args::scaled, H = Args::halpern;
+    static_assert(S || !H, "the Halpern iteration keeps its anchor in the scaled call's side words");
     constexpr int NW = NT / 64;
     extern __shared__ float pd_lds[];
     __shared__ Sum2 s_part2[NW];
@@ -392,20 +486,20 @@ __global__ __launch_bounds__(NT) void pdhg_kernel(const Args A) {
     }
     float* side = A.scratch + off;
     float* tc = S ? side : nullptr;         // [n] dc, then dc^2                              (these four: S only)
-    float* xr = S ? tc + n : nullptr;       // [n] the set-up's C, then x at the last restart
+    float* xr = S ? tc + n : nullptr;       // [n] the set-up's C, then x at the last restart (H: the anchor)
     float* tr = S ? xr + n : nullptr;       // [m] dr, then dr^2
     float* yr = S ? tr + m : nullptr;       // [m] the set-up's R, then y at the last restart
     float* base = IN_LDS ? pd_lds : S ? yr + m : side;
     float* x = base;                // [n] the iterate
     float* xb = x + n;              // [n] 2 x+ - x
-    float* xs = xb + n;             // [n] the sum of the iterates since the last restart
+    float* xs = xb + n;             // [n] the sum of the iterates since the last restart; H: xh, the last step's output
     float* y = xs + n;              // [m]
-    float* ys = y + m;              // [m]
+    float* ys = y + m;              // [m] likewise; H: yh
     const int* a_ptr = A.a_ptr + row0;
     const int* at_ptr = A.at_ptr + col0;
     const float* c = A.c + col0;
     const float* b = A.b + row0;
-    const bool sums = A.check_every > 0;
+    const bool sums = A.check_every > 0;    // (H: no sums -- whether there are checks)
     const bool weigh = A.weigh();
 
     // ---- start: the clipped start, the norms of b and c, where the block tier's rows are ----
@@ -414,7 +508,8 @@ __global__ __launch_bounds__(NT) void pdhg_kernel(const Args A) {
     for (int j = tid; j < n; j += NT) {
         kn[1] = max(kn[1], abs_bits(c[j]));
         x[j] = A.x0 ? clip0(A.x0[col0 + j]) : 0.0f;
-        if (sums) xs[j] = 0.0f;
+        if constexpr (H) xs[j] = x[j];
+        else if (sums) xs[j] = 0.0f;
         if constexpr (S) tc[j] = 1.0f;
         if (row_tier(at_ptr[j + 1] - at_ptr[j]) == 2) {
             kr[0] = max(kr[0], (unsigned)(0x7fffffff - j));
@@ -424,7 +519,8 @@ __global__ __launch_bounds__(NT) void pdhg_kernel(const Args A) {
     for (int i = tid; i < m; i += NT) {
         kn[0] = max(kn[0], abs_bits(b[i]));
         y[i] = A.y0 ? A.y0[row0 + i] : 0.0f;
-        if (sums) ys[i] = 0.0f;
+        if constexpr (H) ys[i] = y[i];
+        else if (sums) ys[i] = 0.0f;
         if constexpr (S) tr[i] = 1.0f;
         if (row_tier(a_ptr[i + 1] - a_ptr[i]) == 2) {
             kr[2] = max(kr[2], (unsigned)(0x7fffffff - i));
@@ -501,20 +597,21 @@ __global__ __launch_bounds__(NT) void pdhg_kernel(const Args A) {
     float w = w0, tau = S ? __fdiv_rn(eta, w) : eta, sigma = S ? __fmul_rn(eta, w) : eta;
 
     long long cnt = 0;
-    // both points of a check (with_avg) or the current iterate alone, in every thread (barriers inside)
+    // both points of a check (with_avg) or the point (px, py) alone, in every thread (barriers inside)
     auto evaluate = [&](bool with_avg, PdhgErr& avg, PdhgErr& cur) {
+        const float *px = H ? xs : x, *py = H ? ys : y;     // H: the point is the step's output
         const float cntf = (float)cnt;
         unsigned key[4] = {0u, 0u, 0u, 0u};     // primal avg, primal cur, dual avg, dual cur
-        wg_sweep<NT>(a_ptr, m, r_lo, r_hi, EvalSweep<true>{A.a_idx, A.a_val, b, col0, with_avg, cntf, x, xs, &key[0], &key[1]}, s_part2);
-        wg_sweep<NT>(at_ptr, n, c_lo, c_hi, EvalSweep<false>{A.at_idx, A.at_val, c, row0, with_avg, cntf, y, ys, &key[2], &key[3]}, s_part2);
+        wg_sweep<NT>(a_ptr, m, r_lo, r_hi, EvalSweep<true>{A.a_idx, A.a_val, b, col0, with_avg, cntf, px, xs, &key[0], &key[1]}, s_part2);
+        wg_sweep<NT>(at_ptr, n, c_lo, c_hi, EvalSweep<false>{A.at_idx, A.at_val, c, row0, with_avg, cntf, py, ys, &key[2], &key[3]}, s_part2);
         Sum2 cx = {0.0f, 0.0f}, by = {0.0f, 0.0f};
         for (int j = tid; j < n; j += NT) {
-            const float v = x[j], a = with_avg ? __fdiv_rn(xs[j], cntf) : v;
+            const float v = px[j], a = with_avg ? __fdiv_rn(xs[j], cntf) : v;
             cx.a = __fmaf_rn(c[j], a, cx.a);
             cx.b = __fmaf_rn(c[j], v, cx.b);
         }
         for (int i = tid; i < m; i += NT) {
-            const float v = y[i], a = with_avg ? __fdiv_rn(ys[i], cntf) : v;
+            const float v = py[i], a = with_avg ? __fdiv_rn(ys[i], cntf) : v;
             by.a = __fmaf_rn(b[i], a, by.a);
             by.b = __fmaf_rn(b[i], v, by.b);
         }
@@ -534,6 +631,57 @@ __global__ __launch_bounds__(NT) void pdhg_kernel(const Args A) {
     float e_last = inf;
     PdhgErr out = {0.0f, 0.0f, 0.0f};
     while (it < A.max_iters) {
+        if constexpr (H) {
+            // The Halpern iteration, whole, ahead of the text of the other two rules (which an `else` or a shared restart would
+            // move: DESIGN.md 4.24).  cnt is the rule's k; both weights come from the integer, alike in every thread
+            const float w1 = __fdiv_rn((float)(cnt + 1), (float)(cnt + 2)), w2 = __fdiv_rn(1.0f, (float)(cnt + 2));
+            const bool reflect = A.reflect != 0;
+            wg_sweep<NT>(at_ptr, n, c_lo, c_hi, HalpernCol{A.at_idx, A.at_val, c, tc, xr, row0, tau, w1, w2, reflect, x, xb, xs, y}, s_part);
+            __syncthreads();
+            wg_sweep<NT>(a_ptr, m, r_lo, r_hi, HalpernRow{A.a_idx, A.a_val, b, tr, yr, col0, sigma, w1, w2, reflect, y, ys, xb}, s_part);
+            __syncthreads();
+            ++it;
+            ++cnt;
+            if (!sums || ++since < A.check_every) continue;
+            since = 0;
+            PdhgErr unused, at;
+            evaluate(false, unused, at);        // ONE point: (xh, yh), which is the output as it stands
+            const float e = at.worst();
+            if (!finite_bits(e) || e <= A.eps) {
+                code = finite_bits(e) ? PD_CODE_OPTIMAL : PD_CODE_NOT_FINITE;
+                out = at;
+                break;
+            }
+            if (!(e <= __fmul_rn(A.beta, e_last) || 25 * cnt >= 9 * it)) continue;
+            ++restarts;
+            e_last = e;
+            cnt = 0;
+            // The restart: (x, y) <- (xh, yh); how far that is from the anchor, in the metric of the scaled variables, for the
+            // weight; the anchor moves there with or without the weight.  Thread t owns words t, t + NT, ... of all of them
+            Sum2 dd = {0.0f, 0.0f};
+            for (int j = tid; j < n; j += NT) {
+                const float v = xs[j], d = __fsub_rn(v, xr[j]);
+                dd.a = __fmaf_rn(d, __fdiv_rn(d, tc[j]), dd.a);
+                x[j] = xr[j] = v;
+            }
+            for (int i = tid; i < m; i += NT) {
+                const float v = ys[i], d = __fsub_rn(v, yr[i]);
+                dd.b = __fmaf_rn(d, __fdiv_rn(d, tr[i]), dd.b);
+                y[i] = yr[i] = v;
+            }
+            __syncthreads();        // the next sweep reads x, y, xr, yr from the lanes that finish rows, not from their writers
+            if (!weigh) continue;
+            dd = block_tree_sum<NW>(dd, s_part2);       // (every thread gets the tree's bits: the same w, tau, sigma in all)
+            const float dx = sqrt_rn(dd.a), dy = sqrt_rn(dd.b);
+            if (finite_pos(dx) && finite_pos(dy)) {
+                const float raw = sqrt_rn(__fmul_rn(w, __fdiv_rn(dy, dx)));
+                const float up = raw > w_lo ? raw : w_lo;
+                w = up < w_hi ? up : w_hi;
+                tau = __fdiv_rn(eta, w);
+                sigma = __fmul_rn(eta, w);
+            }
+            continue;
+        }
         wg_sweep<NT>(at_ptr, n, c_lo, c_hi, ColStep<S>{A.at_idx, A.at_val, c, tc, row0, tau, sums, x, xb, xs, y}, s_part);
         __syncthreads();
         wg_sweep<NT>(a_ptr, m, r_lo, r_hi, RowStep<S>{A.a_idx, A.a_val, b, tr, col0, sigma, sums, y, ys, xb}, s_part);
@@ -606,8 +754,8 @@ __global__ __launch_bounds__(NT) void pdhg_kernel(const Args A) {
         PdhgErr unused;
         evaluate(false, unused, out);
     }
-    for (int j = tid; j < n; j += NT) A.x[col0 + j] = x[j];
-    for (int i = tid; i < m; i += NT) A.y[row0 + i] = y[i];
+    for (int j = tid; j < n; j += NT) A.x[col0 + j] = (H ? xs : x)[j];
+    for (int i = tid; i < m; i += NT) A.y[row0 + i] = (H ? ys : y)[i];
     if (tid == 0) {
         int* st = A.status + 4 * (size_t)k;
         st[0] = code;
@@ -638,7 +786,7 @@ bool overlaps(const void* a, int64_t a_bytes, const void* b, int64_t b_bytes) {
     return a0 < b0 + (uintptr_t)b_bytes && b0 < a0 + (uintptr_t)a_bytes;
 }
 
-// The checks that both entry points make first, and the arguments that both kernels take.
+// The checks that every entry point makes first, and the arguments that every kernel takes.
 template <class Args>
 int pdhg_args(const char* fn, const mllp_graph_t* g, const float* d_x1, const float* d_x2, const float* d_x0, const float* d_y0,
               int64_t max_iters, int64_t check_every, float eps, float step, float beta, int64_t max_lds_words, float* d_x,
@@ -690,6 +838,29 @@ int pdhg_launch(const char* fn, const mllp_graph_t* g, const Args& args, void* s
     return rc;
 }
 
+// The options that mllp_lp_pdhg_scaled adds to mllp_lp_pdhg's, and mllp_lp_pdhg_halpern takes too: their checks, after pdhg_args'.
+template <class Args>
+int scaled_options(const char* fn, int64_t ruiz_passes, int32_t pock_chambolle, int32_t primal_weight, float weight_span, float* d_dr,
+                   float* d_dc, Args* args) {
+    REQUIRE_FOR(fn, ruiz_passes >= 0 && ruiz_passes <= PDHG_SCALED_MAX_RUIZ, "ruiz_passes must be in 0 .. 64");
+    REQUIRE_FOR(fn, std::isfinite(weight_span) && weight_span >= 1.0f, "weight_span must be finite and at least 1");
+    args->span = weight_span;
+    args->ruiz_passes = (int)ruiz_passes;
+    args->pock_chambolle = pock_chambolle != 0;
+    args->primal_weight = primal_weight != 0;
+    args->dr = d_dr;
+    args->dc = d_dc;
+    return MLLP_OK;
+}
+
+int pdhg_scaled_limits(const char* fn, int64_t* limits) {
+    REQUIRE_FOR(fn, limits, "null argument");
+    limits[0] = PDHG_SCALED_LDS_WORDS;
+    limits[1] = PDHG_SCALED_THREADS;
+    limits[2] = PDHG_SCALED_MAX_RUIZ;
+    return MLLP_OK;
+}
+
 int pdhg_scratch_bytes(const char* fn, const mllp_graph_t* g, int64_t max_lds_words, bool side, int64_t* bytes) {
     REQUIRE_FOR(fn, g && bytes, "null argument");
     REQUIRE_FOR(fn, max_lds_words >= 0, "max_lds_words must not be negative");
@@ -710,19 +881,19 @@ extern "C" int mllp_lp_pdhg_limits(int64_t* limits) {
     return MLLP_OK;
 }
 
-extern "C" int mllp_lp_pdhg_scaled_limits(int64_t* limits) {
-    REQUIRE(limits, "null argument");
-    limits[0] = PDHG_SCALED_LDS_WORDS;
-    limits[1] = PDHG_SCALED_THREADS;
-    limits[2] = PDHG_SCALED_MAX_RUIZ;
-    return MLLP_OK;
-}
+extern "C" int mllp_lp_pdhg_scaled_limits(int64_t* limits) { return pdhg_scaled_limits(__func__, limits); }
+
+extern "C" int mllp_lp_pdhg_halpern_limits(int64_t* limits) { return pdhg_scaled_limits(__func__, limits); }
 
 extern "C" int mllp_lp_pdhg_scratch_bytes(const mllp_graph_t* g, int64_t max_lds_words, int64_t* bytes) {
     return pdhg_scratch_bytes(__func__, g, max_lds_words, false, bytes);
 }
 
 extern "C" int mllp_lp_pdhg_scaled_scratch_bytes(const mllp_graph_t* g, int64_t max_lds_words, int64_t* bytes) {
+    return pdhg_scratch_bytes(__func__, g, max_lds_words, true, bytes);
+}
+
+extern "C" int mllp_lp_pdhg_halpern_scratch_bytes(const mllp_graph_t* g, int64_t max_lds_words, int64_t* bytes) {
     return pdhg_scratch_bytes(__func__, g, max_lds_words, true, bytes);
 }
 
@@ -745,13 +916,20 @@ extern "C" int mllp_lp_pdhg_scaled(const mllp_graph_t* g, const float* d_x1, con
     if (int rc = pdhg_args(__func__, g, d_x1, d_x2, d_x0, d_y0, max_iters, check_every, eps, step, beta, max_lds_words, d_x, d_y,
                            d_status, d_kkt, d_scratch, &args))
         return rc;
-    REQUIRE(ruiz_passes >= 0 && ruiz_passes <= PDHG_SCALED_MAX_RUIZ, "ruiz_passes must be in 0 .. 64");
-    REQUIRE(std::isfinite(weight_span) && weight_span >= 1.0f, "weight_span must be finite and at least 1");
-    args.span = weight_span;
-    args.ruiz_passes = (int)ruiz_passes;
-    args.pock_chambolle = pock_chambolle != 0;
-    args.primal_weight = primal_weight != 0;
-    args.dr = d_dr;
-    args.dc = d_dc;
+    if (int rc = scaled_options(__func__, ruiz_passes, pock_chambolle, primal_weight, weight_span, d_dr, d_dc, &args)) return rc;
+    return pdhg_launch(__func__, g, args, stream);
+}
+
+extern "C" int mllp_lp_pdhg_halpern(const mllp_graph_t* g, const float* d_x1, const float* d_x2, const float* d_x0, const float* d_y0,
+                                    int64_t max_iters, int64_t check_every, float eps, float step, float beta, int64_t ruiz_passes,
+                                    int32_t pock_chambolle, int32_t primal_weight, float weight_span, int32_t reflect,
+                                    int64_t max_lds_words, float* d_x, float* d_y, float* d_dr, float* d_dc, int32_t* d_status,
+                                    float* d_kkt, void* d_scratch, void* stream) {
+    HalpernArgs args;
+    if (int rc = pdhg_args(__func__, g, d_x1, d_x2, d_x0, d_y0, max_iters, check_every, eps, step, beta, max_lds_words, d_x, d_y,
+                           d_status, d_kkt, d_scratch, &args))
+        return rc;
+    if (int rc = scaled_options(__func__, ruiz_passes, pock_chambolle, primal_weight, weight_span, d_dr, d_dc, &args)) return rc;
+    args.reflect = reflect != 0;
     return pdhg_launch(__func__, g, args, stream);
 }

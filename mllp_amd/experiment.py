@@ -228,24 +228,35 @@ def pdhg_counts(batch, logits, report):
     the block's tolerances and max_m).  With `warm` the start is the repaired prediction's basic solution where it is
     usable and cold (zeros, which is what repair_basis leaves) otherwise.  PDHG itself has no row limit.  `scaled: true`
     selects the preconditioned call (LPBatch.pdhg_scaled) with its defaults; a mapping {ruiz, pock_chambolle, weight, span}
-    sets its options.  Without the key (or `scaled: false`) the call is LPBatch.pdhg.  No sync."""
+    sets its options.  `halpern: true` selects Halpern's iteration (LPBatch.pdhg_halpern), `halpern: {reflect: false}` its
+    unreflected form; it takes the `scaled:` options too (`scaled: false` beside it is refused: the call is preconditioned).
+    Without either key (or with `false`) the call is LPBatch.pdhg.  No sync."""
     opt = report["pdhg"]
     for key in ("iters", "eps"):
         if key not in opt:
             raise ValueError(f"report_solved: pdhg: {key} is required")
     max_m = report.get("max_m")
     start = batch.repair_basis(logits, max_m=max_m, want=("basis", "x", "y")) if opt.get("warm", True) else None
-    scaled = opt.get("scaled")
-    if scaled is None or scaled is False:
+    scaled, halpern = opt.get("scaled"), opt.get("halpern")
+    halpern = None if halpern is False else halpern
+    if halpern is not None and scaled is False:
+        raise ValueError("report_solved: pdhg: halpern is a preconditioned call: it cannot go with scaled: false")
+    if halpern is None and (scaled is None or scaled is False):
         res = batch.pdhg(int(opt["iters"]), eps=float(opt["eps"]), check_every=int(opt.get("check", 64)), start=start)
     else:
-        more = {} if scaled is True else dict(scaled)
+        more = {} if scaled is True or scaled is None else dict(scaled)
         unknown = set(more) - {"ruiz", "pock_chambolle", "weight", "span"}
         if unknown:
             raise ValueError(f"report_solved: pdhg: scaled: unknown keys {sorted(unknown)}")
-        res = batch.pdhg_scaled(int(opt["iters"]), eps=float(opt["eps"]), check_every=int(opt.get("check", 64)), start=start,
-                                ruiz=int(more.get("ruiz", 10)), pock_chambolle=bool(more.get("pock_chambolle", True)),
-                                primal_weight=bool(more.get("weight", True)), weight_span=float(more.get("span", 16.0)))
+        kw = dict(ruiz=int(more.get("ruiz", 10)), pock_chambolle=bool(more.get("pock_chambolle", True)),
+                  primal_weight=bool(more.get("weight", True)), weight_span=float(more.get("span", 16.0)))
+        if halpern is not None:
+            own = {} if halpern is True else dict(halpern)
+            if set(own) - {"reflect"}:
+                raise ValueError(f"report_solved: pdhg: halpern: unknown keys {sorted(set(own) - {'reflect'})}")
+            kw["reflect"] = bool(own.get("reflect", True))
+        call = batch.pdhg_scaled if halpern is None else batch.pdhg_halpern
+        res = call(int(opt["iters"]), eps=float(opt["eps"]), check_every=int(opt.get("check", 64)), start=start, **kw)
     got = batch.solved(batch.pdhg_basis(res, max_m=max_m), report["feas_tol"], report["opt_tol"])
     return torch.stack([(res.status[:, 0] == 0).sum(), res.status[:, 1].sum(), got["optimal"].sum()]).float()
 

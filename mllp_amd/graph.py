@@ -1180,15 +1180,16 @@ class LPBatch:
         got["pivots"] = res.status[:, 1] + res.status[:, 2]
         return got
 
-    # ---- restarted PDHG on every instance, plain and preconditioned (mllp_lp_pdhg, mllp_lp_pdhg_scaled; csrc/pdhg.hip) ----
+    # ---- restarted PDHG on every instance: plain, preconditioned, and preconditioned with Halpern's iteration (mllp_lp_pdhg,
+    # mllp_lp_pdhg_scaled, mllp_lp_pdhg_halpern; csrc/pdhg.hip) ----
     def _pdhg(self, who, max_iters, check_every, params, x0, y0, start, max_lds_words):
-        """What `pdhg` and `pdhg_scaled` share: the start, the validation, the scratch kept on the batch, the outputs and the
-        call.  `who`: "pdhg" or "pdhg_scaled" -- the prefix of the messages, and what names the entry points (mllp_lp_pdhg,
-        mllp_lp_pdhg_scaled and their _scratch_bytes) and the attribute that keeps the scratch (`_pdhg_scratch`,
-        `_pdhg_scaled_scratch`).  `params`: the entry point's own arguments between check_every and max_lds_words -- eps,
-        step, beta, and for pdhg_scaled ruiz, pock_chambolle, primal_weight, weight_span.  Returns x, y, status, kkt (and dr,
-        dc)."""
-        scaled = who == "pdhg_scaled"
+        """What `pdhg`, `pdhg_scaled` and `pdhg_halpern` share: the start, the validation, the scratch kept on the batch, the
+        outputs and the call.  `who`: "pdhg", "pdhg_scaled" or "pdhg_halpern" -- the prefix of the messages, and what names
+        the entry points (mllp_lp_<who> and its _scratch_bytes) and the attribute that keeps the scratch (`_<who>_scratch`).
+        `params`: the entry point's own arguments between check_every and max_lds_words -- eps, step, beta, for pdhg_scaled
+        also ruiz, pock_chambolle, primal_weight, weight_span, and for pdhg_halpern reflect behind those.  Returns x, y,
+        status, kkt (and dr, dc)."""
+        scaled = who != "pdhg"
         if start is not None:
             if x0 is not None or y0 is not None:
                 raise ValueError(f"{who}: give start or x0 / y0, not both")
@@ -1214,7 +1215,7 @@ class LPBatch:
         flag = lambda v: int(bool(v))                                                         # noqa: E731
         _lib.check(getattr(_lib.lib(), f"mllp_lp_{who}")(
             self._h, _lib.ptr(_pad(self.x1)), _lib.ptr(_pad(self.x2)), _lib.ptr(opt(x0)), _lib.ptr(opt(y0)), max_iters, check_every,
-            *[f(v) for f, v in zip((float, float, float, int, flag, flag, float), params)], max_lds_words, _lib.ptr(x), _lib.ptr(y),
+            *[f(v) for f, v in zip((float, float, float, int, flag, flag, float, flag), params)], max_lds_words, _lib.ptr(x), _lib.ptr(y),
             *[_lib.ptr(t) for t in side], _lib.ptr(status), _lib.ptr(kkt), _lib.ptr(scratch), _lib.current_stream()))
         return (_cut(x, self.N), _cut(y, self.M), _cut(status, self.n_inst, 4), _cut(kkt, self.n_inst, kkt_words),
                 *(_cut(t, n) for t, n in zip(side, (self.M, self.N))))
@@ -1243,6 +1244,19 @@ class LPBatch:
         the batch.  No adaptive step, no infeasibility detection.  No sync."""
         return LPPdhgScaled(*self._pdhg("pdhg_scaled", max_iters, check_every,
                                         (eps, step, beta, ruiz, pock_chambolle, primal_weight, weight_span), x0, y0, start, max_lds_words))
+
+    def pdhg_halpern(self, max_iters, eps=2.0 ** -10, check_every=64, step=0.9, beta=0.5, ruiz=10, pock_chambolle=True,
+                     primal_weight=True, weight_span=16.0, reflect=True, x0=None, y0=None, start=None, max_lds_words=None):
+        """`pdhg_scaled` with Halpern's iteration in place of the running average (mllp_lp_pdhg_halpern; the rule is stated
+        in include/mllp_hip.h): after k iterations since the last restart the iterate moves to (k+1)/(k+2) of the reflected
+        PDHG step 2 T(z) - z plus 1/(k+2) of the last restart point.  A check judges ONE point, the step's output T(z), which
+        is also what the call returns; `status[:, 3]` is 0.  `reflect=False` is the unreflected iteration (slower than
+        `pdhg_scaled`: it pins the reflection in tests).  The scaling, the step, the weight, the other arguments and the codes
+        are `pdhg_scaled`'s, and so are `dr`, `dc`, `kkt[:, 3:5]`.  Returns an `LPPdhgHalpern`.  The scratch is asked for once
+        per max_lds_words and kept on the batch.  No adaptive step, no infeasibility detection.  No sync."""
+        return LPPdhgHalpern(*self._pdhg("pdhg_halpern", max_iters, check_every,
+                                         (eps, step, beta, ruiz, pock_chambolle, primal_weight, weight_span, reflect), x0, y0, start,
+                                         max_lds_words))
 
     def pdhg_basis(self, res, tol=2.0 ** -12, max_m=None):
         """The vertex a PDHG iterate points at: `repair_basis` on the ranking of `res.x` (its m largest entries first), so the
@@ -1325,6 +1339,18 @@ class LPPdhgScaled(LPPdhg):
     def __init__(self, x, y, status, kkt, dr, dc):
         super().__init__(x, y, status, kkt)
         self.dr, self.dc = dr, dc
+
+
+class LPPdhgHalpern(LPPdhgScaled):
+    """What `LPBatch.pdhg_halpern` returns: an `LPPdhgScaled` whose `.x`, `.y` are the last step's output (the point that was
+    checked, at codes 0 and 8) and whose `.status[:, 3]` is 0: there is no average to return."""
+
+
+def pdhg_halpern_limits():
+    """`pdhg_scaled_limits()`, as the Halpern call reports them (mllp_lp_pdhg_halpern_limits; no GPU)"""
+    lim = (c_int64 * 3)()
+    _lib.check(_lib.lib().mllp_lp_pdhg_halpern_limits(lim))
+    return int(lim[0]), int(lim[1]), int(lim[2])
 
 
 def pdhg_scaled_limits():

@@ -1,11 +1,14 @@
-"""Cost and reach of restarted PDHG on the resident batch (mllp_lp_pdhg; with --scaled: mllp_lp_pdhg_scaled).  Prints one
-JSON line (profiles/pdhg_bench.json; profiles/pdhg_scaled_bench.json holds the --scaled runs).
+"""Cost and reach of restarted PDHG on the resident batch (mllp_lp_pdhg; with --scaled: mllp_lp_pdhg_scaled; with --halpern:
+mllp_lp_pdhg_halpern).  Prints one JSON line (profiles/pdhg_bench.json; profiles/pdhg_scaled_bench.json holds the --scaled
+runs, profiles/pdhg_halpern_bench.json the --halpern ones).
 
     python tools/bench_pdhg.py [--calls 2] [--windows 5] [--plain-iters 256] [--netlib-iters 60000] [--synthetic 4]
-                               [--scaled [--ruiz 10] [--no-pock-chambolle] [--no-weight] [--span 16]] [--only PART,...]
+                               [--scaled | --halpern [--no-reflect]] [--ruiz 10] [--no-pock-chambolle] [--no-weight] [--span 16]
+                               [--only PART,...]
 
   --scaled        the same batches and the same Netlib table through LPBatch.pdhg_scaled with the options given; the output
                   gains "call" and "options".  --only per_iteration,netlib,cold_warm,oracle runs the named parts alone.
+  --halpern       the same through LPBatch.pdhg_halpern, with the --scaled options and --no-reflect.
 
   per_iteration   plain PDHG (check_every = 0) for --plain-iters iterations on the Netlib batch, on planted batches (256 and
                   1024 x (50 x 120), all in LDS; 64 x (500 x 1200); the same 64 with max_lds_words = 0, all in scratch) and on
@@ -34,11 +37,11 @@ import torch  # noqa: E402
 from bench_basis_repair import device_window  # noqa: E402
 
 
-SOLVE = {"scaled": False, "options": {}}       # set by main: which call `solve` makes
+SOLVE = {"call": "pdhg", "options": {}}       # set by main: which call `solve` makes
 
 
 def solve(b, iters, **kw):
-    return b.pdhg_scaled(iters, **SOLVE["options"], **kw) if SOLVE["scaled"] else b.pdhg(iters, **kw)
+    return getattr(b, SOLVE["call"])(iters, **SOLVE["options"], **kw)
 
 
 def timed(b, iters, calls, windows, max_lds_words=None, **kw):
@@ -86,6 +89,8 @@ def main():
     ap.add_argument("--netlib-iters", type=int, default=60000)
     ap.add_argument("--synthetic", type=int, default=4)
     ap.add_argument("--scaled", action="store_true")
+    ap.add_argument("--halpern", action="store_true")
+    ap.add_argument("--no-reflect", action="store_true")
     ap.add_argument("--ruiz", type=int, default=10)
     ap.add_argument("--no-pock-chambolle", action="store_true")
     ap.add_argument("--no-weight", action="store_true")
@@ -93,14 +98,17 @@ def main():
     ap.add_argument("--only", default="per_iteration,netlib,cold_warm,oracle")
     args = ap.parse_args()
     parts = set(args.only.split(","))
-    if args.scaled:
-        SOLVE.update(scaled=True, options={"ruiz": args.ruiz, "pock_chambolle": not args.no_pock_chambolle,
-                                           "primal_weight": not args.no_weight, "weight_span": args.span})
+    if args.scaled and args.halpern:
+        ap.error("--scaled and --halpern name two calls: give one")
+    if args.scaled or args.halpern:
+        SOLVE.update(call="pdhg_halpern" if args.halpern else "pdhg_scaled",
+                     options={"ruiz": args.ruiz, "pock_chambolle": not args.no_pock_chambolle, "primal_weight": not args.no_weight,
+                              "weight_span": args.span, **({"reflect": not args.no_reflect} if args.halpern else {})})
     assert torch.cuda.is_available(), "bench_pdhg needs the GPU: there is no CPU path"
     from mllp_amd.data import load_packed
     from mllp_amd.graph import LPBatch, pdhg_limits, synthetic_batch
     from mllp_amd.planted import planted_batch
-    out = {"call": "mllp_lp_pdhg_scaled" if args.scaled else "mllp_lp_pdhg", "options": SOLVE["options"],
+    out = {"call": "mllp_lp_" + SOLVE["call"], "options": SOLVE["options"],
            "limits": {"lds_words": pdhg_limits()[0], "threads": pdhg_limits()[1]}}
     if "oracle" in parts:
         out["oracle_deviation_units"] = oracle_deviation()
