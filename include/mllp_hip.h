@@ -566,6 +566,62 @@ int mllp_lp_pdhg_halpern(const mllp_graph_t* g, const float* d_x1 /*c [N]*/, con
                          float* d_dc /*[N] or NULL*/, int32_t* d_status /*[n_inst,4]*/, float* d_kkt /*[n_inst,6] or NULL*/,
                          void* d_scratch, void* stream);
 
+/* mllp_lp_pdhg_halpern's rule across the whole device (mllp_amd/csrc/pdhg_wide.hip): the same solve as
+ * ordinary kernel launches in stream order, every instance's rows and columns spread over as many workgroups as they need,
+ * where mllp_lp_pdhg_halpern gives an instance one workgroup on one compute unit for the whole call.  Added after ABI 6
+ * without a bump.  mllp_lp_pdhg, mllp_lp_pdhg_scaled and mllp_lp_pdhg_halpern are unchanged.
+ * THE RULE is mllp_lp_pdhg_halpern's, word for word: the scaling, step, weight and start; the iteration with `reflect`; the
+ * check, the restart, the weight update, the limit and the output; the order of every sum.  A row's sum depends on the row's
+ * length alone and every maximum is an integer maximum, so WHICH workgroup sums a row does not reach a bit:
+ *   Identity.  With iter_begin = 0 the outputs d_x, d_y, d_dr, d_dc, d_status and d_kkt are mllp_lp_pdhg_halpern's at
+ *     max_iters = iter_end, bit for bit, for every instance, every rows_per_item and every batch composition.
+ *   Execution.  A work item is rows_per_item consecutive rows of one instance's CSR(A), or columns of CSR(A^T), and one
+ *     workgroup of 1024 threads runs it in the three tiers (a row of more than 1024 terms is summed by the workgroup that owns
+ *     it).  One launch covers the items of every instance.  An iteration is two launches (the column sweep writes xh, xbar, x;
+ *     the row sweep yh, y); a check is its two evaluation sweeps and one launch of one workgroup per instance, which does
+ *     everything the rule sums in the order of c'x, and every decision; the set-up is 3 launches per scaling pass and 3 more;
+ *     the end of a call is an evaluation and one launch that writes every output.  No kernel waits on another workgroup: no
+ *     cooperative launch, no grid barrier, no flag; all ordering between phases is the stream's.  Across workgroups: one
+ *     writer per word, and integer atomicMax on the patterns of non-negative floats.  No float atomics.
+ *   rows_per_item : a positive multiple of 64 up to limits[3], or 0 for the default, limits[2].  It moves no bit.
+ *   mllp_lp_pdhg_wide_limits: {threads per workgroup (1024), largest ruiz_passes (64), default rows_per_item (64), largest
+ *             rows_per_item (4096)}; needs no GPU.
+ *   iter_begin, iter_end : the call runs iterations iter_begin + 1 .. iter_end.  Checks fall on ABSOLUTE multiples of
+ *             check_every.
+ *     iter_begin == 0 : set-up and start, then the iterations.  d_scratch may hold anything.
+ *     iter_begin > 0 : continues from the state that the previous call left in d_scratch -- a call on the same graph with the
+ *             same options and the same d_scratch whose iter_end was this iter_begin; d_x0 and d_y0 are ignored.  Instances at
+ *             code 0 or 8 stay as they are, instances at code 6 go on, and every call writes every requested output, d_dr and
+ *             d_dc included (the factors are kept in the scratch).  The evaluation at the end of a call leaves the state of a
+ *             code-6 instance untouched, so the calls (0, K1) then (K1, K2) give the bits of the call (0, K2), for any K1.
+ *             An instance whose state does not say that a call ended exactly at iter_begin gets code 9, STALE STATE: its
+ *             outputs are zeros, its status {9, 0, 0, 0}, its state is left as found.  The state is sixteen words of VALUES per
+ *             instance (code, iterations, iteration of the last restart, restarts, e_last, w0, w, tau, sigma, eta, the two
+ *             denominators): no index, offset or pointer that a kernel follows, so whatever d_scratch holds, no access leaves
+ *             the buffers.
+ *   d_x1 .. beta, ruiz_passes, pock_chambolle, primal_weight, weight_span, reflect, d_x, d_y, d_dr, d_dc, d_status, d_kkt : as
+ *             mllp_lp_pdhg_halpern; d_status[.][0] may also be 9.
+ *   d_scratch : mllp_lp_pdhg_wide_scratch_bytes(g, rows_per_item) bytes, which is 4 (21 n_inst + 6 N + 5 M): per instance
+ *             the state and five words of the call's own (its flag, two maxima, the first work item of each orientation);
+ *             x, xbar, xh, the anchor, tc and dc [N each]; y, yh, the anchor, tr and dr [M each].  May be NULL when that is 0.
+ * Every requested output is fully written for every instance; n = 0 or m = 0 is legal.  A launch function: `stream` only, no
+ * allocation, no host-to-device copy, no synchronisation, hipGraph-capturable (2 (iter_end - iter_begin) nodes and 3 per
+ * check); the map from a workgroup to (instance, block) is made from inst_ptr_m / inst_ptr_n on the device by the call's
+ * first kernel.  Bitwise reproducible, the same bits alone and inside any batch.
+ * mllp_lp_pdhg_wide is under the MEMORY CONTRACT below as mllp_lp_pdhg is, and the state in d_scratch between a call and the call that continues it is state this header names.
+ * MLLP_EINVAL before any launch, nothing written: every refusal of mllp_lp_pdhg_halpern that does not concern max_lds_words,
+ * in its words, under this call's name (null arguments before any HIP call); iter_begin < 0; iter_end < iter_begin;
+ * rows_per_item negative, above limits[3] or no multiple of 64.                                                            */
+int mllp_lp_pdhg_wide_limits(int64_t limits[4]);
+int mllp_lp_pdhg_wide_scratch_bytes(const mllp_graph_t* g, int64_t rows_per_item, int64_t* bytes);
+int mllp_lp_pdhg_wide(const mllp_graph_t* g, const float* d_x1 /*c [N]*/, const float* d_x2 /*b [M]*/,
+                      const float* d_x0 /*[N] or NULL*/, const float* d_y0 /*[M] or NULL*/, int64_t iter_begin,
+                      int64_t iter_end, int64_t check_every, float eps, float step, float beta, int64_t ruiz_passes,
+                      int32_t pock_chambolle, int32_t primal_weight, float weight_span, int32_t reflect,
+                      int64_t rows_per_item, float* d_x /*[N]*/, float* d_y /*[M]*/, float* d_dr /*[M] or NULL*/,
+                      float* d_dc /*[N] or NULL*/, int32_t* d_status /*[n_inst,4]*/, float* d_kkt /*[n_inst,6] or NULL*/,
+                      void* d_scratch, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Plain CSR SpMM (the roofline kernel named in BASELINE.json's metric):
  *   transpose == 0:  Y[M,16] = A   * H[N,16]       transpose == 1:  Y[N,16] = A^T * H[M,16]

@@ -54,7 +54,11 @@ HOT_PATH_DEFAULTS = {
                              # scaling, a clamped primal weight) under the same three keys, or `scaled: {ruiz: 10,
                              # pock_chambolle: true, weight: true, span: 16}` with any of its options; absent == LPBatch.pdhg;
                              # `halpern: true` (or `halpern: {reflect: false}`) inside `pdhg` solves by the preconditioned call
-                             # with Halpern's iteration (LPBatch.pdhg_halpern), with the `scaled:` options if they are given
+                             # with Halpern's iteration (LPBatch.pdhg_halpern), with the `scaled:` options if they are given;
+                             # `wide: true` (or `wide: {rows: 64, poll: 256}`) inside `pdhg` runs that same rule, bit for bit,
+                             # across the whole device (LPBatch.pdhg_wide: for instances too long for one workgroup), with the
+                             # `halpern:` and `scaled:` options if they are given; `poll` reads the codes back every so many
+                             # iterations and stops once every instance has
     "weight_decay": 0.0,     # decoupled weight decay of the optimizer (torch.optim.AdamW); 0 == the reference's Adam
     "clip_norm": 0.0,        # cap on the global gradient norm of a step (torch.nn.utils.clip_grad_norm_); 0 == no clipping
     "lr_schedule": None,     # the block {warmup: W, total: T, min_ratio: r}: the rate rises linearly over the first W steps, then

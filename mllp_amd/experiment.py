@@ -230,15 +230,24 @@ def pdhg_counts(batch, logits, report):
     selects the preconditioned call (LPBatch.pdhg_scaled) with its defaults; a mapping {ruiz, pock_chambolle, weight, span}
     sets its options.  `halpern: true` selects Halpern's iteration (LPBatch.pdhg_halpern), `halpern: {reflect: false}` its
     unreflected form; it takes the `scaled:` options too (`scaled: false` beside it is refused: the call is preconditioned).
-    Without either key (or with `false`) the call is LPBatch.pdhg.  No sync."""
+    `wide: true` runs Halpern's iteration across the whole device (LPBatch.pdhg_wide: the same rule and the same bits, for
+    instances too long for one workgroup), `wide: {rows: R, poll: P}` with R rows per work item and the codes polled every
+    P iterations (one sync per poll; an early stop then costs nothing); it takes the `halpern:` and `scaled:` options, and
+    `scaled: false` beside it is refused likewise.  Without any of the three keys (or with `false`) the call is
+    LPBatch.pdhg.  No sync unless `poll` is given."""
     opt = report["pdhg"]
     for key in ("iters", "eps"):
         if key not in opt:
             raise ValueError(f"report_solved: pdhg: {key} is required")
     max_m = report.get("max_m")
     start = batch.repair_basis(logits, max_m=max_m, want=("basis", "x", "y")) if opt.get("warm", True) else None
-    scaled, halpern = opt.get("scaled"), opt.get("halpern")
+    scaled, halpern, wide = opt.get("scaled"), opt.get("halpern"), opt.get("wide")
     halpern = None if halpern is False else halpern
+    wide = None if wide is False else wide
+    if wide is not None and scaled is False:
+        raise ValueError("report_solved: pdhg: wide is a preconditioned call: it cannot go with scaled: false")
+    if wide is not None and halpern is None:
+        halpern = True              # the wide call IS Halpern's iteration
     if halpern is not None and scaled is False:
         raise ValueError("report_solved: pdhg: halpern is a preconditioned call: it cannot go with scaled: false")
     if halpern is None and (scaled is None or scaled is False):
@@ -255,7 +264,17 @@ def pdhg_counts(batch, logits, report):
             if set(own) - {"reflect"}:
                 raise ValueError(f"report_solved: pdhg: halpern: unknown keys {sorted(set(own) - {'reflect'})}")
             kw["reflect"] = bool(own.get("reflect", True))
-        call = batch.pdhg_scaled if halpern is None else batch.pdhg_halpern
+        if wide is not None:
+            own = {} if wide is True else dict(wide)
+            if set(own) - {"rows", "poll"}:
+                raise ValueError(f"report_solved: pdhg: wide: unknown keys {sorted(set(own) - {'rows', 'poll'})}")
+            rows, poll = own.get("rows"), own.get("poll")
+            if rows is not None and (int(rows) <= 0 or int(rows) % 64):
+                raise ValueError("report_solved: pdhg: wide: rows must be a positive multiple of 64")
+            if poll is not None and int(poll) <= 0:
+                raise ValueError("report_solved: pdhg: wide: poll must be positive")
+            kw.update(rows_per_item=None if rows is None else int(rows), poll_every=None if poll is None else int(poll))
+        call = batch.pdhg_wide if wide is not None else batch.pdhg_scaled if halpern is None else batch.pdhg_halpern
         res = call(int(opt["iters"]), eps=float(opt["eps"]), check_every=int(opt.get("check", 64)), start=start, **kw)
     got = batch.solved(batch.pdhg_basis(res, max_m=max_m), report["feas_tol"], report["opt_tol"])
     return torch.stack([(res.status[:, 0] == 0).sum(), res.status[:, 1].sum(), got["optimal"].sum()]).float()

@@ -1258,6 +1258,66 @@ class LPBatch:
                                          (eps, step, beta, ruiz, pock_chambolle, primal_weight, weight_span, reflect), x0, y0, start,
                                          max_lds_words))
 
+    def pdhg_wide(self, max_iters, eps=2.0 ** -10, check_every=64, step=0.9, beta=0.5, ruiz=10, pock_chambolle=True,
+                  primal_weight=True, weight_span=16.0, reflect=True, x0=None, y0=None, start=None, rows_per_item=None,
+                  poll_every=None):
+        """`pdhg_halpern`, bit for bit, run across the whole device (mllp_lp_pdhg_wide; csrc/pdhg_wide.hip): every instance's
+        rows and columns are cut into items of `rows_per_item` rows (a multiple of 64; None: the library's default), one
+        workgroup each, and an iteration is two ordinary launches -- where `pdhg_halpern` lasts as long as its slowest instance
+        on ONE compute unit.  The arguments, the codes and the tensors are `pdhg_halpern`'s; `rows_per_item` moves no bit.
+        `poll_every=None`: one C call, no sync.  `poll_every=P`: calls of P iterations each, the codes read back after each
+        (one sync per call), and no further call once no instance is at code 6 -- what makes an early stop cost nothing; the
+        tensors have the single call's bits.  Returns an `LPPdhgWide`, whose `.calls` is the number of C calls made.  The
+        scratch, which also carries the state from one call to the next, is asked for once per rows_per_item and kept on the
+        batch."""
+        who = "pdhg_wide"
+        if start is not None:
+            if x0 is not None or y0 is not None:
+                raise ValueError(f"{who}: give start or x0 / y0, not both")
+            if not isinstance(start, BasisRepair) or start.x is None or start.y is None:
+                raise ValueError(f"{who}: start must be a BasisRepair with x and y")
+            x0, y0 = start.x, start.y
+        for t, n, what in ((x0, self.N, "x0"), (y0, self.M, "y0")):
+            if t is not None:
+                _checked(who, what, t, n)
+        max_iters, check_every = int(max_iters), int(check_every)
+        if max_iters < 0 or check_every < 0:
+            raise ValueError(f"{who}: max_iters and check_every must not be negative")
+        rows = 0 if rows_per_item is None else int(rows_per_item)
+        if rows_per_item is not None and (rows <= 0 or rows % 64 or rows > pdhg_wide_limits()[3]):
+            raise ValueError(f"{who}: rows_per_item must be a positive multiple of 64, at most {pdhg_wide_limits()[3]}")
+        if poll_every is not None and int(poll_every) <= 0:
+            raise ValueError(f"{who}: poll_every must be positive")
+        dev, f32 = self.x1.device, torch.float32
+        scratch = self._kept_scratch("_pdhg_wide_scratch", rows, "mllp_lp_pdhg_wide_scratch_bytes")
+        x, y, dr, dc = _out(self.N, f32, dev), _out(self.M, f32, dev), _out(self.M, f32, dev), _out(self.N, f32, dev)
+        status, kkt = _out(self.n_inst * 4, torch.int32, dev), _out(self.n_inst * 6, f32, dev)
+        opt = lambda t: None if t is None or not t.numel() else t                             # noqa: E731
+        x1, x2 = _pad(self.x1), _pad(self.x2)
+
+        def call(begin, end):
+            _lib.check(_lib.lib().mllp_lp_pdhg_wide(
+                self._h, _lib.ptr(x1), _lib.ptr(x2), _lib.ptr(opt(x0)), _lib.ptr(opt(y0)), begin, end, check_every, float(eps), float(step),
+                float(beta), int(ruiz), int(bool(pock_chambolle)), int(bool(primal_weight)), float(weight_span), int(bool(reflect)), rows,
+                *[_lib.ptr(t) for t in (x, y, dr, dc, status, kkt)], _lib.ptr(scratch), _lib.current_stream()))
+        calls = 0
+        if poll_every is None:
+            call(0, max_iters)
+            calls = 1
+        else:
+            begin = 0
+            while True:
+                end = min(begin + int(poll_every), max_iters)
+                call(begin, end)
+                calls += 1
+                begin = end
+                if begin >= max_iters or not bool((_cut(status, self.n_inst, 4)[:, 0] == 6).any().item()):
+                    break
+        res = LPPdhgWide(_cut(x, self.N), _cut(y, self.M), _cut(status, self.n_inst, 4), _cut(kkt, self.n_inst, 6), _cut(dr, self.M),
+                         _cut(dc, self.N))
+        res.calls = calls
+        return res
+
     def pdhg_basis(self, res, tol=2.0 ** -12, max_m=None):
         """The vertex a PDHG iterate points at: `repair_basis` on the ranking of `res.x` (its m largest entries first), so the
         `BasisRepair` of the best-ranked nonsingular basis and its basic solution, which `solved` certifies -- for the
@@ -1344,6 +1404,21 @@ class LPPdhgScaled(LPPdhg):
 class LPPdhgHalpern(LPPdhgScaled):
     """What `LPBatch.pdhg_halpern` returns: an `LPPdhgScaled` whose `.x`, `.y` are the last step's output (the point that was
     checked, at codes 0 and 8) and whose `.status[:, 3]` is 0: there is no average to return."""
+
+
+class LPPdhgWide(LPPdhgHalpern):
+    """What `LPBatch.pdhg_wide` returns: `pdhg_halpern`'s tensors with `pdhg_halpern`'s bits, and `.calls`, the number of
+    mllp_lp_pdhg_wide calls that made them (1 without `poll_every`).  `status[:, 0]` may also be 9, stale state, which
+    `LPBatch.pdhg_wide` itself never produces: it continues only its own calls."""
+    calls = 1
+
+
+def pdhg_wide_limits():
+    """(threads per workgroup, the most Ruiz passes, the default and the largest rows_per_item) of `LPBatch.pdhg_wide`
+    (mllp_lp_pdhg_wide_limits; no GPU)"""
+    lim = (c_int64 * 4)()
+    _lib.check(_lib.lib().mllp_lp_pdhg_wide_limits(lim))
+    return int(lim[0]), int(lim[1]), int(lim[2]), int(lim[3])
 
 
 def pdhg_halpern_limits():

@@ -1,14 +1,19 @@
 """Cost and reach of restarted PDHG on the resident batch (mllp_lp_pdhg; with --scaled: mllp_lp_pdhg_scaled; with --halpern:
-mllp_lp_pdhg_halpern).  Prints one JSON line (profiles/pdhg_bench.json; profiles/pdhg_scaled_bench.json holds the --scaled
-runs, profiles/pdhg_halpern_bench.json the --halpern ones).
+mllp_lp_pdhg_halpern; with --wide: mllp_lp_pdhg_wide against mllp_lp_pdhg_halpern).  Prints one JSON line
+(profiles/pdhg_bench.json; profiles/pdhg_scaled_bench.json holds the --scaled runs, profiles/pdhg_halpern_bench.json the
+--halpern ones, profiles/pdhg_wide_bench.json the --wide ones).
 
     python tools/bench_pdhg.py [--calls 2] [--windows 5] [--plain-iters 256] [--netlib-iters 60000] [--synthetic 4]
                                [--scaled | --halpern [--no-reflect]] [--ruiz 10] [--no-pock-chambolle] [--no-weight] [--span 16]
-                               [--only PART,...]
+                               [--wide [--rows R] [--poll P]] [--only PART,...]
 
   --scaled        the same batches and the same Netlib table through LPBatch.pdhg_scaled with the options given; the output
                   gains "call" and "options".  --only per_iteration,netlib,cold_warm,oracle runs the named parts alone.
   --halpern       the same through LPBatch.pdhg_halpern, with the --scaled options and --no-reflect.
+  --wide          LPBatch.pdhg_wide (the --halpern options; --rows: rows_per_item, --poll: poll_every of the netlib part) AGAINST
+                  LPBatch.pdhg_halpern from the same build: per_iteration times both calls on every batch, alternating window by
+                  window ("persistent" beside the wide figures, and "wide_max_below_persistent_min"); netlib (eps 1e-3 alone)
+                  runs both under --netlib-iters and reports the wall time of each and whether the converged sets are equal.
 
   per_iteration   plain PDHG (check_every = 0) for --plain-iters iterations on the Netlib batch, on planted batches (256 and
                   1024 x (50 x 120), all in LDS; 64 x (500 x 1200); the same 64 with max_lds_words = 0, all in scratch) and on
@@ -44,17 +49,35 @@ def solve(b, iters, **kw):
     return getattr(b, SOLVE["call"])(iters, **SOLVE["options"], **kw)
 
 
+def figures(dev, iters):
+    med = float(np.median(dev))
+    return {"device_ms_per_call": {"median": round(med * 1e3, 3), "min": round(min(dev) * 1e3, 3), "max": round(max(dev) * 1e3, 3)},
+            "us_per_iteration": {"median": round(med * 1e6 / iters, 3), "min": round(min(dev) * 1e6 / iters, 3),
+                                 "max": round(max(dev) * 1e6 / iters, 3)}}
+
+
 def timed(b, iters, calls, windows, max_lds_words=None, **kw):
+    head = {"iterations": iters, "calls_per_window": calls, "windows": windows}
+    if SOLVE["call"] == "pdhg_wide":
+        # both calls from the same build, alternating window by window; the persistent call takes the same options
+        opts = {k: v for k, v in SOLVE["options"].items() if k != "rows_per_item"}
+        runs = {"persistent": lambda: b.pdhg_halpern(iters, max_lds_words=max_lds_words, **opts, **kw), "wide": lambda: solve(b, iters, **kw)}
+        for run in runs.values():
+            run()
+            run()
+        torch.cuda.synchronize()
+        dev = {name: [] for name in runs}
+        for _ in range(windows):
+            for name, run in runs.items():
+                dev[name].append(device_window(run, calls))
+        return {**head, **figures(dev["wide"], iters), "persistent": figures(dev["persistent"], iters),
+                "wide_max_below_persistent_min": bool(max(dev["wide"]) < min(dev["persistent"]))}
     run = lambda: solve(b, iters, max_lds_words=max_lds_words, **kw)      # noqa: E731
     run()
     run()
     torch.cuda.synchronize()
     dev = [device_window(run, calls) for _ in range(windows)]
-    med = float(np.median(dev))
-    return {"iterations": iters, "calls_per_window": calls, "windows": windows,
-            "device_ms_per_call": {"median": round(med * 1e3, 3), "min": round(min(dev) * 1e3, 3), "max": round(max(dev) * 1e3, 3)},
-            "us_per_iteration": {"median": round(med * 1e6 / iters, 3), "min": round(min(dev) * 1e6 / iters, 3),
-                                 "max": round(max(dev) * 1e6 / iters, 3)}}
+    return {**head, **figures(dev, iters)}
 
 
 def shape_of(b):
@@ -91,6 +114,9 @@ def main():
     ap.add_argument("--scaled", action="store_true")
     ap.add_argument("--halpern", action="store_true")
     ap.add_argument("--no-reflect", action="store_true")
+    ap.add_argument("--wide", action="store_true")
+    ap.add_argument("--rows", type=int, default=None)
+    ap.add_argument("--poll", type=int, default=None)
     ap.add_argument("--ruiz", type=int, default=10)
     ap.add_argument("--no-pock-chambolle", action="store_true")
     ap.add_argument("--no-weight", action="store_true")
@@ -98,18 +124,21 @@ def main():
     ap.add_argument("--only", default="per_iteration,netlib,cold_warm,oracle")
     args = ap.parse_args()
     parts = set(args.only.split(","))
-    if args.scaled and args.halpern:
-        ap.error("--scaled and --halpern name two calls: give one")
-    if args.scaled or args.halpern:
-        SOLVE.update(call="pdhg_halpern" if args.halpern else "pdhg_scaled",
+    if args.scaled + args.halpern + args.wide > 1:
+        ap.error("--scaled, --halpern and --wide name three calls: give one")
+    if args.scaled or args.halpern or args.wide:
+        SOLVE.update(call="pdhg_wide" if args.wide else "pdhg_halpern" if args.halpern else "pdhg_scaled",
                      options={"ruiz": args.ruiz, "pock_chambolle": not args.no_pock_chambolle, "primal_weight": not args.no_weight,
-                              "weight_span": args.span, **({"reflect": not args.no_reflect} if args.halpern else {})})
+                              "weight_span": args.span, **({"reflect": not args.no_reflect} if args.halpern or args.wide else {}),
+                              **({"rows_per_item": args.rows} if args.wide else {})})
     assert torch.cuda.is_available(), "bench_pdhg needs the GPU: there is no CPU path"
     from mllp_amd.data import load_packed
     from mllp_amd.graph import LPBatch, pdhg_limits, synthetic_batch
     from mllp_amd.planted import planted_batch
     out = {"call": "mllp_lp_" + SOLVE["call"], "options": SOLVE["options"],
            "limits": {"lds_words": pdhg_limits()[0], "threads": pdhg_limits()[1]}}
+    if args.wide and "cold_warm" in parts:
+        parts.discard("cold_warm")          # (the rule's reach is --halpern's: the same bits)
     if "oracle" in parts:
         out["oracle_deviation_units"] = oracle_deviation()
     net = LPBatch.from_instances(load_packed())
@@ -128,10 +157,23 @@ def main():
     out["per_iteration"] = per_it
     # Netlib: where the baseline gets within --netlib-iters
     table = {}
-    for eps in (1e-3, 1e-4) if "netlib" in parts else ():
-        res = solve(net, args.netlib_iters, eps=eps)
+    for eps in ((1e-3,) if args.wide else (1e-3, 1e-4)) if "netlib" in parts else ():
+        import time
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res = solve(net, args.netlib_iters, eps=eps, **({"poll_every": args.poll} if args.wide else {}))
         torch.cuda.synchronize()
         st, kkt = res.status.cpu().numpy(), res.kkt.cpu().numpy()
+        if args.wide:
+            wall = time.perf_counter() - t0
+            t0 = time.perf_counter()
+            ref = net.pdhg_halpern(args.netlib_iters, eps=eps, **{k: v for k, v in SOLVE["options"].items() if k != "rows_per_item"})
+            torch.cuda.synchronize()
+            ref_st = ref.status.cpu().numpy()
+            out["netlib_wide_against_persistent"] = {
+                "eps": eps, "poll_every": args.poll, "calls": res.calls, "wide_wall_s": round(wall, 3),
+                "persistent_wall_s": round(time.perf_counter() - t0, 3), "converged_sets_equal": bool(((st[:, 0] == 0) == (ref_st[:, 0] == 0)).all()),
+                "status_equal": bool((st == ref_st).all()), "x_bits_equal": bool(torch.equal(res.x.view(torch.int32), ref.x.view(torch.int32)))}
         for k, name in enumerate(net.names):
             table.setdefault(name, {"m": net.inst_m[k], "n": net.inst_n[k]})[f"eps_{eps:g}"] = {
                 "code": int(st[k, 0]), "iterations": int(st[k, 1]), "restarts": int(st[k, 2]),
