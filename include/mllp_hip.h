@@ -622,6 +622,69 @@ int mllp_lp_pdhg_wide(const mllp_graph_t* g, const float* d_x1 /*c [N]*/, const 
                       float* d_dc /*[N] or NULL*/, int32_t* d_status /*[n_inst,4]*/, float* d_kkt /*[n_inst,6] or NULL*/,
                       void* d_scratch, void* stream);
 
+/* mllp_lp_pdhg_wide with CERTIFICATES OF INFEASIBILITY AND UNBOUNDEDNESS (mllp_amd/csrc/pdhg_wide.hip): codes 4
+ * and 5, as mllp_basis_simplex reports them, for the first-order solver.  Added after ABI 6 without a bump.  mllp_lp_pdhg,
+ * mllp_lp_pdhg_scaled, mllp_lp_pdhg_halpern and mllp_lp_pdhg_wide are unchanged.
+ * The candidate ray costs nothing: the direction from the anchor to the step's output, (xh - xa, yh - ya), converges under
+ * Halpern's iteration to the infimal displacement of the PDHG operator, which is zero for a solvable LP and a Farkas ray or a
+ * recession ray otherwise.  No new vector, no change to the two sweeps of an iteration.
+ * THE RULE is mllp_lp_pdhg_halpern's, word for word, with ONE step inserted into a check, after "e not finite: code 8" and
+ * "e <= eps: code 0" and BEFORE the restart test, and only when ray_eps >= 0:
+ *   Rays.  rx_j = fsub(xh_j, xa_j), ry_i = fsub(yh_i, ya_i).  At a check the anchor is the last restart point, or the start: it
+ *     is always at least check_every iterations old.
+ *   Objectives.  by = sum_i fma(b_i, ry_i, .), cx = sum_j fma(c_j, rx_j, .), both in the order of c'x.
+ *   Residuals.  U = max_j max(sum_i a_ij ry_i, 0).  V = max(max_i |sum_j a_ij rx_j|, max_j max(-rx_j, 0)).  Each term of a sum is
+ *     fma(a_ij, r, q) with the rounded difference as r; the sums run in the row tiers picked by length alone, as in every sweep
+ *     of the rule; the maxima are integer maxima over the bit patterns and keep a NaN.
+ *   Qualities.  qp = fdiv(U, by) when by is finite and > 0, otherwise +inf.  qd = fdiv(V, -cx) when cx is finite and < 0,
+ *     otherwise +inf.  A comparison with a NaN is false.
+ *   Decision.  qp <= ray_eps: code 4, primal infeasible, ry is the certificate.  Otherwise qd <= ray_eps: code 5, dual
+ *     infeasible (unbounded if feasible), rx is the certificate.  Otherwise the restart test runs as before.  An instance at
+ *     code 4 or 5 stops as one at code 0 does; its vectors and its anchor stay as they are.
+ *   Off.  With ray_eps < 0 nothing is evaluated and nothing changes: the six outputs of mllp_lp_pdhg_wide have that call's bits.
+ * WHAT A CERTIFICATE MEANS.  Code 4: every x >= 0 with A x = b satisfies b'ry = x'A'ry <= U |x|_1, so |x|_1 >= 1 / qp >=
+ * 1 / ray_eps: no feasible point is smaller than that.  Code 5: along max(rx, 0) the cost falls by -cx while A x and the sign
+ * constraints move by at most qd times that.  These are PDLP's two relative ray tests written for this LP form; they judge rays
+ * of the ORIGINAL LP, so they do not depend on dr, dc or the weight.
+ * NOT CLAIMED.  The persistent calls (mllp_lp_pdhg, mllp_lp_pdhg_scaled, mllp_lp_pdhg_halpern) get no detection.  Detection is
+ * as slow as the displacement's convergence: an instance on which the iteration stalls may never produce a ray and still ends
+ * with code 6.  A certificate is relative to ray_eps and is in fp32: a FEASIBLE LP all of whose feasible points have |x|_1 >=
+ * 1 / ray_eps ends with code 4, truthfully and uselessly, so ray_eps has to lie below 1 / |x|_1 of the solutions expected
+ * (at 2^-10 that stops 46 of the 97 feasible Netlib LPs).  Still no adaptive step size and no feasibility
+ * polishing.
+ *   d_x1 .. reflect, rows_per_item, d_x, d_y, d_dr, d_dc, d_kkt, iter_begin, iter_end : as mllp_lp_pdhg_wide.  d_x, d_y and d_kkt
+ *             are always (xh, yh) and its errors, also at code 4 or 5.
+ *   ray_eps : finite; negative: no detection.
+ *   d_status [n_inst, 4] : {code, iterations, restarts, 0}; the code may be 0, 4, 5, 6, 8 or 9.
+ *   d_ray_y [M] or NULL : ry for an instance at code 4, zeros otherwise.   d_ray_x [N] or NULL : rx at code 5, zeros otherwise.
+ *             Both are recomputed from the frozen xh - xa, so they carry the bits of the deciding check.
+ *   d_cert [n_inst, 4] or NULL : {qp, by, qd, cx} of the last check at which the instance evaluated its rays (a check that
+ *             stops with code 0 or 8 does not), {+inf, 0, +inf, 0} if there was none, zeros for a stale instance.  The four
+ *             values are kept in the state, so the calls (0, K1) then (K1, K2) give the bits of the call (0, K2) in every
+ *             output, the new ones included.
+ *   d_scratch : mllp_lp_pdhg_rays_scratch_bytes(g, rows_per_item) bytes, which is 4 (27 n_inst + 6 N + 5 M): mllp_lp_pdhg_wide's
+ *             layout with six more words per instance BEHIND the vectors: two ray keys (the call's own) and the four cert words
+ *             (state, values only).  A call with iter_begin > 0 also accepts an instance at code 4 or 5, which stays as it is.
+ *             mllp_lp_pdhg_rays_limits: mllp_lp_pdhg_wide_limits' four values.
+ * Every requested output is fully written for every instance; n = 0 or m = 0 is legal.  A launch function: `stream` only, no
+ * allocation, no host-to-device copy, no synchronisation, hipGraph-capturable, with EXACTLY the launches of mllp_lp_pdhg_wide
+ * for the same arguments: the rays ride in the check's two sweeps (a row is walked once for two accumulators, the point's and
+ * the ray's: one load of the value and of the index per term, two gathers) and in the decision; they are no sweeps of their
+ * own.  Bitwise reproducible, the same bits alone and inside any batch, for every rows_per_item.
+ * mllp_lp_pdhg_rays is under the MEMORY CONTRACT below as mllp_lp_pdhg is, and the state in d_scratch between a call and the call that continues it is state this header names.
+ * MLLP_EINVAL before any launch, nothing written: every refusal of mllp_lp_pdhg_wide, in its words, under this call's name;
+ * ray_eps not finite; d_x0 or d_y0 overlapping d_ray_x, d_ray_y or d_cert.                                                  */
+int mllp_lp_pdhg_rays_limits(int64_t limits[4]);
+int mllp_lp_pdhg_rays_scratch_bytes(const mllp_graph_t* g, int64_t rows_per_item, int64_t* bytes);
+int mllp_lp_pdhg_rays(const mllp_graph_t* g, const float* d_x1 /*c [N]*/, const float* d_x2 /*b [M]*/,
+                      const float* d_x0 /*[N] or NULL*/, const float* d_y0 /*[M] or NULL*/, int64_t iter_begin,
+                      int64_t iter_end, int64_t check_every, float eps, float step, float beta, int64_t ruiz_passes,
+                      int32_t pock_chambolle, int32_t primal_weight, float weight_span, int32_t reflect, float ray_eps,
+                      int64_t rows_per_item, float* d_x /*[N]*/, float* d_y /*[M]*/, float* d_dr /*[M] or NULL*/,
+                      float* d_dc /*[N] or NULL*/, float* d_ray_x /*[N] or NULL*/, float* d_ray_y /*[M] or NULL*/,
+                      int32_t* d_status /*[n_inst,4]*/, float* d_kkt /*[n_inst,6] or NULL*/,
+                      float* d_cert /*[n_inst,4] or NULL*/, void* d_scratch, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Plain CSR SpMM (the roofline kernel named in BASELINE.json's metric):
  *   transpose == 0:  Y[M,16] = A   * H[N,16]       transpose == 1:  Y[N,16] = A^T * H[M,16]

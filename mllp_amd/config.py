@@ -58,7 +58,11 @@ HOT_PATH_DEFAULTS = {
                              # `wide: true` (or `wide: {rows: 64, poll: 256}`) inside `pdhg` runs that same rule, bit for bit,
                              # across the whole device (LPBatch.pdhg_wide: for instances too long for one workgroup), with the
                              # `halpern:` and `scaled:` options if they are given; `poll` reads the codes back every so many
-                             # iterations and stops once every instance has
+                             # iterations and stops once every instance has; `rays: true` (or `rays: {eps: 1.e-3}`) inside
+                             # `pdhg` runs the wide call with certificates (LPBatch.pdhg_rays; implies `wide`) and adds
+                             # pdhg_infeasible / pdhg_unbounded: the instances that ended with code 4 and with code 5.  Both are
+                             # relative to eps: code 4 says "no feasible point with a 1-norm below 1 / eps", which feasible LPs
+                             # with large solutions meet too (at 2^-10: 46 of the 97 Netlib LPs), so choose eps against them
     "weight_decay": 0.0,     # decoupled weight decay of the optimizer (torch.optim.AdamW); 0 == the reference's Adam
     "clip_norm": 0.0,        # cap on the global gradient norm of a step (torch.nn.utils.clip_grad_norm_); 0 == no clipping
     "lr_schedule": None,     # the block {warmup: W, total: T, min_ratio: r}: the rate rises linearly over the first W steps, then

@@ -161,6 +161,8 @@ constexpr int SCRATCH_NS = 20;  // floats per partial-state slot of a split row
 }  // namespace mllp
 
 struct mllp_graph {
+    // (tests/test_pdhg_rays_oracle.py::_sizes stands in for a graph with these four words alone, for refusals and closed forms
+    // that read nothing else of it: keep them first, or change that stand-in with them)
     int64_t M = 0, N = 0, nnz = 0, n_inst = 0;
     mllp::Orient A;   // dst = constraints, src = variables
     mllp::Orient At;  // dst = variables,   src = constraints

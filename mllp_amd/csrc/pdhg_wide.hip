@@ -24,6 +24,10 @@
 // previous call ended exactly at iter_begin (code 0, 6 or 8); otherwise the instance is stale for this call (flag, not state:
 // the state is left as found), its sweeps return at once and finish writes zeros and code 9.
 //
+// mllp_lp_pdhg_rays is the same call with certificates of infeasibility and unboundedness: its own first and
+// last kernel and, with ray_eps >= 0, its own three kernels of a check, further down; every launch of a call has its counterpart
+// in the other call, so the two make the same number of launches.
+//
 // The operator structs and helpers below are copies of pdhg.hip's (ScaledAbs, HalpernCol, HalpernRow, BySum, ByMax,
 // block_max_u32 and the bit helpers), because that file's six kernel instantiations are held to their instruction streams
 // (DESIGN.md 4.22): it is left untouched.  The evaluation walks ONE point with a float accumulator, which is the `cur` half of
@@ -137,8 +141,9 @@ struct ByMax {
 // number: WD_CHUNK rows at a time, and a chunk's rows of the block tier behind its other rows -- a vote of the workgroup says
 // whether it has one, so that every thread takes the barriers of that tier or none does.  No barrier at the end
 template <class Op>
-__device__ __forceinline__ void item_sweep(const int* __restrict__ ptr, int rb, int re, const Op& op, float* part) {
+__device__ __forceinline__ void item_sweep(const int* __restrict__ ptr, int rb, int re, const Op& op, typename Op::Acc* part) {
     using By = typename Op::By;
+    using Acc = typename Op::Acc;
     const int tid = threadIdx.x, lane = tid & 63;
     for (int r0 = rb; r0 < re; r0 += WD_CHUNK) {             // (r0 is uniform in the workgroup)
         const int r = r0 + (tid >> 4);
@@ -147,7 +152,7 @@ __device__ __forceinline__ void item_sweep(const int* __restrict__ ptr, int rb, 
         {   // group tier: every lane reaches the butterfly; a row of another tier runs it over no terms
             const bool mine = in && row_tier(len) == 0;
             const typename Op::Row rc = op.row(mine ? r : rb);
-            const float q = By::template group<16>(strided_terms<16>(op, rc, beg, mine ? len : 0, tid & 15));
+            const Acc q = By::template group<16>(strided_terms<16>(op, rc, beg, mine ? len : 0, tid & 15));
             if (mine && (tid & 15) == 0) op.finish(r, rc, q);
         }
 #pragma unroll
@@ -156,7 +161,7 @@ __device__ __forceinline__ void item_sweep(const int* __restrict__ ptr, int rb, 
             if (row_tier(l4) != 1) continue;                 // (uniform in the wavefront; a row past `re` has no terms)
             const int r4 = r0 + (tid >> 6) * 4 + g;
             const typename Op::Row rc = op.row(r4);
-            const float q = By::template group<64>(strided_terms<64>(op, rc, b4, l4, lane));
+            const Acc q = By::template group<64>(strided_terms<64>(op, rc, b4, l4, lane));
             if (lane == 0) op.finish(r4, rc, q);
         }
         if (!__syncthreads_or(in && row_tier(len) == 2)) continue;
@@ -165,7 +170,7 @@ __device__ __forceinline__ void item_sweep(const int* __restrict__ ptr, int rb, 
             const int b2 = ptr[q2], l2 = ptr[q2 + 1] - b2;
             if (row_tier(l2) != 2) continue;
             const typename Op::Row rc = op.row(q2);
-            const float q = By::template block<WD_NW>(strided_terms<WD_THREADS>(op, rc, b2, l2, tid), part);
+            const Acc q = By::template block<WD_NW>(strided_terms<WD_THREADS>(op, rc, b2, l2, tid), part);
             if (tid == 0) op.finish(q2, rc, q);
         }
     }
@@ -649,6 +654,302 @@ __global__ __launch_bounds__(WD_THREADS) void wide_finish(const WideArgs A) {
     }
 }
 
+// =====================================================================================================================
+// mllp_lp_pdhg_rays: the same call with certificates of infeasibility and unboundedness.  The candidate ray
+// is the direction from the anchor to the step's output, (rx, ry) = (xh - xa, yh - ya), which Halpern's iteration drives to the
+// infimal displacement of the PDHG operator: zero for a solvable LP, a Farkas or recession ray otherwise.  Nothing is stored for
+// it: a check's two sweeps walk every row once for TWO accumulators, the point's and the ray's (pdhg.hip's EvalSweep pair,
+// with zero right-hand sides for the ray), and the decision adds b'ry, c'rx and max(-rx) to the walk that forms c'x and b'y.
+// The kernels above keep their text; with ray_eps < 0 the host launches them for the checks, so that nothing is evaluated.
+//
+// Six more words per instance BEHIND the vectors of the wide layout (which stays as it is): the two ray keys, which are the
+// call's own as the two keys above are, and the four cert words {qp, b'ry, qd, c'rx} of the last check that evaluated the rays,
+// which are STATE (values only) and travel from one call to the next.
+// =====================================================================================================================
+constexpr int WD_CODE_INFEASIBLE = 4, WD_CODE_UNBOUNDED = 5;
+enum { RX_KEY_U = 0, RX_KEY_V, RX_QP, RX_BY, RX_QD, RX_CX, RX_WORDS };
+
+__host__ __device__ constexpr int64_t rays_words(int64_t n_inst, int64_t M, int64_t N) { return wide_words(n_inst, M, N) + RX_WORDS * n_inst; }
+
+// what the new kernels take beside WideArgs (whose layout the kernels above depend on)
+struct RayArgs {
+    float ray_eps;
+    float* ray_x;
+    float* ray_y;
+    float* cert;
+};
+
+__device__ __forceinline__ int* ray_words(const WideArgs& A, int k) {
+    return reinterpret_cast<int*>(A.scratch) + wide_words(A.n_inst, A.M, A.N) + RX_WORDS * (long long)k;
+}
+
+// an evaluation's walk for the point v and the ray fsub(v, va) at once: one load of the value and of the index per term, two
+// gathers.  The point's residual is EvalOne's; the ray's has no right-hand side: |A rx| for rows, max(A'ry, 0) for columns
+template <bool ROWS>
+struct EvalPair {
+    using Acc = Sum2;       // a: the point, b: the ray
+    using Row = NoRow;
+    using By = BySum;
+    const int* __restrict__ idx;
+    const float* __restrict__ val;
+    const float* __restrict__ rhs;
+    int off;
+    const float *v, *va;
+    unsigned* best;         // [2]: the point's key, the ray's
+    __device__ __forceinline__ Row row(int) const { return {}; }
+    __device__ __forceinline__ void term(const Row&, int e, Sum2& q) const {
+        const float a = val[e];
+        const int i = idx[e] - off;
+        const float p = v[i];
+        q.a = __fmaf_rn(a, p, q.a);
+        q.b = __fmaf_rn(a, __fsub_rn(p, va[i]), q.b);
+    }
+    __device__ __forceinline__ void finish(int r, const Row&, Sum2 q) const {
+        const float d = __fsub_rn(q.a, rhs[r]);
+        const unsigned k = ROWS ? abs_bits(d) : pos_bits(d), kr = ROWS ? abs_bits(q.b) : pos_bits(q.b);
+        best[0] = k > best[0] ? k : best[0];
+        best[1] = kr > best[1] ? kr : best[1];
+    }
+};
+
+// ---- the first kernel of a rays call: wide_prep, which also knows codes 4 and 5, clears the ray keys and starts the cert ----
+__global__ __launch_bounds__(WD_THREADS) void rays_prep(const WideArgs A) {
+    __shared__ unsigned s_key[WD_NW * 2];
+    __shared__ long long s_off[WD_NW * 2];
+    const int k = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const WideView V = wide_view(A, k);
+    int* rw = ray_words(A, k);
+    long long fn = 0, fm = 0;
+    for (int j = tid; j < k; j += WD_THREADS) {
+        fn += (A.ptr_n[j + 1] - A.ptr_n[j] + A.rows - 1) / A.rows;
+        fm += (A.ptr_m[j + 1] - A.ptr_m[j] + A.rows - 1) / A.rows;
+    }
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        fn += __shfl_xor(fn, o, 64);
+        fm += __shfl_xor(fm, o, 64);
+    }
+    if (lane == 0) { s_off[wave * 2] = fn; s_off[wave * 2 + 1] = fm; }
+    __syncthreads();
+    if (tid == 0) {
+        fn = fm = 0;
+        for (int w = 0; w < WD_NW; ++w) { fn += s_off[w * 2]; fm += s_off[w * 2 + 1]; }
+        V.ex[WX_FIRST_N] = (int)fn;
+        V.ex[WX_FIRST_M] = (int)fm;
+        V.ex[WX_KEY_COL] = 0;
+        V.ex[WX_KEY_ROW] = 0;
+        rw[RX_KEY_U] = 0;
+        rw[RX_KEY_V] = 0;
+    }
+    if (A.iter_begin > 0) {
+        if (tid == 0) {
+            const int code = V.st[WS_CODE];
+            const bool known = code == WD_CODE_OPTIMAL || code == WD_CODE_LIMIT || code == WD_CODE_NOT_FINITE || code == WD_CODE_INFEASIBLE ||
+                               code == WD_CODE_UNBOUNDED;
+            V.ex[WX_FLAG] = !known || get64(V.st, WS_REACHED_LO) != A.iter_begin ? WD_STALE : code == WD_CODE_LIMIT ? WD_RUN : WD_IDLE;
+        }
+        return;
+    }
+    const float* c = A.c + V.col0;
+    const float* b = A.b + V.row0;
+    unsigned kn[2] = {0u, 0u};      // ||b||inf, ||c||inf
+    for (int j = tid; j < V.n; j += WD_THREADS) {
+        kn[1] = max(kn[1], abs_bits(c[j]));
+        const float v = A.x0 ? clip0(A.x0[V.col0 + j]) : 0.0f;
+        V.x[j] = v;
+        V.xh[j] = v;
+        V.dc[j] = 1.0f;
+    }
+    for (int i = tid; i < V.m; i += WD_THREADS) {
+        kn[0] = max(kn[0], abs_bits(b[i]));
+        const float v = A.y0 ? A.y0[V.row0 + i] : 0.0f;
+        V.y[i] = v;
+        V.yh[i] = v;
+        V.dr[i] = 1.0f;
+    }
+    block_max_u32<WD_NW, 2>(kn, s_key);
+    if (tid == 0) {
+        V.ex[WX_FLAG] = WD_RUN;
+        V.st[WS_CODE] = WD_CODE_LIMIT;
+        put64(V.st, WS_IT_LO, 0);
+        put64(V.st, WS_REACHED_LO, -1);
+        put64(V.st, WS_LAST_LO, 0);
+        V.st[WS_RESTARTS] = 0;
+        V.st[WS_E_LAST] = __float_as_int(__builtin_huge_valf());
+        V.st[WS_DEN_P] = __float_as_int(__fadd_rn(1.0f, __uint_as_float(kn[0])));
+        V.st[WS_DEN_D] = __float_as_int(__fadd_rn(1.0f, __uint_as_float(kn[1])));
+        rw[RX_QP] = __float_as_int(__builtin_huge_valf());      // no check has evaluated the rays
+        rw[RX_BY] = 0;
+        rw[RX_QD] = __float_as_int(__builtin_huge_valf());
+        rw[RX_CX] = 0;
+    }
+}
+
+// ---- a check's two sweeps of (xh, yh) and of the ray, for the running instances.  Two integer maxima per workgroup ----
+template <bool ROWS>
+__global__ __launch_bounds__(WD_THREADS) void rays_eval(const WideArgs A) {
+    __shared__ Sum2 s_part2[WD_NW];
+    __shared__ unsigned s_key[WD_NW * 2];
+    int k, rb, re;
+    if (!wide_item<!ROWS>(A, &k, &rb, &re)) return;
+    const WideView V = wide_view(A, k);
+    if (V.ex[WX_FLAG] != WD_RUN || V.st[WS_CODE] != WD_CODE_LIMIT) return;
+    unsigned best[2] = {0u, 0u};
+    if constexpr (ROWS)
+        item_sweep(A.a_ptr + V.row0, rb, re, EvalPair<true>{A.a_idx, A.a_val, A.b + V.row0, V.col0, V.xh, V.xa, best}, s_part2);
+    else
+        item_sweep(A.at_ptr + V.col0, rb, re, EvalPair<false>{A.at_idx, A.at_val, A.c + V.col0, V.row0, V.yh, V.ya, best}, s_part2);
+    block_max_u32<WD_NW, 2>(best, s_key);
+    if (threadIdx.x != 0) return;
+    int* rw = ray_words(A, k);
+    if (best[0]) atomicMax(reinterpret_cast<unsigned*>(V.ex + (ROWS ? WX_KEY_ROW : WX_KEY_COL)), best[0]);
+    if (best[1]) atomicMax(reinterpret_cast<unsigned*>(rw + (ROWS ? RX_KEY_V : RX_KEY_U)), best[1]);
+}
+
+// ---- a check's decision with the rays: wide_decide with the ray step between "e <= eps" and the restart test ----
+__global__ __launch_bounds__(WD_THREADS) void rays_decide(const WideArgs A, const RayArgs R, long long it) {
+    __shared__ Sum2 s_part2[WD_NW];
+    __shared__ unsigned s_key[WD_NW];
+    const int tid = threadIdx.x;
+    const WideView V = wide_view(A, blockIdx.x);
+    if (V.ex[WX_FLAG] != WD_RUN || V.st[WS_CODE] != WD_CODE_LIMIT) return;
+    int* rw = ray_words(A, blockIdx.x);
+    const long long cnt = it - get64(V.st, WS_LAST_LO);
+    const float e_last = stf(V.st, WS_E_LAST), w0 = stf(V.st, WS_W0), w = stf(V.st, WS_W), eta = stf(V.st, WS_ETA);
+    const int restarts = V.st[WS_RESTARTS];
+    const float* c = A.c + V.col0;
+    const float* b = A.b + V.row0;
+    const unsigned key_p = (unsigned)V.ex[WX_KEY_ROW], key_d = (unsigned)V.ex[WX_KEY_COL];
+    const unsigned key_u = (unsigned)rw[RX_KEY_U], key_v = (unsigned)rw[RX_KEY_V];
+    // one walk: c'x and b'y of the point, c'rx and b'ry of the ray, the largest -rx
+    Sum2 s = {0.0f, 0.0f}, r = {0.0f, 0.0f};
+    unsigned neg[1] = {0u};
+    for (int j = tid; j < V.n; j += WD_THREADS) {
+        const float xh = V.xh[j], rx = __fsub_rn(xh, V.xa[j]);
+        s.a = __fmaf_rn(c[j], xh, s.a);
+        r.a = __fmaf_rn(c[j], rx, r.a);
+        const unsigned kn = pos_bits(-rx);
+        neg[0] = kn > neg[0] ? kn : neg[0];
+    }
+    for (int i = tid; i < V.m; i += WD_THREADS) {
+        const float yh = V.yh[i];
+        s.b = __fmaf_rn(b[i], yh, s.b);
+        r.b = __fmaf_rn(b[i], __fsub_rn(yh, V.ya[i]), r.b);
+    }
+    s = block_tree_sum<WD_NW>(s, s_part2);          // (its barriers: every thread has read the four keys)
+    r = block_tree_sum<WD_NW>(r, s_part2);
+    block_max_u32<WD_NW, 1>(neg, s_key);
+    if (tid == 0) {
+        V.ex[WX_KEY_ROW] = 0;
+        V.ex[WX_KEY_COL] = 0;
+        rw[RX_KEY_U] = 0;
+        rw[RX_KEY_V] = 0;
+    }
+    const float gap = __fdiv_rn(fabsf(__fsub_rn(s.a, s.b)), __fadd_rn(__fadd_rn(1.0f, fabsf(s.a)), fabsf(s.b)));
+    const WideErr at = {__fdiv_rn(__uint_as_float(key_p), stf(V.st, WS_DEN_P)), __fdiv_rn(__uint_as_float(key_d), stf(V.st, WS_DEN_D)), gap};
+    const float e = at.worst();
+    if (!finite_bits(e) || e <= A.eps) {
+        if (tid == 0) {
+            V.st[WS_CODE] = finite_bits(e) ? WD_CODE_OPTIMAL : WD_CODE_NOT_FINITE;
+            put64(V.st, WS_IT_LO, it);
+        }
+        return;
+    }
+    // the rays: qp = U / b'ry, qd = V / -c'rx; a comparison with a NaN is false
+    const float cx = r.a, by = r.b, inf = __builtin_huge_valf();
+    const float U = __uint_as_float(key_u), Vr = __uint_as_float(key_v > neg[0] ? key_v : neg[0]);
+    const float qp = finite_bits(by) && by > 0.0f ? __fdiv_rn(U, by) : inf;
+    const float qd = finite_bits(cx) && cx < 0.0f ? __fdiv_rn(Vr, -cx) : inf;
+    if (tid == 0) {
+        rw[RX_QP] = __float_as_int(qp);
+        rw[RX_BY] = __float_as_int(by);
+        rw[RX_QD] = __float_as_int(qd);
+        rw[RX_CX] = __float_as_int(cx);
+    }
+    if (qp <= R.ray_eps || qd <= R.ray_eps) {
+        if (tid == 0) {
+            V.st[WS_CODE] = qp <= R.ray_eps ? WD_CODE_INFEASIBLE : WD_CODE_UNBOUNDED;
+            put64(V.st, WS_IT_LO, it);
+        }
+        return;
+    }
+    if (!(e <= __fmul_rn(A.beta, e_last) || 25 * cnt >= 9 * it)) return;
+    // the restart, as wide_decide makes it
+    Sum2 dd = {0.0f, 0.0f};
+    for (int j = tid; j < V.n; j += WD_THREADS) {
+        const float v = V.xh[j], d = __fsub_rn(v, V.xa[j]);
+        dd.a = __fmaf_rn(d, __fdiv_rn(d, V.tc[j]), dd.a);
+        V.x[j] = V.xa[j] = v;
+    }
+    for (int i = tid; i < V.m; i += WD_THREADS) {
+        const float v = V.yh[i], d = __fsub_rn(v, V.ya[i]);
+        dd.b = __fmaf_rn(d, __fdiv_rn(d, V.tr[i]), dd.b);
+        V.y[i] = V.ya[i] = v;
+    }
+    dd = block_tree_sum<WD_NW>(dd, s_part2);
+    if (tid != 0) return;
+    V.st[WS_RESTARTS] = restarts + 1;
+    V.st[WS_E_LAST] = __float_as_int(e);
+    put64(V.st, WS_LAST_LO, it);
+    if (!A.primal_weight) return;
+    const float dx = sqrt_rn(dd.a), dy = sqrt_rn(dd.b);
+    if (finite_pos(dx) && finite_pos(dy)) {
+        const float w_lo = __fdiv_rn(w0, A.span), w_hi = __fmul_rn(w0, A.span);
+        const float raw = sqrt_rn(__fmul_rn(w, __fdiv_rn(dy, dx)));
+        const float up = raw > w_lo ? raw : w_lo;
+        const float wn = up < w_hi ? up : w_hi;
+        V.st[WS_W] = __float_as_int(wn);
+        V.st[WS_TAU] = __float_as_int(__fdiv_rn(eta, wn));
+        V.st[WS_SIGMA] = __float_as_int(__fmul_rn(eta, wn));
+    }
+}
+
+// ---- the last kernel of a rays call: wide_finish, and the rays (from the frozen xh - xa, so with the bits of the deciding
+// check) and the cert words ----
+__global__ __launch_bounds__(WD_THREADS) void rays_finish(const WideArgs A, const RayArgs R) {
+    __shared__ Sum2 s_part2[WD_NW];
+    const int tid = threadIdx.x;
+    const WideView V = wide_view(A, blockIdx.x);
+    const bool stale = V.ex[WX_FLAG] == WD_STALE;       // (uniform in the workgroup)
+    const int code = stale ? WD_CODE_STALE : V.st[WS_CODE];
+    WideErr out = {0.0f, 0.0f, 0.0f};
+    if (!stale) out = wide_errors(A, V, s_part2);
+    for (int j = tid; j < V.n; j += WD_THREADS) {
+        A.x_out[V.col0 + j] = stale ? 0.0f : V.xh[j];
+        if (A.dc_out) A.dc_out[V.col0 + j] = stale ? 0.0f : V.dc[j];
+        if (R.ray_x) R.ray_x[V.col0 + j] = code == WD_CODE_UNBOUNDED ? __fsub_rn(V.xh[j], V.xa[j]) : 0.0f;
+    }
+    for (int i = tid; i < V.m; i += WD_THREADS) {
+        A.y_out[V.row0 + i] = stale ? 0.0f : V.yh[i];
+        if (A.dr_out) A.dr_out[V.row0 + i] = stale ? 0.0f : V.dr[i];
+        if (R.ray_y) R.ray_y[V.row0 + i] = code == WD_CODE_INFEASIBLE ? __fsub_rn(V.yh[i], V.ya[i]) : 0.0f;
+    }
+    if (tid != 0) return;
+    int* st = A.status + 4 * (size_t)V.k;
+    float* q = A.kkt ? A.kkt + 6 * (size_t)V.k : nullptr;
+    float* ce = R.cert ? R.cert + 4 * (size_t)V.k : nullptr;
+    if (stale) {
+        st[0] = WD_CODE_STALE; st[1] = 0; st[2] = 0; st[3] = 0;
+        if (q) q[0] = q[1] = q[2] = q[3] = q[4] = q[5] = 0.0f;
+        if (ce) ce[0] = ce[1] = ce[2] = ce[3] = 0.0f;
+        return;
+    }
+    if (code == WD_CODE_LIMIT) put64(V.st, WS_IT_LO, A.iter_end);
+    put64(V.st, WS_REACHED_LO, A.iter_end);
+    st[0] = code;
+    st[1] = (int)min(get64(V.st, WS_IT_LO), (long long)0x7fffffff);
+    st[2] = V.st[WS_RESTARTS];
+    st[3] = 0;
+    if (q) {
+        q[0] = out.p; q[1] = out.d; q[2] = out.g;
+        q[3] = stf(V.st, WS_ETA); q[4] = stf(V.st, WS_W0); q[5] = stf(V.st, WS_W);
+    }
+    if (ce) {
+        const int* rw = ray_words(A, V.k);
+        ce[0] = stf(rw, RX_QP); ce[1] = stf(rw, RX_BY); ce[2] = stf(rw, RX_QD); ce[3] = stf(rw, RX_CX);
+    }
+}
+
 bool overlaps(const void* a, int64_t a_bytes, const void* b, int64_t b_bytes) {
     if (!a || !b || a_bytes <= 0 || b_bytes <= 0) return false;
     const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
@@ -669,60 +970,43 @@ int64_t wide_items(const std::vector<int64_t>& p, int64_t n_inst, int64_t rows) 
     return items;
 }
 
+// a launch of the entry point `fn` ("mllp_" + what an error names it by)
 template <class... KArgs, class... Args>
-int wide_go(void (*kernel)(KArgs...), const char* what, int64_t grid, hipStream_t s, const Args&... args) {
+int wide_go(void (*kernel)(KArgs...), const char* fn, const char* what, int64_t grid, hipStream_t s, const Args&... args) {
     if (grid <= 0) return MLLP_OK;
     hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(WD_THREADS), 0, s, args...);
-    return check_launch(what);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? MLLP_OK : hip_fail(e, (std::string(fn + 5) + " (" + what + ")").c_str());
 }
 
-}  // namespace
-
-}  // namespace mllp
-
-using namespace mllp;
-
-extern "C" int mllp_lp_pdhg_wide_limits(int64_t* limits) {
-    REQUIRE(limits, "null argument");
-    limits[0] = WD_THREADS;
-    limits[1] = WD_MAX_RUIZ;
-    limits[2] = WD_ROWS_DEFAULT;
-    limits[3] = WD_ROWS_MAX;
-    return MLLP_OK;
-}
-
-extern "C" int mllp_lp_pdhg_wide_scratch_bytes(const mllp_graph_t* g, int64_t rows_per_item, int64_t* bytes) {
-    REQUIRE(g && bytes, "null argument");
+// mllp_lp_pdhg_wide (rays == nullptr) and mllp_lp_pdhg_rays: the refusals, the arguments and the launches.  The two calls make
+// the same launches in the same order; with rays the first and the last kernel are the rays' own, and with ray_eps >= 0 so are
+// the three of a check
+int wide_call(const char* fn, const mllp_graph_t* g, const float* d_x1, const float* d_x2, const float* d_x0, const float* d_y0, int64_t iter_begin,
+              int64_t iter_end, int64_t check_every, float eps, float step, float beta, int64_t ruiz_passes, int32_t pock_chambolle,
+              int32_t primal_weight, float weight_span, int32_t reflect, const RayArgs* rays, int64_t rows_per_item, float* d_x, float* d_y,
+              float* d_dr, float* d_dc, int32_t* d_status, float* d_kkt, void* d_scratch, void* stream) {
+    REQUIRE_FOR(fn, g && d_x1 && d_x2 && d_x && d_y && d_status, "null argument (g, d_x1, d_x2, d_x, d_y and d_status are required)");
+    REQUIRE_FOR(fn, iter_begin >= 0, "iter_begin must not be negative");
+    REQUIRE_FOR(fn, iter_end >= iter_begin, "iter_end must not be below iter_begin");
+    REQUIRE_FOR(fn, check_every >= 0, "check_every must not be negative");
+    REQUIRE_FOR(fn, std::isfinite(eps) && eps >= 0.0f, "eps must be finite and not negative");
+    REQUIRE_FOR(fn, std::isfinite(step) && step > 0.0f && step <= 1.0f, "step must be in (0, 1]");
+    REQUIRE_FOR(fn, std::isfinite(beta) && beta > 0.0f && beta < 1.0f, "beta must be in (0, 1)");
+    REQUIRE_FOR(fn, ruiz_passes >= 0 && ruiz_passes <= WD_MAX_RUIZ, "ruiz_passes must be in 0 .. 64");
+    REQUIRE_FOR(fn, std::isfinite(weight_span) && weight_span >= 1.0f, "weight_span must be finite and at least 1");
+    REQUIRE_FOR(fn, !rays || std::isfinite(rays->ray_eps), "ray_eps must be finite (negative: no detection)");
     int64_t rows;
-    if (int rc = wide_rows(__func__, rows_per_item, &rows)) return rc;
-    *bytes = wide_words(g->n_inst, g->M, g->N) * (int64_t)sizeof(float);
-    return MLLP_OK;
-}
-
-extern "C" int mllp_lp_pdhg_wide(const mllp_graph_t* g, const float* d_x1, const float* d_x2, const float* d_x0, const float* d_y0,
-                                 int64_t iter_begin, int64_t iter_end, int64_t check_every, float eps, float step, float beta,
-                                 int64_t ruiz_passes, int32_t pock_chambolle, int32_t primal_weight, float weight_span, int32_t reflect,
-                                 int64_t rows_per_item, float* d_x, float* d_y, float* d_dr, float* d_dc, int32_t* d_status, float* d_kkt,
-                                 void* d_scratch, void* stream) {
-    REQUIRE(g && d_x1 && d_x2 && d_x && d_y && d_status, "null argument (g, d_x1, d_x2, d_x, d_y and d_status are required)");
-    REQUIRE(iter_begin >= 0, "iter_begin must not be negative");
-    REQUIRE(iter_end >= iter_begin, "iter_end must not be below iter_begin");
-    REQUIRE(check_every >= 0, "check_every must not be negative");
-    REQUIRE(std::isfinite(eps) && eps >= 0.0f, "eps must be finite and not negative");
-    REQUIRE(std::isfinite(step) && step > 0.0f && step <= 1.0f, "step must be in (0, 1]");
-    REQUIRE(std::isfinite(beta) && beta > 0.0f && beta < 1.0f, "beta must be in (0, 1)");
-    REQUIRE(ruiz_passes >= 0 && ruiz_passes <= WD_MAX_RUIZ, "ruiz_passes must be in 0 .. 64");
-    REQUIRE(std::isfinite(weight_span) && weight_span >= 1.0f, "weight_span must be finite and at least 1");
-    int64_t rows;
-    if (int rc = wide_rows(__func__, rows_per_item, &rows)) return rc;
-    const int64_t words = wide_words(g->n_inst, g->M, g->N);
-    REQUIRE(words == 0 || d_scratch, "null d_scratch (mllp_lp_pdhg_wide_scratch_bytes is not 0)");
+    if (int rc = wide_rows(fn, rows_per_item, &rows)) return rc;
+    const int64_t words = rays ? rays_words(g->n_inst, g->M, g->N) : wide_words(g->n_inst, g->M, g->N);
+    REQUIRE_FOR(fn, words == 0 || d_scratch, std::string("null d_scratch (") + fn + "_scratch_bytes is not 0)");
     const struct {
         const void* p;
         int64_t bytes;
-    } outs[] = {{d_x, g->N * 4}, {d_y, g->M * 4}, {d_dr, g->M * 4}, {d_dc, g->N * 4}, {d_status, g->n_inst * 16}, {d_kkt, g->n_inst * 24}};
+    } outs[] = {{d_x, g->N * 4}, {d_y, g->M * 4}, {d_dr, g->M * 4}, {d_dc, g->N * 4}, {d_status, g->n_inst * 16}, {d_kkt, g->n_inst * 24},
+                {rays ? rays->ray_x : nullptr, g->N * 4}, {rays ? rays->ray_y : nullptr, g->M * 4}, {rays ? rays->cert : nullptr, g->n_inst * 16}};
     for (const auto& o : outs)
-        REQUIRE(!overlaps(d_x0, g->N * 4, o.p, o.bytes) && !overlaps(d_y0, g->M * 4, o.p, o.bytes), "d_x0 or d_y0 overlaps an output");
+        REQUIRE_FOR(fn, !overlaps(d_x0, g->N * 4, o.p, o.bytes) && !overlaps(d_y0, g->M * 4, o.p, o.bytes), "d_x0 or d_y0 overlaps an output");
     if (g->n_inst <= 0) return MLLP_OK;
 
     WideArgs a{};
@@ -736,36 +1020,97 @@ extern "C" int mllp_lp_pdhg_wide(const mllp_graph_t* g, const float* d_x1, const
     a.M = (long long)g->M; a.N = (long long)g->N;
     a.x_out = d_x; a.y_out = d_y; a.dr_out = d_dr; a.dc_out = d_dc; a.status = d_status; a.kkt = d_kkt;
     a.scratch = static_cast<float*>(d_scratch);
+    const bool detect = rays && rays->ray_eps >= 0.0f;
+    const RayArgs r = rays ? *rays : RayArgs{};
 
     hipStream_t s = (hipStream_t)stream;
     const int64_t K = g->n_inst;
     const int64_t items_n = wide_items(g->h_inst_ptr_n, K, rows), items_m = wide_items(g->h_inst_ptr_m, K, rows);
-    int rc = wide_go(wide_prep, "lp_pdhg_wide (prep)", K, s, a);
+    int rc = rays ? wide_go(rays_prep, fn, "prep", K, s, a) : wide_go(wide_prep, fn, "prep", K, s, a);
     if (!rc && iter_begin == 0) {
         for (int64_t p = 0; !rc && p < ruiz_passes + (pock_chambolle ? 1 : 0); ++p) {
             if (p < ruiz_passes) {
-                rc = wide_go(wide_scale_walk<true, true, false>, "lp_pdhg_wide (scaling, columns)", items_n, s, a);
-                if (!rc) rc = wide_go(wide_scale_walk<false, true, false>, "lp_pdhg_wide (scaling, rows)", items_m, s, a);
+                rc = wide_go(wide_scale_walk<true, true, false>, fn, "scaling, columns", items_n, s, a);
+                if (!rc) rc = wide_go(wide_scale_walk<false, true, false>, fn, "scaling, rows", items_m, s, a);
             } else {
-                rc = wide_go(wide_scale_walk<true, false, false>, "lp_pdhg_wide (scaling, columns)", items_n, s, a);
-                if (!rc) rc = wide_go(wide_scale_walk<false, false, false>, "lp_pdhg_wide (scaling, rows)", items_m, s, a);
+                rc = wide_go(wide_scale_walk<true, false, false>, fn, "scaling, columns", items_n, s, a);
+                if (!rc) rc = wide_go(wide_scale_walk<false, false, false>, fn, "scaling, rows", items_m, s, a);
             }
-            if (!rc) rc = wide_go(wide_scale_update, "lp_pdhg_wide (scaling, update)", K, s, a);
+            if (!rc) rc = wide_go(wide_scale_update, fn, "scaling, update", K, s, a);
         }
-        if (!rc) rc = wide_go(wide_scale_walk<true, false, true>, "lp_pdhg_wide (norm, columns)", items_n, s, a);
-        if (!rc) rc = wide_go(wide_scale_walk<false, false, true>, "lp_pdhg_wide (norm, rows)", items_m, s, a);
-        if (!rc) rc = wide_go(wide_start, "lp_pdhg_wide (start)", K, s, a);
+        if (!rc) rc = wide_go(wide_scale_walk<true, false, true>, fn, "norm, columns", items_n, s, a);
+        if (!rc) rc = wide_go(wide_scale_walk<false, false, true>, fn, "norm, rows", items_m, s, a);
+        if (!rc) rc = wide_go(wide_start, fn, "start", K, s, a);
     }
     for (long long it = (long long)iter_begin; !rc && it < (long long)iter_end; ++it) {
-        rc = wide_go(wide_step<true>, "lp_pdhg_wide (columns)", items_n, s, a, it);
-        if (!rc) rc = wide_go(wide_step<false>, "lp_pdhg_wide (rows)", items_m, s, a, it);
+        rc = wide_go(wide_step<true>, fn, "columns", items_n, s, a, it);
+        if (!rc) rc = wide_go(wide_step<false>, fn, "rows", items_m, s, a, it);
         if (rc || check_every == 0 || (it + 1) % check_every) continue;
-        rc = wide_go(wide_eval<true, false>, "lp_pdhg_wide (check, rows)", items_m, s, a);
-        if (!rc) rc = wide_go(wide_eval<false, false>, "lp_pdhg_wide (check, columns)", items_n, s, a);
-        if (!rc) rc = wide_go(wide_decide, "lp_pdhg_wide (check)", K, s, a, it + 1);
+        if (detect) {
+            rc = wide_go(rays_eval<true>, fn, "check, rows", items_m, s, a);
+            if (!rc) rc = wide_go(rays_eval<false>, fn, "check, columns", items_n, s, a);
+            if (!rc) rc = wide_go(rays_decide, fn, "check", K, s, a, r, it + 1);
+        } else {
+            rc = wide_go(wide_eval<true, false>, fn, "check, rows", items_m, s, a);
+            if (!rc) rc = wide_go(wide_eval<false, false>, fn, "check, columns", items_n, s, a);
+            if (!rc) rc = wide_go(wide_decide, fn, "check", K, s, a, it + 1);
+        }
     }
-    if (!rc) rc = wide_go(wide_eval<true, true>, "lp_pdhg_wide (evaluation, rows)", items_m, s, a);
-    if (!rc) rc = wide_go(wide_eval<false, true>, "lp_pdhg_wide (evaluation, columns)", items_n, s, a);
-    if (!rc) rc = wide_go(wide_finish, "lp_pdhg_wide (finish)", K, s, a);
+    if (!rc) rc = wide_go(wide_eval<true, true>, fn, "evaluation, rows", items_m, s, a);
+    if (!rc) rc = wide_go(wide_eval<false, true>, fn, "evaluation, columns", items_n, s, a);
+    if (!rc) rc = rays ? wide_go(rays_finish, fn, "finish", K, s, a, r) : wide_go(wide_finish, fn, "finish", K, s, a);
     return rc;
 }
+
+}  // namespace
+
+}  // namespace mllp
+
+using namespace mllp;
+
+static int wide_limits(const char* fn, int64_t* limits) {
+    REQUIRE_FOR(fn, limits, "null argument");
+    limits[0] = WD_THREADS;
+    limits[1] = WD_MAX_RUIZ;
+    limits[2] = WD_ROWS_DEFAULT;
+    limits[3] = WD_ROWS_MAX;
+    return MLLP_OK;
+}
+
+static int wide_scratch_bytes(const char* fn, const mllp_graph_t* g, int64_t rows_per_item, bool rays, int64_t* bytes) {
+    REQUIRE_FOR(fn, g && bytes, "null argument");
+    int64_t rows;
+    if (int rc = wide_rows(fn, rows_per_item, &rows)) return rc;
+    *bytes = (rays ? rays_words(g->n_inst, g->M, g->N) : wide_words(g->n_inst, g->M, g->N)) * (int64_t)sizeof(float);
+    return MLLP_OK;
+}
+
+extern "C" int mllp_lp_pdhg_wide_limits(int64_t* limits) { return wide_limits(__func__, limits); }
+extern "C" int mllp_lp_pdhg_rays_limits(int64_t* limits) { return wide_limits(__func__, limits); }
+
+extern "C" int mllp_lp_pdhg_wide_scratch_bytes(const mllp_graph_t* g, int64_t rows_per_item, int64_t* bytes) {
+    return wide_scratch_bytes(__func__, g, rows_per_item, false, bytes);
+}
+extern "C" int mllp_lp_pdhg_rays_scratch_bytes(const mllp_graph_t* g, int64_t rows_per_item, int64_t* bytes) {
+    return wide_scratch_bytes(__func__, g, rows_per_item, true, bytes);
+}
+
+extern "C" int mllp_lp_pdhg_wide(const mllp_graph_t* g, const float* d_x1, const float* d_x2, const float* d_x0, const float* d_y0,
+                                 int64_t iter_begin, int64_t iter_end, int64_t check_every, float eps, float step, float beta,
+                                 int64_t ruiz_passes, int32_t pock_chambolle, int32_t primal_weight, float weight_span, int32_t reflect,
+                                 int64_t rows_per_item, float* d_x, float* d_y, float* d_dr, float* d_dc, int32_t* d_status, float* d_kkt,
+                                 void* d_scratch, void* stream) {
+    return wide_call(__func__, g, d_x1, d_x2, d_x0, d_y0, iter_begin, iter_end, check_every, eps, step, beta, ruiz_passes, pock_chambolle,
+                     primal_weight, weight_span, reflect, nullptr, rows_per_item, d_x, d_y, d_dr, d_dc, d_status, d_kkt, d_scratch, stream);
+}
+
+extern "C" int mllp_lp_pdhg_rays(const mllp_graph_t* g, const float* d_x1, const float* d_x2, const float* d_x0, const float* d_y0,
+                                 int64_t iter_begin, int64_t iter_end, int64_t check_every, float eps, float step, float beta,
+                                 int64_t ruiz_passes, int32_t pock_chambolle, int32_t primal_weight, float weight_span, int32_t reflect,
+                                 float ray_eps, int64_t rows_per_item, float* d_x, float* d_y, float* d_dr, float* d_dc, float* d_ray_x,
+                                 float* d_ray_y, int32_t* d_status, float* d_kkt, float* d_cert, void* d_scratch, void* stream) {
+    const RayArgs rays{ray_eps, d_ray_x, d_ray_y, d_cert};
+    return wide_call(__func__, g, d_x1, d_x2, d_x0, d_y0, iter_begin, iter_end, check_every, eps, step, beta, ruiz_passes, pock_chambolle,
+                     primal_weight, weight_span, reflect, &rays, rows_per_item, d_x, d_y, d_dr, d_dc, d_status, d_kkt, d_scratch, stream);
+}
+

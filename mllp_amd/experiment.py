@@ -218,6 +218,21 @@ def pivot_counts(batch, logits, report):
 
 
 PDHG_KEYS = ("pdhg_converged", "pdhg_iterations", "optimal_after_pdhg")
+PDHG_RAY_KEYS = ("pdhg_infeasible", "pdhg_unbounded")       # with `rays` inside the pdhg block
+
+
+def _pdhg_rays(opt):
+    """the `rays` option of the pdhg block: None when absent or false, else ray_eps"""
+    rays = opt.get("rays")
+    if rays is None or rays is False:
+        return None
+    own = {} if rays is True else dict(rays)
+    if set(own) - {"eps"}:
+        raise ValueError(f"report_solved: pdhg: rays: unknown keys {sorted(set(own) - {'eps'})}")
+    ray_eps = float(own.get("eps", 2.0 ** -10))
+    if not ray_eps >= 0.0 or ray_eps == float("inf"):
+        raise ValueError("report_solved: pdhg: rays: eps must be finite and not negative")
+    return ray_eps
 
 
 def pdhg_counts(batch, logits, report):
@@ -233,8 +248,12 @@ def pdhg_counts(batch, logits, report):
     `wide: true` runs Halpern's iteration across the whole device (LPBatch.pdhg_wide: the same rule and the same bits, for
     instances too long for one workgroup), `wide: {rows: R, poll: P}` with R rows per work item and the codes polled every
     P iterations (one sync per poll; an early stop then costs nothing); it takes the `halpern:` and `scaled:` options, and
-    `scaled: false` beside it is refused likewise.  Without any of the three keys (or with `false`) the call is
-    LPBatch.pdhg.  No sync unless `poll` is given."""
+    `scaled: false` beside it is refused likewise.  `rays: true` or `rays: {eps: E}` selects the wide call with certificates
+    of infeasibility and unboundedness (LPBatch.pdhg_rays, ray_eps E, default 2^-10): it implies `wide` (`wide: false` beside
+    it is refused), takes its options, and two more counts are returned, by PDHG_RAY_KEYS: the instances that ended with
+    code 4 and with code 5 -- "no feasible point with a 1-norm below 1 / E" and its dual, which is infeasibility only where E
+    is small against the solutions' size.  Without any of the four keys (or with `false`) the call is LPBatch.pdhg.  No sync unless `poll`
+    is given."""
     opt = report["pdhg"]
     for key in ("iters", "eps"):
         if key not in opt:
@@ -242,8 +261,13 @@ def pdhg_counts(batch, logits, report):
     max_m = report.get("max_m")
     start = batch.repair_basis(logits, max_m=max_m, want=("basis", "x", "y")) if opt.get("warm", True) else None
     scaled, halpern, wide = opt.get("scaled"), opt.get("halpern"), opt.get("wide")
+    ray_eps = _pdhg_rays(opt)
+    if ray_eps is not None and wide is False:
+        raise ValueError("report_solved: pdhg: rays runs on the wide call: it cannot go with wide: false")
     halpern = None if halpern is False else halpern
     wide = None if wide is False else wide
+    if ray_eps is not None and wide is None:
+        wide = True                 # the call with certificates IS the wide call
     if wide is not None and scaled is False:
         raise ValueError("report_solved: pdhg: wide is a preconditioned call: it cannot go with scaled: false")
     if wide is not None and halpern is None:
@@ -274,16 +298,24 @@ def pdhg_counts(batch, logits, report):
             if poll is not None and int(poll) <= 0:
                 raise ValueError("report_solved: pdhg: wide: poll must be positive")
             kw.update(rows_per_item=None if rows is None else int(rows), poll_every=None if poll is None else int(poll))
-        call = batch.pdhg_wide if wide is not None else batch.pdhg_scaled if halpern is None else batch.pdhg_halpern
+        if ray_eps is not None:
+            kw["ray_eps"] = ray_eps
+        call = (batch.pdhg_rays if ray_eps is not None else batch.pdhg_wide if wide is not None else batch.pdhg_scaled if halpern is None
+                else batch.pdhg_halpern)
         res = call(int(opt["iters"]), eps=float(opt["eps"]), check_every=int(opt.get("check", 64)), start=start, **kw)
     got = batch.solved(batch.pdhg_basis(res, max_m=max_m), report["feas_tol"], report["opt_tol"])
-    return torch.stack([(res.status[:, 0] == 0).sum(), res.status[:, 1].sum(), got["optimal"].sum()]).float()
+    counts = [(res.status[:, 0] == 0).sum(), res.status[:, 1].sum(), got["optimal"].sum()]
+    if ray_eps is not None:
+        counts += [(res.status[:, 0] == 4).sum(), (res.status[:, 0] == 5).sum()]
+    return torch.stack(counts).float()
 
 
 def report_keys(report):
     """the keys `report_solved` adds to the log: SOLVED_KEYS, PIVOT_KEYS when the block has `pivots`, PDHG_KEYS when it
-    has `pdhg`"""
-    return SOLVED_KEYS + (PIVOT_KEYS if report.get("pivots") is not None else ()) + (PDHG_KEYS if report.get("pdhg") is not None else ())
+    has `pdhg`, and PDHG_RAY_KEYS when that has `rays`"""
+    pdhg = report.get("pdhg")
+    return (SOLVED_KEYS + (PIVOT_KEYS if report.get("pivots") is not None else ()) + (PDHG_KEYS if pdhg is not None else ())
+            + (PDHG_RAY_KEYS if pdhg is not None and _pdhg_rays(pdhg) is not None else ()))
 
 
 def report_counts(batch, logits, report):

@@ -1270,7 +1270,30 @@ class LPBatch:
         tensors have the single call's bits.  Returns an `LPPdhgWide`, whose `.calls` is the number of C calls made.  The
         scratch, which also carries the state from one call to the next, is asked for once per rows_per_item and kept on the
         batch."""
-        who = "pdhg_wide"
+        return self._pdhg_wide("pdhg_wide", max_iters, check_every, (eps, step, beta, ruiz, pock_chambolle, primal_weight, weight_span, reflect),
+                               x0, y0, start, rows_per_item, poll_every)
+
+    def pdhg_rays(self, max_iters, eps=2.0 ** -10, check_every=64, step=0.9, beta=0.5, ruiz=10, pock_chambolle=True,
+                  primal_weight=True, weight_span=16.0, reflect=True, ray_eps=2.0 ** -10, x0=None, y0=None, start=None,
+                  rows_per_item=None, poll_every=None):
+        """`pdhg_wide` that can say "this LP has no solution" (mllp_lp_pdhg_rays; the rule is stated in include/mllp_hip.h): at
+        every check the direction from the anchor to the step's output is judged as a ray of the original LP, and an instance
+        stops with code 4 (primal infeasible; `.ray_y` is the Farkas certificate) or code 5 (dual infeasible: unbounded if
+        feasible; `.ray_x` is the recession ray) once its relative quality is at most `ray_eps`.  The test is RELATIVE: code 4
+        proves that every feasible point has a 1-norm of at least 1 / ray_eps, which also holds for feasible LPs with large
+        solutions -- choose `ray_eps` below 1 / |x|_1 of the solutions expected.  A negative `ray_eps` turns
+        detection off, and the result has `pdhg_wide`'s bits.  The rays ride in the check's own sweeps: the call makes exactly
+        `pdhg_wide`'s launches.  The other arguments are `pdhg_wide`'s; polling stops once no instance is at code 6.  Returns
+        an `LPPdhgRays`.  The scratch is asked for once per rows_per_item and kept on the batch, under its own name."""
+        return self._pdhg_wide("pdhg_rays", max_iters, check_every,
+                               (eps, step, beta, ruiz, pock_chambolle, primal_weight, weight_span, reflect, ray_eps), x0, y0, start, rows_per_item,
+                               poll_every)
+
+    def _pdhg_wide(self, who, max_iters, check_every, params, x0, y0, start, rows_per_item, poll_every):
+        """What `pdhg_wide` and `pdhg_rays` share: the start, the validation, the scratch kept on the batch (`_<who>_scratch`),
+        the outputs, the call mllp_lp_<who> and the continuation loop.  `params`: eps .. reflect, and for pdhg_rays ray_eps behind
+        them."""
+        rays = who == "pdhg_rays"
         if start is not None:
             if x0 is not None or y0 is not None:
                 raise ValueError(f"{who}: give start or x0 / y0, not both")
@@ -1289,17 +1312,20 @@ class LPBatch:
         if poll_every is not None and int(poll_every) <= 0:
             raise ValueError(f"{who}: poll_every must be positive")
         dev, f32 = self.x1.device, torch.float32
-        scratch = self._kept_scratch("_pdhg_wide_scratch", rows, "mllp_lp_pdhg_wide_scratch_bytes")
+        scratch = self._kept_scratch(f"_{who}_scratch", rows, f"mllp_lp_{who}_scratch_bytes")
         x, y, dr, dc = _out(self.N, f32, dev), _out(self.M, f32, dev), _out(self.M, f32, dev), _out(self.N, f32, dev)
         status, kkt = _out(self.n_inst * 4, torch.int32, dev), _out(self.n_inst * 6, f32, dev)
+        ray_x, ray_y, cert = (_out(self.N, f32, dev), _out(self.M, f32, dev), _out(self.n_inst * 4, f32, dev)) if rays else (None, None, None)
         opt = lambda t: None if t is None or not t.numel() else t                             # noqa: E731
+        flag = lambda v: int(bool(v))                                                         # noqa: E731
         x1, x2 = _pad(self.x1), _pad(self.x2)
+        scalars = [f(v) for f, v in zip((float, float, float, int, flag, flag, float, flag, float), params)]
+        outs = (x, y, dr, dc, ray_x, ray_y, status, kkt, cert) if rays else (x, y, dr, dc, status, kkt)
+        entry = getattr(_lib.lib(), f"mllp_lp_{who}")
 
         def call(begin, end):
-            _lib.check(_lib.lib().mllp_lp_pdhg_wide(
-                self._h, _lib.ptr(x1), _lib.ptr(x2), _lib.ptr(opt(x0)), _lib.ptr(opt(y0)), begin, end, check_every, float(eps), float(step),
-                float(beta), int(ruiz), int(bool(pock_chambolle)), int(bool(primal_weight)), float(weight_span), int(bool(reflect)), rows,
-                *[_lib.ptr(t) for t in (x, y, dr, dc, status, kkt)], _lib.ptr(scratch), _lib.current_stream()))
+            _lib.check(entry(self._h, _lib.ptr(x1), _lib.ptr(x2), _lib.ptr(opt(x0)), _lib.ptr(opt(y0)), begin, end, check_every, *scalars, rows,
+                             *[_lib.ptr(t) for t in outs], _lib.ptr(scratch), _lib.current_stream()))
         calls = 0
         if poll_every is None:
             call(0, max_iters)
@@ -1313,8 +1339,11 @@ class LPBatch:
                 begin = end
                 if begin >= max_iters or not bool((_cut(status, self.n_inst, 4)[:, 0] == 6).any().item()):
                     break
-        res = LPPdhgWide(_cut(x, self.N), _cut(y, self.M), _cut(status, self.n_inst, 4), _cut(kkt, self.n_inst, 6), _cut(dr, self.M),
-                         _cut(dc, self.N))
+        res = (_cut(x, self.N), _cut(y, self.M), _cut(status, self.n_inst, 4), _cut(kkt, self.n_inst, 6), _cut(dr, self.M), _cut(dc, self.N))
+        if rays:
+            res = LPPdhgRays(*res, _cut(ray_x, self.N), _cut(ray_y, self.M), _cut(cert, self.n_inst, 4))
+        else:
+            res = LPPdhgWide(*res)
         res.calls = calls
         return res
 
@@ -1411,6 +1440,25 @@ class LPPdhgWide(LPPdhgHalpern):
     mllp_lp_pdhg_wide calls that made them (1 without `poll_every`).  `status[:, 0]` may also be 9, stale state, which
     `LPBatch.pdhg_wide` itself never produces: it continues only its own calls."""
     calls = 1
+
+
+class LPPdhgRays(LPPdhgWide):
+    """What `LPBatch.pdhg_rays` returns: an `LPPdhgWide` whose `status[:, 0]` may also be 4 (primal infeasible RELATIVE to
+    ray_eps: no feasible point with a 1-norm below 1 / ray_eps, which a feasible LP with large solutions meets too) or 5 (dual
+    infeasible in the same relative sense), with `.ray_y` [M] (the certificate of an instance at code 4, zeros elsewhere), `.ray_x` [N] (of one at code 5)
+    and `.cert` (float32 [n_inst, 4] = qp, b'ry, qd, c'rx of the last check that evaluated the instance's rays; +inf, 0, +inf, 0
+    if none did).  `.x`, `.y`, `.kkt` are the last step's output and its errors at every code."""
+
+    def __init__(self, x, y, status, kkt, dr, dc, ray_x, ray_y, cert):
+        super().__init__(x, y, status, kkt, dr, dc)
+        self.ray_x, self.ray_y, self.cert = ray_x, ray_y, cert
+
+
+def pdhg_rays_limits():
+    """`pdhg_wide_limits()`, as the call with certificates reports them (mllp_lp_pdhg_rays_limits; no GPU)"""
+    lim = (c_int64 * 4)()
+    _lib.check(_lib.lib().mllp_lp_pdhg_rays_limits(lim))
+    return int(lim[0]), int(lim[1]), int(lim[2]), int(lim[3])
 
 
 def pdhg_wide_limits():

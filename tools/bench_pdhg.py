@@ -1,11 +1,12 @@
 """Cost and reach of restarted PDHG on the resident batch (mllp_lp_pdhg; with --scaled: mllp_lp_pdhg_scaled; with --halpern:
-mllp_lp_pdhg_halpern; with --wide: mllp_lp_pdhg_wide against mllp_lp_pdhg_halpern).  Prints one JSON line
-(profiles/pdhg_bench.json; profiles/pdhg_scaled_bench.json holds the --scaled runs, profiles/pdhg_halpern_bench.json the
---halpern ones, profiles/pdhg_wide_bench.json the --wide ones).
+mllp_lp_pdhg_halpern; with --wide: mllp_lp_pdhg_wide against mllp_lp_pdhg_halpern; with --rays: mllp_lp_pdhg_rays against
+mllp_lp_pdhg_wide).  Prints one JSON line (profiles/pdhg_bench.json; profiles/pdhg_scaled_bench.json holds the --scaled runs,
+profiles/pdhg_halpern_bench.json the --halpern ones, profiles/pdhg_wide_bench.json the --wide ones, profiles/pdhg_rays_bench.json
+the --rays ones).
 
     python tools/bench_pdhg.py [--calls 2] [--windows 5] [--plain-iters 256] [--netlib-iters 60000] [--synthetic 4]
                                [--scaled | --halpern [--no-reflect]] [--ruiz 10] [--no-pock-chambolle] [--no-weight] [--span 16]
-                               [--wide [--rows R] [--poll P]] [--only PART,...]
+                               [--wide [--rows R] [--poll P]] [--rays [--ray-eps E] [--runs NAME,...]] [--only PART,...]
 
   --scaled        the same batches and the same Netlib table through LPBatch.pdhg_scaled with the options given; the output
                   gains "call" and "options".  --only per_iteration,netlib,cold_warm,oracle runs the named parts alone.
@@ -14,6 +15,13 @@ mllp_lp_pdhg_halpern; with --wide: mllp_lp_pdhg_wide against mllp_lp_pdhg_halper
                   LPBatch.pdhg_halpern from the same build: per_iteration times both calls on every batch, alternating window by
                   window ("persistent" beside the wide figures, and "wide_max_below_persistent_min"); netlib (eps 1e-3 alone)
                   runs both under --netlib-iters and reports the wall time of each and whether the converged sets are equal.
+  --rays          what certificates cost (the --wide options): on Netlib, planted 64 x (500 x 1200) and planted 256 x (50 x 120),
+                  --plain-iters iterations at check_every 64 and at check_every 0, with eps = 0 so that no instance stops, through
+                  LPBatch.pdhg_wide ("wide"), LPBatch.pdhg_rays with ray_eps = -1 ("rays_off": the wide call's kernels) and with
+                  ray_eps = 0 ("rays_on": every check evaluates the rays and none decides), alternating window by window; per run
+                  the figures of per_iteration and "us_per_check", (the median at 64 - the median at 0) x 64 / iterations.  --runs
+                  wide times that call alone, which is all a tree from before the call has.  --ray-eps E: the detection part,
+                  Netlib at eps 1e-3 under --netlib-iters with ray_eps E against the wide call (codes and iterations equal?).
 
   per_iteration   plain PDHG (check_every = 0) for --plain-iters iterations on the Netlib batch, on planted batches (256 and
                   1024 x (50 x 120), all in LDS; 64 x (500 x 1200); the same 64 with max_lds_words = 0, all in scratch) and on
@@ -104,6 +112,67 @@ def oracle_deviation():
     return out
 
 
+def rays_bench(args, opts):
+    """--rays: see the module's docstring"""
+    from mllp_amd.data import load_packed
+    from mllp_amd.graph import LPBatch
+    from mllp_amd.planted import planted_batch
+    names = args.runs.split(",")
+    calls = {"wide": lambda b, it, ce: b.pdhg_wide(it, check_every=ce, eps=0.0, **opts),
+             "rays_off": lambda b, it, ce: b.pdhg_rays(it, check_every=ce, eps=0.0, ray_eps=-1.0, **opts),
+             "rays_on": lambda b, it, ce: b.pdhg_rays(it, check_every=ce, eps=0.0, ray_eps=0.0, **opts)}
+    net = LPBatch.from_instances(load_packed())
+    mid, _, _ = planted_batch(64, 500, 1200, 6.0, 2)
+    small, _, _ = planted_batch(256, 50, 120, 6.0, 1)
+    out = {"call": "mllp_lp_pdhg_rays", "against": "mllp_lp_pdhg_wide", "options": opts, "runs": names, "per_iteration": []}
+    iters = args.plain_iters
+    for name, b in ((f"Netlib {net.n_inst} instances", net), ("planted 64 x (500 x 1200)", mid), ("planted 256 x (50 x 120)", small)):
+        runs = {(n, ce): (lambda n=n, ce=ce: calls[n](b, iters, ce)) for ce in (64, 0) for n in names}
+        for run in runs.values():
+            run()
+            run()
+        torch.cuda.synchronize()
+        dev = {key: [] for key in runs}
+        for _ in range(args.windows):
+            for key, run in runs.items():
+                dev[key].append(device_window(run, args.calls))
+        row = {"batch": name, "instances": b.n_inst, "nnz": b.dims()["nnz"], "iterations": iters, "calls_per_window": args.calls, "windows": args.windows}
+        for n in names:
+            with_checks, without = figures(dev[n, 64], iters), figures(dev[n, 0], iters)
+            running = int((calls[n](b, iters, 64).status[:, 0] == 6).sum().item())
+            row[n] = {"check_every_64": with_checks, "check_every_0": without, "still_running": running,
+                      "us_per_check": round((with_checks["us_per_iteration"]["median"] - without["us_per_iteration"]["median"]) * 64, 3)}
+        out["per_iteration"].append(row)
+    if args.ray_eps is not None and "rays_on" in names:
+        import time
+        res = {}
+        for n, run in (("wide", lambda: net.pdhg_wide(args.netlib_iters, eps=1e-3, poll_every=args.poll, **opts)),
+                       ("rays", lambda: net.pdhg_rays(args.netlib_iters, eps=1e-3, ray_eps=args.ray_eps, poll_every=args.poll, **opts))):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            r = run()
+            torch.cuda.synchronize()
+            res[n] = (r, time.perf_counter() - t0)
+        (w, tw), (r, tr) = res["wide"], res["rays"]
+        st, ws = r.status.cpu().numpy(), w.status.cpu().numpy()
+        cert = r.cert.cpu().numpy()
+        out["netlib_detection"] = {
+            "eps": 1e-3, "ray_eps": args.ray_eps, "max_iters": args.netlib_iters, "poll_every": args.poll, "wide_wall_s": round(tw, 3),
+            "rays_wall_s": round(tr, 3), "calls": [w.calls, r.calls], "codes": {str(c): int((st[:, 0] == c).sum()) for c in sorted(set(st[:, 0]))},
+            "status_equal_to_wide": bool((st == ws).all()), "x_bits_equal_to_wide": bool(torch.equal(r.x.view(torch.int32), w.x.view(torch.int32))),
+            "stopped_by_a_ray": {net.names[k]: [int(v) for v in st[k]] for k in np.flatnonzero((st[:, 0] == 4) | (st[:, 0] == 5))},
+            "smallest_quality_at_the_last_check": float(f"{np.minimum(cert[:, 0], cert[:, 2]).min():.3g}")}
+        # a certificate of code 4 says |x|_1 >= 1 / qp for every feasible x: where the wide call SOLVED the instance, compare with its x
+        off = np.concatenate([[0], np.cumsum(net.inst_n)])
+        wx = w.x.cpu().numpy()
+        out["netlib_detection"]["code_4_on_instances_the_wide_call_solves"] = {
+            net.names[k]: {"iterations": int(st[k, 1]), "bound_on_x_1norm": float(f"{1.0 / cert[k, 0]:.4g}"),
+                           "x_1norm_of_the_wide_solution": float(f"{np.abs(wx[off[k]:off[k + 1]]).sum():.4g}")}
+            for k in np.flatnonzero((st[:, 0] == 4) & (ws[:, 0] == 0))}
+        out["netlib_detection"]["converged_wide"] = int((ws[:, 0] == 0).sum())
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=2)
@@ -115,6 +184,9 @@ def main():
     ap.add_argument("--halpern", action="store_true")
     ap.add_argument("--no-reflect", action="store_true")
     ap.add_argument("--wide", action="store_true")
+    ap.add_argument("--rays", action="store_true")
+    ap.add_argument("--ray-eps", type=float, default=None)
+    ap.add_argument("--runs", default="wide,rays_off,rays_on")
     ap.add_argument("--rows", type=int, default=None)
     ap.add_argument("--poll", type=int, default=None)
     ap.add_argument("--ruiz", type=int, default=10)
@@ -124,8 +196,12 @@ def main():
     ap.add_argument("--only", default="per_iteration,netlib,cold_warm,oracle")
     args = ap.parse_args()
     parts = set(args.only.split(","))
-    if args.scaled + args.halpern + args.wide > 1:
-        ap.error("--scaled, --halpern and --wide name three calls: give one")
+    if args.scaled + args.halpern + args.wide + args.rays > 1:
+        ap.error("--scaled, --halpern, --wide and --rays name four calls: give one")
+    if args.rays:
+        assert torch.cuda.is_available(), "bench_pdhg needs the GPU: there is no CPU path"
+        return rays_bench(args, {"ruiz": args.ruiz, "pock_chambolle": not args.no_pock_chambolle, "primal_weight": not args.no_weight,
+                                 "weight_span": args.span, "reflect": not args.no_reflect, "rows_per_item": args.rows})
     if args.scaled or args.halpern or args.wide:
         SOLVE.update(call="pdhg_wide" if args.wide else "pdhg_halpern" if args.halpern else "pdhg_scaled",
                      options={"ruiz": args.ruiz, "pock_chambolle": not args.no_pock_chambolle, "primal_weight": not args.no_weight,
