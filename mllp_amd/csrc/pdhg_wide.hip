@@ -24,20 +24,23 @@
 // previous call ended exactly at iter_begin (code 0, 6 or 8); otherwise the instance is stale for this call (flag, not state:
 // the state is left as found), its sweeps return at once and finish writes zeros and code 9.
 //
-// mllp_lp_pdhg_rays is the same call with certificates of infeasibility and unboundedness: its own first and
-// last kernel and, with ray_eps >= 0, its own three kernels of a check, further down; every launch of a call has its counterpart
-// in the other call, so the two make the same number of launches.
+// mllp_lp_pdhg_rays is the same call with certificates of infeasibility and unboundedness.  Its first and last
+// kernel are the wide call's bodies with their additions under `if constexpr (RAYS)` (prep_body, finish_body: the entry points
+// are one-line wrappers), and with ray_eps >= 0 it has its own three kernels of a check, further down, whose restart is the
+// wide call's (wide_restart); every launch of a call has its counterpart in the other call, so the two make the same number of
+// launches.  A value that RAYS changes is DEFINED once, never set and then overwritten (DESIGN.md 4.22's habit).
 //
-// The operator structs and helpers below are copies of pdhg.hip's (ScaledAbs, HalpernCol, HalpernRow, BySum, ByMax,
-// block_max_u32 and the bit helpers), because that file's six kernel instantiations are held to their instruction streams
-// (DESIGN.md 4.22): it is left untouched.  The evaluation walks ONE point with a float accumulator, which is the `cur` half of
-// pdhg.hip's Sum2 walk: the two halves of a Sum2 never meet.
+// WHAT IS DEFINED WHERE.  pdhg_ops.h, shared with pdhg.hip: the status codes, the bit helpers, block_max_u32,
+// BySum and ByMax, ScaledAbs, HalpernCol, HalpernRow -- the iteration and the set-up walk are written once for both executions.
+// This file: the walker of an item (item_sweep: pdhg.hip's wg_sweep places the block tier differently, see pdhg_ops.h) and the
+// operators that only these kernels instantiate.  EvalOne walks ONE point with a float accumulator, which is the `cur` half of
+// pdhg.hip's Sum2 walk (EvalSweep): the two halves of a Sum2 never meet.
 #include <cmath>
 #include <string>
-#include <type_traits>
 
 #include "internal.h"
 #include "ordered_sum.h"
+#include "pdhg_ops.h"
 
 namespace mllp {
 
@@ -48,8 +51,6 @@ constexpr int WD_NW = WD_THREADS / 64;
 constexpr int WD_CHUNK = WD_THREADS / 16;          // rows that a workgroup takes at a time: one 16-lane group each
 constexpr int64_t WD_ROWS_DEFAULT = 64, WD_ROWS_MAX = 4096;
 constexpr int64_t WD_MAX_RUIZ = 64;
-
-constexpr int WD_CODE_OPTIMAL = 0, WD_CODE_LIMIT = 6, WD_CODE_NOT_FINITE = 8, WD_CODE_STALE = 9;
 
 // the state's words (int or float, by the name)
 enum {
@@ -68,74 +69,6 @@ constexpr int WD_RUN = 1, WD_IDLE = 2, WD_STALE = 3;
 constexpr int64_t WD_INST_WORDS = WS_WORDS + WX_WORDS;
 
 __host__ __device__ constexpr int64_t wide_words(int64_t n_inst, int64_t M, int64_t N) { return WD_INST_WORDS * n_inst + 6 * N + 5 * M; }
-
-__device__ __forceinline__ unsigned abs_bits(float v) { return __float_as_uint(v) & 0x7fffffffu; }
-// the key of max(v, 0) that keeps a NaN
-__device__ __forceinline__ unsigned pos_bits(float v) { return (v > 0.0f || v != v) ? abs_bits(v) : 0u; }
-__device__ __forceinline__ float clip0(float t) { return t > 0.0f ? t : 0.0f; }
-__device__ __forceinline__ float nn_max(float a, float b) {
-    const unsigned ka = abs_bits(a), kb = abs_bits(b);
-    return __uint_as_float(ka > kb ? ka : kb);
-}
-__device__ __forceinline__ bool finite_bits(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
-__device__ __forceinline__ float sqrt_rn(float v) { return __builtin_sqrtf(v); }
-__device__ __forceinline__ bool finite_pos(float v) { return finite_bits(v) && v > 0.0f; }
-
-// the maxima of K integers over the workgroup, in every thread (two barriers; `s` [NW * K] is reusable afterwards)
-template <int NW, int K>
-__device__ __forceinline__ void block_max_u32(unsigned (&v)[K], unsigned* s) {
-#pragma unroll
-    for (int q = 0; q < K; ++q) {
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned u = (unsigned)__shfl_xor((int)v[q], o, 64);
-            v[q] = u > v[q] ? u : v[q];
-        }
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int q = 0; q < K; ++q) s[(threadIdx.x >> 6) * K + q] = v[q];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < K; ++q) {
-        unsigned best = 0u;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) best = s[w * K + q] > best ? s[w * K + q] : best;
-        v[q] = best;
-    }
-    __syncthreads();
-}
-
-struct BySum {
-    template <int G, class T>
-    static __device__ __forceinline__ T group(T v) { return group_sum<G>(v); }
-    template <int NW, class T>
-    static __device__ __forceinline__ T block(T v, T* part) { return block_tree_sum<NW>(v, part); }
-};
-struct ByMax {
-    template <int G>
-    static __device__ __forceinline__ float group(float v) {
-        unsigned k = __float_as_uint(v);
-#pragma unroll
-        for (int o = 1; o < G; o <<= 1) {
-            const unsigned u = (unsigned)__shfl_xor((int)k, o, 64);
-            k = u > k ? u : k;
-        }
-        return __uint_as_float(k);
-    }
-    template <int NW>
-    static __device__ __forceinline__ float block(float v, float* part) {
-        v = group<64>(v);
-        if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-        __syncthreads();
-        float best = 0.0f;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) best = nn_max(best, part[w]);
-        __syncthreads();
-        return best;
-    }
-};
 
 // pdhg.hip's wg_sweep for the rows [rb, re) of an instance (ptr: the row pointers of the instance's first row), re - rb any
 // number: WD_CHUNK rows at a time, and a chunk's rows of the block tier behind its other rows -- a vote of the workgroup says
@@ -175,86 +108,6 @@ __device__ __forceinline__ void item_sweep(const int* __restrict__ ptr, int rb, 
         }
     }
 }
-
-struct NoRow {};
-struct OwnFactor {
-    float d;
-};
-
-// pdhg.hip's set-up walk of one orientation over s_e = fmul(fmul(|a_e|, dr_i), dc_j)
-template <bool ROWS, bool MAX>
-struct ScaledAbs {
-    using Acc = float;
-    using Row = OwnFactor;
-    using By = std::conditional_t<MAX, ByMax, BySum>;
-    const int* __restrict__ idx;
-    const float* __restrict__ val;
-    int off;
-    const float *own, *other;
-    float* out;
-    unsigned* best;
-    __device__ __forceinline__ Row row(int r) const { return {own[r]}; }
-    __device__ __forceinline__ void term(const Row& rc, int e, float& q) const {
-        const float o = other[idx[e] - off], a = fabsf(val[e]);
-        const float s = ROWS ? __fmul_rn(__fmul_rn(a, rc.d), o) : __fmul_rn(__fmul_rn(a, o), rc.d);
-        q = MAX ? nn_max(q, s) : __fadd_rn(q, s);
-    }
-    __device__ __forceinline__ void finish(int r, const Row&, float q) const {
-        if (out) out[r] = q;
-        const unsigned k = abs_bits(q);
-        *best = k > *best ? k : *best;
-    }
-};
-
-// pdhg.hip's column sweep of a Halpern iteration
-struct HalpernCol {
-    using Acc = float;
-    using Row = NoRow;
-    using By = BySum;
-    const int* __restrict__ idx;
-    const float* __restrict__ val;
-    const float* __restrict__ c;       // of the instance's first column
-    const float *tc, *xa;              // the column's step factor, the anchor
-    int row0;
-    float tau, w1, w2;
-    bool reflect;
-    float *x, *xb, *xh;
-    const float* y;
-    __device__ __forceinline__ Row row(int) const { return {}; }
-    __device__ __forceinline__ void term(const Row&, int e, float& q) const { q = __fmaf_rn(val[e], y[idx[e] - row0], q); }
-    __device__ __forceinline__ void finish(int j, const Row&, float s) const {
-        const float g = __fsub_rn(c[j], s), xo = x[j];
-        const float xn = clip0(__fsub_rn(xo, __fmul_rn(__fmul_rn(tau, tc[j]), g)));
-        const float xf = __fsub_rn(__fadd_rn(xn, xn), xo);
-        xh[j] = xn;
-        xb[j] = xf;
-        x[j] = __fmaf_rn(w1, reflect ? xf : xn, __fmul_rn(w2, xa[j]));
-    }
-};
-
-// pdhg.hip's row sweep of a Halpern iteration
-struct HalpernRow {
-    using Acc = float;
-    using Row = NoRow;
-    using By = BySum;
-    const int* __restrict__ idx;
-    const float* __restrict__ val;
-    const float* __restrict__ b;       // of the instance's first row
-    const float *tr, *ya;              // the row's step factor, the anchor
-    int col0;
-    float sigma, w1, w2;
-    bool reflect;
-    float *y, *yh;
-    const float* xb;
-    __device__ __forceinline__ Row row(int) const { return {}; }
-    __device__ __forceinline__ void term(const Row&, int e, float& q) const { q = __fmaf_rn(val[e], xb[idx[e] - col0], q); }
-    __device__ __forceinline__ void finish(int i, const Row&, float t) const {
-        const float yo = y[i];
-        const float yn = __fadd_rn(yo, __fmul_rn(__fmul_rn(sigma, tr[i]), __fsub_rn(b[i], t)));
-        yh[i] = yn;
-        y[i] = __fmaf_rn(w1, reflect ? __fsub_rn(__fadd_rn(yn, yn), yo) : yn, __fmul_rn(w2, ya[i]));
-    }
-};
 
 // an evaluation's walk of one orientation: the product with the OTHER side's point, then the residual against `rhs`: |.| for
 // rows (primal), max(., 0) for columns (dual).  The `cur` half of pdhg.hip's EvalSweep
@@ -338,6 +191,25 @@ __device__ __forceinline__ void put64(int* st, int lo, long long v) {
 }
 __device__ __forceinline__ float stf(const int* st, int w) { return __int_as_float(st[w]); }
 
+// mllp_lp_pdhg_rays: six more words per instance BEHIND the vectors of the wide layout (which stays as it is): the two ray keys,
+// which are the call's own as the two keys above are, and the four cert words {qp, b'ry, qd, c'rx} of the last check that
+// evaluated the rays, which are STATE (values only) and travel from one call to the next
+enum { RX_KEY_U = 0, RX_KEY_V, RX_QP, RX_BY, RX_QD, RX_CX, RX_WORDS };
+
+__host__ __device__ constexpr int64_t rays_words(int64_t n_inst, int64_t M, int64_t N) { return wide_words(n_inst, M, N) + RX_WORDS * n_inst; }
+
+// what the rays' kernels take beside WideArgs (whose layout every kernel of the wide call depends on)
+struct RayArgs {
+    float ray_eps;
+    float* ray_x;
+    float* ray_y;
+    float* cert;
+};
+
+__device__ __forceinline__ int* ray_words(const WideArgs& A, int k) {
+    return reinterpret_cast<int*>(A.scratch) + wide_words(A.n_inst, A.M, A.N) + RX_WORDS * (long long)k;
+}
+
 // the workgroup's item: the instance k with first[k] <= blockIdx.x < first[k + 1] (the table is made by wide_prep of THIS call
 // from inst_ptr alone; thread t looks at instances t, t + 1024, ..., so the search costs one round of loads and two barriers),
 // and the block inside it.  False, for the whole workgroup: no item (cannot happen with the grid the host computes from the
@@ -374,12 +246,15 @@ __device__ __forceinline__ void publish_max(unsigned best, int* word, unsigned* 
     if (threadIdx.x == 0 && v[0]) atomicMax(reinterpret_cast<unsigned*>(word), v[0]);
 }
 
-// ---- the call's first kernel: the item table, the flags; iter_begin == 0: the start and the state ----
-__global__ __launch_bounds__(WD_THREADS) void wide_prep(const WideArgs A) {
+// ---- the call's first kernel: the item table, the flags; iter_begin == 0: the start and the state.  RAYS: it also knows codes
+// 4 and 5, clears the ray keys and starts the cert ----
+template <bool RAYS>
+__device__ __forceinline__ void prep_body(const WideArgs A) {
     __shared__ unsigned s_key[WD_NW * 2];
     __shared__ long long s_off[WD_NW * 2];
     const int k = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const WideView V = wide_view(A, k);
+    int* rw = RAYS ? ray_words(A, k) : nullptr;
     // the items of the earlier instances (integer sums: exact)
     long long fn = 0, fm = 0;
     for (int j = tid; j < k; j += WD_THREADS) {
@@ -400,12 +275,18 @@ __global__ __launch_bounds__(WD_THREADS) void wide_prep(const WideArgs A) {
         V.ex[WX_FIRST_M] = (int)fm;
         V.ex[WX_KEY_COL] = 0;
         V.ex[WX_KEY_ROW] = 0;
+        if constexpr (RAYS) {
+            rw[RX_KEY_U] = 0;
+            rw[RX_KEY_V] = 0;
+        }
     }
     if (A.iter_begin > 0) {
+        // which codes a continued call accepts; anything else, or a state that did not end at iter_begin, is stale
         if (tid == 0) {
             const int code = V.st[WS_CODE];
-            const bool known = code == WD_CODE_OPTIMAL || code == WD_CODE_LIMIT || code == WD_CODE_NOT_FINITE;
-            V.ex[WX_FLAG] = !known || get64(V.st, WS_REACHED_LO) != A.iter_begin ? WD_STALE : code == WD_CODE_LIMIT ? WD_RUN : WD_IDLE;
+            const bool known = code == PD_CODE_OPTIMAL || code == PD_CODE_LIMIT || code == PD_CODE_NOT_FINITE ||
+                               (RAYS && (code == PD_CODE_INFEASIBLE || code == PD_CODE_UNBOUNDED));
+            V.ex[WX_FLAG] = !known || get64(V.st, WS_REACHED_LO) != A.iter_begin ? WD_STALE : code == PD_CODE_LIMIT ? WD_RUN : WD_IDLE;
         }
         return;
     }
@@ -430,7 +311,7 @@ __global__ __launch_bounds__(WD_THREADS) void wide_prep(const WideArgs A) {
     block_max_u32<WD_NW, 2>(kn, s_key);
     if (tid == 0) {
         V.ex[WX_FLAG] = WD_RUN;
-        V.st[WS_CODE] = WD_CODE_LIMIT;
+        V.st[WS_CODE] = PD_CODE_LIMIT;
         put64(V.st, WS_IT_LO, 0);
         put64(V.st, WS_REACHED_LO, -1);     // (no call has ended on this state yet)
         put64(V.st, WS_LAST_LO, 0);
@@ -438,8 +319,16 @@ __global__ __launch_bounds__(WD_THREADS) void wide_prep(const WideArgs A) {
         V.st[WS_E_LAST] = __float_as_int(__builtin_huge_valf());
         V.st[WS_DEN_P] = __float_as_int(__fadd_rn(1.0f, __uint_as_float(kn[0])));
         V.st[WS_DEN_D] = __float_as_int(__fadd_rn(1.0f, __uint_as_float(kn[1])));
+        if constexpr (RAYS) {
+            rw[RX_QP] = __float_as_int(__builtin_huge_valf());      // no check has evaluated the rays
+            rw[RX_BY] = 0;
+            rw[RX_QD] = __float_as_int(__builtin_huge_valf());
+            rw[RX_CX] = 0;
+        }
     }
 }
+__global__ __launch_bounds__(WD_THREADS) void wide_prep(const WideArgs A) { prep_body<false>(A); }
+__global__ __launch_bounds__(WD_THREADS) void rays_prep(const WideArgs A) { prep_body<true>(A); }
 
 // ---- the set-up's walks.  MAX: a Ruiz pass, else the sums; LAST: no result per row, the largest into the keys ----
 template <bool COLS, bool MAX, bool LAST>
@@ -514,7 +403,7 @@ __global__ __launch_bounds__(WD_THREADS) void wide_step(const WideArgs A, long l
     int k, rb, re;
     if (!wide_item<COLS>(A, &k, &rb, &re)) return;
     const WideView V = wide_view(A, k);
-    if (V.ex[WX_FLAG] != WD_RUN || V.st[WS_CODE] != WD_CODE_LIMIT) return;
+    if (V.ex[WX_FLAG] != WD_RUN || V.st[WS_CODE] != PD_CODE_LIMIT) return;
     const long long cnt = it - get64(V.st, WS_LAST_LO);         // the rule's k
     const float w1 = __fdiv_rn((float)(cnt + 1), (float)(cnt + 2)), w2 = __fdiv_rn(1.0f, (float)(cnt + 2));
     const bool reflect = A.reflect != 0;
@@ -535,7 +424,7 @@ __global__ __launch_bounds__(WD_THREADS) void wide_eval(const WideArgs A) {
     if (!wide_item<!ROWS>(A, &k, &rb, &re)) return;
     const WideView V = wide_view(A, k);
     const int flag = V.ex[WX_FLAG];
-    if (FINAL ? flag == WD_STALE : (flag != WD_RUN || V.st[WS_CODE] != WD_CODE_LIMIT)) return;
+    if (FINAL ? flag == WD_STALE : (flag != WD_RUN || V.st[WS_CODE] != PD_CODE_LIMIT)) return;
     unsigned best = 0u;
     if constexpr (ROWS)
         item_sweep(A.a_ptr + V.row0, rb, re, EvalOne<true>{A.a_idx, A.a_val, A.b + V.row0, V.col0, V.xh, &best}, s_part);
@@ -548,6 +437,12 @@ struct WideErr {
     float p, d, g;
     __device__ __forceinline__ float worst() const { return nn_max(nn_max(p, d), g); }
 };
+
+// the three errors of a point from the keys of its two evaluation sweeps and s = (c'x, b'y)
+__device__ __forceinline__ WideErr wide_err(const WideView& V, unsigned key_p, unsigned key_d, float cx, float by) {
+    const float gap = __fdiv_rn(fabsf(__fsub_rn(cx, by)), __fadd_rn(__fadd_rn(1.0f, fabsf(cx)), fabsf(by)));
+    return {__fdiv_rn(__uint_as_float(key_p), stf(V.st, WS_DEN_P)), __fdiv_rn(__uint_as_float(key_d), stf(V.st, WS_DEN_D)), gap};
+}
 
 // the three errors of (xh, yh) from the keys of the two evaluation sweeps, in every thread; clears the keys
 __device__ __forceinline__ WideErr wide_errors(const WideArgs& A, const WideView& V, Sum2* s_part2) {
@@ -563,31 +458,16 @@ __device__ __forceinline__ WideErr wide_errors(const WideArgs& A, const WideView
         V.ex[WX_KEY_ROW] = 0;
         V.ex[WX_KEY_COL] = 0;
     }
-    const float gap = __fdiv_rn(fabsf(__fsub_rn(s.a, s.b)), __fadd_rn(__fadd_rn(1.0f, fabsf(s.a)), fabsf(s.b)));
-    return {__fdiv_rn(__uint_as_float(key_p), stf(V.st, WS_DEN_P)), __fdiv_rn(__uint_as_float(key_d), stf(V.st, WS_DEN_D)), gap};
+    return wide_err(V, key_p, key_d, s.a, s.b);
 }
 
-// ---- a check's decision, after its two sweeps.  `it`: the iterations done ----
-__global__ __launch_bounds__(WD_THREADS) void wide_decide(const WideArgs A, long long it) {
-    __shared__ Sum2 s_part2[WD_NW];
+// A check's restart, by every thread of the instance's workgroup: (x, y) <- (xh, yh), how far that is from the anchor in the
+// metric of the scaled variables, the anchor moves there; then thread 0 writes the state: the restart's count, error and
+// iteration, and with primal_weight the weight moved to sqrt(w dy / dx), clamped to [w0 / span, w0 span], and the two steps.
+// restarts, w0, w, eta: the state as every thread read it before any of it was written
+__device__ __forceinline__ void wide_restart(const WideArgs& A, const WideView& V, long long it, float e, int restarts, float w0, float w,
+                                             float eta, Sum2* s_part2) {
     const int tid = threadIdx.x;
-    const WideView V = wide_view(A, blockIdx.x);
-    if (V.ex[WX_FLAG] != WD_RUN || V.st[WS_CODE] != WD_CODE_LIMIT) return;
-    // the state, in every thread, before thread 0 writes any of it (the barriers of wide_errors lie between)
-    const long long cnt = it - get64(V.st, WS_LAST_LO);
-    const float e_last = stf(V.st, WS_E_LAST), w0 = stf(V.st, WS_W0), w = stf(V.st, WS_W), eta = stf(V.st, WS_ETA);
-    const int restarts = V.st[WS_RESTARTS];
-    const WideErr at = wide_errors(A, V, s_part2);
-    const float e = at.worst();
-    if (!finite_bits(e) || e <= A.eps) {
-        if (tid == 0) {
-            V.st[WS_CODE] = finite_bits(e) ? WD_CODE_OPTIMAL : WD_CODE_NOT_FINITE;
-            put64(V.st, WS_IT_LO, it);
-        }
-        return;
-    }
-    if (!(e <= __fmul_rn(A.beta, e_last) || 25 * cnt >= 9 * it)) return;
-    // the restart: (x, y) <- (xh, yh), how far that is from the anchor, the anchor moves there
     Sum2 dd = {0.0f, 0.0f};
     for (int j = tid; j < V.n; j += WD_THREADS) {
         const float v = V.xh[j], d = __fsub_rn(v, V.xa[j]);
@@ -617,32 +497,63 @@ __global__ __launch_bounds__(WD_THREADS) void wide_decide(const WideArgs A, long
     }
 }
 
-// ---- the call's last kernel, after the final evaluation's sweeps: every output of every instance ----
-__global__ __launch_bounds__(WD_THREADS) void wide_finish(const WideArgs A) {
+// ---- a check's decision, after its two sweeps.  `it`: the iterations done ----
+__global__ __launch_bounds__(WD_THREADS) void wide_decide(const WideArgs A, long long it) {
+    __shared__ Sum2 s_part2[WD_NW];
+    const int tid = threadIdx.x;
+    const WideView V = wide_view(A, blockIdx.x);
+    if (V.ex[WX_FLAG] != WD_RUN || V.st[WS_CODE] != PD_CODE_LIMIT) return;
+    // the state, in every thread, before thread 0 writes any of it (the barriers of wide_errors lie between)
+    const long long cnt = it - get64(V.st, WS_LAST_LO);
+    const float e_last = stf(V.st, WS_E_LAST), w0 = stf(V.st, WS_W0), w = stf(V.st, WS_W), eta = stf(V.st, WS_ETA);
+    const int restarts = V.st[WS_RESTARTS];
+    const WideErr at = wide_errors(A, V, s_part2);
+    const float e = at.worst();
+    if (!finite_bits(e) || e <= A.eps) {
+        if (tid == 0) {
+            V.st[WS_CODE] = finite_bits(e) ? PD_CODE_OPTIMAL : PD_CODE_NOT_FINITE;
+            put64(V.st, WS_IT_LO, it);
+        }
+        return;
+    }
+    if (!(e <= __fmul_rn(A.beta, e_last) || 25 * cnt >= 9 * it)) return;
+    wide_restart(A, V, it, e, restarts, w0, w, eta, s_part2);
+}
+
+// ---- the call's last kernel, after the final evaluation's sweeps: every output of every instance.  RAYS: also the rays (from
+// the frozen xh - xa, so with the bits of the deciding check) and the cert words.  A stale instance gets zeros and code 9 ----
+template <bool RAYS>
+__device__ __forceinline__ void finish_body(const WideArgs A, const RayArgs R) {
     __shared__ Sum2 s_part2[WD_NW];
     const int tid = threadIdx.x;
     const WideView V = wide_view(A, blockIdx.x);
     const bool stale = V.ex[WX_FLAG] == WD_STALE;       // (uniform in the workgroup: a word that this call's prep wrote)
+    const int code = stale ? PD_CODE_STALE : V.st[WS_CODE];
     WideErr out = {0.0f, 0.0f, 0.0f};
     if (!stale) out = wide_errors(A, V, s_part2);
     for (int j = tid; j < V.n; j += WD_THREADS) {
         A.x_out[V.col0 + j] = stale ? 0.0f : V.xh[j];
         if (A.dc_out) A.dc_out[V.col0 + j] = stale ? 0.0f : V.dc[j];
+        if constexpr (RAYS)
+            if (R.ray_x) R.ray_x[V.col0 + j] = code == PD_CODE_UNBOUNDED ? __fsub_rn(V.xh[j], V.xa[j]) : 0.0f;
     }
     for (int i = tid; i < V.m; i += WD_THREADS) {
         A.y_out[V.row0 + i] = stale ? 0.0f : V.yh[i];
         if (A.dr_out) A.dr_out[V.row0 + i] = stale ? 0.0f : V.dr[i];
+        if constexpr (RAYS)
+            if (R.ray_y) R.ray_y[V.row0 + i] = code == PD_CODE_INFEASIBLE ? __fsub_rn(V.yh[i], V.ya[i]) : 0.0f;
     }
     if (tid != 0) return;
     int* st = A.status + 4 * (size_t)V.k;
     float* q = A.kkt ? A.kkt + 6 * (size_t)V.k : nullptr;
+    float* ce = RAYS && R.cert ? R.cert + 4 * (size_t)V.k : nullptr;
     if (stale) {
-        st[0] = WD_CODE_STALE; st[1] = 0; st[2] = 0; st[3] = 0;
+        st[0] = PD_CODE_STALE; st[1] = 0; st[2] = 0; st[3] = 0;
         if (q) q[0] = q[1] = q[2] = q[3] = q[4] = q[5] = 0.0f;
+        if (ce) ce[0] = ce[1] = ce[2] = ce[3] = 0.0f;
         return;
     }
-    const int code = V.st[WS_CODE];
-    if (code == WD_CODE_LIMIT) put64(V.st, WS_IT_LO, A.iter_end);
+    if (code == PD_CODE_LIMIT) put64(V.st, WS_IT_LO, A.iter_end);
     put64(V.st, WS_REACHED_LO, A.iter_end);
     st[0] = code;
     st[1] = (int)min(get64(V.st, WS_IT_LO), (long long)0x7fffffff);
@@ -652,37 +563,23 @@ __global__ __launch_bounds__(WD_THREADS) void wide_finish(const WideArgs A) {
         q[0] = out.p; q[1] = out.d; q[2] = out.g;
         q[3] = stf(V.st, WS_ETA); q[4] = stf(V.st, WS_W0); q[5] = stf(V.st, WS_W);
     }
+    if (ce) {
+        const int* rw = ray_words(A, V.k);
+        ce[0] = stf(rw, RX_QP); ce[1] = stf(rw, RX_BY); ce[2] = stf(rw, RX_QD); ce[3] = stf(rw, RX_CX);
+    }
 }
+__global__ __launch_bounds__(WD_THREADS) void wide_finish(const WideArgs A) { finish_body<false>(A, RayArgs{}); }
+__global__ __launch_bounds__(WD_THREADS) void rays_finish(const WideArgs A, const RayArgs R) { finish_body<true>(A, R); }
 
 // =====================================================================================================================
-// mllp_lp_pdhg_rays: the same call with certificates of infeasibility and unboundedness.  The candidate ray
+// mllp_lp_pdhg_rays: a check with certificates of infeasibility and unboundedness.  The candidate ray
 // is the direction from the anchor to the step's output, (rx, ry) = (xh - xa, yh - ya), which Halpern's iteration drives to the
 // infimal displacement of the PDHG operator: zero for a solvable LP, a Farkas or recession ray otherwise.  Nothing is stored for
 // it: a check's two sweeps walk every row once for TWO accumulators, the point's and the ray's (pdhg.hip's EvalSweep pair,
 // with zero right-hand sides for the ray), and the decision adds b'ry, c'rx and max(-rx) to the walk that forms c'x and b'y.
-// The kernels above keep their text; with ray_eps < 0 the host launches them for the checks, so that nothing is evaluated.
-//
-// Six more words per instance BEHIND the vectors of the wide layout (which stays as it is): the two ray keys, which are the
-// call's own as the two keys above are, and the four cert words {qp, b'ry, qd, c'rx} of the last check that evaluated the rays,
-// which are STATE (values only) and travel from one call to the next.
+// With ray_eps < 0 the host launches the three kernels of a check above instead, so that nothing is evaluated.  The call's first
+// and last kernel are prep_body and finish_body with RAYS, above; the restart is wide_restart, as in wide_decide.
 // =====================================================================================================================
-constexpr int WD_CODE_INFEASIBLE = 4, WD_CODE_UNBOUNDED = 5;
-enum { RX_KEY_U = 0, RX_KEY_V, RX_QP, RX_BY, RX_QD, RX_CX, RX_WORDS };
-
-__host__ __device__ constexpr int64_t rays_words(int64_t n_inst, int64_t M, int64_t N) { return wide_words(n_inst, M, N) + RX_WORDS * n_inst; }
-
-// what the new kernels take beside WideArgs (whose layout the kernels above depend on)
-struct RayArgs {
-    float ray_eps;
-    float* ray_x;
-    float* ray_y;
-    float* cert;
-};
-
-__device__ __forceinline__ int* ray_words(const WideArgs& A, int k) {
-    return reinterpret_cast<int*>(A.scratch) + wide_words(A.n_inst, A.M, A.N) + RX_WORDS * (long long)k;
-}
-
 // an evaluation's walk for the point v and the ray fsub(v, va) at once: one load of the value and of the index per term, two
 // gathers.  The point's residual is EvalOne's; the ray's has no right-hand side: |A rx| for rows, max(A'ry, 0) for columns
 template <bool ROWS>
@@ -712,79 +609,6 @@ struct EvalPair {
     }
 };
 
-// ---- the first kernel of a rays call: wide_prep, which also knows codes 4 and 5, clears the ray keys and starts the cert ----
-__global__ __launch_bounds__(WD_THREADS) void rays_prep(const WideArgs A) {
-    __shared__ unsigned s_key[WD_NW * 2];
-    __shared__ long long s_off[WD_NW * 2];
-    const int k = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const WideView V = wide_view(A, k);
-    int* rw = ray_words(A, k);
-    long long fn = 0, fm = 0;
-    for (int j = tid; j < k; j += WD_THREADS) {
-        fn += (A.ptr_n[j + 1] - A.ptr_n[j] + A.rows - 1) / A.rows;
-        fm += (A.ptr_m[j + 1] - A.ptr_m[j] + A.rows - 1) / A.rows;
-    }
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        fn += __shfl_xor(fn, o, 64);
-        fm += __shfl_xor(fm, o, 64);
-    }
-    if (lane == 0) { s_off[wave * 2] = fn; s_off[wave * 2 + 1] = fm; }
-    __syncthreads();
-    if (tid == 0) {
-        fn = fm = 0;
-        for (int w = 0; w < WD_NW; ++w) { fn += s_off[w * 2]; fm += s_off[w * 2 + 1]; }
-        V.ex[WX_FIRST_N] = (int)fn;
-        V.ex[WX_FIRST_M] = (int)fm;
-        V.ex[WX_KEY_COL] = 0;
-        V.ex[WX_KEY_ROW] = 0;
-        rw[RX_KEY_U] = 0;
-        rw[RX_KEY_V] = 0;
-    }
-    if (A.iter_begin > 0) {
-        if (tid == 0) {
-            const int code = V.st[WS_CODE];
-            const bool known = code == WD_CODE_OPTIMAL || code == WD_CODE_LIMIT || code == WD_CODE_NOT_FINITE || code == WD_CODE_INFEASIBLE ||
-                               code == WD_CODE_UNBOUNDED;
-            V.ex[WX_FLAG] = !known || get64(V.st, WS_REACHED_LO) != A.iter_begin ? WD_STALE : code == WD_CODE_LIMIT ? WD_RUN : WD_IDLE;
-        }
-        return;
-    }
-    const float* c = A.c + V.col0;
-    const float* b = A.b + V.row0;
-    unsigned kn[2] = {0u, 0u};      // ||b||inf, ||c||inf
-    for (int j = tid; j < V.n; j += WD_THREADS) {
-        kn[1] = max(kn[1], abs_bits(c[j]));
-        const float v = A.x0 ? clip0(A.x0[V.col0 + j]) : 0.0f;
-        V.x[j] = v;
-        V.xh[j] = v;
-        V.dc[j] = 1.0f;
-    }
-    for (int i = tid; i < V.m; i += WD_THREADS) {
-        kn[0] = max(kn[0], abs_bits(b[i]));
-        const float v = A.y0 ? A.y0[V.row0 + i] : 0.0f;
-        V.y[i] = v;
-        V.yh[i] = v;
-        V.dr[i] = 1.0f;
-    }
-    block_max_u32<WD_NW, 2>(kn, s_key);
-    if (tid == 0) {
-        V.ex[WX_FLAG] = WD_RUN;
-        V.st[WS_CODE] = WD_CODE_LIMIT;
-        put64(V.st, WS_IT_LO, 0);
-        put64(V.st, WS_REACHED_LO, -1);
-        put64(V.st, WS_LAST_LO, 0);
-        V.st[WS_RESTARTS] = 0;
-        V.st[WS_E_LAST] = __float_as_int(__builtin_huge_valf());
-        V.st[WS_DEN_P] = __float_as_int(__fadd_rn(1.0f, __uint_as_float(kn[0])));
-        V.st[WS_DEN_D] = __float_as_int(__fadd_rn(1.0f, __uint_as_float(kn[1])));
-        rw[RX_QP] = __float_as_int(__builtin_huge_valf());      // no check has evaluated the rays
-        rw[RX_BY] = 0;
-        rw[RX_QD] = __float_as_int(__builtin_huge_valf());
-        rw[RX_CX] = 0;
-    }
-}
-
 // ---- a check's two sweeps of (xh, yh) and of the ray, for the running instances.  Two integer maxima per workgroup ----
 template <bool ROWS>
 __global__ __launch_bounds__(WD_THREADS) void rays_eval(const WideArgs A) {
@@ -793,7 +617,7 @@ __global__ __launch_bounds__(WD_THREADS) void rays_eval(const WideArgs A) {
     int k, rb, re;
     if (!wide_item<!ROWS>(A, &k, &rb, &re)) return;
     const WideView V = wide_view(A, k);
-    if (V.ex[WX_FLAG] != WD_RUN || V.st[WS_CODE] != WD_CODE_LIMIT) return;
+    if (V.ex[WX_FLAG] != WD_RUN || V.st[WS_CODE] != PD_CODE_LIMIT) return;
     unsigned best[2] = {0u, 0u};
     if constexpr (ROWS)
         item_sweep(A.a_ptr + V.row0, rb, re, EvalPair<true>{A.a_idx, A.a_val, A.b + V.row0, V.col0, V.xh, V.xa, best}, s_part2);
@@ -812,7 +636,7 @@ __global__ __launch_bounds__(WD_THREADS) void rays_decide(const WideArgs A, cons
     __shared__ unsigned s_key[WD_NW];
     const int tid = threadIdx.x;
     const WideView V = wide_view(A, blockIdx.x);
-    if (V.ex[WX_FLAG] != WD_RUN || V.st[WS_CODE] != WD_CODE_LIMIT) return;
+    if (V.ex[WX_FLAG] != WD_RUN || V.st[WS_CODE] != PD_CODE_LIMIT) return;
     int* rw = ray_words(A, blockIdx.x);
     const long long cnt = it - get64(V.st, WS_LAST_LO);
     const float e_last = stf(V.st, WS_E_LAST), w0 = stf(V.st, WS_W0), w = stf(V.st, WS_W), eta = stf(V.st, WS_ETA);
@@ -845,12 +669,10 @@ __global__ __launch_bounds__(WD_THREADS) void rays_decide(const WideArgs A, cons
         rw[RX_KEY_U] = 0;
         rw[RX_KEY_V] = 0;
     }
-    const float gap = __fdiv_rn(fabsf(__fsub_rn(s.a, s.b)), __fadd_rn(__fadd_rn(1.0f, fabsf(s.a)), fabsf(s.b)));
-    const WideErr at = {__fdiv_rn(__uint_as_float(key_p), stf(V.st, WS_DEN_P)), __fdiv_rn(__uint_as_float(key_d), stf(V.st, WS_DEN_D)), gap};
-    const float e = at.worst();
+    const float e = wide_err(V, key_p, key_d, s.a, s.b).worst();
     if (!finite_bits(e) || e <= A.eps) {
         if (tid == 0) {
-            V.st[WS_CODE] = finite_bits(e) ? WD_CODE_OPTIMAL : WD_CODE_NOT_FINITE;
+            V.st[WS_CODE] = finite_bits(e) ? PD_CODE_OPTIMAL : PD_CODE_NOT_FINITE;
             put64(V.st, WS_IT_LO, it);
         }
         return;
@@ -868,86 +690,13 @@ __global__ __launch_bounds__(WD_THREADS) void rays_decide(const WideArgs A, cons
     }
     if (qp <= R.ray_eps || qd <= R.ray_eps) {
         if (tid == 0) {
-            V.st[WS_CODE] = qp <= R.ray_eps ? WD_CODE_INFEASIBLE : WD_CODE_UNBOUNDED;
+            V.st[WS_CODE] = qp <= R.ray_eps ? PD_CODE_INFEASIBLE : PD_CODE_UNBOUNDED;
             put64(V.st, WS_IT_LO, it);
         }
         return;
     }
     if (!(e <= __fmul_rn(A.beta, e_last) || 25 * cnt >= 9 * it)) return;
-    // the restart, as wide_decide makes it
-    Sum2 dd = {0.0f, 0.0f};
-    for (int j = tid; j < V.n; j += WD_THREADS) {
-        const float v = V.xh[j], d = __fsub_rn(v, V.xa[j]);
-        dd.a = __fmaf_rn(d, __fdiv_rn(d, V.tc[j]), dd.a);
-        V.x[j] = V.xa[j] = v;
-    }
-    for (int i = tid; i < V.m; i += WD_THREADS) {
-        const float v = V.yh[i], d = __fsub_rn(v, V.ya[i]);
-        dd.b = __fmaf_rn(d, __fdiv_rn(d, V.tr[i]), dd.b);
-        V.y[i] = V.ya[i] = v;
-    }
-    dd = block_tree_sum<WD_NW>(dd, s_part2);
-    if (tid != 0) return;
-    V.st[WS_RESTARTS] = restarts + 1;
-    V.st[WS_E_LAST] = __float_as_int(e);
-    put64(V.st, WS_LAST_LO, it);
-    if (!A.primal_weight) return;
-    const float dx = sqrt_rn(dd.a), dy = sqrt_rn(dd.b);
-    if (finite_pos(dx) && finite_pos(dy)) {
-        const float w_lo = __fdiv_rn(w0, A.span), w_hi = __fmul_rn(w0, A.span);
-        const float raw = sqrt_rn(__fmul_rn(w, __fdiv_rn(dy, dx)));
-        const float up = raw > w_lo ? raw : w_lo;
-        const float wn = up < w_hi ? up : w_hi;
-        V.st[WS_W] = __float_as_int(wn);
-        V.st[WS_TAU] = __float_as_int(__fdiv_rn(eta, wn));
-        V.st[WS_SIGMA] = __float_as_int(__fmul_rn(eta, wn));
-    }
-}
-
-// ---- the last kernel of a rays call: wide_finish, and the rays (from the frozen xh - xa, so with the bits of the deciding
-// check) and the cert words ----
-__global__ __launch_bounds__(WD_THREADS) void rays_finish(const WideArgs A, const RayArgs R) {
-    __shared__ Sum2 s_part2[WD_NW];
-    const int tid = threadIdx.x;
-    const WideView V = wide_view(A, blockIdx.x);
-    const bool stale = V.ex[WX_FLAG] == WD_STALE;       // (uniform in the workgroup)
-    const int code = stale ? WD_CODE_STALE : V.st[WS_CODE];
-    WideErr out = {0.0f, 0.0f, 0.0f};
-    if (!stale) out = wide_errors(A, V, s_part2);
-    for (int j = tid; j < V.n; j += WD_THREADS) {
-        A.x_out[V.col0 + j] = stale ? 0.0f : V.xh[j];
-        if (A.dc_out) A.dc_out[V.col0 + j] = stale ? 0.0f : V.dc[j];
-        if (R.ray_x) R.ray_x[V.col0 + j] = code == WD_CODE_UNBOUNDED ? __fsub_rn(V.xh[j], V.xa[j]) : 0.0f;
-    }
-    for (int i = tid; i < V.m; i += WD_THREADS) {
-        A.y_out[V.row0 + i] = stale ? 0.0f : V.yh[i];
-        if (A.dr_out) A.dr_out[V.row0 + i] = stale ? 0.0f : V.dr[i];
-        if (R.ray_y) R.ray_y[V.row0 + i] = code == WD_CODE_INFEASIBLE ? __fsub_rn(V.yh[i], V.ya[i]) : 0.0f;
-    }
-    if (tid != 0) return;
-    int* st = A.status + 4 * (size_t)V.k;
-    float* q = A.kkt ? A.kkt + 6 * (size_t)V.k : nullptr;
-    float* ce = R.cert ? R.cert + 4 * (size_t)V.k : nullptr;
-    if (stale) {
-        st[0] = WD_CODE_STALE; st[1] = 0; st[2] = 0; st[3] = 0;
-        if (q) q[0] = q[1] = q[2] = q[3] = q[4] = q[5] = 0.0f;
-        if (ce) ce[0] = ce[1] = ce[2] = ce[3] = 0.0f;
-        return;
-    }
-    if (code == WD_CODE_LIMIT) put64(V.st, WS_IT_LO, A.iter_end);
-    put64(V.st, WS_REACHED_LO, A.iter_end);
-    st[0] = code;
-    st[1] = (int)min(get64(V.st, WS_IT_LO), (long long)0x7fffffff);
-    st[2] = V.st[WS_RESTARTS];
-    st[3] = 0;
-    if (q) {
-        q[0] = out.p; q[1] = out.d; q[2] = out.g;
-        q[3] = stf(V.st, WS_ETA); q[4] = stf(V.st, WS_W0); q[5] = stf(V.st, WS_W);
-    }
-    if (ce) {
-        const int* rw = ray_words(A, V.k);
-        ce[0] = stf(rw, RX_QP); ce[1] = stf(rw, RX_BY); ce[2] = stf(rw, RX_QD); ce[3] = stf(rw, RX_CX);
-    }
+    wide_restart(A, V, it, e, restarts, w0, w, eta, s_part2);
 }
 
 bool overlaps(const void* a, int64_t a_bytes, const void* b, int64_t b_bytes) {
