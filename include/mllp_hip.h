@@ -685,6 +685,63 @@ int mllp_lp_pdhg_rays(const mllp_graph_t* g, const float* d_x1 /*c [N]*/, const 
                       int32_t* d_status /*[n_inst,4]*/, float* d_kkt /*[n_inst,6] or NULL*/,
                       float* d_cert /*[n_inst,4] or NULL*/, void* d_scratch, void* stream);
 
+/* mllp_lp_pdhg_rays with a SPECTRAL STEP SIZE (mllp_amd/csrc/pdhg_wide.hip): the step's denominator is an
+ * estimate of |S|_2, S = diag(dr) A diag(dc), by power iteration on S'S, where every call before it takes the upper bound
+ * sqrt(|S|_1 |S|_inf), which is 1.3 to 6.7 times |S|_2 on this project's data.  Added after ABI 6 without a bump.  mllp_lp_pdhg,
+ * mllp_lp_pdhg_scaled, mllp_lp_pdhg_halpern, mllp_lp_pdhg_wide and mllp_lp_pdhg_rays are unchanged.
+ * THE RULE is mllp_lp_pdhg_rays', word for word, with ONE step inserted into the set-up (iter_begin = 0), after the scaling and
+ * the two norms |S|_1, |S|_inf and before eta is formed.  P = power_iters; fp32, every operation rounded to nearest, as written:
+ *   Start.  h_j = 1 + ((j 2654435761 mod 2^32) >> 9) 2^-23, j the column's index INSIDE its instance: an exact fp32 value in
+ *     [1, 2) whose bits do not depend on the batch, and no constant vector (A 1 = 0 for some Netlib matrices).
+ *     nu_0 = fsqrt(sum_j fma(h_j, h_j, .)), v_j = fdiv(h_j, nu_0).
+ *   Round r = 1 .. P.  u_i = fmul(dr_i, sum_j fma(a_ij, fmul(dc_j, v_j), .)), walking CSR(A);
+ *     w_j = fmul(dc_j, sum_i fma(a_ij, fmul(dr_i, u_i), .)), walking CSR(A');
+ *     nu_r = fsqrt(sum_j fma(w_j, w_j, .)), v_j = fdiv(w_j, nu_r).
+ *     The row and column sums run in the tiers picked by the row's length alone, as every sweep of the rule; the sums over j
+ *     of h^2 and w^2 run in the order of c'x (thread t adds t, t + 1024, ..., then the butterfly and the tree); every fsqrt is
+ *     correctly rounded.  If nu_r (or nu_0) is not finite and > 0 the instance's estimate is VOID and its rounds end.
+ *   Estimate.  sigma_est = fsqrt(nu_P), or 0 when void or P = 0.  In exact arithmetic sqrt(|S'S v|) <= |S|_2 for a unit v, and
+ *     it is at least |S v|: a lower bound, the tighter of the two.
+ *   Step.  L_bound = fsqrt(fmul(|S|_1, |S|_inf)) by mllp_lp_pdhg's own instruction, as before.  L = sigma_est if that is > 0 and
+ *     <= L_bound, otherwise L = L_bound.  eta = fdiv(step, L); eta = step when the product is not > 0, as before.  w0, tau,
+ *     sigma and everything else that depends on eta are formed as before.
+ *   Identity.  With power_iters = 0 every output that mllp_lp_pdhg_rays has is that call's, bit for bit -- mllp_lp_pdhg_wide's
+ *     with ray_eps < 0, and through it mllp_lp_pdhg_halpern's -- and d_norm is {0, L_bound}.
+ * NOT CLAIMED.  sigma_est is a LOWER bound of |S|_2: a start vector nearly orthogonal to the leading singular space would make
+ * the step too long.  The margin is `step` (0.9 against a smallest observed sigma_est / |S|_2 of 0.97 at P = 40); raise
+ * power_iters or lower step where that is not enough.  Nothing is added for the persistent calls, and nothing is claimed about
+ * the instances on which every rule so far stalls.
+ *   d_x1 .. ray_eps, rows_per_item, d_x .. d_cert, iter_begin, iter_end : as mllp_lp_pdhg_rays.  d_kkt[.][3] is the eta in use.
+ *   power_iters : 0 .. limits[4] (1024).  Ignored when iter_begin > 0: the set-up does not run and eta is the state's.
+ *   d_norm [n_inst, 2] or NULL : {sigma_est, L_bound}; zeros for a stale instance.  Both are kept in the state, so every call
+ *             writes them and the calls (0, K1) then (K1, K2) give the bits of the call (0, K2) in every output.
+ *   d_scratch : mllp_lp_pdhg_spectral_scratch_bytes(g, rows_per_item) bytes, which is 4 (29 n_inst + 6 N + 5 M):
+ *             mllp_lp_pdhg_rays' layout with two more words per instance BEHIND it (sigma_est and L_bound: state, values only;
+ *             during the set-up the first holds nu_r).  v, u and w live in xbar and the two anchors, which the set-up does not
+ *             read between the scaling and the start: no vector is added.
+ *             mllp_lp_pdhg_spectral_limits: mllp_lp_pdhg_wide_limits' four values and the largest power_iters (1024).
+ * Every requested output is fully written for every instance; n = 0 or m = 0 is legal (the estimate is void).  A launch
+ * function: `stream` only, no allocation, no host-to-device copy, no synchronisation, hipGraph-capturable.  With power_iters = 0
+ * it makes EXACTLY the launches of mllp_lp_pdhg_rays; with P > 0 and iter_begin = 0 the set-up makes 3 P + 1 more: one of one
+ * workgroup per instance for the start vector, and per round the row sweep, the column sweep (the items of the iteration's
+ * sweeps) and one of one workgroup per instance that normalises and records nu_r.  All are ordinary launches of 1024 threads
+ * in stream order: no cooperative launch, no grid barrier, no float atomics, one writer per word.  Bitwise reproducible, the
+ * same bits alone and inside any batch, for every rows_per_item.
+ * mllp_lp_pdhg_spectral is under the MEMORY CONTRACT below as mllp_lp_pdhg is, and the state in d_scratch between a call and the call that continues it is state this header names.
+ * MLLP_EINVAL before any launch, nothing written: every refusal of mllp_lp_pdhg_rays, in its words, under this call's name;
+ * power_iters outside 0 .. 1024; d_x0 or d_y0 overlapping d_norm.                                                          */
+int mllp_lp_pdhg_spectral_limits(int64_t limits[5]);
+int mllp_lp_pdhg_spectral_scratch_bytes(const mllp_graph_t* g, int64_t rows_per_item, int64_t* bytes);
+int mllp_lp_pdhg_spectral(const mllp_graph_t* g, const float* d_x1 /*c [N]*/, const float* d_x2 /*b [M]*/,
+                          const float* d_x0 /*[N] or NULL*/, const float* d_y0 /*[M] or NULL*/, int64_t iter_begin,
+                          int64_t iter_end, int64_t check_every, float eps, float step, float beta, int64_t ruiz_passes,
+                          int32_t pock_chambolle, int32_t primal_weight, float weight_span, int32_t reflect, float ray_eps,
+                          int64_t power_iters, int64_t rows_per_item, float* d_x /*[N]*/, float* d_y /*[M]*/,
+                          float* d_dr /*[M] or NULL*/, float* d_dc /*[N] or NULL*/, float* d_ray_x /*[N] or NULL*/,
+                          float* d_ray_y /*[M] or NULL*/, int32_t* d_status /*[n_inst,4]*/,
+                          float* d_kkt /*[n_inst,6] or NULL*/, float* d_cert /*[n_inst,4] or NULL*/,
+                          float* d_norm /*[n_inst,2] or NULL*/, void* d_scratch, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Plain CSR SpMM (the roofline kernel named in BASELINE.json's metric):
  *   transpose == 0:  Y[M,16] = A   * H[N,16]       transpose == 1:  Y[N,16] = A^T * H[M,16]

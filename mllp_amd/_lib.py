@@ -102,6 +102,11 @@ _PROTOTYPES = {
     "mllp_lp_pdhg_rays": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_float, c_float,
                                   c_float, c_int64, c_int32, c_int32, c_float, c_int32, c_float, c_int64, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mllp_lp_pdhg_spectral_limits": (c_int, [POINTER(c_int64)]),
+    "mllp_lp_pdhg_spectral_scratch_bytes": (c_int, [c_void_p, c_int64, POINTER(c_int64)]),
+    "mllp_lp_pdhg_spectral": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_float, c_float,
+                                      c_float, c_int64, c_int32, c_int32, c_float, c_int32, c_float, c_int64, c_int64, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mllp_graph_build_spmm_copy": (c_int, [c_void_p, c_int, c_int, c_void_p]),
     "mllp_graph_drop_spmm_copy": (c_int, [c_void_p, c_int]),
     "mllp_graph_spmm_copy_info": (c_int, [c_void_p, c_int, POINTER(c_int64)]),

@@ -62,7 +62,9 @@ HOT_PATH_DEFAULTS = {
                              # `pdhg` runs the wide call with certificates (LPBatch.pdhg_rays; implies `wide`) and adds
                              # pdhg_infeasible / pdhg_unbounded: the instances that ended with code 4 and with code 5.  Both are
                              # relative to eps: code 4 says "no feasible point with a 1-norm below 1 / eps", which feasible LPs
-                             # with large solutions meet too (at 2^-10: 46 of the 97 Netlib LPs), so choose eps against them
+                             # with large solutions meet too (at 2^-10: 46 of the 97 Netlib LPs), so choose eps against them;
+                             # `spectral: true` (or `spectral: {iters: 40}`) inside `pdhg` runs the wide call with the step
+                             # from power iteration on the device (LPBatch.pdhg_spectral; implies `wide`, combines with `rays`)
     "weight_decay": 0.0,     # decoupled weight decay of the optimizer (torch.optim.AdamW); 0 == the reference's Adam
     "clip_norm": 0.0,        # cap on the global gradient norm of a step (torch.nn.utils.clip_grad_norm_); 0 == no clipping
     "lr_schedule": None,     # the block {warmup: W, total: T, min_ratio: r}: the rate rises linearly over the first W steps, then

@@ -2,7 +2,8 @@
 // workgroup, and pdhg_wide.hip, which cuts an instance into items across the device.  The bar between the two is bit equality
 // (DESIGN.md 4.25), so what a sweep does with a term and with a finished row is written ONCE, here: the status codes, the
 // helpers on the bit patterns of floats, the workgroup's integer maxima, how the lanes of a row are combined (BySum, ByMax),
-// and the operators of the set-up walk (ScaledAbs) and of a Halpern iteration (HalpernCol, HalpernRow).  An operator says
+// and the operators of the set-up walks (ScaledAbs; ScaledProd, the power round of mllp_lp_pdhg_spectral, which only
+// pdhg_wide.hip instantiates) and of a Halpern iteration (HalpernCol, HalpernRow).  An operator says
 //   Acc, Row, By    the accumulator, what a row's lanes hold of the row beside it, how the lanes are combined
 //   row(r)          that Row;  term(rc, e, q): entry e into the accumulator;  finish(r, rc, q): the row's result, by ONE lane
 // and knows nothing of who walks the rows.
@@ -129,6 +130,28 @@ struct ScaledAbs {
         if (out) out[r] = q;
         const unsigned k = abs_bits(q);
         *best = k > *best ? k : *best;
+    }
+};
+
+// a power round's walk of one orientation (mllp_lp_pdhg_spectral): the product of the matrix with a gathered vector `g` that
+// already carries the OTHER side's factor (fmul(dc_j, v_j) for rows, fmul(dr_i, u_i) for columns: ONE gather per term), an fma
+// chain, times this row's own factor.  ROWS: out_i = fmul(dr_i, u_i) with u_i = fmul(dr_i, sum) -- what the column walk
+// gathers; columns: out_j = w_j = fmul(dc_j, sum)
+template <bool ROWS>
+struct ScaledProd {
+    using Acc = float;
+    using Row = OwnFactor;
+    using By = BySum;
+    const int* __restrict__ idx;
+    const float* __restrict__ val;
+    int off;
+    const float *own, *g;
+    float* out;
+    __device__ __forceinline__ Row row(int r) const { return {own[r]}; }
+    __device__ __forceinline__ void term(const Row&, int e, float& q) const { q = __fmaf_rn(val[e], g[idx[e] - off], q); }
+    __device__ __forceinline__ void finish(int r, const Row& rc, float q) const {
+        const float p = __fmul_rn(rc.d, q);
+        out[r] = ROWS ? __fmul_rn(rc.d, p) : p;
     }
 };
 

@@ -30,8 +30,13 @@
 // wide call's (wide_restart); every launch of a call has its counterpart in the other call, so the two make the same number of
 // launches.  A value that RAYS changes is DEFINED once, never set and then overwritten (DESIGN.md 4.22's habit).
 //
+// mllp_lp_pdhg_spectral is the rays call whose set-up estimates |S|_2 by power iteration between the last walk
+// and the start: spec_init, then per round spec_product<rows>, spec_product<columns>, spec_normalize -- 3 P + 1 launches, none
+// at P = 0 -- and spec_start / spec_finish, which are the wide start and the rays finish with the estimate (start_body<SPEC>) and
+// d_norm.  Its two state words lie BEHIND the rays' words.
+//
 // WHAT IS DEFINED WHERE.  pdhg_ops.h, shared with pdhg.hip: the status codes, the bit helpers, block_max_u32,
-// BySum and ByMax, ScaledAbs, HalpernCol, HalpernRow -- the iteration and the set-up walk are written once for both executions.
+// BySum and ByMax, ScaledAbs, ScaledProd, HalpernCol, HalpernRow -- the iteration and the set-up walks are written once.
 // This file: the walker of an item (item_sweep: pdhg.hip's wg_sweep places the block tier differently, see pdhg_ops.h) and the
 // operators that only these kernels instantiate.  EvalOne walks ONE point with a float accumulator, which is the `cur` half of
 // pdhg.hip's Sum2 walk (EvalSweep): the two halves of a Sum2 never meet.
@@ -210,6 +215,24 @@ __device__ __forceinline__ int* ray_words(const WideArgs& A, int k) {
     return reinterpret_cast<int*>(A.scratch) + wide_words(A.n_inst, A.M, A.N) + RX_WORDS * (long long)k;
 }
 
+// mllp_lp_pdhg_spectral: two more words per instance BEHIND the rays' words, both STATE (values only): the
+// estimate sigma_est (0: void, or power_iters = 0) and the bound sqrt(|S|_1 |S|_inf), which every call writes to d_norm.  During
+// the set-up the first word is the power iteration's own: nu of the last round (|h|_2 before the first), 0 once void
+enum { SX_SIGMA = 0, SX_BOUND, SX_WORDS };
+constexpr int64_t WD_MAX_POWER = 1024;
+
+__host__ __device__ constexpr int64_t spectral_words(int64_t n_inst, int64_t M, int64_t N) { return rays_words(n_inst, M, N) + SX_WORDS * n_inst; }
+
+// what mllp_lp_pdhg_spectral takes beside the rays' arguments (host only: the kernels get them as arguments of their own)
+struct SpecArgs {
+    int64_t power_iters;
+    float* norm;
+};
+
+__device__ __forceinline__ int* spec_words(const WideArgs& A, int k) {
+    return reinterpret_cast<int*>(A.scratch) + rays_words(A.n_inst, A.M, A.N) + SX_WORDS * (long long)k;
+}
+
 // the workgroup's item: the instance k with first[k] <= blockIdx.x < first[k + 1] (the table is made by wide_prep of THIS call
 // from inst_ptr alone; thread t looks at instances t, t + 1024, ..., so the search costs one round of loads and two barriers),
 // and the block inside it.  False, for the whole workgroup: no item (cannot happen with the grid the host computes from the
@@ -359,15 +382,26 @@ __global__ __launch_bounds__(WD_THREADS) void wide_scale_update(const WideArgs A
     }
 }
 
-// after the last walk: eta, the weight's start, the factors' squares, the anchor
-__global__ __launch_bounds__(WD_THREADS) void wide_start(const WideArgs A) {
+// after the last walk: eta, the weight's start, the factors' squares, the anchor.  SPEC (mllp_lp_pdhg_spectral): the step's
+// denominator is the power iteration's estimate where that is finite, positive and not above the bound; the two go to the state
+template <bool SPEC>
+__device__ __forceinline__ void start_body(const WideArgs A, long long power_iters) {
     __shared__ Sum2 s_part2[WD_NW];
     const int tid = threadIdx.x;
     const WideView V = wide_view(A, blockIdx.x);
     const float* c = A.c + V.col0;
     const float* b = A.b + V.row0;
     const float prod = __fmul_rn(__int_as_float(V.ex[WX_KEY_COL]), __int_as_float(V.ex[WX_KEY_ROW]));
-    const float eta = prod > 0.0f ? __fdiv_rn(A.step, __fsqrt_rn(prod)) : A.step;      // (the hardware's root, as pdhg.hip takes it)
+    int* sw = SPEC ? spec_words(A, blockIdx.x) : nullptr;
+    float bound = 0.0f, est = 0.0f, eta;
+    if constexpr (SPEC) {
+        const float nu = power_iters > 0 ? stf(sw, SX_SIGMA) : 0.0f;        // (read before thread 0 writes: the tree's barriers lie between)
+        bound = __fsqrt_rn(prod);
+        est = finite_pos(nu) ? sqrt_rn(nu) : 0.0f;
+        eta = prod > 0.0f ? __fdiv_rn(A.step, est > 0.0f && est <= bound ? est : bound) : A.step;
+    } else {
+        eta = prod > 0.0f ? __fdiv_rn(A.step, __fsqrt_rn(prod)) : A.step;      // (the hardware's root, as pdhg.hip takes it)
+    }
     Sum2 nn = {0.0f, 0.0f};     // |dc o c|^2, |dr o b|^2
     for (int j = tid; j < V.n; j += WD_THREADS) {
         const float d = V.dc[j], v = __fmul_rn(d, c[j]);
@@ -393,7 +427,64 @@ __global__ __launch_bounds__(WD_THREADS) void wide_start(const WideArgs A) {
         V.st[WS_SIGMA] = __float_as_int(__fmul_rn(eta, w0));
         V.ex[WX_KEY_COL] = 0;
         V.ex[WX_KEY_ROW] = 0;
+        if constexpr (SPEC) {
+            sw[SX_SIGMA] = __float_as_int(est);
+            sw[SX_BOUND] = __float_as_int(bound);
+        }
     }
+}
+__global__ __launch_bounds__(WD_THREADS) void wide_start(const WideArgs A) { start_body<false>(A, 0); }
+__global__ __launch_bounds__(WD_THREADS) void spec_start(const WideArgs A, long long power_iters) { start_body<true>(A, power_iters); }
+
+// ---- mllp_lp_pdhg_spectral's power iteration on S'S, S = diag(dr) A diag(dc), between the last walk and the start.  xb holds
+// fmul(dc_j, v_j), ya holds fmul(dr_i, u_i), xa holds w: the three are free here (xa and ya were the scaling's C and R, xb is
+// not read before the first column sweep writes it).  An instance whose word is 0 is void: its kernels return at once ----
+// the start vector: h_j = 1 + ((j 2654435761 mod 2^32) >> 9) 2^-23, j inside the instance; v = h / |h|_2
+__global__ __launch_bounds__(WD_THREADS) void spec_init(const WideArgs A) {
+    __shared__ float s_part[WD_NW];
+    const int tid = threadIdx.x;
+    const WideView V = wide_view(A, blockIdx.x);
+    float q = 0.0f;
+    for (int j = tid; j < V.n; j += WD_THREADS) {
+        const float h = __uint_as_float(0x3f800000u | (((unsigned)j * 2654435761u) >> 9));
+        q = __fmaf_rn(h, h, q);
+    }
+    const float nh = sqrt_rn(block_tree_sum<WD_NW>(q, s_part));
+    const bool good = finite_pos(nh);
+    for (int j = tid; good && j < V.n; j += WD_THREADS) {
+        const float h = __uint_as_float(0x3f800000u | (((unsigned)j * 2654435761u) >> 9));
+        V.xb[j] = __fmul_rn(V.dc[j], __fdiv_rn(h, nh));
+    }
+    if (tid == 0) spec_words(A, blockIdx.x)[SX_SIGMA] = good ? __float_as_int(nh) : 0;
+}
+
+// a round's two sweeps: rows, u = dr o (A (dc o v)), stored with dr once more; then columns, w = dc o (A' (dr o u))
+template <bool COLS>
+__global__ __launch_bounds__(WD_THREADS) void spec_product(const WideArgs A) {
+    __shared__ float s_part[WD_NW];
+    int k, rb, re;
+    if (!wide_item<COLS>(A, &k, &rb, &re)) return;
+    const WideView V = wide_view(A, k);
+    if (spec_words(A, k)[SX_SIGMA] == 0) return;        // (uniform in the workgroup: no kernel of this launch writes the word)
+    if constexpr (COLS)
+        item_sweep(A.at_ptr + V.col0, rb, re, ScaledProd<false>{A.at_idx, A.at_val, V.row0, V.dc, V.ya, V.xa}, s_part);
+    else
+        item_sweep(A.a_ptr + V.row0, rb, re, ScaledProd<true>{A.a_idx, A.a_val, V.col0, V.dr, V.xb, V.ya}, s_part);
+}
+
+// a round's end: nu = |w|_2 in the order of c'x, v = w / nu (stored as fmul(dc_j, v_j)); nu not finite and positive: void
+__global__ __launch_bounds__(WD_THREADS) void spec_normalize(const WideArgs A) {
+    __shared__ float s_part[WD_NW];
+    const int tid = threadIdx.x;
+    const WideView V = wide_view(A, blockIdx.x);
+    int* sw = spec_words(A, blockIdx.x);
+    if (sw[SX_SIGMA] == 0) return;      // (every thread reads it before the tree's barriers, thread 0 writes it behind them)
+    float q = 0.0f;
+    for (int j = tid; j < V.n; j += WD_THREADS) q = __fmaf_rn(V.xa[j], V.xa[j], q);
+    const float nu = sqrt_rn(block_tree_sum<WD_NW>(q, s_part));
+    const bool good = finite_pos(nu);
+    for (int j = tid; good && j < V.n; j += WD_THREADS) V.xb[j] = __fmul_rn(V.dc[j], __fdiv_rn(V.xa[j], nu));
+    if (tid == 0) sw[SX_SIGMA] = good ? __float_as_int(nu) : 0;
 }
 
 // ---- an iteration's two sweeps.  `it`: the iterations done before this one ----
@@ -570,6 +661,15 @@ __device__ __forceinline__ void finish_body(const WideArgs A, const RayArgs R) {
 }
 __global__ __launch_bounds__(WD_THREADS) void wide_finish(const WideArgs A) { finish_body<false>(A, RayArgs{}); }
 __global__ __launch_bounds__(WD_THREADS) void rays_finish(const WideArgs A, const RayArgs R) { finish_body<true>(A, R); }
+// mllp_lp_pdhg_spectral: the rays' last kernel, then d_norm from the state (zeros for a stale instance)
+__global__ __launch_bounds__(WD_THREADS) void spec_finish(const WideArgs A, const RayArgs R, float* norm) {
+    finish_body<true>(A, R);
+    if (threadIdx.x != 0 || !norm) return;
+    const bool stale = wide_view(A, blockIdx.x).ex[WX_FLAG] == WD_STALE;
+    const int* sw = spec_words(A, blockIdx.x);
+    norm[2 * (size_t)blockIdx.x] = stale ? 0.0f : stf(sw, SX_SIGMA);
+    norm[2 * (size_t)blockIdx.x + 1] = stale ? 0.0f : stf(sw, SX_BOUND);
+}
 
 // =====================================================================================================================
 // mllp_lp_pdhg_rays: a check with certificates of infeasibility and unboundedness.  The candidate ray
@@ -719,6 +819,11 @@ int64_t wide_items(const std::vector<int64_t>& p, int64_t n_inst, int64_t rows) 
     return items;
 }
 
+// the scratch's words of the three calls: each layout is the one before it with words behind
+int64_t call_words(const mllp_graph_t* g, bool rays, bool spec) {
+    return spec ? spectral_words(g->n_inst, g->M, g->N) : rays ? rays_words(g->n_inst, g->M, g->N) : wide_words(g->n_inst, g->M, g->N);
+}
+
 // a launch of the entry point `fn` ("mllp_" + what an error names it by)
 template <class... KArgs, class... Args>
 int wide_go(void (*kernel)(KArgs...), const char* fn, const char* what, int64_t grid, hipStream_t s, const Args&... args) {
@@ -730,11 +835,12 @@ int wide_go(void (*kernel)(KArgs...), const char* fn, const char* what, int64_t 
 
 // mllp_lp_pdhg_wide (rays == nullptr) and mllp_lp_pdhg_rays: the refusals, the arguments and the launches.  The two calls make
 // the same launches in the same order; with rays the first and the last kernel are the rays' own, and with ray_eps >= 0 so are
-// the three of a check
+// the three of a check.  mllp_lp_pdhg_spectral (spec != nullptr, which comes with rays): the rays call's launches with its own
+// start and finish, and 3 P + 1 more between the last walk and the start when P = power_iters > 0
 int wide_call(const char* fn, const mllp_graph_t* g, const float* d_x1, const float* d_x2, const float* d_x0, const float* d_y0, int64_t iter_begin,
               int64_t iter_end, int64_t check_every, float eps, float step, float beta, int64_t ruiz_passes, int32_t pock_chambolle,
-              int32_t primal_weight, float weight_span, int32_t reflect, const RayArgs* rays, int64_t rows_per_item, float* d_x, float* d_y,
-              float* d_dr, float* d_dc, int32_t* d_status, float* d_kkt, void* d_scratch, void* stream) {
+              int32_t primal_weight, float weight_span, int32_t reflect, const RayArgs* rays, const SpecArgs* spec, int64_t rows_per_item,
+              float* d_x, float* d_y, float* d_dr, float* d_dc, int32_t* d_status, float* d_kkt, void* d_scratch, void* stream) {
     REQUIRE_FOR(fn, g && d_x1 && d_x2 && d_x && d_y && d_status, "null argument (g, d_x1, d_x2, d_x, d_y and d_status are required)");
     REQUIRE_FOR(fn, iter_begin >= 0, "iter_begin must not be negative");
     REQUIRE_FOR(fn, iter_end >= iter_begin, "iter_end must not be below iter_begin");
@@ -745,15 +851,17 @@ int wide_call(const char* fn, const mllp_graph_t* g, const float* d_x1, const fl
     REQUIRE_FOR(fn, ruiz_passes >= 0 && ruiz_passes <= WD_MAX_RUIZ, "ruiz_passes must be in 0 .. 64");
     REQUIRE_FOR(fn, std::isfinite(weight_span) && weight_span >= 1.0f, "weight_span must be finite and at least 1");
     REQUIRE_FOR(fn, !rays || std::isfinite(rays->ray_eps), "ray_eps must be finite (negative: no detection)");
+    REQUIRE_FOR(fn, !spec || (spec->power_iters >= 0 && spec->power_iters <= WD_MAX_POWER), "power_iters must be in 0 .. 1024");
     int64_t rows;
     if (int rc = wide_rows(fn, rows_per_item, &rows)) return rc;
-    const int64_t words = rays ? rays_words(g->n_inst, g->M, g->N) : wide_words(g->n_inst, g->M, g->N);
+    const int64_t words = call_words(g, rays != nullptr, spec != nullptr);
     REQUIRE_FOR(fn, words == 0 || d_scratch, std::string("null d_scratch (") + fn + "_scratch_bytes is not 0)");
     const struct {
         const void* p;
         int64_t bytes;
     } outs[] = {{d_x, g->N * 4}, {d_y, g->M * 4}, {d_dr, g->M * 4}, {d_dc, g->N * 4}, {d_status, g->n_inst * 16}, {d_kkt, g->n_inst * 24},
-                {rays ? rays->ray_x : nullptr, g->N * 4}, {rays ? rays->ray_y : nullptr, g->M * 4}, {rays ? rays->cert : nullptr, g->n_inst * 16}};
+                {rays ? rays->ray_x : nullptr, g->N * 4}, {rays ? rays->ray_y : nullptr, g->M * 4}, {rays ? rays->cert : nullptr, g->n_inst * 16},
+                {spec ? spec->norm : nullptr, g->n_inst * 8}};
     for (const auto& o : outs)
         REQUIRE_FOR(fn, !overlaps(d_x0, g->N * 4, o.p, o.bytes) && !overlaps(d_y0, g->M * 4, o.p, o.bytes), "d_x0 or d_y0 overlaps an output");
     if (g->n_inst <= 0) return MLLP_OK;
@@ -789,7 +897,14 @@ int wide_call(const char* fn, const mllp_graph_t* g, const float* d_x1, const fl
         }
         if (!rc) rc = wide_go(wide_scale_walk<true, false, true>, fn, "norm, columns", items_n, s, a);
         if (!rc) rc = wide_go(wide_scale_walk<false, false, true>, fn, "norm, rows", items_m, s, a);
-        if (!rc) rc = wide_go(wide_start, fn, "start", K, s, a);
+        const long long P = spec ? (long long)spec->power_iters : 0;
+        if (!rc && P > 0) rc = wide_go(spec_init, fn, "power, start", K, s, a);
+        for (long long r = 0; !rc && r < P; ++r) {
+            rc = wide_go(spec_product<false>, fn, "power, rows", items_m, s, a);
+            if (!rc) rc = wide_go(spec_product<true>, fn, "power, columns", items_n, s, a);
+            if (!rc) rc = wide_go(spec_normalize, fn, "power, norm", K, s, a);
+        }
+        if (!rc) rc = spec ? wide_go(spec_start, fn, "start", K, s, a, P) : wide_go(wide_start, fn, "start", K, s, a);
     }
     for (long long it = (long long)iter_begin; !rc && it < (long long)iter_end; ++it) {
         rc = wide_go(wide_step<true>, fn, "columns", items_n, s, a, it);
@@ -807,7 +922,10 @@ int wide_call(const char* fn, const mllp_graph_t* g, const float* d_x1, const fl
     }
     if (!rc) rc = wide_go(wide_eval<true, true>, fn, "evaluation, rows", items_m, s, a);
     if (!rc) rc = wide_go(wide_eval<false, true>, fn, "evaluation, columns", items_n, s, a);
-    if (!rc) rc = rays ? wide_go(rays_finish, fn, "finish", K, s, a, r) : wide_go(wide_finish, fn, "finish", K, s, a);
+    if (!rc)
+        rc = spec   ? wide_go(spec_finish, fn, "finish", K, s, a, r, spec->norm)
+             : rays ? wide_go(rays_finish, fn, "finish", K, s, a, r)
+                    : wide_go(wide_finish, fn, "finish", K, s, a);
     return rc;
 }
 
@@ -826,22 +944,30 @@ static int wide_limits(const char* fn, int64_t* limits) {
     return MLLP_OK;
 }
 
-static int wide_scratch_bytes(const char* fn, const mllp_graph_t* g, int64_t rows_per_item, bool rays, int64_t* bytes) {
+static int wide_scratch_bytes(const char* fn, const mllp_graph_t* g, int64_t rows_per_item, bool rays, bool spec, int64_t* bytes) {
     REQUIRE_FOR(fn, g && bytes, "null argument");
     int64_t rows;
     if (int rc = wide_rows(fn, rows_per_item, &rows)) return rc;
-    *bytes = (rays ? rays_words(g->n_inst, g->M, g->N) : wide_words(g->n_inst, g->M, g->N)) * (int64_t)sizeof(float);
+    *bytes = call_words(g, rays, spec) * (int64_t)sizeof(float);
     return MLLP_OK;
 }
 
 extern "C" int mllp_lp_pdhg_wide_limits(int64_t* limits) { return wide_limits(__func__, limits); }
 extern "C" int mllp_lp_pdhg_rays_limits(int64_t* limits) { return wide_limits(__func__, limits); }
+extern "C" int mllp_lp_pdhg_spectral_limits(int64_t* limits) {
+    if (int rc = wide_limits(__func__, limits)) return rc;
+    limits[4] = WD_MAX_POWER;
+    return MLLP_OK;
+}
 
 extern "C" int mllp_lp_pdhg_wide_scratch_bytes(const mllp_graph_t* g, int64_t rows_per_item, int64_t* bytes) {
-    return wide_scratch_bytes(__func__, g, rows_per_item, false, bytes);
+    return wide_scratch_bytes(__func__, g, rows_per_item, false, false, bytes);
 }
 extern "C" int mllp_lp_pdhg_rays_scratch_bytes(const mllp_graph_t* g, int64_t rows_per_item, int64_t* bytes) {
-    return wide_scratch_bytes(__func__, g, rows_per_item, true, bytes);
+    return wide_scratch_bytes(__func__, g, rows_per_item, true, false, bytes);
+}
+extern "C" int mllp_lp_pdhg_spectral_scratch_bytes(const mllp_graph_t* g, int64_t rows_per_item, int64_t* bytes) {
+    return wide_scratch_bytes(__func__, g, rows_per_item, true, true, bytes);
 }
 
 extern "C" int mllp_lp_pdhg_wide(const mllp_graph_t* g, const float* d_x1, const float* d_x2, const float* d_x0, const float* d_y0,
@@ -850,7 +976,7 @@ extern "C" int mllp_lp_pdhg_wide(const mllp_graph_t* g, const float* d_x1, const
                                  int64_t rows_per_item, float* d_x, float* d_y, float* d_dr, float* d_dc, int32_t* d_status, float* d_kkt,
                                  void* d_scratch, void* stream) {
     return wide_call(__func__, g, d_x1, d_x2, d_x0, d_y0, iter_begin, iter_end, check_every, eps, step, beta, ruiz_passes, pock_chambolle,
-                     primal_weight, weight_span, reflect, nullptr, rows_per_item, d_x, d_y, d_dr, d_dc, d_status, d_kkt, d_scratch, stream);
+                     primal_weight, weight_span, reflect, nullptr, nullptr, rows_per_item, d_x, d_y, d_dr, d_dc, d_status, d_kkt, d_scratch, stream);
 }
 
 extern "C" int mllp_lp_pdhg_rays(const mllp_graph_t* g, const float* d_x1, const float* d_x2, const float* d_x0, const float* d_y0,
@@ -860,6 +986,18 @@ extern "C" int mllp_lp_pdhg_rays(const mllp_graph_t* g, const float* d_x1, const
                                  float* d_ray_y, int32_t* d_status, float* d_kkt, float* d_cert, void* d_scratch, void* stream) {
     const RayArgs rays{ray_eps, d_ray_x, d_ray_y, d_cert};
     return wide_call(__func__, g, d_x1, d_x2, d_x0, d_y0, iter_begin, iter_end, check_every, eps, step, beta, ruiz_passes, pock_chambolle,
-                     primal_weight, weight_span, reflect, &rays, rows_per_item, d_x, d_y, d_dr, d_dc, d_status, d_kkt, d_scratch, stream);
+                     primal_weight, weight_span, reflect, &rays, nullptr, rows_per_item, d_x, d_y, d_dr, d_dc, d_status, d_kkt, d_scratch, stream);
+}
+
+extern "C" int mllp_lp_pdhg_spectral(const mllp_graph_t* g, const float* d_x1, const float* d_x2, const float* d_x0, const float* d_y0,
+                                     int64_t iter_begin, int64_t iter_end, int64_t check_every, float eps, float step, float beta,
+                                     int64_t ruiz_passes, int32_t pock_chambolle, int32_t primal_weight, float weight_span, int32_t reflect,
+                                     float ray_eps, int64_t power_iters, int64_t rows_per_item, float* d_x, float* d_y, float* d_dr,
+                                     float* d_dc, float* d_ray_x, float* d_ray_y, int32_t* d_status, float* d_kkt, float* d_cert,
+                                     float* d_norm, void* d_scratch, void* stream) {
+    const RayArgs rays{ray_eps, d_ray_x, d_ray_y, d_cert};
+    const SpecArgs spec{power_iters, d_norm};
+    return wide_call(__func__, g, d_x1, d_x2, d_x0, d_y0, iter_begin, iter_end, check_every, eps, step, beta, ruiz_passes, pock_chambolle,
+                     primal_weight, weight_span, reflect, &rays, &spec, rows_per_item, d_x, d_y, d_dr, d_dc, d_status, d_kkt, d_scratch, stream);
 }
 

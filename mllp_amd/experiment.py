@@ -235,6 +235,20 @@ def _pdhg_rays(opt):
     return ray_eps
 
 
+def _pdhg_spectral(opt):
+    """the `spectral` option of the pdhg block: None when absent or false, else power_iters"""
+    spectral = opt.get("spectral")
+    if spectral is None or spectral is False:
+        return None
+    own = {} if spectral is True else dict(spectral)
+    if set(own) - {"iters"}:
+        raise ValueError(f"report_solved: pdhg: spectral: unknown keys {sorted(set(own) - {'iters'})}")
+    power = int(own.get("iters", 40))
+    if power < 0:
+        raise ValueError("report_solved: pdhg: spectral: iters must not be negative")
+    return power
+
+
 def pdhg_counts(batch, logits, report):
     """[3] device counts over a batch's instances, by PDHG_KEYS, under `report_solved` {..., pdhg: {iters: K, eps: E}}
     (optional: `check`, default 64, and `warm`, default true): every instance solved by restarted PDHG on the device
@@ -252,8 +266,11 @@ def pdhg_counts(batch, logits, report):
     of infeasibility and unboundedness (LPBatch.pdhg_rays, ray_eps E, default 2^-10): it implies `wide` (`wide: false` beside
     it is refused), takes its options, and two more counts are returned, by PDHG_RAY_KEYS: the instances that ended with
     code 4 and with code 5 -- "no feasible point with a 1-norm below 1 / E" and its dual, which is infeasibility only where E
-    is small against the solutions' size.  Without any of the four keys (or with `false`) the call is LPBatch.pdhg.  No sync unless `poll`
-    is given."""
+    is small against the solutions' size.  `spectral: true` or `spectral: {iters: P}` selects the wide call whose step comes
+    from P rounds (default 40) of power iteration on the device (LPBatch.pdhg_spectral): it implies `wide` (`wide: false` or
+    `scaled: false` beside it is refused), takes its options, and combines with `rays` (without `rays` detection is off and
+    the log keys are the ones they were).  Without any of the five keys (or with `false`) the call is LPBatch.pdhg.  No sync
+    unless `poll` is given."""
     opt = report["pdhg"]
     for key in ("iters", "eps"):
         if key not in opt:
@@ -264,10 +281,13 @@ def pdhg_counts(batch, logits, report):
     ray_eps = _pdhg_rays(opt)
     if ray_eps is not None and wide is False:
         raise ValueError("report_solved: pdhg: rays runs on the wide call: it cannot go with wide: false")
+    power = _pdhg_spectral(opt)
+    if power is not None and wide is False:
+        raise ValueError("report_solved: pdhg: spectral runs on the wide call: it cannot go with wide: false")
     halpern = None if halpern is False else halpern
     wide = None if wide is False else wide
-    if ray_eps is not None and wide is None:
-        wide = True                 # the call with certificates IS the wide call
+    if (ray_eps is not None or power is not None) and wide is None:
+        wide = True                 # the call with certificates, and the one with the spectral step, ARE the wide call
     if wide is not None and scaled is False:
         raise ValueError("report_solved: pdhg: wide is a preconditioned call: it cannot go with scaled: false")
     if wide is not None and halpern is None:
@@ -300,7 +320,9 @@ def pdhg_counts(batch, logits, report):
             kw.update(rows_per_item=None if rows is None else int(rows), poll_every=None if poll is None else int(poll))
         if ray_eps is not None:
             kw["ray_eps"] = ray_eps
-        call = (batch.pdhg_rays if ray_eps is not None else batch.pdhg_wide if wide is not None else batch.pdhg_scaled if halpern is None
+        if power is not None:
+            kw["power_iters"] = power
+        call = (batch.pdhg_spectral if power is not None else batch.pdhg_rays if ray_eps is not None else batch.pdhg_wide if wide is not None else batch.pdhg_scaled if halpern is None
                 else batch.pdhg_halpern)
         res = call(int(opt["iters"]), eps=float(opt["eps"]), check_every=int(opt.get("check", 64)), start=start, **kw)
     got = batch.solved(batch.pdhg_basis(res, max_m=max_m), report["feas_tol"], report["opt_tol"])

@@ -1289,11 +1289,29 @@ class LPBatch:
                                (eps, step, beta, ruiz, pock_chambolle, primal_weight, weight_span, reflect, ray_eps), x0, y0, start, rows_per_item,
                                poll_every)
 
+    def pdhg_spectral(self, max_iters, eps=2.0 ** -10, check_every=64, step=0.9, beta=0.5, ruiz=10, pock_chambolle=True,
+                      primal_weight=True, weight_span=16.0, reflect=True, power_iters=40, ray_eps=-1.0, x0=None, y0=None, start=None,
+                      rows_per_item=None, poll_every=None):
+        """`pdhg_rays` with a spectral step size (mllp_lp_pdhg_spectral; the rule is stated in include/mllp_hip.h): the step is
+        `step` over an estimate of the scaled matrix's 2-norm from `power_iters` rounds of power iteration on the device, where
+        every other call divides by sqrt(|S|_1 |S|_inf), an upper bound that is 1.3 to 6.7 times too large on this project's
+        data.  The estimate is a LOWER bound; where it is void or above the bound, the bound is used.  `power_iters=0` gives
+        `pdhg_rays`' bits.  Detection is OFF by default here (`ray_eps=-1`: 2^-10 stops 46 feasible Netlib LPs).  The other
+        arguments are `pdhg_rays`'.  Returns an `LPPdhgSpectral`, whose `.norm` is [n_inst, 2] = the estimate (0: none), the
+        bound; `.kkt[:, 3]` is the eta in use."""
+        power_iters = int(power_iters)
+        if power_iters < 0 or power_iters > pdhg_spectral_limits()[4]:
+            raise ValueError(f"pdhg_spectral: power_iters must be in 0 .. {pdhg_spectral_limits()[4]}")
+        return self._pdhg_wide("pdhg_spectral", max_iters, check_every,
+                               (eps, step, beta, ruiz, pock_chambolle, primal_weight, weight_span, reflect, ray_eps, power_iters), x0, y0, start,
+                               rows_per_item, poll_every)
+
     def _pdhg_wide(self, who, max_iters, check_every, params, x0, y0, start, rows_per_item, poll_every):
-        """What `pdhg_wide` and `pdhg_rays` share: the start, the validation, the scratch kept on the batch (`_<who>_scratch`),
-        the outputs, the call mllp_lp_<who> and the continuation loop.  `params`: eps .. reflect, and for pdhg_rays ray_eps behind
-        them."""
-        rays = who == "pdhg_rays"
+        """What `pdhg_wide`, `pdhg_rays` and `pdhg_spectral` share: the start, the validation, the scratch kept on the batch
+        (`_<who>_scratch`), the outputs, the call mllp_lp_<who> and the continuation loop.  `params`: eps .. reflect, for pdhg_rays
+        ray_eps behind them, and for pdhg_spectral power_iters behind that."""
+        spectral = who == "pdhg_spectral"
+        rays = spectral or who == "pdhg_rays"
         if start is not None:
             if x0 is not None or y0 is not None:
                 raise ValueError(f"{who}: give start or x0 / y0, not both")
@@ -1319,8 +1337,9 @@ class LPBatch:
         opt = lambda t: None if t is None or not t.numel() else t                             # noqa: E731
         flag = lambda v: int(bool(v))                                                         # noqa: E731
         x1, x2 = _pad(self.x1), _pad(self.x2)
-        scalars = [f(v) for f, v in zip((float, float, float, int, flag, flag, float, flag, float), params)]
-        outs = (x, y, dr, dc, ray_x, ray_y, status, kkt, cert) if rays else (x, y, dr, dc, status, kkt)
+        norm = _out(self.n_inst * 2, f32, dev) if spectral else None
+        scalars = [f(v) for f, v in zip((float, float, float, int, flag, flag, float, flag, float, int), params)]
+        outs = (x, y, dr, dc, ray_x, ray_y, status, kkt, cert) + ((norm,) if spectral else ()) if rays else (x, y, dr, dc, status, kkt)
         entry = getattr(_lib.lib(), f"mllp_lp_{who}")
 
         def call(begin, end):
@@ -1340,7 +1359,9 @@ class LPBatch:
                 if begin >= max_iters or not bool((_cut(status, self.n_inst, 4)[:, 0] == 6).any().item()):
                     break
         res = (_cut(x, self.N), _cut(y, self.M), _cut(status, self.n_inst, 4), _cut(kkt, self.n_inst, 6), _cut(dr, self.M), _cut(dc, self.N))
-        if rays:
+        if spectral:
+            res = LPPdhgSpectral(*res, _cut(ray_x, self.N), _cut(ray_y, self.M), _cut(cert, self.n_inst, 4), _cut(norm, self.n_inst, 2))
+        elif rays:
             res = LPPdhgRays(*res, _cut(ray_x, self.N), _cut(ray_y, self.M), _cut(cert, self.n_inst, 4))
         else:
             res = LPPdhgWide(*res)
@@ -1452,6 +1473,23 @@ class LPPdhgRays(LPPdhgWide):
     def __init__(self, x, y, status, kkt, dr, dc, ray_x, ray_y, cert):
         super().__init__(x, y, status, kkt, dr, dc)
         self.ray_x, self.ray_y, self.cert = ray_x, ray_y, cert
+
+
+class LPPdhgSpectral(LPPdhgRays):
+    """What `LPBatch.pdhg_spectral` returns: an `LPPdhgRays` with `.norm` (float32 [n_inst, 2] = the power iteration's estimate
+    of the scaled matrix's 2-norm, 0 where it is void or `power_iters` was 0, and the bound sqrt(|S|_1 |S|_inf)).  `.kkt[:, 3]`
+    is the step eta in use: `step` over the estimate where that is positive and not above the bound, else over the bound."""
+
+    def __init__(self, x, y, status, kkt, dr, dc, ray_x, ray_y, cert, norm):
+        super().__init__(x, y, status, kkt, dr, dc, ray_x, ray_y, cert)
+        self.norm = norm
+
+
+def pdhg_spectral_limits():
+    """`pdhg_wide_limits()` and the largest `power_iters` (mllp_lp_pdhg_spectral_limits; no GPU)"""
+    lim = (c_int64 * 5)()
+    _lib.check(_lib.lib().mllp_lp_pdhg_spectral_limits(lim))
+    return int(lim[0]), int(lim[1]), int(lim[2]), int(lim[3]), int(lim[4])
 
 
 def pdhg_rays_limits():

@@ -1,12 +1,14 @@
 """Cost and reach of restarted PDHG on the resident batch (mllp_lp_pdhg; with --scaled: mllp_lp_pdhg_scaled; with --halpern:
 mllp_lp_pdhg_halpern; with --wide: mllp_lp_pdhg_wide against mllp_lp_pdhg_halpern; with --rays: mllp_lp_pdhg_rays against
-mllp_lp_pdhg_wide).  Prints one JSON line (profiles/pdhg_bench.json; profiles/pdhg_scaled_bench.json holds the --scaled runs,
+mllp_lp_pdhg_wide; with --spectral: mllp_lp_pdhg_spectral against mllp_lp_pdhg_wide, profiles/pdhg_spectral_bench.json).
+Prints one JSON line (profiles/pdhg_bench.json; profiles/pdhg_scaled_bench.json holds the --scaled runs,
 profiles/pdhg_halpern_bench.json the --halpern ones, profiles/pdhg_wide_bench.json the --wide ones, profiles/pdhg_rays_bench.json
 the --rays ones).
 
     python tools/bench_pdhg.py [--calls 2] [--windows 5] [--plain-iters 256] [--netlib-iters 60000] [--synthetic 4]
                                [--scaled | --halpern [--no-reflect]] [--ruiz 10] [--no-pock-chambolle] [--no-weight] [--span 16]
-                               [--wide [--rows R] [--poll P]] [--rays [--ray-eps E] [--runs NAME,...]] [--only PART,...]
+                               [--wide [--rows R] [--poll P]] [--rays [--ray-eps E] [--runs NAME,...]] [--spectral [--power P]]
+                               [--only PART,...]
 
   --scaled        the same batches and the same Netlib table through LPBatch.pdhg_scaled with the options given; the output
                   gains "call" and "options".  --only per_iteration,netlib,cold_warm,oracle runs the named parts alone.
@@ -22,6 +24,13 @@ the --rays ones).
                   the figures of per_iteration and "us_per_check", (the median at 64 - the median at 0) x 64 / iterations.  --runs
                   wide times that call alone, which is all a tree from before the call has.  --ray-eps E: the detection part,
                   Netlib at eps 1e-3 under --netlib-iters with ray_eps E against the wide call (codes and iterations equal?).
+  --spectral      what the spectral step costs and reaches (the --wide options; --power P: power_iters, default 40).  per_iteration:
+                  on Netlib, planted 64 x (500 x 1200) and the synthetic batch, LPBatch.pdhg_wide and LPBatch.pdhg_spectral from the
+                  same build alternate window by window, each also with no iterations (the set-up alone; the spectral call also at
+                  power_iters = 0); an iteration's time is a window less the median set-up of the same call, and the bar of DESIGN
+                  4.21 is evaluated on it (each median inside the other call's smallest window - 1 % .. largest + 1 %).  netlib: the 97
+                  instances under --netlib-iters and --poll at eps 1e-3 and 1e-4 with power_iters 0 and P: converged counts, gains
+                  and losses by name, iterations on the instances both solve, and the instances whose estimate fell back.
 
   per_iteration   plain PDHG (check_every = 0) for --plain-iters iterations on the Netlib batch, on planted batches (256 and
                   1024 x (50 x 120), all in LDS; 64 x (500 x 1200); the same 64 with max_lds_words = 0, all in scratch) and on
@@ -173,6 +182,66 @@ def rays_bench(args, opts):
     print(json.dumps(out))
 
 
+def spectral_bench(args, opts):
+    """--spectral: see the module's docstring"""
+    import time
+    from mllp_amd.data import load_packed
+    from mllp_amd.graph import LPBatch, synthetic_batch
+    from mllp_amd.planted import planted_batch
+    P, iters = args.power, args.plain_iters
+    net = LPBatch.from_instances(load_packed())
+    out = {"call": "mllp_lp_pdhg_spectral", "against": "mllp_lp_pdhg_wide", "options": opts, "power_iters": P, "per_iteration": [], "set_up": []}
+    batches = [(f"Netlib {net.n_inst} instances", net, iters, args.calls, args.windows), ("planted 64 x (500 x 1200)", planted_batch(64, 500, 1200, 6.0, 2)[0], iters, args.calls, args.windows)]
+    if args.synthetic > 0:
+        batches.append((f"synthetic {args.synthetic} x (10000 x 20000)", synthetic_batch(n_inst=args.synthetic), 16, 1, 3))
+    for name, b, K, n_calls, windows in () if "per_iteration" not in args.parts else batches:
+        runs = {"wide": lambda K=K: b.pdhg_wide(K, check_every=0, **opts), "spectral": lambda K=K: b.pdhg_spectral(K, check_every=0, power_iters=P, **opts),
+                "wide_set_up": lambda: b.pdhg_wide(0, check_every=0, **opts), "spectral_set_up_P0": lambda: b.pdhg_spectral(0, check_every=0, power_iters=0, **opts),
+                "spectral_set_up": lambda: b.pdhg_spectral(0, check_every=0, power_iters=P, **opts)}
+        for run in runs.values():
+            run()
+            run()
+        torch.cuda.synchronize()
+        dev = {key: [] for key in runs}
+        for _ in range(windows):
+            for key, run in runs.items():
+                dev[key].append(device_window(run, n_calls))
+        head = {"batch": name, "instances": b.n_inst, "nnz": b.dims()["nnz"], "iterations": K, "calls_per_window": n_calls, "windows": windows}
+        # an iteration: the call's windows less the median set-up of the SAME call (the spectral call's set-up has 3 P + 1 launches more)
+        net_dev = {n: [w - float(np.median(dev[s])) for w in dev[n]] for n, s in (("wide", "wide_set_up"), ("spectral", "spectral_set_up"))}
+        fig = {n: figures(v, K)["us_per_iteration"] for n, v in net_dev.items()}
+        inside = all(fig[o]["min"] * 0.99 <= fig[n]["median"] <= fig[o]["max"] * 1.01 for n, o in (("wide", "spectral"), ("spectral", "wide")))
+        out["per_iteration"].append({**head, "us_per_iteration_without_set_up": fig, "whole_call": {n: figures(dev[n], K) for n in ("wide", "spectral")},
+                                     "each_median_inside_the_others_windows_1pct": bool(inside)})
+        out["set_up"].append({"batch": name, "calls_per_window": n_calls, "windows": windows,
+                              **{n: figures(dev[n], 1)["device_ms_per_call"] for n in ("wide_set_up", "spectral_set_up_P0", "spectral_set_up")}})
+    table, summary = {}, {}
+    for eps in (1e-3, 1e-4) if "netlib" in args.parts else ():
+        got = {}
+        for power in (0, P):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            r = net.pdhg_spectral(args.netlib_iters, eps=eps, power_iters=power, poll_every=args.poll, **opts)
+            torch.cuda.synchronize()
+            got[power] = (r.status.cpu().numpy(), r.norm.cpu().numpy(), round(time.perf_counter() - t0, 3), r.calls)
+        (s0, _, t_0, c0), (s1, nm, t_1, c1) = got[0], got[P]
+        both = (s0[:, 0] == 0) & (s1[:, 0] == 0)
+        fell = ~((nm[:, 0] > 0) & (nm[:, 0] <= nm[:, 1]))
+        key = f"eps_{eps:g}"
+        summary[key] = {"converged": {"P0": int((s0[:, 0] == 0).sum()), f"P{P}": int((s1[:, 0] == 0).sum())},
+                        "gained": [net.names[k] for k in np.flatnonzero((s0[:, 0] != 0) & (s1[:, 0] == 0))],
+                        "lost": [net.names[k] for k in np.flatnonzero((s0[:, 0] == 0) & (s1[:, 0] != 0))],
+                        "iterations_on_those_both_solve": {"P0": int(s0[both, 1].sum()), f"P{P}": int(s1[both, 1].sum())},
+                        "fewer_equal_more": [int((s1[both, 1] < s0[both, 1]).sum()), int((s1[both, 1] == s0[both, 1]).sum()), int((s1[both, 1] > s0[both, 1]).sum())],
+                        "fell_back": [net.names[k] for k in np.flatnonzero(fell)], "wall_s": {"P0": t_0, f"P{P}": t_1}, "calls": {"P0": c0, f"P{P}": c1},
+                        "bound_over_estimate": {"min": float(f"{(nm[~fell, 1] / nm[~fell, 0]).min():.3g}"), "max": float(f"{(nm[~fell, 1] / nm[~fell, 0]).max():.3g}")}}
+        for k, name in enumerate(net.names):
+            table.setdefault(name, {"m": net.inst_m[k], "n": net.inst_n[k], "sigma_est": float(f"{nm[k, 0]:.4g}"), "bound": float(f"{nm[k, 1]:.4g}")})[key] = {
+                "P0": [int(s0[k, 0]), int(s0[k, 1])], f"P{P}": [int(s1[k, 0]), int(s1[k, 1])]}
+    out.update(netlib_max_iters=args.netlib_iters, poll_every=args.poll, netlib_summary=summary, netlib=table)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=2)
@@ -185,6 +254,8 @@ def main():
     ap.add_argument("--no-reflect", action="store_true")
     ap.add_argument("--wide", action="store_true")
     ap.add_argument("--rays", action="store_true")
+    ap.add_argument("--spectral", action="store_true")
+    ap.add_argument("--power", type=int, default=40)
     ap.add_argument("--ray-eps", type=float, default=None)
     ap.add_argument("--runs", default="wide,rays_off,rays_on")
     ap.add_argument("--rows", type=int, default=None)
@@ -196,8 +267,13 @@ def main():
     ap.add_argument("--only", default="per_iteration,netlib,cold_warm,oracle")
     args = ap.parse_args()
     parts = set(args.only.split(","))
-    if args.scaled + args.halpern + args.wide + args.rays > 1:
-        ap.error("--scaled, --halpern, --wide and --rays name four calls: give one")
+    if args.scaled + args.halpern + args.wide + args.rays + args.spectral > 1:
+        ap.error("--scaled, --halpern, --wide, --rays and --spectral name five calls: give one")
+    if args.spectral:
+        assert torch.cuda.is_available(), "bench_pdhg needs the GPU: there is no CPU path"
+        args.parts = parts
+        return spectral_bench(args, {"ruiz": args.ruiz, "pock_chambolle": not args.no_pock_chambolle, "primal_weight": not args.no_weight,
+                                     "weight_span": args.span, "reflect": not args.no_reflect, "rows_per_item": args.rows})
     if args.rays:
         assert torch.cuda.is_available(), "bench_pdhg needs the GPU: there is no CPU path"
         return rays_bench(args, {"ruiz": args.ruiz, "pock_chambolle": not args.no_pock_chambolle, "primal_weight": not args.no_weight,
